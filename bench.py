@@ -1,28 +1,36 @@
 #!/usr/bin/env python3
 """Benchmark of the Diff-UNet hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR]
+
+In every config the headline (value, ms_per_step) is timed over exactly the K = --steps steps that follow the W = --warmup
+ones.  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller as
+DIR/<name>.npy (float32; a fixed seeded sample of the elements when the arrays exceed 64 MB in all).  Inputs, weights and
+noise keys are seeded: the same arguments give the same inputs on every run, so two builds can be compared output for output.
 
 --config 2 (default, the headline: BASELINE.json configs[1]): DiffUNet(in=1, out=16), one 96^3 patch per GPU, DDPM
   ancestral sampling (`diffusion.p_sample_loop` semantics) -- a "step" is ONE reverse-diffusion step = one denoiser
   evaluation (18 conv3x3x3 + 4 deconv + 1x1 head, 1.0564 TFLOP algorithmic) + the sampler update, with inputs resident in
   HBM, in-kernel Philox noise, replayed from a captured HIP graph.  The conditioning encoder pass (once per patch,
   0.28 TFLOP) runs before the timed region like x_T generation.  Metric: denoised voxel-steps / s.  HEADLINE (value,
-  ms_per_step) = the WHOLE 1000-step loop through the public API, net.diffusion.p_sample_loop(net.model, shape, model_kwargs):
-  the loop the parity test covers, the two exact-fp32 finishing steps of an fp16 plan included, second call, bracketed by
-  the ranks' barrier, maximum over the ranks; the --warmup / --steps replays of the captured fp16 step are reported beside
-  it (replayed_step_ms, replayed_value).  Config 2 does not shard (1000 strictly sequential steps on one tensor, SURVEY.md
-  8(e)) => N independent replicas, weak scaling, no data-path collective.
+  ms_per_step) = the --steps replays of the captured fp16 step after --warmup replays, bracketed by the ranks' barrier,
+  maximum over the ranks (past step 1000 the replays continue from t = 999 on the current state); dumped output: `sample`,
+  x_{t-1} of the last replay (NCDHW).  The WHOLE 1000-step loop through the public API,
+  net.diffusion.p_sample_loop(net.model, shape, model_kwargs) -- the loop the parity test covers, the two exact-fp32
+  finishing steps of an fp16 plan included -- is reported beside it (full_loop).  Config 2 does not shard (1000 strictly
+  sequential steps on one tensor) => N independent replicas, weak scaling, no data-path collective.
 --config 3 (BASELINE.json configs[2]): sliding-window DDIM inference of a 256x256x192 volume (48 windows of 96^3,
   50 steps), windows sharded over the ranks, ONE RCCL all_gather_into_tensor of the per-window outputs, identical
-  blend on every rank.  A "step" is one whole volume; reports seconds per volume and the all-gather share.
+  blend on every rank.  A "step" is one whole volume; reports seconds per volume and the all-gather share.  Dumped
+  outputs: `logits` (the blended window outputs) and `segmentation` (binarised), sampled.
 --config 4 (BASELINE.json configs[3]): DDP training step (q_sample + denoise + mse/bce/dice + backward + AdamW) on
   synthetic 96^3 x 16-class batches, 2 samples per GPU, gradients averaged over RCCL (DDP buckets overlapped with
-  backward); reports samples/s and the share a flat all-reduce of the 153.6 MB of gradients would take.
+  backward); reports samples/s and the share a flat all-reduce of the 153.6 MB of gradients would take.  Dumped outputs:
+  `loss` and `parameters` (the updated parameters, flattened in module order, sampled).
 --config 5 (BASELINE.json configs[4]): the diff_swin_unetr variant -- DiffSwinUNETR(in=1, out=16, feature_size 48), one
   96^3 patch per GPU; a "step" is one reverse-diffusion step = one SwinUNETRDenoiser evaluation (8 shifted-window
   attention blocks, 4 patch mergings, 10 UnetResBlocks, 5 transposed convolutions, 1x1x1 head) + the sampler update,
-  replayed from a captured HIP graph; same metric as config 2.
+  replayed from a captured HIP graph; same metric and dumped output as config 2.
 
 Launch: with no WORLD_SIZE in the environment and --gpus N > 1 this script starts its own N ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) BEFORE touching the GPU
@@ -290,6 +298,12 @@ def roofline_by_kernel(fl, by_launch, kern, peak, largest_name):
     return out
 
 
+def step_order(T, n):
+    """Rows of the replayed steps: the reverse order T-1 .. 0 of the T-step process, repeated until it covers n steps, so that
+    any --warmup / --steps count runs (the step counter the kernels read never leaves the table)."""
+    return list(range(T))[::-1] * -(-n // T)
+
+
 def full_loop_config2(net, image, shape, D=None):
     """BASELINE config 2 as it is worded: the whole 1000-step DDPM loop through the public API,
     ``net.diffusion.p_sample_loop(net.model, shape, model_kwargs=...)`` (gaussian_diffusion.py:441-485 of the reference),
@@ -534,6 +548,26 @@ def cpu_baseline(net_state, threads, swin=False):
                       f"{dt:.2f} s/step; sampler update excluded (<1%)"}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor, what the last timed step returned to its caller) as <dirname>/<name>.npy,
+    float32 (float64 tensors stay float64).  When they exceed DUMP_BYTES in all, each array is replaced by the same fraction of
+    its elements, flattened, at positions drawn from a generator seeded with 0 (sorted): the same for every run and build."""
+    import numpy as np
+    arrays = {k: v.detach().double() if v.dtype == torch.float64 else v.detach().float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    g = torch.Generator().manual_seed(0)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if total > DUMP_BYTES:
+            n = max(1, v.numel() * DUMP_BYTES // total)
+            idx = torch.randint(0, v.numel(), (n,), generator=g).sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        np.save(os.path.join(dirname, f"{name}.npy"), v.cpu().numpy())
+
+
 def self_launch(args):
     """No WORLD_SIZE and --gpus N > 1: start the N ranks ourselves, before any GPU call in this process (a process that
     has initialised the GPU must never exec another program; this one only waits for its children)."""
@@ -608,13 +642,12 @@ def run_config2(args, D):
     diffusion = net.diffusion                      # 1000-step process; we time K of its steps
     with torch.no_grad():
         net.embed_model(image)                     # encoder once per patch (not in the timed region)
-        x_T = torch.randn(B, CLASSES, 96, 96, 96, device=dev)
+        x_T = torch.randn(B, CLASSES, 96, 96, 96, generator=torch.Generator().manual_seed(2 + rank)).to(dev)
         ops.to_channels_last(x_T, plan.x_state, 0, plan.cx)
         ops.to_channels_last(x_T, plan.xin, 0, plan.C)
         plan.x_sum.zero_()
         plan.refresh_weights()
-        T = diffusion.num_timesteps
-        order = list(range(T))[::-1]
+        order = step_order(diffusion.num_timesteps, 1 + args.warmup + args.steps)
         coef_table = diffusion.ddpm_coef(torch.tensor(order)).to(dev).contiguous()
         row_of_step = torch.tensor(order, dtype=torch.int32, device=dev)
         plan.counter.zero_()
@@ -623,7 +656,6 @@ def run_config2(args, D):
         def one_step():          # dua_denoiser_step: step begin + 18 conv + 4 deconv + materialise passes + fused tail
             plan.native_step(nv.MODE_DDPM, row_of_step=row_of_step, coef_table=coef_table, use_sum=False)
 
-        assert args.warmup + args.steps + 2 <= T, "the 1000-step process bounds warmup+steps"
         one_step()
         torch.cuda.synchronize()
         if args.no_graph:
@@ -643,11 +675,13 @@ def run_config2(args, D):
         dt = D.max_over_ranks(time.perf_counter() - t0)
         D.barrier()
         finite = bool(torch.isfinite(plan.x_state).all())
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"sample": ops.from_channels_last(plan.x_state, plan.C)})
 
     # config 2 end to end, whatever --steps says: the 1000-step loop through the public sampler API, on every rank (replicas).
-    # THIS is the headline: the loop the parity test covers (test_thousand_step_p_sample_loop_matches_oracle), with the two
-    # exact-fp32 finishing steps of an fp16 plan inside the timed region; the K replayed steps above are kept beside it.  It runs
-    # BEFORE rank 0's per-kernel measurements (the bare-MFMA probe holds the chip at its power cap for two seconds).
+    # Reported beside the headline (the K replayed steps above): the loop the parity test covers
+    # (test_thousand_step_p_sample_loop_matches_oracle), with the two exact-fp32 finishing steps of an fp16 plan inside its timed
+    # region.  It runs BEFORE rank 0's per-kernel measurements (the bare-MFMA probe holds the chip at its power cap for two seconds).
     loop = None
     if not args.no_graph and not args.no_full_loop:
         loop = full_loop_config2(net, image, (B, CLASSES, 96, 96, 96), D)
@@ -668,21 +702,19 @@ def run_config2(args, D):
             # the matrix pipes run what is EXECUTED: the folded launch is priced by its executed figure against the ceiling
             roof["largest_launch"]["frac_of_ceiling"] = round(roof["largest_launch"].get("executed_tflops", roof["largest_launch"]["tflops"]) / ceil_tf, 4)
     if rank == 0:
-        replayed_ms = dt / args.steps * 1e3
-        ms = loop["seconds"] / loop["steps"] * 1e3 if loop is not None else replayed_ms
+        ms = dt / args.steps * 1e3
         line = {
             "metric": "denoised voxel-steps/sec on 96^3 16-class AMOS patches",
-            "value": world * B * VOX / (ms * 1e-3), "unit": "voxel-steps/s", "n_gpus": world, "steps": args.steps,
+            "value": world * B * VOX * args.steps / dt, "unit": "voxel-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": "DiffUNet 96^3 patch, 16 classes, 1000-step DDPM p_sample_loop (BASELINE.json configs[1]); "
                                    "one patch per GPU, replicas only",
                        "patch": [96, 96, 96], "classes": CLASSES, "batch_per_gpu": B, "graph_replay": not args.no_graph,
                        "noise": "in-kernel Philox4x32-10", "weights": "torch.manual_seed(0) default init"},
-            "headline": ("full_loop: value / ms_per_step = the whole 1000-step net.diffusion.p_sample_loop through the API (second "
-                         "call; fp32 finishing steps included), max over ranks; replayed_step_ms = the --steps replays of the "
-                         "captured fp16 step after --warmup replays") if loop is not None else "replayed steps (--no-full-loop / --no-graph)",
-            "replayed_step_ms": replayed_ms, "replayed_value": world * B * VOX * args.steps / dt,
+            "headline": ("value / ms_per_step = the --steps replays of the captured step after --warmup replays, max over ranks; "
+                         "full_loop = the whole 1000-step net.diffusion.p_sample_loop through the API (second call; fp32 "
+                         "finishing steps included)") if not args.no_graph else "value / ms_per_step = the --steps eager steps after --warmup",
             "step_tflops": B * 1.0564e12 / (ms * 1e-3) / 1e12, "finite": finite,
         }
         if loop is not None:
@@ -717,7 +749,7 @@ def run_config3(args, D):
                                                             timings=timings)
         else:
             out = inference.sliding_window_inference(vol, (96, 96, 96), swb, net, 0.25, pred_type="ddim_sample")
-        return inference.binarise(out)
+        return out, inference.binarise(out)
 
     with torch.no_grad():
         # pack weights and capture the step graph of every batch size this rank's sampler passes will have (sharded: the rank's
@@ -732,10 +764,12 @@ def run_config3(args, D):
         timings.clear()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            seg = one_volume()
+            out, seg = one_volume()
         torch.cuda.synchronize()
         dt = D.max_over_ranks(time.perf_counter() - t0)
         D.barrier()
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"logits": out, "segmentation": seg})
         roof = None
         if rank == 0 and not args.no_roofline:      # the conv kernel over one denoiser evaluation of the sampler's own plan
             roof = conv_roofline(net._rt.plan(swb, (96, 96, 96), dev), "f16")
@@ -783,6 +817,9 @@ def run_config4(args, D):
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0)
     D.barrier()
+    if rank == 0 and args.dump_outputs:
+        with torch.no_grad():
+            dump_outputs(args.dump_outputs, {"loss": loss, "parameters": torch.cat([p.reshape(-1) for p in net.parameters()])})
     # what one flat all-reduce of all gradients costs on its own (upper bound of the share when it is not overlapped)
     grads = [torch.zeros_like(p) for p in net.parameters()]
     allreduce_mean_(grads)
@@ -835,11 +872,10 @@ def run_config5(args, D):
     diffusion = net.diffusion
     with torch.no_grad():
         net.embed_model(image)                     # encoder once per patch (not in the timed region)
-        x_T = torch.randn(B, CLASSES, 96, 96, 96, device=dev)
+        x_T = torch.randn(B, CLASSES, 96, 96, 96, generator=torch.Generator().manual_seed(2 + rank)).to(dev)
         ops.to_channels_last(x_T, plan.x_state, 0, plan.cx)
         ops.to_channels_last(x_T, plan.xin, 0, plan.C)
-        T = diffusion.num_timesteps
-        order = list(range(T))[::-1]
+        order = step_order(diffusion.num_timesteps, 1 + args.warmup + args.steps)
         coef_table = diffusion.ddpm_coef(torch.tensor(order)).to(dev).contiguous()
         row_of_step = torch.tensor(order, dtype=torch.int32, device=dev)
         plan.counter.zero_()
@@ -852,7 +888,6 @@ def run_config5(args, D):
             plan.denoiser_body(zero_stats=False)
             plan.tail(nv.MODE_DDPM)
 
-        assert args.warmup + args.steps + 2 <= T
         if args.no_graph:
             one_step()
             torch.cuda.synchronize()
@@ -870,6 +905,8 @@ def run_config5(args, D):
         dt = D.max_over_ranks(time.perf_counter() - t0)
         D.barrier()
         finite = bool(torch.isfinite(plan.x_state).all())
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"sample": ops.from_channels_last(plan.x_state, plan.C)})
         roof = None
         if rank == 0 and not args.no_roofline:
             # the 3x3x3 convolutions are the largest share of this step too (20 launches, ~45 %): the same HIP-event timing as
@@ -927,6 +964,8 @@ def main():
     ap.add_argument("--fold-min-tiles", type=int, default=None, help="diagnostics: engine.Plan.UPCONV_MIN_TILES for this run (0 = fold every level that can; a huge value = never)")
     ap.add_argument("--no-fold", action="store_true", help="diagnostics: keep every transposed convolution + convolution on two launches (net.fold_upconv = False; A/B)")
     ap.add_argument("--no-fold-residual", action="store_true", help="diagnostics (config 5): decoder1's 1x1x1 residual branch as transposed convolution + token GEMM (net.fold_residual = False; A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--conv-variant", type=int, default=0, help="diagnostics: dua_conv3_desc.policy of every convolution launch (same-box A/B of launch forms)")
     args = ap.parse_args()
     defaults = {2: (200, 20), 3: (1, 0), 4: (5, 2), 5: (100, 10)}[args.config]

@@ -1,9 +1,9 @@
-"""Generate tests/golden/*.npz from the REFERENCE ITSELF (run in the build
-container only; /root/reference does not exist on the GPU box).
+"""Generate tests/golden/*.npz from the REFERENCE ITSELF (needs a checkout of aarchiiive/diff-unet-amos; the
+tests only read the committed fixtures).
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py <reference checkout>
 
-What is imported from /root/reference (read-only, nothing is copied):
+What is imported from the reference checkout (read-only, nothing is copied):
   * guided_diffusion.{gaussian_diffusion,respace,resample}  (needs numpy+torch only)
   * models/diffusion/utils.py, loaded by file path (its package __init__ pulls MONAI)
 The fixtures are data only: inputs and the reference's outputs for them.
@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import torch
 
-REF = "/root/reference"
+REF = sys.argv[1] if len(sys.argv) > 1 else None          # the reference checkout
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
@@ -96,6 +96,8 @@ class _InjectNoise:
 
 
 def main():
+    if not REF:
+        sys.exit("usage: python oracle/make_golden.py <checkout of aarchiiive/diff-unet-amos>")
     os.makedirs(OUT, exist_ok=True)
     gd, respace, resample, tu = _ref_modules()
     g = {}

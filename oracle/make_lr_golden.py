@@ -1,6 +1,6 @@
-"""Generate tests/golden/lr_golden.npz from the REFERENCE's own scheduler (build container only).
+"""Generate tests/golden/lr_golden.npz from the REFERENCE's own scheduler (needs a checkout of aarchiiive/diff-unet-amos).
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/make_lr_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_lr_golden.py <reference checkout>
 
 light_training/utils/lr_scheduler.py needs only torch; it is loaded by file path (its package __init__ pulls MONAI).
 Nothing is copied: the fixture holds the learning rates the reference's class produced, epoch by epoch, for
@@ -17,11 +17,13 @@ import warnings
 import numpy as np
 import torch
 
-REF = "/root/reference"
+REF = sys.argv[1] if len(sys.argv) > 1 else None          # the reference checkout
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
 def main():
+    if not REF:
+        sys.exit("usage: python oracle/make_lr_golden.py <checkout of aarchiiive/diff-unet-amos>")
     sys.dont_write_bytecode = True
     spec = importlib.util.spec_from_file_location("ref_lr_scheduler", os.path.join(REF, "light_training/utils/lr_scheduler.py"))
     mod = importlib.util.module_from_spec(spec)

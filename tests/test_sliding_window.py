@@ -134,30 +134,45 @@ def _bench_line(args, timeout):
 
 
 @pytest.mark.gpu
-def test_bench_config3_runs_end_to_end_on_two_ranks():
+def test_bench_config3_runs_end_to_end_on_two_ranks(tmp_path):
     """The driver's first N > 1 run must not be the code's first: `bench.py --config 3 --gpus 2` (windows sharded over the
-    ranks, one all-gather, blend on every rank) on a 144 x 144 x 96 volume = 4 windows, two per rank in ONE balanced call."""
-    line = _bench_line(["--config", "3", "--steps", "1", "--warmup", "0", "--volume", "144", "144", "96"], 600)
+    ranks, one all-gather, blend on every rank) on a 144 x 144 x 96 volume = 4 windows, two per rank in ONE balanced call.
+    Its two outputs (2 x 127 MB) are dumped as seeded samples within the 64 MB budget."""
+    out = tmp_path / "dump"
+    line = _bench_line(["--config", "3", "--steps", "1", "--warmup", "0", "--volume", "144", "144", "96", "--dump-outputs", str(out)], 600)
     assert line["n_gpus"] == 2 and line["config"]["windows"] == 4 and line["scaling"] == "strong"
     assert line["all_gather_seconds"] > 0 and line["gathered_bytes"] == 2 * 2 * 16 * 96 ** 3 * 4
     assert line["value"] > 0 and 0.0 <= line["foreground_fraction"] <= 1.0
+    assert sorted(os.listdir(out)) == ["logits.npy", "segmentation.npy"]
+    logits, seg = np.load(out / "logits.npy"), np.load(out / "segmentation.npy")
+    assert logits.dtype == seg.dtype == np.float32 and logits.ndim == seg.ndim == 1
+    assert 0 < logits.nbytes + seg.nbytes <= 64 << 20 and np.isfinite(logits).all() and set(np.unique(seg)) <= {0.0, 1.0}
 
 
 @pytest.mark.gpu
-def test_bench_config4_runs_end_to_end_on_two_ranks():
+def test_bench_config4_runs_end_to_end_on_two_ranks(tmp_path):
     """`bench.py --config 4 --gpus 2 --batch 1`: the DDP reducer's bucketed all-reduce under backward, two ranks."""
-    line = _bench_line(["--config", "4", "--steps", "2", "--warmup", "1", "--batch", "1"], 900)
+    out = tmp_path / "dump"
+    line = _bench_line(["--config", "4", "--steps", "2", "--warmup", "1", "--batch", "1", "--dump-outputs", str(out)], 900)
+    assert np.load(out / "loss.npy").item() == line["loss"]
+    assert np.isfinite(np.load(out / "parameters.npy")).all()
     assert line["n_gpus"] == 2 and line["config"]["batch_per_gpu"] == 1
     assert np.isfinite(line["loss"]) and line["value"] > 0 and line["flat_allreduce_seconds"] > 0
     assert line["gradient_bytes"] == 38405520 * 4
 
 
 @pytest.mark.gpu
-def test_bench_config2_runs_end_to_end_on_two_ranks():
-    """`bench.py --gpus 2` (the headline config: replicas only, no data-path collective): both ranks run the 1000-step loop
-    between barriers, rank 0 prints the contract line with the aggregate of the two replicas."""
-    line = _bench_line(["--steps", "5", "--warmup", "2"], 900)
+def test_bench_config2_runs_end_to_end_on_two_ranks(tmp_path):
+    """`bench.py --gpus 2` (the headline config: replicas only, no data-path collective): both ranks replay the --steps steps
+    and run the 1000-step loop between barriers, rank 0 prints the contract line with the aggregate of the two replicas and
+    alone writes the --dump-outputs files."""
+    out = tmp_path / "dump"
+    line = _bench_line(["--steps", "5", "--warmup", "2", "--dump-outputs", str(out)], 900)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["finite"] is True
-    assert line["full_loop"]["steps"] == 1000 and abs(line["ms_per_step"] * 1000 - line["full_loop"]["seconds"] * 1e3) < 1e-6
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["full_loop"]["steps"] == 1000 and line["full_loop"]["seconds"] > 0 and line["full_loop"]["finite"] is True
     assert abs(line["value"] - 2 * 96 ** 3 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
-    assert line["replayed_step_ms"] > 0 and "roofline" not in line
+    assert "roofline" not in line
+    assert sorted(os.listdir(out)) == ["sample.npy"]
+    sample = np.load(out / "sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (1, 16, 96, 96, 96) and np.isfinite(sample).all()

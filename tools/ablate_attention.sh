@@ -6,7 +6,7 @@
 # DUA_HIP_LIB: the shipped library and its objects are never touched, an interrupted run leaves nothing to restore.
 # usage (on the GPU box): tools/ablate_attention.sh <out dir>
 set -e -o pipefail
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$ROOT/gpurun_out/$1; mkdir -p "$OUT"
+ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$(realpath -m "$1"); mkdir -p "$OUT"
 for v in ${ABL_LIST:-0 1 2 4 8 15 16}; do
   lib=$("$ROOT/tools/build_diag.sh" wa_abl_$v -DWA_ABL=$v | tail -1)
   export DUA_HIP_LIB=$lib

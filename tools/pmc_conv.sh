@@ -2,7 +2,7 @@
 # SQ/LDS counter passes over the conv3d_k3 kernel on the big layer shapes (tools/bench_conv.py).
 # usage: tools/pmc_conv.sh <out dir under gpurun_out> <variants> <shape indices> [kernel-name substring]
 set -e -o pipefail
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$1; VAR=${2:-0}; IDX=${3:-1,2}; NAME=${4:-conv3d_k3}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # SQ / LDS counter passes over one kernel of the DiffSwinUNETR step (bench.py --config 5, eager launches).
 # usage: tools/pmc_swin.sh <out dir under gpurun_out> <kernel-name substring>
 set -e -o pipefail
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$1; NAME=${2:-window_attention}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # SQ/LDS counter passes over the folded up-convolution kernel (tools/bench_upconv.py level0).
 # usage: tools/pmc_upconv.sh <out dir under gpurun_out> [level0|level1]
 set -e -o pipefail
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$1; LV=${2:-level0}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # SQ / LDS counter passes over the 3x3x3 weight-gradient kernel on its 96^3 layers (tools/bench_wgrad.py --only 2).
 # usage: tools/pmc_wgrad.sh <out dir under gpurun_out> [kernel-name substring; default conv3d_k3_wgrad]
 set -e -o pipefail
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$1
 NAME=${2:-conv3d_k3_wgrad}
 mkdir -p $OUT
