@@ -72,7 +72,7 @@ class TailResidual(C.Structure):
 IN_BLOCKED, OUT_BLOCKED = 1, 2            # dua_conv3_desc.layout bits
 POLICY_NO_FINISH = 256                    # dua_conv3_desc.policy bit: skip the split-K finish kernel (timing only)
 MODE_LOGITS, MODE_DDPM, MODE_DDIM = 0, 1, 2
-OP_CONV3, OP_MATERIALIZE, OP_DECONV, OP_UPCONV = 1, 2, 3, 4
+OP_CONV3, OP_MATERIALIZE, OP_DECONV, OP_UPCONV, OP_DECONV_PAD = 1, 2, 3, 4, 5
 
 
 class StepOp(C.Structure):
@@ -140,6 +140,7 @@ _SIGS = {
     "dua_mfma_probe": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
     "dua_chain_probe": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P]),
     "dua_deconv_k2s2_fwd": (C.c_int, [C.POINTER(Conv3Desc), _P, _P, _P, C.POINTER(InNorm), _P, _P]),
+    "dua_deconv_k2s2_pad_fwd": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_int, C.c_int, _P, _P, _P, C.POINTER(InNorm), _P, _P]),
     "dua_conv3d_k3_dgrad_reduce_supported": (C.c_int, [C.POINTER(Conv3Desc)]),
     "dua_conv3d_k3_dgrad_reduce": (C.c_int, [C.POINTER(Conv3Desc), _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(InNorm), _P, _P]),
     "dua_deconv_k2s2_res_supported": (C.c_int, [C.POINTER(Conv3Desc), C.c_int]),
@@ -187,6 +188,7 @@ _SIGS = {
     "dua_pack_deconv_weights_dgrad": (C.c_long, [C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dua_deconv_k2s2_bwd_workspace": (C.c_long, [C.POINTER(Conv3Desc)]),
     "dua_deconv_k2s2_bwd": (C.c_int, [C.POINTER(Conv3Desc), _P, _P, _P, _P, _P, _P, C.c_long, _P]),
+    "dua_deconv_k2s2_pad_bwd": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_long, _P]),
     "dua_head_fwd": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "dua_head_bwd_workspace": (C.c_long, [C.c_long]),
     "dua_head_bwd": (C.c_int, [C.c_int, C.c_long, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_long, _P]),

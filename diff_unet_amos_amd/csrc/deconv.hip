@@ -4,6 +4,10 @@
 // "upsampled" half of torch.cat([x_e, x_0], 1) at denoiser.py:190: the result is written
 // straight into channels [Cout_off, Cout_off+Cout) of the concat buffer.
 //   out[n, 2d+i, 2h+j, 2w+k, co] = bias[co] + sum_ci x[n,d,h,w,ci] * W[ci,co,i,j,k]
+// Replicate pad (dua_deconv_k2s2_pad_fwd, DeconvArgs.pad): the concat buffer of a level with an odd extent S has one plane more
+// than the 2 floor(S/2) the transposed convolution computes; UpCat.forward replicate-pads it (denoiser.py:176-186).  The
+// epilogue stores every voxel of the last computed plane 2 floor(S/2) - 1 of such an axis a second time, to plane S - 1 (edges
+// and corners: every combination).  A wave-uniform branch; without the pad no copy is looked for.
 // GEMM view per tap: M = input voxels, N = Cout, K = Cin.  Workgroup: 256 consecutive input
 // voxels x 64 output channels x one tap; wave w owns voxels [64w, 64w+64) as 2x2 MFMA 32x32
 // accumulators.  The producer's InstanceNorm+LeakyReLU is applied while staging (InXform).
@@ -27,7 +31,20 @@ struct DeconvArgs {
   int Cin, Cin_stride, Cin_off, Cout, Cout_stride, Cout_off;
   int nchunks, nct, lds_base;
   int out_blk;                     // y in 16-channel blocks (dua_conv3_desc.layout; the all-taps kernel only)
+  int Do, Ho, Wo;                  // output extents: 2D or 2D + 1 per axis
+  int pad;                         // 1 = some output extent is 2 x input + 1 (replicate-pad copies in the epilogue)
 };
+
+// st(voxel) for every replicate-pad copy of output voxel ov: one per combination of the axes on whose last computed plane
+// (2 x input - 1, output extent odd) ov lies.
+template <typename F>
+__device__ __forceinline__ void pad_copies(const DeconvArgs& a, long ov, F&& st) {
+  const long hw = (long)a.Ho * a.Wo;
+  const int od = (int)(ov / hw), oh = (int)((ov / a.Wo) % a.Ho), ow = (int)(ov % a.Wo);
+  const int e = ((a.Do & 1) && od == a.Do - 2 ? 4 : 0) | ((a.Ho & 1) && oh == a.Ho - 2 ? 2 : 0) | ((a.Wo & 1) && ow == a.Wo - 2 ? 1 : 0);
+  for (int c = 1; c < 8; ++c)
+    if ((c & e) == c) st(ov + ((c & 4) ? hw : 0) + ((c & 2) ? a.Wo : 0) + (c & 1));
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void deconv_k2s2_kernel(DeconvArgs a) {
@@ -125,8 +142,8 @@ __global__ __launch_bounds__(256) void deconv_k2s2_kernel(DeconvArgs a) {
   __syncthreads();
   constexpr int GPV = BN / EPG, VPI = 64 / GPV;
   const int ti = tap >> 2, tj = (tap >> 1) & 1, tk = tap & 1;
-  const int H2 = 2 * a.H, W2 = 2 * a.W;
-  T* yout = (T*)a.y + (long)n * vox * 8 * a.Cout_stride + a.Cout_off + ct * BN;
+  const int H2 = a.Ho, W2 = a.Wo;
+  T* yout = (T*)a.y + (long)n * a.Do * H2 * W2 * a.Cout_stride + a.Cout_off + ct * BN;
 #pragma unroll
   for (int it = 0; it < 64 / VPI; ++it) {
     const int vl = it * VPI + lane / GPV, cg = lane % GPV;
@@ -135,7 +152,9 @@ __global__ __launch_bounds__(256) void deconv_k2s2_kernel(DeconvArgs a) {
       const int w = (int)(v % a.W); const long t = v / a.W;
       const int h = (int)(t % a.H), d = (int)(t / a.H);
       const long ov = ((long)(2 * d + ti) * H2 + (2 * h + tj)) * W2 + (2 * w + tk);
-      *(Frag*)(yout + ov * a.Cout_stride + cg * EPG) = *(const Frag*)(ot + vl * OS + cg * 16);
+      const Frag o = *(const Frag*)(ot + vl * OS + cg * 16);
+      *(Frag*)(yout + ov * a.Cout_stride + cg * EPG) = o;
+      if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * EPG) = o; });
     }
   }
 }
@@ -254,8 +273,8 @@ __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a
   __syncthreads();
   // thread = (voxel row, 8 output channels): partials of waves 0..3 in that order, + bias, pixel-shuffle store
   const int ti = tap >> 2, tj = (tap >> 1) & 1, tk = tap & 1;
-  const int H2 = 2 * a.H, W2 = 2 * a.W;
-  T* yout = (T*)a.y + (long)n * vox * 8 * a.Cout_stride + a.Cout_off + ct * BN;
+  const int H2 = a.Ho, W2 = a.Wo;
+  T* yout = (T*)a.y + (long)n * a.Do * H2 * W2 * a.Cout_stride + a.Cout_off + ct * BN;
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int item = tid + 256 * it, vl = item >> 3, cg = item & 7;
@@ -280,6 +299,7 @@ __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = (T)(o[e] + a.bias[ct * BN + cg * 8 + e]);
         *(Frag*)dst = f;
+        if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * 8) = f; });
       } else {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -287,6 +307,7 @@ __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a
 #pragma unroll
           for (int e = 0; e < 4; ++e) f[e] = (T)(o[4 * g + e] + a.bias[ct * BN + cg * 8 + 4 * g + e]);
           *(Frag*)(dst + 4 * g) = f;
+          if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * 8 + 4 * g) = f; });
         }
       }
     }
@@ -385,8 +406,9 @@ __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) 
   store_pair(0);
   __syncthreads();
 
-  const int H2 = 2 * a.H, W2 = 2 * a.W;
-  T* yout = (T*)a.y + (long)n * vox * 8 * a.Cout_stride;
+  const int H2 = a.Ho, W2 = a.Wo;
+  const long ovox = (long)a.Do * H2 * W2;
+  T* yout = (T*)a.y + (long)n * ovox * a.Cout_stride;
   const float bq0 = a.bias[ct * BN + r], bq1 = a.bias[ct * BN + 32 + r];
   char* ot = stg + wave * 2 * WR * RB;                      // staged row 2 vl + tk: the two taps of a pair interleaved like their outputs
   int ovb[NST];                                             // output voxel (before the pair's (ti, tj) offset) of this lane's staged rows, or -1
@@ -441,9 +463,12 @@ __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) 
 #pragma unroll
       for (int it = 0; it < NST; ++it) {
         const int j = it * VPI + lane / GPV, cg = lane % GPV;
-        if (ovb[it] >= 0 && ct * BN + q * 32 + cg * EPG < a.Cout)
-          *(Frag*)(yout + chan_off(a.out_blk, ovb[it] + toff, a.Cout_off + ct * BN + q * 32 + cg * EPG, a.Cout_stride, vox * 8)) =
-              *(const Frag*)(ot + j * RB + cg * 16);
+        if (ovb[it] >= 0 && ct * BN + q * 32 + cg * EPG < a.Cout) {
+          const Frag o = *(const Frag*)(ot + j * RB + cg * 16);
+          const int c0 = a.Cout_off + ct * BN + q * 32 + cg * EPG;
+          *(Frag*)(yout + chan_off(a.out_blk, ovb[it] + toff, c0, a.Cout_stride, ovox)) = o;
+          if (a.pad) pad_copies(a, ovb[it] + toff, [&](long c) { *(Frag*)(yout + chan_off(a.out_blk, c, c0, a.Cout_stride, ovox)) = o; });
+        }
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -683,7 +708,7 @@ static int deconv_kernel_kind(const dua_conv3_desc* d) {
 
 template <typename T>
 static int launch_deconv(const dua_conv3_desc* d, const void* x, const void* w, const float* bias,
-                         const dua_in_norm* in, void* y, hipStream_t s) {
+                         const dua_in_norm* in, void* y, hipStream_t s, int Do = 0, int Ho = 0, int Wo = 0) {
   constexpr int CK = dc::KG * Elem<T>::EPG;
   DeconvArgs a;
   a.x = x; a.w = w; a.bias = bias; a.y = y;
@@ -693,13 +718,15 @@ static int launch_deconv(const dua_conv3_desc* d, const void* x, const void* w, 
   a.Cout = d->Cout; a.Cout_stride = d->Cout_stride; a.Cout_off = d->Cout_off;
   a.nchunks = (d->Cin + CK - 1) / CK;
   a.nct = (d->Cout + dc::BN - 1) / dc::BN;
+  a.Do = Do ? Do : 2 * d->D; a.Ho = Ho ? Ho : 2 * d->H; a.Wo = Wo ? Wo : 2 * d->W;
+  a.pad = (a.Do | a.Ho | a.Wo) & 1;
   const long vox = (long)d->D * d->H * d->W;
   if (int e = ensure_prepared()) return e;
   if (d->policy != 0 && d->policy != 6) return DUA_ERR_ARG;
   const int g_conv_variant = d->policy;
   a.out_blk = d->layout & DUA_OUT_BLOCKED ? 1 : 0;
   if (d->layout & DUA_IN_BLOCKED) return DUA_ERR_ARG;
-  if (a.out_blk && (deconv_kernel_kind(d) != 2 || d->Cout_off % 16 || d->Cout_stride % 16 || vox * 8 * 16 >= 0x7fffffffL)) return DUA_ERR_ARG;
+  if (a.out_blk && (deconv_kernel_kind(d) != 2 || d->Cout_off % 16 || d->Cout_stride % 16 || (long)a.Do * a.Ho * a.Wo * 16 >= 0x7fffffffL)) return DUA_ERR_ARG;
   if (vox >= 256L * 128 && a.nchunks <= 4) {          // enough tiles to fill the chip with one workgroup per 8 taps
     // 128-voxel tiles: two workgroups per CU up to 64 input channels (70 KB each), one's pixel-shuffle stores under the
     // other's loads; policy 6 keeps the 256-voxel form (one workgroup per CU) for A/B where it fits
@@ -746,6 +773,21 @@ extern "C" int dua_deconv_k2s2_fwd(const dua_conv3_desc* d, const void* x, const
     return DUA_ERR_ARG;
   if (d->dtype == DUA_F16) return dua::launch_deconv<dua::f16>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream);
   if (d->dtype == DUA_F32) return dua::launch_deconv<float>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream);
+  return DUA_ERR_ARG;
+}
+
+/* see include/dua_hip.h */
+extern "C" int dua_deconv_k2s2_pad_fwd(const dua_conv3_desc* d, int Do, int Ho, int Wo, const void* x, const void* w_packed,
+                                       const float* bias_padded, const dua_in_norm* in, void* y, void* stream) {
+  if (!d || d->D <= 0 || d->H <= 0 || d->W <= 0) return DUA_ERR_ARG;
+  if ((Do != 2 * d->D && Do != 2 * d->D + 1) || (Ho != 2 * d->H && Ho != 2 * d->H + 1) || (Wo != 2 * d->W && Wo != 2 * d->W + 1))
+    return DUA_ERR_ARG;
+  if (!x || !w_packed || !bias_padded || !y) return DUA_ERR_ARG;
+  if (in && in->stats && (!in->gamma || !in->beta || in->c_pad < d->Cin || in->count <= 0 || !(in->slope >= 0.f && in->slope <= 1.f))) return DUA_ERR_ARG;
+  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8)
+    return DUA_ERR_ARG;
+  if (d->dtype == DUA_F16) return dua::launch_deconv<dua::f16>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
+  if (d->dtype == DUA_F32) return dua::launch_deconv<float>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
   return DUA_ERR_ARG;
 }
 

@@ -9,6 +9,10 @@
 //                    child tiles are staged as they lie in HBM and read with ds_read_b64_tr_b16 (as conv3d_wgrad.hip);
 //                    workgroup = 8 waves = 8 taps x 64 ci x 64 co, persistent over 128-voxel tiles, partial sums to a
 //                    workspace + reduce kernel.  f32 (parity) form: MFMA 32x32x2, plain reads.
+// Replicate pad (dua_deconv_k2s2_pad_bwd, DeconvBwdArgs.pad): dy lies on the grid of a level with an odd extent, one plane longer
+// than 2 floor(S/2) on that axis: the forward stored the last computed plane twice (denoiser.py:176-186), so its adjoint adds the
+// gradient of the copy to the voxel it copies -- done while the dy operand is read (sum in fp32, rounded once), for the data and
+// the weight gradient alike.  A wave-uniform branch; without the pad the loads are the plain ones.
 #include "common.hpp"
 #include "../../include/dua_hip.h"
 
@@ -27,7 +31,34 @@ struct DeconvBwdArgs {
   int Cin, Cin_stride, Cin_off;    // x / dx channel slice
   int Cout, Cout_stride, Cout_off; // dy channel slice
   int nchunks, nct, P, total_tiles, ncc;
+  int Do, Ho, Wo;                  // dy extents: 2D or 2D + 1 per axis
+  int pad;                         // 1 = some dy extent is 2 x input + 1
 };
+
+// dy row of child voxel ov plus the rows of its replicate-pad copies (every combination of the axes on whose last computed
+// plane, 2 x input - 1 of an odd extent, ov lies): the gradient that reaches ov through the pad.  row = dy + ov * Cout_stride.
+template <typename T>
+__device__ __forceinline__ typename Elem<T>::Frag load_folded(const DeconvBwdArgs& a, const T* row, long ov) {
+  using Frag = typename Elem<T>::Frag;
+  constexpr int EPG = Elem<T>::EPG;
+  Frag f = *(const Frag*)row;
+  const long hw = (long)a.Ho * a.Wo;
+  const int od = (int)(ov / hw), oh = (int)((ov / a.Wo) % a.Ho), ow = (int)(ov % a.Wo);
+  const int e = ((a.Do & 1) && od == a.Do - 2 ? 4 : 0) | ((a.Ho & 1) && oh == a.Ho - 2 ? 2 : 0) | ((a.Wo & 1) && ow == a.Wo - 2 ? 1 : 0);
+  if (e == 0) return f;
+  float s[EPG];
+#pragma unroll
+  for (int k = 0; k < EPG; ++k) s[k] = (float)f[k];
+  for (int c = 1; c < 8; ++c)
+    if ((c & e) == c) {
+      const Frag g = *(const Frag*)(row + (((c & 4) ? hw : 0) + ((c & 2) ? a.Wo : 0) + (c & 1)) * a.Cout_stride);
+#pragma unroll
+      for (int k = 0; k < EPG; ++k) s[k] += (float)g[k];
+    }
+#pragma unroll
+  for (int k = 0; k < EPG; ++k) f[k] = (T)s[k];
+  return f;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -45,8 +76,8 @@ __global__ __launch_bounds__(256) void deconv_k2s2_dgrad_kernel(DeconvBwdArgs a)
   const long vox = (long)a.D * a.H * a.W;
   const long v0 = (long)blockIdx.x * TM;
   const int ct = blockIdx.y, n = blockIdx.z;
-  const int H2 = 2 * a.H, W2 = 2 * a.W;
-  const T* dyb = (const T*)a.dy + (long)n * vox * 8 * a.Cout_stride + a.Cout_off;
+  const int H2 = a.Ho, W2 = a.Wo;
+  const T* dyb = (const T*)a.dy + (long)n * a.Do * H2 * W2 * a.Cout_stride + a.Cout_off;
   // packed weights: [tap][ct over Cin][chunk over Cout][kg][64 ci][EPG co]
   const char* wsrc = (const char*)a.w + (long)ct * a.nchunks * W_BYTES;
   const long wtap = (long)a.nct * a.nchunks * W_BYTES;
@@ -80,8 +111,10 @@ __global__ __launch_bounds__(256) void deconv_k2s2_dgrad_kernel(DeconvBwdArgs a)
     const bool cok = c0 < a.Cout;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (child0[j] >= 0 && cok) pa[j] = *(const Frag*)(dyb + (child0[j] + toff) * a.Cout_stride + c0);
-      else
+      if (child0[j] >= 0 && cok) {
+        const T* row = dyb + (child0[j] + toff) * a.Cout_stride + c0;
+        pa[j] = a.pad ? load_folded<T>(a, row, child0[j] + toff) : *(const Frag*)row;
+      } else
 #pragma unroll
         for (int e = 0; e < EPG; ++e) pa[j][e] = (T)0.f;
     }
@@ -164,7 +197,7 @@ __global__ __launch_bounds__(dwg::NT) void deconv_k2s2_wgrad_kernel(DeconvBwdArg
   const int part_id = blockIdx.x, tap = blockIdx.y & 7, combo = blockIdx.y >> 3;
   const int ci_t = combo / a.ncc, co_t = combo % a.ncc;          // ncc = co tiles
   const int vox = a.D * a.H * a.W;                 // the launcher checks that 8 * vox fits an int
-  const int H2 = 2 * a.H, W2 = 2 * a.W;
+  const int H2 = a.Ho, W2 = a.Wo;
   const int toff = ((tap >> 2) * H2 + ((tap >> 1) & 1)) * W2 + (tap & 1);
   const int tiles_per_n = (vox + TV - 1) / TV;
 
@@ -197,7 +230,7 @@ __global__ __launch_bounds__(dwg::NT) void deconv_k2s2_wgrad_kernel(DeconvBwdArg
     const int n = tile / tiles_per_n, v0 = (tile - n * tiles_per_n) * TV;
     // channel groups behind Cin / Cout are zero-filled below: their loads go to the slice's first group (a real address)
     const T* xb = (const T*)a.x + (long)n * vox * a.Cin_stride + a.Cin_off + (xg_ok ? ci_t * 64 + g * EPG : 0);
-    const T* yb = (const T*)a.dy + (long)n * vox * 8 * a.Cout_stride + a.Cout_off + (yg_ok ? co_t * 64 + g * EPG : 0);
+    const T* yb = (const T*)a.dy + (long)n * a.Do * H2 * W2 * a.Cout_stride + a.Cout_off + (yg_ok ? co_t * 64 + g * EPG : 0);
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int v = v0 + vl0 + VSTEP * j;
@@ -206,7 +239,7 @@ __global__ __launch_bounds__(dwg::NT) void deconv_k2s2_wgrad_kernel(DeconvBwdArg
       const int w = vc % a.W, t = vc / a.W, h = t % a.H, d = t / a.H;
       const long ov = (long)((2 * d) * H2 + 2 * h) * W2 + 2 * w + toff;
       xr[j] = *(const Frag*)(xb + (long)vc * a.Cin_stride);             // unconditional loads on clamped addresses
-      yr[j] = *(const Frag*)(yb + ov * a.Cout_stride);
+      yr[j] = a.pad ? load_folded<T>(a, yb + ov * a.Cout_stride, ov) : *(const Frag*)(yb + ov * a.Cout_stride);
       if (!(in && xg_ok)) {
 #pragma unroll
         for (int e = 0; e < EPG; ++e) xr[j][e] = (T)0.f;
@@ -339,13 +372,15 @@ static const LdsAttrs kDeconvBwdLdsReg(kDeconvBwdLdsAttrs);
 
 template <typename T>
 static int launch_deconv_bwd(const dua_conv3_desc* d, const void* x, const void* dy, const void* w_packed, void* dx,
-                             float* dw, float* ws, long ws_bytes, hipStream_t s) {
+                             float* dw, float* ws, long ws_bytes, hipStream_t s, int Do = 0, int Ho = 0, int Wo = 0) {
   constexpr int CK = db::KG * Elem<T>::EPG;
   DeconvBwdArgs a{};
   a.x = x; a.dy = dy; a.w = w_packed; a.dx = dx; a.dw = dw; a.part = ws;
   a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cin_stride = d->Cin_stride; a.Cin_off = d->Cin_off;
   a.Cout = d->Cout; a.Cout_stride = d->Cout_stride; a.Cout_off = d->Cout_off;
+  a.Do = Do ? Do : 2 * d->D; a.Ho = Ho ? Ho : 2 * d->H; a.Wo = Wo ? Wo : 2 * d->W;
+  a.pad = (a.Do | a.Ho | a.Wo) & 1;
   const long vox = (long)d->D * d->H * d->W;
   if (int e = ensure_prepared()) return e;
   if (dx) {
@@ -362,7 +397,7 @@ static int launch_deconv_bwd(const dua_conv3_desc* d, const void* x, const void*
     a.P = P; a.ncc = (d->Cout + 63) / 64;
     constexpr int TV = dwg::tile_voxels<T>();
     a.total_tiles = (int)(d->N * ((vox + TV - 1) / TV));
-    if (vox * 8 > 0x7fffffffL) return DUA_ERR_ARG;                      // the kernel indexes voxels with ints
+    if ((long)a.Do * a.Ho * a.Wo > 0x7fffffffL) return DUA_ERR_ARG;     // the kernel indexes voxels with ints
     const int lds = 4 * (TV * 32 * (int)sizeof(T) + 64);                // x and dy tile, two half images each (>= 32 KB: the
                                                                         // end-of-kernel reduction reuses it)
     hipLaunchKernelGGL(deconv_k2s2_wgrad_kernel<T>, dim3(P, 8 * ncombo), dim3(dwg::NT), lds, s, a);
@@ -433,6 +468,22 @@ int dua_deconv_k2s2_bwd(const dua_conv3_desc* d, const void* x, const void* dy, 
     return dua::launch_deconv_bwd<dua::f16>(d, x, dy, w_packed_dgrad, dx, dw, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (d->dtype == DUA_F32)
     return dua::launch_deconv_bwd<float>(d, x, dy, w_packed_dgrad, dx, dw, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+  return DUA_ERR_ARG;
+}
+
+int dua_deconv_k2s2_pad_bwd(const dua_conv3_desc* d, int Do, int Ho, int Wo, const void* x, const void* dy, const void* w_packed_dgrad,
+                            void* dx, float* dw, void* workspace, long workspace_bytes, void* stream) {
+  if (!d || d->D <= 0 || d->H <= 0 || d->W <= 0) return DUA_ERR_ARG;
+  if ((Do != 2 * d->D && Do != 2 * d->D + 1) || (Ho != 2 * d->H && Ho != 2 * d->H + 1) || (Wo != 2 * d->W && Wo != 2 * d->W + 1))
+    return DUA_ERR_ARG;
+  if (!dy || (!dx && !dw) || (dx && !w_packed_dgrad) || (dw && !x)) return DUA_ERR_ARG;
+  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8) return DUA_ERR_ARG;
+  if (d->dtype == DUA_F16)
+    return dua::launch_deconv_bwd<dua::f16>(d, x, dy, w_packed_dgrad, dx, dw, (float*)workspace, workspace_bytes, (hipStream_t)stream,
+                                            Do, Ho, Wo);
+  if (d->dtype == DUA_F32)
+    return dua::launch_deconv_bwd<float>(d, x, dy, w_packed_dgrad, dx, dw, (float*)workspace, workspace_bytes, (hipStream_t)stream,
+                                         Do, Ho, Wo);
   return DUA_ERR_ARG;
 }
 

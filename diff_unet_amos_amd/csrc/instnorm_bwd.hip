@@ -223,9 +223,11 @@ int dua_instnorm_bwd_apply(const dua_norm_bwd_desc* d, const void* dA, const voi
 // x_l feeds the skip half of the decoder's concat AND the pooling of the next level (denoiser.py:100,106,190):
 //   out[v] = dA[v] + (v is the arg-max of its 2x2x2 window ? dP[window] : 0)
 // The arg-max is recomputed from the stored activation, first maximum in (d, h, w) scan order as torch's max_pool3d.
+// ODD (some un-pooled extent odd): the blocks tile ceil(S/2) per axis; a block on the trailing plane of an odd axis was never
+// pooled (floor) and passes dA alone.
 namespace dua {
 
-template <typename T>
+template <typename T, bool ODD = false>
 __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const T* __restrict__ act, int act_stride, int act_off,
                                                                const T* __restrict__ dA, int da_stride, int da_off,
                                                                const T* __restrict__ dP, int dp_stride,
@@ -235,13 +237,30 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const T* __restri
   constexpr int EPG = Elem<T>::EPG;
   const int gpc = C / EPG, n = blockIdx.y;
   const int W2 = W >> 1, H2 = H >> 1;
+  const int WB = ODD ? (W + 1) >> 1 : W2, HB = ODD ? (H + 1) >> 1 : H2;          // blocks per axis
   const long vox_n = (long)D * H * W;
   for (long it = blockIdx.x * 256L + threadIdx.x; it < total; it += (long)gridDim.x * 256) {
     const int cg = (int)(it % gpc);
     long v = it / gpc;
-    const int pw = (int)(v % W2); v /= W2;
-    const int ph = (int)(v % H2); const int pd = (int)(v / H2);
-    const long pv = n * (vox_n >> 3) + ((long)pd * H2 + ph) * W2 + pw;
+    const int pw = (int)(v % WB); v /= WB;
+    const int ph = (int)(v % HB); const int pd = (int)(v / HB);
+    if (ODD && (pd >= (D >> 1) || ph >= H2 || pw >= W2)) {
+      // trailing plane(s): out = dA (or 0) on the voxels of this block that exist
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int d = 2 * pd + (k >> 2), h = 2 * ph + ((k >> 1) & 1), w = 2 * pw + (k & 1);
+        if (d >= D || h >= H || w >= W) continue;
+        const long gv = n * vox_n + ((long)d * H + h) * W + w;
+        Frag o;
+        if (dA) o = *(const Frag*)(dA + gv * da_stride + da_off + cg * EPG);
+        else
+#pragma unroll
+          for (int e = 0; e < EPG; ++e) o[e] = (T)0.f;
+        *(Frag*)(out + gv * out_stride + cg * EPG) = o;
+      }
+      continue;
+    }
+    const long pv = n * (ODD ? (long)(D >> 1) * H2 * W2 : vox_n >> 3) + ((long)pd * H2 + ph) * W2 + pw;
     const Frag g = *(const Frag*)(dP + pv * dp_stride + cg * EPG);
     Frag a[8];
     long gv[8];
@@ -279,9 +298,24 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const T* __restri
 extern "C" int dua_maxpool2_bwd_add(int dtype, int N, int D, int H, int W, int C, const void* act, int act_stride,
                                     int act_off, const void* dA, int da_stride, int da_off, const void* dP, int dp_stride,
                                     void* out, int out_stride, void* stream) {
-  if (!act || !dP || !out || N <= 0 || C <= 0 || C % 8 || (D | H | W) & 1 || D <= 0 || H <= 0 || W <= 0) return DUA_ERR_ARG;
+  if (!act || !dP || !out || N <= 0 || C <= 0 || C % 8 || D < 2 || H < 2 || W < 2) return DUA_ERR_ARG;
   if (act_stride % 8 || act_off % 8 || dp_stride % 8 || out_stride % 8 || (dA && (da_stride % 8 || da_off % 8))) return DUA_ERR_ARG;
   const int epg = dtype == DUA_F16 ? 8 : 4;
+  if ((D | H | W) & 1) {            // floor pooling: blocks over ceil(S/2) per axis
+    const long total = (long)((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2) * (C / epg);
+    long b = (total + 255) / 256;
+    dim3 grid((unsigned)(b > 8192 ? 8192 : b), N);
+    if (dtype == DUA_F16)
+      hipLaunchKernelGGL((dua::maxpool2_bwd_add_kernel<dua::f16, true>), grid, dim3(256), 0, (hipStream_t)stream, (const dua::f16*)act,
+                         act_stride, act_off, (const dua::f16*)dA, da_stride, da_off, (const dua::f16*)dP, dp_stride,
+                         (dua::f16*)out, out_stride, C, D, H, W, total);
+    else if (dtype == DUA_F32)
+      hipLaunchKernelGGL((dua::maxpool2_bwd_add_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)act,
+                         act_stride, act_off, (const float*)dA, da_stride, da_off, (const float*)dP, dp_stride, (float*)out,
+                         out_stride, C, D, H, W, total);
+    else return DUA_ERR_ARG;
+    return (int)hipGetLastError();
+  }
   const long total = (long)(D / 2) * (H / 2) * (W / 2) * (C / epg);
   long b = (total + 255) / 256;
   dim3 grid((unsigned)(b > 8192 ? 8192 : b), N);

@@ -50,23 +50,34 @@ class EmbeddingList(list):
         return (self[i] for i in range(5))
 
 
+def level_geometry(D, H, W):
+    """Extents of the five levels of a (D, H, W) patch and the replicate pad of each decoder level.
+
+    nn.MaxPool3d(2) floors, so level l has extent S >> l per axis.  UpCat at level l (< 4) concatenates the skip (extent S_l)
+    with the transposed convolution of level l + 1 (extent 2 S_(l+1) = S_l - (S_l & 1)) and replicate-pads the latter by one
+    plane on every axis where it is short (denoiser.py:176-186).  Returns (S, pad): S[l] = (D_l, H_l, W_l) for l = 0..4,
+    pad[l] = per-axis 0 / 1 for l = 0..3.  Extents below 32 are refused: the bottom level must keep > 1 voxel per axis for
+    InstanceNorm3d."""
+    assert D >= 32 and H >= 32 and W >= 32, "InstanceNorm3d needs >1 voxel at the bottom level (SURVEY F7)"
+    S = [(D >> l, H >> l, W >> l) for l in range(5)]
+    pad = [tuple(e & 1 for e in S[l]) for l in range(4)]
+    return S, pad
+
+
 class Plan:
-    """Buffers + launch sequences for one (N, D, H, W, dtype)."""
+    """Buffers + launch sequences for one (N, D, H, W, dtype).  Any extent >= 32 (odd ones included: level_geometry)."""
 
     def __init__(self, net, N, D, H, W, dtype, device):
         f = tuple(net.features)
         assert len(f) == 6 and all(c % 8 == 0 for c in f), "feature sizes must be multiples of 8"
-        assert D % 16 == 0 and H % 16 == 0 and W % 16 == 0, \
-            "patch extents must be multiples of 16 (four 2x poolings; the reference recommends the same)"
-        assert D >= 32 and H >= 32 and W >= 32, "InstanceNorm3d needs >1 voxel at the bottom level (SURVEY F7)"
+        S, self.pad = level_geometry(D, H, W)
         self.net, self.N, self.dims, self.dtype, self.dev, self.f = net, N, (D, H, W), dtype, device, f
         nv.prepare(device)            # function attributes of every kernel: before the first launch and before any capture
         self.C = net.num_classes
         self.cx = ops.state_stride(self.C)
         self.cin0 = -(-(self.C + 1) // 8) * 8           # [x_t (C) | image | zero pad]
         self.up = (f[1], f[2] // 2, f[3] // 2, f[4] // 2)   # deconv output channels landing at level 0..3
-        S = [(D >> l, H >> l, W >> l) for l in range(5)]
-        self.S = S
+        self.S = S                # floor extents per level; a level with an odd extent gets its deconv half replicate-padded
         z = lambda l, c, dt=dtype: torch.zeros((N, *S[l], c), dtype=dt, device=device)  # noqa: E731
         # encoder
         # The encoder's first TwoConv (two 96^3 convolutions, ONCE per patch) runs on the exact-fp32 MFMA path also in an

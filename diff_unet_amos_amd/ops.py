@@ -596,8 +596,8 @@ def instnorm_bwd(dA, da_off, raw, Cc, norm, dY, dy_off=0, want_add=True, dadd_ou
 def maxpool2_bwd_add(act, act_off, Cc, dA, da_off, dP):
     """dA[..., da_off:da_off+Cc] (or zeros when dA is None) + MaxPool3d(2) backward of dP routed through ``act``."""
     _cl_check(act, "act"); _cl_check(dP, "dP")
-    N, D, H, W, _ = act.shape
-    assert tuple(dP.shape[:4]) == (N, D // 2, H // 2, W // 2) and dP.shape[-1] >= Cc and dP.dtype == act.dtype
+    N, D, H, W, _ = act.shape            # odd extents: floor pooling, the trailing plane gets dA only
+    assert min(D, H, W) >= 2 and tuple(dP.shape[:4]) == (N, D // 2, H // 2, W // 2) and dP.shape[-1] >= Cc and dP.dtype == act.dtype
     if dA is not None:
         _cl_check(dA, "dA")
         assert tuple(dA.shape[:4]) == (N, D, H, W) and dA.dtype == act.dtype
@@ -610,14 +610,19 @@ def maxpool2_bwd_add(act, act_off, Cc, dA, da_off, dP):
 
 def deconv_k2s2_bwd(x, cin, cin_off, dy, cout, cout_off, w, need_dx=True, need_dw=True):
     """Backward of deconv_k2s2: x [N,D,H,W,*] (slice cin@cin_off), dy [N,2D,2H,2W,*] (slice cout@cout_off, read in place),
-    w fp32 [Cin, Cout, 2,2,2].  Returns (dx [N,D,H,W,cin] or None, dw fp32 like w or None)."""
+    w fp32 [Cin, Cout, 2,2,2].  Returns (dx [N,D,H,W,cin] or None, dw fp32 like w or None).  dy may be one plane longer on any
+    axis (the replicate-padded forward, see deconv_k2s2): its padded planes' gradient is folded into the planes they copy."""
     _cl_check(x, "x"); _cl_check(dy, "dy")
     N, D, H, W, cs_in = x.shape
-    assert x.dtype == dy.dtype and tuple(dy.shape[:4]) == (N, 2 * D, 2 * H, 2 * W)
+    Do, Ho, Wo = dy.shape[1:4]
+    padded = (Do, Ho, Wo) != (2 * D, 2 * H, 2 * W)
+    assert x.dtype == dy.dtype and dy.shape[0] == N and Do - 2 * D in (0, 1) and Ho - 2 * H in (0, 1) and Wo - 2 * W in (0, 1)
     assert cin % 8 == 0 and cin_off % 8 == 0 and cin_off + cin <= cs_in
     assert cout % 8 == 0 and cout_off % 8 == 0 and cout_off + cout <= dy.shape[-1]
     assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (cin, cout, 2, 2, 2)
     L, code = nv.lib(), nv.dt_code(x.dtype)
+    run = ((lambda d, *a: L.dua_deconv_k2s2_pad_bwd(d, Do, Ho, Wo, *a)) if padded else       # noqa: E731
+           L.dua_deconv_k2s2_bwd)
     dx = dw = wp = ws = None
     ws_bytes = 0
     d_out = nv.Conv3Desc(code, N, D, H, W, cin, cin, 0, cout, dy.shape[-1], cout_off)      # dx is its own dense buffer
@@ -628,15 +633,15 @@ def deconv_k2s2_bwd(x, cin, cin_off, dy, cout, cout_off, w, need_dx=True, need_d
         if rc != nbytes:
             raise RuntimeError(f"dua_pack_deconv_weights_dgrad failed ({rc})")
         dx = torch.empty((N, D, H, W, cin), dtype=x.dtype, device=x.device)
-        nv.check(L.dua_deconv_k2s2_bwd(C.byref(d_out), None, nv.ptr(dy), nv.ptr(wp), nv.ptr(dx), None, None, 0,
-                                       nv.stream_ptr()), "dua_deconv_k2s2_bwd(dx)")
+        nv.check(run(C.byref(d_out), None, nv.ptr(dy), nv.ptr(wp), nv.ptr(dx), None, None, 0, nv.stream_ptr()),
+                 "dua_deconv_k2s2_bwd(dx)")
     if need_dw:
         d_in = nv.Conv3Desc(code, N, D, H, W, cin, cs_in, cin_off, cout, dy.shape[-1], cout_off)
         ws_bytes = int(L.dua_deconv_k2s2_bwd_workspace(C.byref(d_in)))
         ws = _wgrad_ws(ws_bytes, x.device)
         dw = zeros(tuple(w.shape), w.dtype, w.device)
-        nv.check(L.dua_deconv_k2s2_bwd(C.byref(d_in), nv.ptr(x), nv.ptr(dy), None, None, nv.ptr(dw), nv.ptr(ws), ws.numel(),
-                                       nv.stream_ptr()), "dua_deconv_k2s2_bwd(dw)")
+        nv.check(run(C.byref(d_in), nv.ptr(x), nv.ptr(dy), None, None, nv.ptr(dw), nv.ptr(ws), ws.numel(), nv.stream_ptr()),
+                 "dua_deconv_k2s2_bwd(dw)")
     return dx, dw
 
 
@@ -723,9 +728,9 @@ def materialize(raw, Cc, norm, out, out_off, emb=None, pooled=None, out_blocked=
         assert tuple(emb.shape[:4]) == (N, D, H, W) and emb.dtype == raw.dtype and emb.shape[-1] >= Cc
         es = emb.shape[-1]
     ps = 0
-    if pooled is not None:
+    if pooled is not None:                  # MaxPool3d(2): floor(S/2) per axis, odd extents included
         _cl_check(pooled, "pooled")
-        assert D % 2 == 0 and H % 2 == 0 and W % 2 == 0
+        assert min(D, H, W) >= 2
         assert tuple(pooled.shape[:4]) == (N, D // 2, H // 2, W // 2) and pooled.dtype == raw.dtype and pooled.shape[-1] >= Cc
         ps = pooled.shape[-1]
     d = nv.MaterializeDesc(nv.dt_code(raw.dtype), N, D, H, W, Cc, rs, es, out.shape[-1], out_off, ps, 1 if out_blocked else 0)
@@ -739,10 +744,14 @@ def materialize(raw, Cc, norm, out, out_off, emb=None, pooled=None, out_blocked=
 
 
 def deconv_k2s2(x, cin, cin_off, w_packed, bias_pad, cout, y, cout_off, norm=None, out_blocked=False):
-    """ConvTranspose3d(k2,s2) of a channel slice of ``x`` into a channel slice of ``y`` (2x spatial)."""
+    """ConvTranspose3d(k2,s2) of a channel slice of ``x`` into a channel slice of ``y`` (2x spatial).  ``y`` may be one plane
+    longer on any axis (the concat buffer of a level with an odd extent): that plane is the replicate pad of UpCat.forward
+    (denoiser.py:176-186), written by the same launch (dua_deconv_k2s2_pad_fwd, op DECONV_PAD)."""
     _cl_check(x, "x"); _cl_check(y, "y")
     N, D, H, W, cs_in = x.shape
-    assert x.dtype == y.dtype and tuple(y.shape[:4]) == (N, 2 * D, 2 * H, 2 * W)
+    Do, Ho, Wo = y.shape[1:4]
+    padded = (Do, Ho, Wo) != (2 * D, 2 * H, 2 * W)
+    assert x.dtype == y.dtype and y.shape[0] == N and Do - 2 * D in (0, 1) and Ho - 2 * H in (0, 1) and Wo - 2 * W in (0, 1)
     assert cin % 8 == 0 and cin_off % 8 == 0 and cin_off + cin <= cs_in
     assert cout % 8 == 0 and cout_off % 8 == 0 and cout_off + cout <= y.shape[-1]
     ck = chunk_elems(x.dtype)
@@ -753,8 +762,15 @@ def deconv_k2s2(x, cin, cin_off, w_packed, bias_pad, cout, y, cout_off, norm=Non
                      nv.OUT_BLOCKED if out_blocked else 0, 6 if (CONV_POLICY & 0xff) == 6 else 0)
     if _RECORD is not None:
         has, nval = _norm_value(norm, N, cin)
-        _RECORD.append(nv.StepOp(nv.OP_DECONV, has, d, nv.MaterializeDesc(), nval, _addr(x), _addr(w_packed), _addr(bias_pad),
+        kind, mat = nv.OP_DECONV, nv.MaterializeDesc()
+        if padded:                          # the op carries y's extents in its (otherwise unused) materialise descriptor
+            kind, mat.D, mat.H, mat.W = nv.OP_DECONV_PAD, Do, Ho, Wo
+        _RECORD.append(nv.StepOp(kind, has, d, mat, nval, _addr(x), _addr(w_packed), _addr(bias_pad),
                                  _addr(y), None, None, None))
+        return
+    if padded:
+        nv.check(nv.lib().dua_deconv_k2s2_pad_fwd(C.byref(d), Do, Ho, Wo, nv.ptr(x), nv.ptr(w_packed), nv.ptr(bias_pad),
+                                                  _norm_ref(norm, N, cin), nv.ptr(y), nv.stream_ptr()), "dua_deconv_k2s2_pad_fwd")
         return
     nv.check(nv.lib().dua_deconv_k2s2_fwd(C.byref(d), nv.ptr(x), nv.ptr(w_packed), nv.ptr(bias_pad), _norm_ref(norm, N, cin),
                                           nv.ptr(y), nv.stream_ptr()), "dua_deconv_k2s2_fwd")

@@ -212,7 +212,8 @@ int dua_deconv_k2s2_res_fwd(const dua_conv3_desc* d, const void* lo, const void*
 /* Backward of nn.MaxPool3d(2) (denoiser.py:100,106) fused with the sum of x_l's two gradient paths:
  *   out[v] = dA[v] (or 0 when dA is NULL) + (v is the arg-max of its 2x2x2 window ? dP[window] : 0),
  * arg-max recomputed from the stored activation (first maximum in d,h,w scan order, as torch).  D, H, W = the
- * un-pooled extent (even); act/dA are channel slices [off, off+C) of strided buffers, dP/out start at channel 0. */
+ * un-pooled extent (>= 2); an odd extent pools floor(S/2) windows (nn.MaxPool3d(2)), so its trailing plane receives dA only;
+ * dP is [N][D/2][H/2][W/2] (floor).  act/dA are channel slices [off, off+C) of strided buffers, dP/out start at channel 0. */
 int dua_maxpool2_bwd_add(int dtype, int N, int D, int H, int W, int C, const void* act, int act_stride, int act_off,
                          const void* dA, int da_stride, int da_off, const void* dP, int dp_stride, void* out,
                          int out_stride, void* stream);
@@ -228,6 +229,12 @@ long dua_pack_deconv_weights_dgrad(int dtype, int Cin, int Cout, const float* w,
 long dua_deconv_k2s2_bwd_workspace(const dua_conv3_desc* d);
 int dua_deconv_k2s2_bwd(const dua_conv3_desc* d, const void* x, const void* dy, const void* w_packed_dgrad, void* dx,
                         float* dw, void* workspace, long workspace_bytes, void* stream);
+/* The adjoint of dua_deconv_k2s2_pad_fwd (UpCat's replicate pad, models/basic_unet/denoiser.py:176-186, under train.py:258-268):
+ * dy has extents Do x Ho x Wo (each 2D or 2D + 1, as the forward's y); the gradient of every padded plane is added to the plane
+ * it copies while dy is read, for dx and dw alike.  Arguments otherwise as dua_deconv_k2s2_bwd (same workspace size); with
+ * Do, Ho, Wo = 2D, 2H, 2W it IS dua_deconv_k2s2_bwd.  The bias gradient stays the column sum of all of dy, copies included. */
+int dua_deconv_k2s2_pad_bwd(const dua_conv3_desc* d, int Do, int Ho, int Wo, const void* x, const void* dy,
+                            const void* w_packed_dgrad, void* dx, float* dw, void* workspace, long workspace_bytes, void* stream);
 
 /* final_conv (1x1x1, denoiser.py:282,311) for the training step, on a materialised activation u (channels-last
  * [voxels][u_stride], first C channels; C <= 64, multiple of 8) with W fp32 [K][C], b fp32 [K], K <= 16 classes:
@@ -380,7 +387,8 @@ typedef struct {
   int raw_stride;               /* channel stride of raw (offset 0) */
   int emb_stride;               /* channel stride of emb (offset 0), ignored when emb is NULL */
   int out_stride, out_off;
-  int pool_stride;              /* channel stride of pooled (offset 0); D,H,W must be even */
+  int pool_stride;              /* channel stride of pooled (offset 0); pooled is [N][D/2][H/2][W/2] (floor, as nn.MaxPool3d(2):
+                                   the trailing plane of an odd extent is written to out but not pooled); D, H, W >= 2 */
   int out_blocked;              /* 1 = `out` is stored in 16-channel blocks (dua_conv3_desc.layout; out_stride, out_off
                                    multiples of 16); raw, emb and pooled are always channels-last */
 } dua_materialize_desc;
@@ -394,6 +402,14 @@ int dua_materialize(const dua_materialize_desc* d, const void* raw, const dua_in
  * buffer (torch.cat at denoiser.py:190).  d->D/H/W are the INPUT extents; y has 2D x 2H x 2W. */
 int dua_deconv_k2s2_fwd(const dua_conv3_desc* d, const void* x, const void* w_packed, const float* bias_padded,
                         const dua_in_norm* in, void* y, void* stream);
+
+/* The same into the concat buffer of a level with odd extents: y has Do x Ho x Wo voxels, each 2D or 2D + 1 (the extent S of
+ * the skip tensor; the coarse level is floor(S/2)).  Where an extent is 2D + 1 the last computed plane is stored twice, to
+ * 2D - 1 and 2D: UpCat.forward's F.pad(x_0, ..., "replicate") (models/basic_unet/denoiser.py:176-186), in the same launch.
+ * Every kernel form of dua_deconv_k2s2_fwd (and dua_deconv_k2s2_kernel_kind, d->layout, d->policy) applies; with
+ * Do, Ho, Wo = 2D, 2H, 2W it IS dua_deconv_k2s2_fwd. */
+int dua_deconv_k2s2_pad_fwd(const dua_conv3_desc* d, int Do, int Ho, int Wo, const void* x, const void* w_packed,
+                            const float* bias_padded, const dua_in_norm* in, void* y, void* stream);
 
 /* ---- diffusion elementwise arithmetic (guided_diffusion/gaussian_diffusion.py) ----------------
  * Tensors are contiguous fp32 with the batch outermost (any layout inside a sample).
@@ -496,6 +512,7 @@ int dua_step_begin_clear(int N, int P, const float* table, int table_rows, const
 #define DUA_OP_MATERIALIZE 2  /* dua_materialize(mat, raw = x, norm, emb, out = y, pooled) */
 #define DUA_OP_DECONV 3       /* dua_deconv_k2s2_fwd(conv, x, w, bias, norm?, y) */
 #define DUA_OP_UPCONV 4       /* dua_upconv_k3_fwd(up, xskip = x, u, norm, w, wu, bias (= bias_table), y, stats) */
+#define DUA_OP_DECONV_PAD 5   /* dua_deconv_k2s2_pad_fwd(conv, mat.D, mat.H, mat.W (= y's extents), x, w, bias, norm?, y) */
 typedef struct {
   int kind;                /* DUA_OP_* */
   int has_norm;            /* norm below describes the producer of x (fused InstanceNorm + LeakyReLU + add) */
