@@ -205,6 +205,10 @@ _SIGS = {
     "dua_stats_channel_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dua_seg_loss_finish": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "dua_q_sample_affine": (C.c_int, [C.c_int, C.c_long, _P, C.c_float, C.c_float, _P, _P, C.c_int, _P, _P, _P]),
+    "dua_multi_neighbor_columns": (C.c_int, [C.c_int] * 7 + [_P, C.c_int, _P, _P, _P]),
+    "dua_multi_neighbor_angles": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
+    "dua_seg_loss_finish_mn": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P,
+                                         _P]),
     "dua_temb_train_fwd": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(TembBlocks), _P, _P, _P]),
     "dua_temb_train_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(TembBlocks), _P, _P, _P, _P, _P, _P, _P, _P]),
     "dua_grads_nonfinite": (C.c_int, [C.POINTER(AdamWList), _P, _P]),

@@ -2,7 +2,8 @@
 // normalisation pass.  Each kernel here replaces a chain of small torch / hipBLASLt launches that the captured step used to
 // replay one after the other at ~4.8 us apiece (172 of them, 1.5 ms of a 15.6 ms step):
 //   stats_channel_sums   bias gradient of a transposed convolution from the statistics words over its output gradient
-//   seg_loss_finish      losses/loss.py:64-86, the scalar tail (terms, combine, derivative of the combine)
+//   seg_loss_finish      losses/loss.py:64-86, the scalar tail (terms, combine, derivative of the combine); the _mn form also
+//                        folds in the multi_neighbor term (losses/loss.py:234-301) from csrc/multi_neighbor.hip's partials
 //   q_sample_affine      x_start = label * 2 - 1 (train.py:258) and q_sample (gaussian_diffusion.py:214-231) in one pass,
 //                        coefficients gathered by the device-resident timesteps
 //   temb_train_*         TimeStepEmbedder + swish + the nine temb_proj (utils.py:5-54, denoiser.py:51-52,65), forward and
@@ -41,10 +42,13 @@ __global__ __launch_bounds__(256) void stats_channel_sums_kernel(int N, int C, i
 }
 
 // ---- loss tail ------------------------------------------------------------------------------------------------------------
+// mn: the multi_neighbor partials of csrc/multi_neighbor.hip ([mn_N][mn_K + 1]: per-row sums of squared angle differences,
+// then the sample's entry count) or null; the term is their mean over all samples' entries together
 __global__ __launch_bounds__(64) void seg_loss_finish_kernel(int NC, double M, int use_mse, int use_bce, int use_dice, int combine,
-                                                             const double* __restrict__ sums, float* loss, float* dcomb) {
+                                                             const double* __restrict__ sums, float* loss, float* dcomb,
+                                                             const double* __restrict__ mn, int mn_N, int mn_K) {
   double d = 0.0;
-  for (int i = threadIdx.x; i < NC; i += 64) {
+  for (int i = threadIdx.x; use_dice && i < NC; i += 64) {
     const double* q = sums + 4L * i;
     d += 1.0 - (2.0 * q[0] + 1e-5) / (q[1] + q[2] + 1e-5);
   }
@@ -56,6 +60,16 @@ __global__ __launch_bounds__(64) void seg_loss_finish_kernel(int NC, double M, i
   if (use_mse) { total += sums[4L * NC] / M; ++count; }
   if (use_bce) { total += sums[4L * NC + 1] / M; ++count; }
   if (use_dice) { total += d / (double)NC; ++count; }
+  if (mn) {
+    double sq = 0.0, entries = 0.0;
+    for (int n = 0; n < mn_N; ++n) {
+      const double* r = mn + (long)n * (mn_K + 1);
+      for (int a = 0; a < mn_K; ++a) sq += r[a];
+      entries += r[mn_K];
+    }
+    total += sq / entries;
+    ++count;
+  }
   double L = total, dc = 1.0;
   if (count > 1 && combine == 1) { L = total / count; dc = 1.0 / count; }
   else if (count > 1 && combine == 2) { L = log(1.0 + total); dc = 1.0 / (1.0 + total); }
@@ -474,7 +488,18 @@ int dua_seg_loss_finish(int N, int C, long voxels, int use_mse, int use_bce, int
       !(use_mse || use_bce || use_dice))
     return DUA_ERR_ARG;
   hipLaunchKernelGGL(dua::seg_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, N * C,
-                     (double)N * (double)C * (double)voxels, use_mse, use_bce, use_dice, combine, sums, loss, dcomb);
+                     (double)N * (double)C * (double)voxels, use_mse, use_bce, use_dice, combine, sums, loss, dcomb, nullptr, 0, 0);
+  return (int)hipGetLastError();
+}
+
+int dua_seg_loss_finish_mn(int N, int C, long voxels, int use_mse, int use_bce, int use_dice, int K, const double* mn_partials,
+                           int combine, const double* sums, float* loss, float* dcomb, void* stream) {
+  if (N <= 0 || C <= 0 || voxels <= 0 || !loss || !dcomb || combine < 0 || combine > 2 || !mn_partials || K <= 0 ||
+      ((use_mse || use_bce || use_dice) && !sums))
+    return DUA_ERR_ARG;
+  hipLaunchKernelGGL(dua::seg_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, N * C,
+                     (double)N * (double)C * (double)voxels, use_mse, use_bce, use_dice, combine, sums, loss, dcomb,
+                     mn_partials, N, K);
   return (int)hipGetLastError();
 }
 

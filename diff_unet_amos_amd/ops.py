@@ -685,7 +685,8 @@ LOSS_NAMES = ("mse", "bce", "dice")
 
 def seg_loss_reduce(logits, labels, names=LOSS_NAMES, combine="sum"):
     """logits: channels-last [N, D, H, W, Cs] (first C = labels.shape[1] channels); labels fp32 [N, C, D, H, W].
-    Loss of losses/loss.py:25-86 for ``names`` (a subset of mse / bce / dice) combined by "sum" / "mean" / "log".
+    Loss of losses/loss.py:25-86 for ``names`` (a subset of SEG_LOSS_NAMES: mse / bce / dice / multi_neighbor, the last
+    with K = C classes) combined by "sum" / "mean" / "log".
     Returns (L as a 0-dim fp32 tensor, the fp64 sums the gradient kernel needs, d L / d (sum of terms) as a 0-dim fp32
     device tensor -- 1 for "sum", 1/len(names) for "mean", 1/(1 + sum) for "log")."""
     assert logits.is_cuda and logits.is_contiguous() and logits.dim() == 5
@@ -693,15 +694,53 @@ def seg_loss_reduce(logits, labels, names=LOSS_NAMES, combine="sum"):
     V = labels.shape[2] * labels.shape[3] * labels.shape[4]
     assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
     assert tuple(logits.shape[:4]) == (N, *labels.shape[2:]) and logits.shape[-1] >= Cc
-    assert names and all(n_ in LOSS_NAMES for n_ in names) and combine in ("sum", "mean", "log")
+    assert names and all(n_ in SEG_LOSS_NAMES for n_ in names) and combine in ("sum", "mean", "log")
     sums = zeros((N * Cc * 4 + 2,), torch.float64, logits.device)
     nv.check(nv.lib().dua_seg_loss_reduce(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1], nv.ptr(labels),
                                           nv.ptr(sums), nv.stream_ptr()), "dua_seg_loss_reduce")
     out = torch.empty(2, dtype=torch.float32, device=logits.device)             # (L, d L / d total)
-    nv.check(nv.lib().dua_seg_loss_finish(N, Cc, V, int("mse" in names), int("bce" in names), int("dice" in names),
-                                          ("sum", "mean", "log").index(combine), nv.ptr(sums), nv.ptr(out[0:]), nv.ptr(out[1:]),
-                                          nv.stream_ptr()), "dua_seg_loss_finish")
-    return out[0], sums, out[1]
+    return out[0], sums, seg_loss_finish(N, Cc, V, names, combine, sums, out,
+                                         multi_neighbor_partials(logits, labels) if "multi_neighbor" in names else None)
+
+
+# every name seg_loss_reduce accepts: LOSS_NAMES (the terms with a gradient, in seg_loss_grad's weight order) and
+# "multi_neighbor" (losses/loss.py:234-301: no gradient, it adds to the value and to the combine's count / total)
+SEG_LOSS_NAMES = LOSS_NAMES + ("multi_neighbor",)
+
+
+def seg_loss_finish(N, Cc, V, names, combine, sums, out, mn=None):
+    """The loss tail (losses/loss.py:64-86) into ``out`` = fp32 (L, d L / d total); ``mn``: multi_neighbor_partials(...) to
+    count the multi_neighbor term among the terms, or None.  Returns out[1], d L / d total (0-dim)."""
+    use = [int(n_ in names) for n_ in LOSS_NAMES]
+    if mn is None:
+        nv.check(nv.lib().dua_seg_loss_finish(N, Cc, V, *use, ("sum", "mean", "log").index(combine), nv.ptr(sums),
+                                              nv.ptr(out[0:]), nv.ptr(out[1:]), nv.stream_ptr()), "dua_seg_loss_finish")
+    else:
+        nv.check(nv.lib().dua_seg_loss_finish_mn(N, Cc, V, *use, mn.shape[1] - 1, nv.ptr(mn), ("sum", "mean", "log").index(combine),
+                                                 nv.ptr(sums), nv.ptr(out[0:]), nv.ptr(out[1:]), nv.stream_ptr()),
+                 "dua_seg_loss_finish_mn")
+    return out[1]
+
+
+def multi_neighbor_partials(logits, labels, num_classes=None):
+    """losses/loss.py:234-301 (MultiNeighborLoss) on the device, up to its final mean: logits channels-last [N, D, H, W, Cs]
+    (fp16 / fp32, first C = labels.shape[1] channels), labels fp32 [N, C, D, H, W], ``num_classes`` K (default C, <= 64).
+    Returns fp64 [N, K + 1]: per sample the sums of squared angle differences of rows a < K, then its entry count; the term is
+    partials[:, :K].sum() / partials[:, K].sum() (what seg_loss_finish folds in).  Scratch comes from ``zeros`` (the trainer's
+    arena); no host read, so it can be captured."""
+    assert logits.is_cuda and logits.is_contiguous() and logits.dim() == 5
+    assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 5
+    N, Cc, D, H, W = labels.shape
+    assert tuple(logits.shape[:4]) == (N, D, H, W) and logits.shape[-1] >= Cc
+    K = Cc if num_classes is None else int(num_classes)
+    assert 0 < K <= 64, "multi_neighbor: 1..64 classes"
+    csums = zeros((N, 2, K, 4), torch.int64, logits.device)
+    partials = zeros((N, K + 1), torch.float64, logits.device)
+    nv.check(nv.lib().dua_multi_neighbor_columns(nv.dt_code(logits.dtype), N, Cc, K, D, H, W, nv.ptr(logits), logits.shape[-1],
+                                                 nv.ptr(labels), nv.ptr(csums), nv.stream_ptr()), "dua_multi_neighbor_columns")
+    nv.check(nv.lib().dua_multi_neighbor_angles(N, K, nv.ptr(csums), nv.ptr(partials), nv.stream_ptr()),
+             "dua_multi_neighbor_angles")
+    return partials
 
 
 def seg_loss_grad(logits, labels, sums, gscale, names=LOSS_NAMES):

@@ -68,11 +68,12 @@ class _TembAdds(torch.autograd.Function):
 
 
 def parse_losses(losses="mse,bce,dice", loss_combine="sum"):
-    """losses/loss.py:25-62: comma-separated loss names and the combine rule; the names the HIP loss kernels cover."""
+    """losses/loss.py:25-62: comma-separated loss names and the combine rule; the names the HIP loss kernels cover
+    (ops.SEG_LOSS_NAMES: mse, bce, dice and multi_neighbor, in any order -- cfg/amos/train.yaml's set is all four)."""
     names = tuple(losses.split(","))
-    from .ops import LOSS_NAMES
+    from .ops import SEG_LOSS_NAMES
     for n in names:
-        if n not in LOSS_NAMES:
+        if n not in SEG_LOSS_NAMES:
             raise NotImplementedError(f"Loss ({n}) is not listed yet")
     if loss_combine not in ("sum", "mean", "log"):
         raise NotImplementedError("Unsupported value for loss_combine. Please choose from 'sum', 'mean', or 'log'.")
@@ -430,8 +431,10 @@ class _Head(torch.autograd.Function):
 
 
 class _SegLoss(torch.autograd.Function):
-    """losses/loss.py:25-86 for any subset of mse / bce / dice under "sum" / "mean" / "log" on channels-last logits: one
-    reduce pass forward, one gradient pass backward."""
+    """losses/loss.py:25-86 for any subset of mse / bce / dice / multi_neighbor under "sum" / "mean" / "log" on channels-last
+    logits: one reduce pass forward (plus the two multi_neighbor launches when that name is in use), one gradient pass
+    backward.  multi_neighbor has no gradient (its argmax cuts the graph): it reaches the backward only through dcomb, the
+    derivative of the combine (1/count under "mean", 1/(1 + total) under "log")."""
 
     @staticmethod
     def forward(ctx, logits, labels, names=("mse", "bce", "dice"), combine="sum"):
@@ -661,6 +664,10 @@ class NativeConvTrainer:
             dev = next(net.parameters()).device
             self.module = DistributedDataParallel(self.module, device_ids=[dev.index], bucket_cap_mb=32)
         self.loss_names, self.loss_combine = parse_losses(losses, loss_combine)
+        if all(n == "multi_neighbor" for n in self.loss_names):
+            # the reference builds this criterion and fails at backward(): its loss tensor has no grad_fn
+            raise ValueError("losses='multi_neighbor' alone has no gradient (its argmax cuts the graph): nothing to train; "
+                             "combine it with mse / bce / dice")
         self.params = [p for p in net.parameters() if p.requires_grad]
         # graph mode always uses the library's AdamW; ``fused_optimizer=False`` selects torch.optim.AdamW for eager steps
         self.native_opt = bool(fused_optimizer or graph)

@@ -284,6 +284,26 @@ int dua_seg_loss_finish(int N, int C, long voxels, int use_mse, int use_bce, int
 int dua_q_sample_affine(int N, long per_sample, const float* src, float a, float b, const float* eps, const float* sched, int T,
                         const long long* t, float* out, void* stream);
 
+/* The "multi_neighbor" loss term (losses/loss.py:234-301, MultiNeighborLoss with reduction "mean", combined by Loss.__call__ at
+ * :64-86).  Per sample, labels[n] and sigmoid(logits[n]) ([C][D][H][W] each) are reduced by argmax over DEPTH (the reference's
+ * dim=1, reproduced as it is: t[c][h][w] is a depth index, first maximum wins, NaN counts as the maximum); class k < K's centroid is
+ * the mean (c, h, w) over t == k; the classes that occur in the label map are kept in class order, and the squared difference of
+ * the pairwise angles acos(clamp(n_ab . n_ae)), b < e, of the two sides' normalised centroid differences n_ab is averaged over all
+ * samples' entries (a sample with fewer than two classes contributes one entry 0).  No gradient: it adds to the loss value and
+ * to the combine's count / total only.  Deterministic (integer atomics only); graph-capturable (no host read).
+ * dua_multi_neighbor_columns: csums (u64 [N][2][K][4], pre-zeroed) += per (sample, side 0 labels / 1 prediction, class)
+ *   (sum c, sum h, sum w, count) of the argmax columns.  logits: channels-last [N][D][H][W][logits_stride] (first C used),
+ *   fp16 or fp32; labels: fp32 NCDHW [N][C][D][H][W]; K <= 64 classes.
+ * dua_multi_neighbor_angles: partials (fp64 [N][K + 1], WRITTEN) = per (sample, row a) the sum over b < e of the squared angle
+ *   differences, then the sample's entry count.
+ * dua_seg_loss_finish_mn: dua_seg_loss_finish with the multi_neighbor term (sum of partials rows / sum of entry counts) counted
+ *   as one more term of the combine; sums may be NULL when no use_* is set. */
+int dua_multi_neighbor_columns(int dtype, int N, int C, int K, int D, int H, int W, const void* logits, int logits_stride,
+                               const float* labels, unsigned long long* csums, void* stream);
+int dua_multi_neighbor_angles(int N, int K, const unsigned long long* csums, double* partials, void* stream);
+int dua_seg_loss_finish_mn(int N, int C, long voxels, int use_mse, int use_bce, int use_dice, int K, const double* mn_partials,
+                           int combine, const double* sums, float* loss, float* dcomb, void* stream);
+
 /* Timestep embedding under training (models/diffusion/utils.py:5-54, denoiser.py:51-52,65): for sample n
  *   e = [sin | cos](t[n] * freqs), z1 = W0 e + b0, h1 = swish(z1), z2 = W1 h1 + b1, s = swish(z2), add_b = Wp_b s + bp_b
  * for every TwoConv block b (its temb_proj).  ``add`` / ``dadd`` are BLOCK-MAJOR: block b's [N][cout_b] rows are contiguous
