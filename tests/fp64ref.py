@@ -1,0 +1,357 @@
+"""fp64 references of the denoiser's forward kernels at sampled output voxels, and per-element error bounds.
+
+A plain helper module of the suite (imported as ``from fp64ref import ...``).  The references are evaluated on the EXACT
+operands a kernel read: activations gathered from its input buffer, weights rounded to fp16 the way the packer rounds them (or
+decoded from the packed buffer), a fused input transform emulated in the kernel's own arithmetic.  The only legitimate
+differences left are then the kernel's fp32 accumulation and the rounding of what it stores, which ``bound`` turns into a
+per-element limit derived from the arithmetic (not calibrated on measurements):
+
+    |got - ref| <= 2^-24 * n_chain * sum_k |a_k w_k|          fp32 accumulation
+                 + u_out * |ref| + floor_out                     rounding of the stored value
+                 + c_rss * u_in * sqrt(sum_k (a_k w_k)^2)       1-ulp differences of emulated inputs (fused transforms only)
+                 + extra                                        terms a caller derives for its own operand (bias table, tail split)
+
+* Accumulation: a sum formed as a chain of n fp32 additions (each operand exact: fp16 x fp16 products fit fp32) is off by at
+  most (n - 1) 2^-24 sum |terms| (recursive summation, first order).  An MFMA adds k products into its accumulator per step
+  (k = 16 / 32 for fp16): n_chain = ceil(K / k) + log2(k) for the adds inside the instruction, + 1 for the bias, + the number
+  of split-K partials that a finish kernel adds up.  The fp32 kernels chain one fmaf per product: n_chain = K + 1.
+* Output: round-to-nearest into fp16 moves a value by at most 2^-11 of itself (2^-24 for fp32) above the normal range, and by
+  half the smallest subnormal (2^-25 / 2^-150) below it.
+* Emulated inputs: the emulation rounds the transform once from float64 where the kernel rounds fp32 intermediates (a fused
+  multiply-add contracted or not): once in a while an input lands one fp16 ulp (2 * 2^-11
+  relative) away.  If every input did so with random signs the sum would move by 2^-10 sqrt(sum (a w)^2); c_rss = 2 at
+  u_in = 2^-11 covers that, far more than the rare flips need.  fp32 plans: the same form with u_in = 2^-24.
+
+``check(got, ref, bound)`` reports max(|err| / bound) and the worst element.
+"""
+from __future__ import annotations
+
+import itertools
+import math
+
+import numpy as np
+import torch
+
+U16, U32 = 2.0 ** -11, 2.0 ** -24            # unit roundoff (half an ulp, relative)
+FLOOR16, FLOOR32 = 2.0 ** -25, 2.0 ** -150   # half the smallest subnormal
+C_RSS = 2.0
+SLOPE = 0.1
+
+
+def unit(dtype):
+    return (U16, FLOOR16) if dtype == torch.float16 else (U32, FLOOR32)
+
+
+def chain_length(K, dtype, split_parts=0):
+    """Longest fp32 accumulation chain of a K-term contraction (module docstring)."""
+    if dtype == torch.float16:
+        return -(-K // 16) + 4 + 1 + split_parts
+    return K + 1 + split_parts
+
+
+def bound(ref, abs_sum, sq_sum, n_chain, dtype_out, emulated_in=None, extra=0.0):
+    """Per-element bound (float64, the shape of ``ref``); ``emulated_in``: dtype of emulated inputs or None."""
+    u_out, floor = unit(dtype_out)
+    b = U32 * n_chain * abs_sum * (1 + u_out) + u_out * ref.abs() + floor
+    if emulated_in is not None:
+        b = b + C_RSS * unit(emulated_in)[0] * sq_sum.sqrt()
+    return b + extra
+
+
+class CheckResult:
+    def __init__(self, ratio, where, got, ref, bnd):
+        self.ratio, self.where, self.got, self.ref, self.bound = ratio, where, got, ref, bnd
+
+    def __repr__(self):
+        return (f"max |err|/bound = {self.ratio:.3g} at {self.where}: got {self.got:.6g}, ref {self.ref:.6g}, "
+                f"bound {self.bound:.3g}")
+
+
+def check(got, ref, bnd, coords=None):
+    """max(|got - ref| / bound) and the worst element (index tuple, or ``coords[row]`` + column for 2-D results).  A non-finite
+    value counts as infinitely far off."""
+    got, ref, bnd = got.double(), ref.double(), bnd.double()
+    err = (got - ref).abs()
+    r = err / bnd
+    r = torch.where(torch.isfinite(r), r, torch.full_like(r, math.inf))
+    k = int(torch.argmax(r))
+    idx = tuple(int(i) for i in np.unravel_index(k, tuple(r.shape)))
+    where = idx if coords is None else (tuple(int(v) for v in coords[idx[0]]), *idx[1:])
+    return CheckResult(float(r.view(-1)[k]), where, float(got.view(-1)[k]), float(ref.view(-1)[k]), float(bnd.view(-1)[k]))
+
+
+# ---- which voxels ------------------------------------------------------------------------------------------------------------
+def _boundary_coords(S):
+    """Coordinates of one axis on 8-voxel tile edges (0, 7 mod 8) and 4-plane slab edges (3, 4 mod 8), plus the last plane."""
+    return sorted({c for c in range(S) if c % 8 in (0, 3, 4, 7)} | {S - 1})
+
+
+def sample_voxels(N, dims, n_random=2000, seed=0):
+    """int64 [P, 4] (n, d, h, w), unique and sorted: the 8 corners, points on every face and edge, a lattice through tile and
+    slab boundaries (every combination near both ends of every axis, a seeded subset of the interior), ~n_random seeded random
+    voxels; every sample index gets the structured points, the random ones are spread over the samples."""
+    g = np.random.default_rng(seed)
+    D, H, W = dims
+    axes = [_boundary_coords(S) for S in dims]
+    ends = [[c for c in a if c < 9 or c >= S - 9] for a, S in zip(axes, dims)]
+    pts = set()
+    for n in range(N):
+        for corner in itertools.product(*[(0, S - 1) for S in dims]):
+            pts.add((n, *corner))
+        # edges: two coordinates at an end, the third along the axis; faces: one at an end, two along it
+        for ax in range(3):
+            others = [a for a in range(3) if a != ax]
+            for e0, e1 in itertools.product((0, 1), repeat=2):
+                for c in g.choice(axes[ax], size=min(6, len(axes[ax])), replace=False):
+                    p = [0, 0, 0]
+                    p[ax] = int(c)
+                    p[others[0]] = 0 if e0 == 0 else dims[others[0]] - 1
+                    p[others[1]] = 0 if e1 == 0 else dims[others[1]] - 1
+                    pts.add((n, *p))
+            for end in (0, dims[ax] - 1):
+                for _ in range(12):
+                    p = [0, 0, 0]
+                    p[ax] = end
+                    for o in others:
+                        p[o] = int(g.choice(axes[o]))
+                    pts.add((n, *p))
+        for p in itertools.product(*ends):
+            pts.add((n, *p))
+        for _ in range(600):
+            pts.add((n, *(int(g.choice(a)) for a in axes)))
+    for _ in range(n_random):
+        pts.add((int(g.integers(N)), int(g.integers(D)), int(g.integers(H)), int(g.integers(W))))
+    return torch.tensor(sorted(pts), dtype=torch.int64)
+
+
+TAPS = torch.tensor(list(itertools.product((-1, 0, 1), repeat=3)), dtype=torch.int64)     # tap t = (kd * 3 + kh) * 3 + kw
+
+
+def gather_taps(x, pts, c_off, cin):
+    """x: channels-last [N, D, H, W, Cs] (any device, channels-last rows); pts [P, 4] -> float64 CPU [P, 27, cin] of the 3x3x3
+    neighbourhoods with zero padding, plus the in-volume mask [P, 27].  Gathered on x's device, only the samples move."""
+    N, D, H, W, _ = x.shape
+    p = pts.to(x.device)
+    c = p[:, None, 1:] + TAPS.to(x.device)[None]
+    ok = ((c >= 0) & (c < torch.tensor([D, H, W], device=x.device))).all(-1)
+    cc = torch.where(ok[..., None], c, torch.zeros_like(c))
+    v = x[p[:, None, 0].expand_as(ok), cc[..., 0], cc[..., 1], cc[..., 2], c_off:c_off + cin]
+    v = torch.where(ok[..., None], v, torch.zeros_like(v))
+    return v.cpu().double(), ok.cpu()
+
+
+def gather_points(x, pts, c_off, cin):
+    """channels-last x at pts -> float64 CPU [P, cin]"""
+    p = pts.to(x.device)
+    return x[p[:, 0], p[:, 1], p[:, 2], p[:, 3], c_off:c_off + cin].cpu().double()
+
+
+# ---- the fused input transform, in the kernel's arithmetic ------------------------------------------------------------------
+def finalize(sums, gamma, beta, count, eps=1e-5):
+    """InstanceNorm scale = gamma / sqrt(var + eps), shift = beta - mean * scale in float64 from the decoded statistics words
+    (float64 [N, c_pad, 2]), [N, C] each, and the per-element bounds on how far the consumers' fp32 preamble may land from
+    them: 1 / sqrt(var + eps) rounded to fp32, the gamma product (scale: 2 roundings, with double-precision error far below);
+    the mean rounded to fp32, its product with the fp32 scale, the subtraction from beta (shift: the product's and the scale's
+    roundings carry |mean * scale|, the subtraction |shift|).  The transforms are then emulated on the kernel's own fp32
+    constants (ops.instnorm_finalize), which these bounds hold to fp64."""
+    C = gamma.numel()
+    S, Q = sums[:, :C, 0].double(), sums[:, :C, 1].double()
+    mean = S / count
+    var = (Q / count - mean * mean).clamp_min(0)
+    sc = gamma.double()[None] / torch.sqrt(var + float(np.float32(eps)))
+    sh = beta.double()[None] - mean * sc
+    b_sc = 3 * U32 * sc.abs() + 1e-300
+    b_sh = U32 * (6 * (mean * sc).abs() + sh.abs()) + 1e-300
+    return sc, sh, b_sc, b_sh
+
+
+def _f16_rne(v):
+    """float64 -> fp16 with one round-to-nearest-even (numpy converts directly; torch goes through fp32)."""
+    return torch.from_numpy(v.numpy().astype(np.float16).astype(np.float64))
+
+
+def transform(raw, sc, sh, add, dtype, slope=SLOPE):
+    """LeakyReLU(raw * sc + sh) + add for raw float64 [..., C] (exact values of the stored operands) with per-channel fp32 sc,
+    sh, add broadcast to it.  fp16: max(fp16(raw * sc + (sh + add)), fp16(raw * (slope sc) + fma(slope, sh, add))) -- the
+    kernels' two mixed-precision fma and a max (csrc/common.hpp xform_frag_mix); fp32: fmaf, the slope, the add, in fp32.
+    Returns float64 values of the kernel's operand type."""
+    sc, sh, add = sc.double(), sh.double(), add.double()
+    if dtype == torch.float16:
+        b = (sh + add).float().double()
+        sn = (np.float32(slope) * sc.float()).double()
+        an = (np.float32(slope) * sh + add).float().double()
+        return torch.maximum(_f16_rne(raw * sc + b), _f16_rne(raw * sn + an))
+    y = (raw * sc + sh).float()
+    y = torch.where(y > 0, y, y * np.float32(slope))
+    return (y + add.float()).double()
+
+
+def tail_transform(raw, sc, sh, slope=SLOPE):
+    """The 1x1x1 head's input: LeakyReLU(fmaf(raw, sc, sh)) in fp32, not rounded further (csrc/sampler.hip)."""
+    y = (raw * sc.double() + sh.double()).float()
+    return torch.where(y > 0, y, y * np.float32(slope)).double()
+
+
+# ---- references ----------------------------------------------------------------------------------------------------------
+def contract(A, Wm):
+    """A [P, K], Wm [K, O] (float64) -> (sum a w, sum |a w|, sum (a w)^2), each [P, O]."""
+    return A @ Wm, A.abs() @ Wm.abs(), (A * A) @ (Wm * Wm)
+
+
+def conv3_weights(w, dtype):
+    """nn.Conv3d weight [Cout, Cin, 3, 3, 3] -> float64 [27 * Cin, Cout] in gather_taps order, rounded as the packer rounds."""
+    wq = w.detach().float().cpu()
+    if dtype == torch.float16:
+        wq = wq.half()
+    Cout, Cin = w.shape[:2]
+    return wq.double().reshape(Cout, Cin, 27).permute(2, 1, 0).reshape(27 * Cin, Cout)
+
+
+def conv3_ref(A, Wm, bias):
+    """A [P, 27, Cin] (the activation the kernel multiplies: zero outside the volume) -> (ref, abs_sum, sq_sum) [P, Cout];
+    the bias counts as one more term of the chain."""
+    ref, ab, sq = contract(A.reshape(A.shape[0], -1), Wm)
+    b = bias.detach().double().cpu()[None]
+    return ref + b, ab + b.abs(), sq
+
+
+def deconv_ref(A, w, bias, dtype, child):
+    """ConvTranspose3d(k2, s2) at sampled output voxels: A [P, Cin] = the activation at each voxel's parent, ``child`` [P] =
+    (d & 1) * 4 + (h & 1) * 2 + (w & 1); w [Cin, Cout, 2, 2, 2]."""
+    wq = w.detach().float().cpu()
+    if dtype == torch.float16:
+        wq = wq.half()
+    Wc = wq.double().reshape(w.shape[0], w.shape[1], 8)[:, :, child].permute(2, 0, 1)       # [P, Cin, Cout]
+    ref = torch.einsum("pc,pco->po", A, Wc)
+    ab = torch.einsum("pc,pco->po", A.abs(), Wc.abs())
+    sq = torch.einsum("pc,pco->po", A * A, Wc * Wc)
+    b = bias.detach().double().cpu()[None]
+    return ref + b, ab + b.abs(), sq
+
+
+def replicate_source(pts, coarse_dims):
+    """Output voxels of a transposed convolution whose buffer is one plane longer on an odd axis: the replicate-padded plane
+    2 * S copies plane 2 * S - 1 (UpCat.forward's pad).  Returns the voxel the value is computed at."""
+    lim = torch.tensor([2 * s - 1 for s in coarse_dims], dtype=torch.int64)
+    q = pts.clone()
+    q[:, 1:] = torch.minimum(q[:, 1:], lim)
+    return q
+
+
+def border_class(pts, dims):
+    """(cd * 3 + ch) * 3 + cw per voxel: 0 on the low face of an axis, 2 on the high face, 1 inside (the fold's bias table)."""
+    cls = torch.zeros(pts.shape[0], dtype=torch.int64)
+    for a, S in enumerate(dims):
+        c = pts[:, 1 + a]
+        k = torch.where(c == 0, 0, torch.where(c == S - 1, 2, 1))
+        cls = cls * 3 + k
+    return cls
+
+
+def fold_bias_table(wc_up, bc, bd):
+    """[27, Cout] float64 bias per border class of the folded up-convolution and the matching sum of |terms|: bc + the
+    transposed convolution's bias through every conv tap that stays inside the volume (csrc/upconv.hip)."""
+    wc_up = wc_up.detach().double().cpu()
+    Cout = wc_up.shape[0]
+    bcd = torch.zeros(Cout, dtype=torch.float64) if bc is None else bc.detach().double().cpu()
+    bdd = torch.zeros(wc_up.shape[1], dtype=torch.float64) if bd is None else bd.detach().double().cpu()
+    rows, arows = [], []
+    for cd, ch, cw in itertools.product(range(3), repeat=3):
+        v, a = bcd.clone(), bcd.abs()
+        for kd, kh, kw in itertools.product(range(3), repeat=3):
+            if any((c == 0 and k == 0) or (c == 2 and k == 2) for c, k in ((cd, kd), (ch, kh), (cw, kw))):
+                continue
+            v = v + wc_up[:, :, kd, kh, kw] @ bdd
+            a = a + wc_up[:, :, kd, kh, kw].abs() @ bdd.abs()
+        rows.append(v)
+        arows.append(a)
+    return torch.stack(rows), torch.stack(arows)
+
+
+def _taps_1d(phi, delta):
+    """(conv tap k, deconv child a) pairs of one axis whose input voxel o + k - 1 (o = 2 m + phi) is child a of parent
+    m + delta - 1 + phi"""
+    return {(0, 0): [(0, 1)], (0, 1): [(1, 0), (2, 1)], (1, 0): [(0, 0), (1, 1)], (1, 1): [(2, 0)]}[(phi, delta)]
+
+
+def compose_fold(wc_up, wd):
+    """W'[(phi, delta)] = sum over taps Wc_up[tap] Wd[child]^T, float64 [Cout, Cu], and the matching sum of |products|."""
+    wc_up, wd = wc_up.detach().double().cpu(), wd.detach().double().cpu()
+    out = {}
+    for phi in itertools.product(range(2), repeat=3):
+        for delta in itertools.product(range(2), repeat=3):
+            acc = abs_acc = 0
+            for (kd, ad), (kh, ah), (kw, aw) in itertools.product(*(_taps_1d(p, d) for p, d in zip(phi, delta))):
+                acc = acc + wc_up[:, :, kd, kh, kw] @ wd[:, :, ad, ah, aw].t()
+                abs_acc = abs_acc + wc_up[:, :, kd, kh, kw].abs() @ wd[:, :, ad, ah, aw].abs().t()
+            out[phi + delta] = (acc, abs_acc)
+    return out
+
+
+def decode_fold_weights(wu, Cout, Cu):
+    """The packed composed weights (dua_pack_upconv_weights, streaming order
+    [cout tile][pd][ph][g][dd][dh][hcl][pw][dw][q][hh][r][e]) -> {(pd, ph, pw, dd, dh, dw): float64 [Cout, Cu]}."""
+    nct, G = -(-Cout // 64), Cu // 64
+    t = wu.view(torch.float16).view(nct, 2, 2, G, 2, 2, 4, 2, 2, 2, 2, 32, 8).cpu().double()
+    out = {}
+    for pd, ph, pw, dd, dh, dw in itertools.product(range(2), repeat=6):
+        m = t[:, pd, ph, :, dd, dh, :, pw, dw]                       # [ct][g][hcl][q][hh][r][e]
+        m = m.permute(0, 3, 5, 1, 2, 4, 6).reshape(nct * 64, Cu)      # [ct q r] x [g hcl hh e]
+        out[(pd, ph, pw, dd, dh, dw)] = m[:Cout]
+    return out
+
+
+def fold_parents(pts, dims):
+    """Per output voxel o = 2 m + phi and each delta in {0,1}^3: its coarse parent m + delta - 1 + phi (int64 [P, 8, 3]), the
+    in-volume mask [P, 8] and the parity phi [P, 3]."""
+    phi = pts[:, 1:] & 1
+    m = pts[:, 1:] >> 1
+    deltas = torch.tensor(list(itertools.product((0, 1), repeat=3)), dtype=torch.int64)
+    par = m[:, None] + deltas[None] - 1 + phi[:, None]
+    lim = torch.tensor([S // 2 for S in dims], dtype=torch.int64)
+    ok = ((par >= 0) & (par < lim)).all(-1)
+    return par, ok, phi, deltas
+
+
+def fold_ref(A_skip, Wm_skip, U, ok, phi, deltas, Wp, bias_rows, bias_abs):
+    """The folded up-convolution: skip half as a 3x3x3 convolution (A_skip [P, 27, Cskip], Wm_skip [27 Cskip, Cout]) + the
+    composed weights over the 8 parents (U [P, 8, Cu] activations of the parents, zero outside; Wp from decode_fold_weights)
+    + the border-class bias (bias_rows / bias_abs [P, Cout])."""
+    ref, ab, sq = contract(A_skip.reshape(A_skip.shape[0], -1), Wm_skip)
+    keys = [tuple(p) for p in phi.tolist()]
+    for j, dl in enumerate(deltas.tolist()):
+        Wj = torch.stack([Wp[k + tuple(dl)] for k in keys])                # [P, Cout, Cu]
+        Uj = torch.where(ok[:, j, None], U[:, j], torch.zeros_like(U[:, j]))
+        ref = ref + torch.einsum("pc,poc->po", Uj, Wj)
+        ab = ab + torch.einsum("pc,poc->po", Uj.abs(), Wj.abs())
+        sq = sq + torch.einsum("pc,poc->po", Uj * Uj, Wj * Wj)
+    return ref + bias_rows, ab + bias_abs, sq
+
+
+def materialize_ref(raw, sc, sh, add, emb):
+    """LeakyReLU(raw sc + sh) + add (+ emb) in float64 from the fp32 constants, and the sum of |terms| of its four fp32
+    operations (fmaf, slope, add, emb add)."""
+    t = raw * sc.double() + sh.double()
+    y = torch.where(t > 0, t, t * float(np.float32(SLOPE))) + add.double()
+    mag = (raw * sc.double()).abs() + sh.double().abs() + add.double().abs()
+    if emb is not None:
+        y = y + emb
+        mag = mag + emb.abs()
+    return y, mag
+
+
+def materialize_bound(ref, mag, dtype):
+    """fmaf, the slope product, two adds: at most 4 fp32 roundings of values bounded by ``mag``, plus 1 ulp of the fp32
+    scale / shift (the preamble's order of operations), then the rounding of the stored value."""
+    u_out, floor = unit(dtype)
+    return U32 * 6 * mag + u_out * ref.abs() + floor
+
+
+def stats_bound(y_abs_sum, y_sq_sum, dtype, n_contrib):
+    """Bound on |statistics words - fp64 sums of the stored output| per (n, c): the kernels sum their fp32 accumulators (at
+    most 2^-11 / 2^-24 from the stored values) in fp32 chains of at most 1024 values per contribution before converting to
+    fixed-point words (2^-44 each)."""
+    u_out, _ = unit(dtype)
+    bs = (u_out + U32 * 1024) * y_abs_sum + n_contrib * 2.0 ** -43
+    bq = (2 * u_out + u_out * u_out + U32 * 1024) * y_sq_sum + n_contrib * 2.0 ** -43
+    return bs, bq

@@ -1,0 +1,184 @@
+"""The fp64 bound check (tests/fp64ref.py) has teeth: a torch CPU fp32 evaluation on fp16-rounded operands, stored as fp16, passes
+it; the same result with one wrong product, one tap read with wrap-around instead of zero padding, or the bias of the wrong border
+class of the folded up-convolution does not -- at a border voxel and at an interior tile-boundary voxel, for a 64-channel and a
+128-channel (concat) contraction."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import fp64ref as R
+
+DIMS = (16, 16, 24)
+BORDER = (0, 0, 7, 8)          # low depth face, on tile edges along h and w
+INTERIOR = (0, 7, 8, 4)        # inside, on an 8-voxel tile edge (d = 7 | 8), a slab edge in w
+
+
+def _conv_case(cin):
+    """A 64- or 128-input-channel convolution: fp16-rounded operands, the kernel's stand-in (torch CPU fp32, stored fp16), and
+    the checker's reference at the sampled voxels."""
+    g = torch.Generator().manual_seed(cin)
+    x = torch.randn(1, cin, *DIMS, generator=g).half().float()
+    w = torch.randn(64, cin, 3, 3, 3, generator=g) / (27 * cin) ** 0.5
+    b = torch.randn(64, generator=g)
+    got = F.conv3d(x, w.half().float(), b, padding=1).half()              # [1, 64, D, H, W]
+    pts = R.sample_voxels(1, DIMS, n_random=300, seed=cin)
+    A, _ = R.gather_taps(x.permute(0, 2, 3, 4, 1).contiguous(), pts, 0, cin)
+    Wm = R.conv3_weights(w, torch.float16)
+    ref, ab, sq = R.conv3_ref(A, Wm, b)
+    bnd = R.bound(ref, ab, sq, R.chain_length(27 * cin, torch.float16), torch.float16)
+    return dict(x=x, w=w.half().double(), got=got, pts=pts, A=A, Wm=Wm, ref=ref, bnd=bnd)
+
+
+def _fold_case():
+    """UpCat's first convolution over cat([skip 64, deconv(u) 64]) in the folded form (composed weights rounded once to fp16,
+    27-class bias table in fp32), evaluated in fp32 as the kernel's stand-in."""
+    g = torch.Generator().manual_seed(7)
+    Cs, Cu, Cm, Co = 64, 64, 64, 64
+    xs = torch.randn(1, Cs, *DIMS, generator=g).half().float()
+    u = torch.randn(1, Cu, *(s // 2 for s in DIMS), generator=g).half().float()
+    wc = torch.randn(Co, Cs + Cm, 3, 3, 3, generator=g) / (27 * (Cs + Cm)) ** 0.5
+    bc = torch.randn(Co, generator=g)
+    wd = torch.randn(Cu, Cm, 2, 2, 2, generator=g) / Cu ** 0.5
+    bd = torch.randn(Cm, generator=g)
+    Wp = {k: v[0].half().double() for k, v in R.compose_fold(wc[:, Cs:], wd).items()}
+    rows, arows = R.fold_bias_table(wc[:, Cs:], bc, bd)
+    pts = R.sample_voxels(1, DIMS, n_random=300, seed=5)
+    par, ok, phi, deltas = R.fold_parents(pts, DIMS)
+    ucl = u.permute(0, 2, 3, 4, 1).contiguous()
+    U = ucl[pts[:, None, 0].expand_as(ok), par[..., 0].clamp(0, DIMS[0] // 2 - 1), par[..., 1].clamp(0, DIMS[1] // 2 - 1),
+            par[..., 2].clamp(0, DIMS[2] // 2 - 1)].double()
+    A, _ = R.gather_taps(xs.permute(0, 2, 3, 4, 1).contiguous(), pts, 0, Cs)
+    Wm = R.conv3_weights(wc[:, :Cs], torch.float16)
+    cls = R.border_class(pts, DIMS)
+    ref, ab, sq = R.fold_ref(A, Wm, U, ok, phi, deltas, Wp, rows[cls], arows[cls])
+    btab32 = rows.float().double()           # the packer's fp32 table
+    got, _, _ = R.fold_ref(A.float(), Wm.float(), U.float(), ok, phi, deltas, {k: v.float() for k, v in Wp.items()},
+                           btab32[cls].float(), arows[cls].float())
+    got = got.half().double()
+    bnd = R.bound(ref, ab, sq, R.chain_length(27 * Cs + 8 * Cu, torch.float16), torch.float16, extra=R.U32 * 1800 * arows[cls])
+    return dict(pts=pts, A=A, Wm=Wm, U=U, ok=ok, phi=phi, deltas=deltas, Wp=Wp, rows=btab32, cls=cls, ref=ref, bnd=bnd, got=got,
+                xs=xs)
+
+
+def _row(pts, p):
+    hit = (pts == torch.tensor(p)).all(1).nonzero()
+    assert hit.numel() == 1, f"{p} is not among the sampled voxels"
+    return int(hit[0, 0])
+
+
+def _got_conv(c):
+    pts = c["pts"]
+    return c["got"][pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]].double()       # [P, 64]
+
+
+def test_structured_voxels_are_sampled():
+    D, H, W = 63, 48, 40
+    pts = R.sample_voxels(2, (D, H, W), n_random=100)
+    assert len({tuple(p) for p in pts.tolist()}) == pts.shape[0]
+    for n in range(2):
+        for corner in [(0, 0, 0), (D - 1, H - 1, W - 1), (0, H - 1, 0), (D - 1, 0, W - 1)]:
+            _row(pts, (n, *corner))
+        for p in [(0, 7, 8), (0, 8, 39), (62, 47, 0), (7, 4, 3), (55, 40, 32), (56, 39, 39)]:
+            _row(pts, (n, *p))
+    for a, S in enumerate((D, H, W)):
+        seen = set(pts[:, 1 + a].tolist())
+        assert {0, 3, 4, 7, 8, S - 1} <= seen
+
+
+@pytest.mark.parametrize("cin", [64, 128])
+def test_unmutated_result_passes(cin):
+    c = _conv_case(cin)
+    r = R.check(_got_conv(c), c["ref"], c["bnd"], c["pts"])
+    assert r.ratio <= 1, r
+    assert r.ratio > 0.05, f"the bound is loose where it should be tight: {r}"
+
+
+def test_unmutated_fold_passes():
+    c = _fold_case()
+    r = R.check(c["got"], c["ref"], c["bnd"], c["pts"])
+    assert r.ratio <= 1, r
+
+
+@pytest.mark.parametrize("cin", [64, 128])
+@pytest.mark.parametrize("where", [BORDER, INTERIOR], ids=["border", "interior"])
+def test_one_dropped_product_is_rejected(cin, where):
+    c = _conv_case(cin)
+    i, o = _row(c["pts"], where), 5
+    prods = (c["A"][i].reshape(-1) * c["Wm"][:, o]).abs()
+    nz = prods[prods > 0]
+    k = int((prods - nz.median()).abs().argmin())
+    got = _got_conv(c)
+    got[i, o] = float(torch.as_tensor(got[i, o] - c["A"][i].reshape(-1)[k] * c["Wm"][k, o]).half())
+    r = R.check(got, c["ref"], c["bnd"], c["pts"])
+    assert r.ratio > 1 and r.where[0] == where, r
+
+
+@pytest.mark.parametrize("cin", [64, 128])
+@pytest.mark.parametrize("where", [BORDER, INTERIOR], ids=["border", "interior"])
+def test_one_wrapped_tap_is_rejected(cin, where):
+    """Border voxel: the tap at depth -1 read from the last plane instead of zero padding.  Interior voxel: the tap across the
+    tile edge (depth 8) read from the first plane of the voxel's own tile (depth 0), a halo that was never loaded."""
+    c = _conv_case(cin)
+    i, o = _row(c["pts"], where), 3
+    n, d, h, w = where
+    t = 4 if d == 0 else 22                     # tap (kd, kh, kw) = (0, 1, 1): depth -1; (2, 1, 1): depth + 1
+    src_d = DIMS[0] - 1 if d == 0 else (d + 1) - 8
+    want_d = d - 1 if d == 0 else d + 1
+    x = c["x"][n].double()
+    right = x[:, want_d, h, w] if 0 <= want_d < DIMS[0] else torch.zeros_like(x[:, 0, h, w])
+    wrong = x[:, src_d, h, w]
+    wt = c["w"][o, :, t // 9, (t // 3) % 3, t % 3]
+    got = _got_conv(c)
+    got[i, o] = float(torch.as_tensor(got[i, o] + ((wrong - right) * wt).sum()).half())
+    r = R.check(got, c["ref"], c["bnd"], c["pts"])
+    assert r.ratio > 1 and r.where[0] == where, r
+
+
+@pytest.mark.parametrize("where", [BORDER, INTERIOR], ids=["border", "interior"])
+@pytest.mark.parametrize("mutation", ["product", "wrap", "bias_class"])
+def test_fold_mutations_are_rejected(where, mutation):
+    c = _fold_case()
+    i, o = _row(c["pts"], where), 9
+    got = c["got"].clone()
+    if mutation == "product":
+        prods = (c["A"][i].reshape(-1) * c["Wm"][:, o]).abs()
+        k = int((prods - prods[prods > 0].median()).abs().argmin())
+        delta = -c["A"][i].reshape(-1)[k] * c["Wm"][k, o]
+    elif mutation == "wrap":
+        n, d, h, w = where
+        t = 4 if d == 0 else 22
+        src_d = DIMS[0] - 1 if d == 0 else d + 1 - 8
+        x = c["xs"][n].double()
+        right = torch.zeros_like(x[:, 0, h, w]) if d == 0 else x[:, d + 1, h, w]
+        wrong = x[:, src_d, h, w]
+        delta = ((wrong - right) * c["Wm"].reshape(27, -1, 64)[t, :, o]).sum()
+    else:
+        cls = int(c["cls"][i])
+        other = 13 if cls != 13 else 12          # interior <-> the low w face
+        delta = c["rows"][other, o] - c["rows"][cls, o]
+    got[i, o] = float(torch.as_tensor(got[i, o] + delta).half())
+    r = R.check(got, c["ref"], c["bnd"], c["pts"])
+    assert r.ratio > 1 and r.where[0] == where, (mutation, r)
+
+
+def test_fp16_transform_emulation_rounds_once():
+    """The fused input transform: two mixed fmas rounded once into fp16, the larger kept; against the same arithmetic spelled
+    out per element with numpy's direct float64 -> fp16 conversion."""
+    import numpy as np
+    g = torch.Generator().manual_seed(3)
+    raw = torch.randn(4000, 16, generator=g).half().double()
+    sc = (torch.rand(16, generator=g) + 0.5).float()
+    sh = torch.randn(16, generator=g).float()
+    add = torch.randn(16, generator=g).float()
+    got = R.transform(raw, sc, sh, add, torch.float16)
+    for k in range(0, 4000, 97):
+        for c in range(16):
+            x = float(raw[k, c])
+            p = np.float16(x * float(sc[c]) + float(np.float32(sh[c]) + np.float32(add[c])))
+            sn = np.float32(np.float32(0.1) * np.float32(sc[c]))
+            an = np.float32(float(np.float32(0.1)) * float(sh[c]) + float(add[c]))
+            q = np.float16(x * float(sn) + float(an))
+            assert float(got[k, c]) == float(max(p, q))
+    # against the exact function: within one fp16 ulp everywhere
+    exact = torch.nn.functional.leaky_relu(raw * sc.double() + sh.double(), 0.1) + add.double()
+    assert bool(((got - exact).abs() <= 2 ** -10 * exact.abs() + 2 ** -24).all())

@@ -79,6 +79,35 @@ def _producer(raw, dtype, g, add=None):
     return ops.Norm(stats, gamma.cuda(), beta.cuda(), count, **kw), act
 
 
+def _kernel_act(raw, norm, dtype):
+    """NCDHW float64 activation a consumer multiplies when ``norm`` (ops.Norm) is fused into its staging: raw stored in ``dtype``
+    through the transform in the kernels' arithmetic (fp64ref.transform) on their own fp32 scale / shift (instnorm_finalize)."""
+    import fp64ref as R
+    ops = _ops()
+    N, C = raw.shape[:2]
+    sc, sh = (t.cpu() for t in ops.instnorm_finalize(norm, N, C))
+    add = norm.keep[3]
+    ad = torch.zeros(N, C) if add is None else add.cpu().view(N, C)
+    x = raw.to(dtype).double().permute(0, 2, 3, 4, 1)
+    v = lambda t: t[:, None, None, None, :]          # noqa: E731
+    return R.transform(x.contiguous(), v(sc), v(sh), v(ad), dtype).permute(0, 4, 1, 2, 3).contiguous()
+
+
+def _fp64_bound_check(got, act, w, b, dtype, emulated=False, split_parts=0, seed=0):
+    """Section-1 check of tests/fp64ref.py: ``got`` NCDHW (the stored output) against the fp64 convolution of ``act`` (NCDHW, the
+    exact values the kernel multiplied) with ``w`` rounded as the packer rounds, at the sampled voxels, per element."""
+    import fp64ref as R
+    N, cin, D, H, W = act.shape
+    pts = R.sample_voxels(N, (D, H, W), n_random=1000, seed=seed)
+    A, _ = R.gather_taps(act.double().permute(0, 2, 3, 4, 1).contiguous(), pts, 0, cin)
+    ref, ab, sq = R.conv3_ref(A, R.conv3_weights(w, dtype), b)
+    bnd = R.bound(ref, ab, sq, R.chain_length(27 * cin, dtype, split_parts), dtype, emulated_in=dtype if emulated else None)
+    g = got.double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]]
+    r = R.check(g, ref, bnd, pts)
+    assert r.ratio <= 1, r
+    return r
+
+
 @pytest.fixture
 def conv_variant(request):
     """Force one of the conv3d_k3 launch shapes (0: automatic policy with split-K / 2x8x8 tiles where they pay,
@@ -124,6 +153,9 @@ def test_conv3_raw_and_stats(dtype, shape, conv_variant):
     ops.conv3d_k3(xcl, Cin, 0, wp, bp, Cout, y, 0, stats)
     got = ops.from_channels_last(y, Cout).cpu()
     assert torch.allclose(got, ref, **TOL[dtype]), float((got - ref).abs().max())
+    cs = -(-Cin // 8) * 8
+    assert ops.conv3_kernel_kind(dtype, N, D, H, W, cs, cs, Cout) == ops.KIND_V2
+    _fp64_bound_check(got, xq, w, b, dtype, seed=sum(shape))
 
     # statistics (taken from the fp32 accumulators) -> scale/shift, against instance_norm of the exact conv
     st = ops.stats_decode(stats).cpu()[:, :Cout]
@@ -190,6 +222,10 @@ def test_conv3_wide_tile_form(shape, fused, conv_variant_any, layout):
     ycl = ops.from_blocked(ybuf) if out_blk else ybuf
     got = ops.from_channels_last(ycl, Cout, ooff).cpu()
     assert torch.allclose(got, ref, **TOL[dtype]), float((got - ref).abs().max())
+    want_kind = ops.KIND_V2 if conv_variant_any == 7 else ops.KIND_WIDE
+    assert ops.conv3_kernel_kind(dtype, N, D, H, W, Cin, istride, Cout, fused) == want_kind
+    _fp64_bound_check(got, _kernel_act(raw, norm, dtype) if fused else raw.to(dtype).double(), w, b, dtype, emulated=fused,
+                      seed=sum(shape))
     if ooff:
         assert float((ycl[..., :ooff].float() + 5).abs().max()) == 0
     if ooff + Cout < ostride:
@@ -245,6 +281,9 @@ def test_conv3_split_k(dtype, shape, conv_variant):
     ops.conv3d_k3(_cl(raw, dtype), Cin, 0, wp, bp, Cout, y, 8, stats, norm=norm, workspace=ws)
     got = ops.from_channels_last(y, Cout, 8).cpu()
     assert torch.allclose(got, ref, **TOL[dtype]), float((got - ref).abs().max())
+    assert ops.conv3_kernel_kind(dtype, N, D, H, W, Cin, Cin, Cout, True) == ops.KIND_V2
+    _fp64_bound_check(got, _kernel_act(raw, norm, dtype), w, b, dtype, emulated=True,
+                      split_parts=3 * -(-Cin // ops.chunk_elems(dtype)), seed=sum(shape))
     assert float((y[..., :8].float() - 2).abs().max()) == 0
     st = ops.stats_decode(stats).cpu()[:, :Cout]
     gd = got.double().flatten(2)                        # the split-K finish kernel takes its sums from the stored values
@@ -304,6 +343,8 @@ def test_conv3_single_channel_tap_form(classes, shape, cout):
     try:
         for tap, variant in ((None, 0), (classes, 0), (classes, 6)):
             ops.CONV_POLICY = variant
+            want_kind = ops.KIND_FIRST if (tap is not None and variant == 0 and classes == 16) else ops.KIND_V2
+            assert ops.conv3_kernel_kind(torch.float16, N, D, H, W, cin_p, cin_p, cout, False, tap) == want_kind
             wp, bp = ops.pack_conv3_weights(w.cuda(), b.cuda(), torch.float16, cin_packed=cin_p, perm=perm, tap_channel=tap)
             y = torch.full((N, D, H, W, cout + 8), -5.0, dtype=torch.float16, device="cuda")
             st = ops.stats_buffer(N, cout, "cuda")
@@ -315,6 +356,7 @@ def test_conv3_single_channel_tap_form(classes, shape, cout):
     want = F.conv3d(x.half().float().cuda(), w.half().float().cuda(), b.cuda(), padding=1).cpu()
     for got, st in outs:
         assert (got - want).abs().max() < 2e-2, float((got - want).abs().max())
+        _fp64_bound_check(got, x.half().double(), w, b, torch.float16, seed=classes + D)
         gd = got.double().permute(1, 0, 2, 3, 4).reshape(cout, N, -1).permute(1, 0, 2)
         # the sums are taken from the fp32 accumulators, the stored values are their fp16 roundings (a random walk over the voxels)
         walk = 1e-3 * (D * H * W) ** 0.5

@@ -162,7 +162,7 @@ def test_training_step_through_the_forward_boundary(dtype):
     gp = dict(net.named_parameters())
     num = den = 0.0
     for k, p in ref.named_parameters():
-        if k.endswith("conv.bias"):
+        if k.endswith(".conv.bias"):
             continue
         g = gp[k].grad.detach().cpu().double() / scale
         num += float(((g - p.grad.double()) ** 2).sum()); den += float((p.grad.double() ** 2).sum())
@@ -232,7 +232,7 @@ def test_native_conv_training_path_matches_oracle_autograd(dtype):
     for k, p in ref.named_parameters():
         g = gp[k].grad.detach().cpu().double() / scale
         ref_g = p.grad.double()
-        if k.endswith("conv.bias"):          # bias before InstanceNorm: true gradient is zero, both sides hold rounding noise
+        if k.endswith(".conv.bias"):          # bias before InstanceNorm: true gradient is zero, both sides hold rounding noise
             continue
         errs.append(((g - ref_g).abs().max().item() / (ref_g.abs().max().item() + 1e-6), k))
         num += float(((g - ref_g) ** 2).sum()); den += float((ref_g ** 2).sum())
@@ -468,10 +468,12 @@ def test_training_forward_fold_equals_the_unfolded_forward():
     assert (outs[0] - outs[1]).abs().max().item() < 3e-2
     num = den = 0.0
     for (k, a), (_, b) in zip(nets[0].named_parameters(), nets[1].named_parameters()):
-        if k.endswith("conv.bias") or a.grad is None:
+        if k.endswith(".conv.bias") or a.grad is None:
             continue
         num += float(((a.grad.double() - b.grad.double()) ** 2).sum()); den += float((b.grad.double() ** 2).sum())
     assert (num / den) ** 0.5 < 3e-2, (num / den) ** 0.5
+    _check_real_bias_gradients(dict(nets[0].named_parameters()), nets[1].named_parameters(), 1.0, "fold vs unfolded",
+                               deconv=(3e-2, 0.995), final=(3e-2, 0.995))
 
 
 @pytest.mark.gpu
@@ -505,7 +507,7 @@ def test_full_size_gradients_fp16_path_vs_oracle():
     num = den = 0.0
     coss = []
     for k, p in ref.named_parameters():
-        if k.endswith("conv.bias"):
+        if k.endswith(".conv.bias"):
             continue
         a = gp[k].grad.detach().cpu().double() / scale
         b = p.grad.double()
@@ -517,6 +519,42 @@ def test_full_size_gradients_fp16_path_vs_oracle():
     print(f"[96^3 x 16, fp16 path] loss {float(lg):.6f} vs {float(lw):.6f}; whole-gradient relative L2 error {rel:.2e}; "
           f"lowest cosine: " + ", ".join(f"{k} {c:.4f}" for c, k in coss[:3]))
     assert rel < 3e-2 and coss[0][0] > 0.98, (rel, coss[0])
+    # measured here (relative L2 / cosine): upcat_4 .. upcat_1 deconv.bias 1.25e-1 / 0.9922, 8.3e-2 / 0.9966, 4.6e-2 / 0.9989,
+    # 7.1e-3 / 0.99998; final_conv.bias 7.1e-5 / 1.0
+    _check_real_bias_gradients(gp, ref.named_parameters(), scale, "96^3 x 16, fp16 path vs oracle", deconv=(0.25, 0.97),
+                               final=(1e-3, 0.9999))
+
+
+def _real_bias_gradient(k):
+    """The biases whose gradient is real although their names end in "conv.bias": the head's and the four transposed
+    convolutions' (the Conv3d biases in front of an InstanceNorm are the ones with a zero true gradient)."""
+    return k.endswith("final_conv.bias") or k.endswith("upsample.deconv.bias")
+
+
+def _check_real_bias_gradients(got_params, want_named, scale, what, deconv, final):
+    """Per tensor, so that a 16- or 64-entry gradient cannot hide inside the whole-gradient aggregate: relative L2 error and
+    cosine of final_conv.bias and each upsample.deconv.bias, within ``final`` / ``deconv`` = (relative L2, cosine) bounds.
+    The head's bias gradient is a plain sum of the logits' gradient.  A transposed convolution's bias reaches the loss through
+    the convolution that reads the concat and the InstanceNorm behind it, which cancels a constant field everywhere but near
+    the borders: its true gradient is a small difference of large sums, and fp16 rounding of those sums weighs more on it the
+    fewer voxels a level has (a whole-gradient relative L2 of 3e-2 corresponds to per-tensor errors of that order only for
+    tensors that are not such differences).  A missing, mis-scaled or mis-signed gradient has a relative L2 error near 1 and a
+    cosine far from 1."""
+    seen = []
+    for k, p in want_named:
+        if not _real_bias_gradient(k):
+            continue
+        a = got_params[k].grad.detach().cpu().double() / scale
+        b = p.grad.detach().cpu().double()
+        rel = float((a - b).norm() / (b.norm() + 1e-30))
+        cos = float((a * b).sum() / (a.norm() * b.norm() + 1e-30))
+        seen.append((k, rel, cos))
+    print(f"[{what}] real bias gradients, per tensor (relative L2, cosine): "
+          + ", ".join(f"{k} {r:.2e} {c:.5f}" for k, r, c in seen))
+    assert len(seen) == 5, [k for k, _, _ in seen]
+    for k, rel, cos in seen:
+        rmax, cmin = final if k.endswith("final_conv.bias") else deconv
+        assert rel < rmax and cos > cmin, (k, rel, cos)
 
 
 @pytest.mark.gpu

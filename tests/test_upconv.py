@@ -85,6 +85,37 @@ def _ops():
     return ops
 
 
+def _fp64_fold_check(got, xs_act, u_act, wc, bc, wd, bd, wu, up_first, emulated, seed=0):
+    """Section-1 check of tests/fp64ref.py on the folded launch: ``got`` NCDHW against the skip half as a 3x3x3 convolution with
+    fp16-rounded weights + the composed fp16 weights the kernel streams (decoded from ``wu``) over the 8 parents of each voxel
+    + the 27-class bias table formed in fp64 from the original parameters, per element at the sampled voxels.  ``xs_act`` /
+    ``u_act``: NCDHW float64 values the kernel multiplied (skip half on the fine grid, activation of the coarse tensor)."""
+    import fp64ref as R
+    N, Cs, D, H, W = xs_act.shape
+    Cu = u_act.shape[1]
+    Cout = wc.shape[0]
+    Cmid = wc.shape[1] - Cs
+    wc_up, wc_sk = (wc[:, :Cmid], wc[:, Cmid:]) if up_first else (wc[:, Cs:], wc[:, :Cs])
+    Wp = R.decode_fold_weights(wu, Cout, -(-Cu // 64) * 64)
+    Wp = {k: v[:, :Cu] for k, v in Wp.items()}
+    pts = R.sample_voxels(N, (D, H, W), n_random=1000, seed=seed)
+    A, _ = R.gather_taps(xs_act.permute(0, 2, 3, 4, 1).contiguous(), pts, 0, Cs)
+    par, ok, phi, deltas = R.fold_parents(pts, (D, H, W))
+    lim = torch.tensor([D // 2 - 1, H // 2 - 1, W // 2 - 1])
+    pc = torch.minimum(par.clamp_min(0), lim)
+    ucl = u_act.permute(0, 2, 3, 4, 1)
+    U = ucl[pts[:, None, 0].expand_as(ok), pc[..., 0], pc[..., 1], pc[..., 2]]
+    U = torch.where(ok[..., None], U, torch.zeros_like(U))
+    rows, arows = R.fold_bias_table(wc_up, bc, bd)
+    cls = R.border_class(pts, (D, H, W))
+    ref, ab, sq = R.fold_ref(A, R.conv3_weights(wc_sk, torch.float16), U, ok, phi, deltas, Wp, rows[cls], arows[cls])
+    bnd = R.bound(ref, ab, sq, R.chain_length(27 * Cs + 8 * Cu, torch.float16), torch.float16,
+                  emulated_in=torch.float16 if emulated else None, extra=R.U32 * (27 * Cmid + 1) * arows[cls])
+    r = R.check(got.double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]], ref, bnd, pts)
+    assert r.ratio <= 1, r
+    return r
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(64, 64, 64, 64), (72, 32, 24, 128)])
 def test_packer_writes_the_composed_weights_in_streaming_order(shape):
@@ -152,6 +183,9 @@ def test_upconv_matches_deconv_cat_conv(shape, layout):
     got = ops.from_channels_last(ycl, Cout, ooff).cpu()
     err = (got - ref).abs()
     assert torch.allclose(got, ref, **TOL16), (float(err.max()), [int(v) for v in torch.nonzero(err == err.max())[0]])
+    assert ops.upconv_supported(dt, N, D, H, W, Cs, sstride, Cu, ustride, Cout, ostride, in_blk, out_blk)
+    from test_kernels_gpu import _kernel_act
+    _fp64_fold_check(got, xs.to(dt).double(), _kernel_act(raw_u, norm, dt), wc, bc, wd, bd, wu, False, True, seed=sum(shape))
     if ooff:
         assert float((ycl[..., :ooff].float() + 5).abs().max()) == 0
     if ooff + Cout < ostride:
@@ -209,6 +243,8 @@ def test_upconv_swin_decoder_form(shape):
     got = ops.from_channels_last(y, Cout, 0).cpu()
     err = (got - ref).abs()
     assert torch.allclose(got, ref, **TOL16), (float(err.max()), [int(v) for v in torch.nonzero(err == err.max())[0]])
+    assert ops.upconv_supported(dt, N, D, H, W, Cs, Cmid + Cs, cu_packed, cu_packed, Cout, Cout)
+    _fp64_fold_check(got, skip.to(dt).double(), u.to(dt).double(), wc, bc, wd, None, wu, True, False, seed=sum(shape))
     st = ops.stats_decode(stats).cpu()[:, :Cout]
     gd = got.double().flatten(2)
     assert bool(((st[..., 0] - gd.sum(-1)).abs() <= 1e-3 * gd.abs().sum(-1) + 0.5).all())
@@ -244,6 +280,23 @@ def test_deconv_res_matches_deconv_cat_pointwise(shape):
     got = ops.from_channels_last(y, Cout, 0).cpu()
     err = (got - ref).abs()
     assert torch.allclose(got, ref, **TOL16), (float(err.max()), [int(v) for v in torch.nonzero(err == err.max())[0]])
+    # section-1 check of tests/fp64ref.py: the composed weights W3_up . Wd[child] formed in fp32 and rounded once to fp16 (as
+    # pack_deconv_res_weights does; a one-ulp flip of a weight whose fp32 composition sums in another order is the RSS term),
+    # the skip weights rounded to fp16, per element at the sampled fine-grid voxels
+    import fp64ref as R
+    comp = torch.einsum("umk,om->uok", wd.float().reshape(Cu, Cmid, 8), w3[:, :Cmid].float()).half().double()   # [Cu, Cout, 8]
+    wsk = w3[:, Cmid:].half().double().t()                                                                       # [Cs, Cout]
+    pts = R.sample_voxels(N, (2 * D, 2 * H, 2 * W), n_random=1000, seed=sum(shape))
+    child = (pts[:, 1] & 1) * 4 + (pts[:, 2] & 1) * 2 + (pts[:, 3] & 1)
+    lo_q = lo.to(dt).double()[pts[:, 0], :, pts[:, 1] >> 1, pts[:, 2] >> 1, pts[:, 3] >> 1]                    # [P, Cu]
+    sk_q = skip.to(dt).double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]]                                  # [P, Cs]
+    Wc = comp[:, :, child].permute(2, 0, 1)                                                                       # [P, Cu, Cout]
+    ref64 = torch.einsum("pc,pco->po", lo_q, Wc) + sk_q @ wsk
+    ab = torch.einsum("pc,pco->po", lo_q.abs(), Wc.abs()) + sk_q.abs() @ wsk.abs()
+    sq = torch.einsum("pc,pco->po", lo_q ** 2, Wc ** 2) + sk_q ** 2 @ wsk ** 2
+    bnd = R.bound(ref64, ab, sq, R.chain_length(Cu + Cs, dt), dt, emulated_in=dt)
+    r = R.check(got.double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]], ref64, bnd, pts)
+    assert r.ratio <= 1, r
     st = ops.stats_decode(stats).cpu()[:, :Cout]
     gd = got.double().flatten(2)
     assert bool(((st[..., 0] - gd.sum(-1)).abs() <= 1e-3 * gd.abs().sum(-1) + 0.5).all())
@@ -309,6 +362,13 @@ def test_upconv_random_shapes(seed):
     desc = dict(N=N, dims=(D, H, W), Cs=Cs, Cu=Cu, Cmid=Cmid, Cout=Cout, up_first=up_first, norm=with_norm, blocked=blocked,
                 soff=soff, sstride=sstride, uoff=uoff, ustride=ustride, ooff=ooff, ostride=ostride)
     assert torch.allclose(got, ref, **TOL16), (float((got - ref).abs().max()), desc)
+    assert ops.upconv_supported(dt, N, D, H, W, Cs, sstride, Cu, ustride, Cout, ostride, blocked, blocked), desc
+    if with_norm:
+        from test_kernels_gpu import _kernel_act
+        u_act = _kernel_act(raw_u, norm, dt)
+    else:
+        u_act = raw_u.to(dt).double()
+    _fp64_fold_check(got, skip.to(dt).double(), u_act, wc, bc, wd, bd, wu, up_first, with_norm, seed=seed)
     if ooff:
         assert float((ycl[..., :ooff].float() + 5).abs().max()) == 0, desc
     if ooff + Cout < ostride:
