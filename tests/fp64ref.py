@@ -355,3 +355,237 @@ def stats_bound(y_abs_sum, y_sq_sum, dtype, n_contrib):
     bs = (u_out + U32 * 1024) * y_abs_sum + n_contrib * 2.0 ** -43
     bq = (2 * u_out + u_out * u_out + U32 * 1024) * y_sq_sum + n_contrib * 2.0 ** -43
     return bs, bq
+
+
+# ---- backward kernels ---------------------------------------------------------------------------------------------------------
+# The same bound form as the forward kernels: 2^-24 * (longest fp32 chain) * sum |terms| + the rounding of the stored value, with
+# the chain read off each launcher.  A partial sum that a reduce kernel adds is one term of its chain; the chains nest, so an
+# element's total chain is the length inside the main kernel plus the length of every reduction it then passes through.
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def wgrad_fo_partitions(N, D, H, W, Cin, Cout, policy=0):
+    """Mirror of wgrad_fo_partitions (csrc/conv3d_wgrad_fo.hip): (P, combos, total tiles) of the fetch-once form (4x8x8 tiles,
+    64 co x 32 ci combos).  Pinned against dua_conv3d_k3_wgrad_workspace by the GPU tests."""
+    combos = _cdiv(Cout, 64) * _cdiv(Cin, 32)
+    total = N * _cdiv(D, 4) * _cdiv(H, 8) * _cdiv(W, 8)
+    mult = ((policy & 31) >> 1) or 1
+    P = min(_cdiv(256 * mult, combos), total)
+    if P >= 8:
+        P &= ~7
+    return max(P, 1), combos, total
+
+
+def wgrad_fo_route(combos, perm):
+    """The reduce kernel the fetch-once launcher picks: "taps" (wgrad_fo_reduce_taps_kernel) for >= 32 slabs and the identity
+    channel map, else "plain" (wgrad_fo_reduce_kernel)."""
+    return "taps" if combos >= 32 and perm is None else "plain"
+
+
+def wgrad_fo_chain(P, total, route):
+    """Longest chain of one dW element through the fetch-once form.  A partition walks tiles part, part + P, ...: at most
+    ceil(total / P) tiles of 256 voxels, 16 MFMA 32x32x16 steps each, + log2(16) = 4 adds inside the instruction.  The plain
+    reduce sums P partials in four interleaved chains of ceil(P / 4) and adds the four in a tree of depth 2; the tap-gathering
+    reduce sums them in one chain of P.  + 1: the += into dW."""
+    main = _cdiv(total, P) * 16 + 4
+    red = (_cdiv(P, 4) + 2) if route == "plain" else P
+    return main + red + 1
+
+
+def wgrad_3kd_partitions(N, D, H, W, Cin, Cout, policy):
+    """Mirror of wgrad_partitions (csrc/conv3d_wgrad.hip): (P, combos, total tiles) of the three-kd form (2x8x8 tiles, one kd
+    plane of 64 co x 64 ci per workgroup)."""
+    combos = _cdiv(Cout, 64) * _cdiv(Cin, 64) * 3
+    total = N * _cdiv(D, 2) * _cdiv(H, 8) * _cdiv(W, 8)
+    mv = (policy & 31) >> 1
+    mult = mv or (1 if total < 32 else 3)
+    P = min(_cdiv(256 * mult, combos), total)
+    if P >= 8:
+        P = (P + 7) & ~7
+    return max(P, 1), combos, total
+
+
+def wgrad_3kd_workspace(P, combos):
+    return P * combos * 9 * 4096 * 4 if P > 1 else 0
+
+
+def wgrad_3kd_chain(P, total, dtype, partials):
+    """Longest chain of one dW element through the three-kd form: ceil(total / P) tiles of 128 voxels; fp16: 8 MFMA 32x32x16
+    steps per tile + 4 adds inside the instruction; fp32: 64 MFMA 32x32x2 steps + 1 add inside + 1 for the product's rounding.
+    With partial sums: wgrad_reduce_kernel's four chains of ceil(P / 4), a depth-2 tree and the += (+ 3).  Without: the P
+    workgroups' fp32 atomics into dW, in any order -- a chain of P adds."""
+    main = _cdiv(total, P) * (8 + 4 if dtype == torch.float16 else 64 + 2)
+    return main + (_cdiv(P, 4) + 3 if partials else P)
+
+
+def wgrad_ref(x, c_off, cin, dy, co_off, cout, cin_src=None, perm=None):
+    """fp64 weight gradient of the 3x3x3 convolution as 27 shifted GEMMs on x's device (no fp64 convolution), in the
+    reference layout [cout, cin_src, 3, 3, 3], and sum |x| |dy| per element.  x, dy: channels-last buffers (the kernel's exact
+    operands); ``perm`` (packed channel -> source channel, < 0: none) or the first ``cin_src`` packed channels."""
+    N, D, H, W, _ = x.shape
+    xp = torch.zeros((N, D + 2, H + 2, W + 2, cin), dtype=torch.float64, device=x.device)
+    xp[:, 1:-1, 1:-1, 1:-1] = x[..., c_off:c_off + cin].double()
+    g = dy[..., co_off:co_off + cout].double().reshape(-1, cout)
+    ga = g.abs()
+    ref = torch.empty((27, cout, cin), dtype=torch.float64, device=x.device)
+    ab = torch.empty_like(ref)
+    for t, (kd, kh, kw) in enumerate(itertools.product(range(3), repeat=3)):
+        xs = xp[:, kd:kd + D, kh:kh + H, kw:kw + W].reshape(-1, cin)
+        ref[t] = g.t() @ xs
+        ab[t] = ga.t() @ xs.abs()
+    ref, ab = ref.permute(1, 2, 0), ab.permute(1, 2, 0)          # [cout, cin packed, 27]
+    if perm is None:
+        cs = cin if cin_src is None else cin_src
+        ref, ab = ref[:, :cs], ab[:, :cs]
+    else:
+        p = perm[:cin].long().cpu()
+        cs = cin_src
+        keep = [(cp, int(ci)) for cp, ci in enumerate(p.tolist()) if 0 <= ci < cs]
+        r2 = torch.zeros((cout, cs, 27), dtype=torch.float64, device=x.device)
+        a2 = torch.zeros_like(r2)
+        for cp, ci in keep:
+            r2[:, ci] += ref[:, cp]
+            a2[:, ci] += ab[:, cp]
+        ref, ab = r2, a2
+    return ref.reshape(cout, cs, 3, 3, 3).contiguous(), ab.reshape(cout, cs, 3, 3, 3).contiguous()
+
+
+def wgrad_bound(ref, abs_sum, dw0, n_chain):
+    """Bound on dW = dw0 + (the kernel's sum) against dw0 + ref: the starting value is one more term of the chain (the += adds
+    it), the fp32 result is stored as it is (its last rounding is that += , counted in n_chain)."""
+    d0 = dw0.double()
+    return U32 * n_chain * (abs_sum + d0.abs()) * (1 + U32) + FLOOR32
+
+
+# InstanceNorm + LeakyReLU backward (csrc/instnorm_bwd.hip): z = zh * gamma + beta, zh = (y - mean) * rstd; dZ = dA or slope dA
+def in_bwd_reduce_chain(C, vox, dtype):
+    """Per-thread fp32 chain of in_bwd_reduce_kernel: gpc = C / EPG channel groups, tpg = 256 / gpc threads per group, blocks =
+    clamp(ceil(vox / (8 tpg)), 1, 1024) per sample; a thread walks the voxels tpg * blocks apart.  The block and replica
+    reductions after it are in fp64 (2^-53 per add, below 2^-24 by far: counted as 2 fp32 steps)."""
+    epg = 8 if dtype == torch.float16 else 4
+    tpg = 256 // (C // epg)
+    blocks = min(max(_cdiv(vox, tpg * 8), 1), 1024)
+    return _cdiv(vox, tpg * blocks) + 2
+
+
+DGRAD_REDUCE_CHAIN = 2 * 8 + 3 + 2
+"""Per-lane fp32 chain of conv3d_k3_dgrad_reduce's sums (csrc/conv3d_wide.hip backward-sums epilogue): MB / 2 <= 2 plane pairs x 8
+voxels per lane and tile (the halo holds at most 10 planes: TD = 2 MB <= 8), a 3-level shuffle tree; fp64 after that (+2)."""
+
+
+def in_bwd_ref(dA, raw, sums_dec, gamma, beta, count, eps=1e-5, slope=SLOPE):
+    """fp64 InstanceNorm + LeakyReLU backward on x's device.  dA, raw: [N, V, C] exact operand values (any float type);
+    ``sums_dec``: stats_decode of the forward statistics words (the kernels' own), float64 [N, c_pad, 2].  Returns a dict:
+    S0, S1, S2 [N, C]; their abs sums A0, A1, A2; dY [N, V, C]; and per-element pieces the bounds need: zhat, z, dz, rstd,
+    mean, e_zh (bound on the kernel's fp32 zh), near (|z| within the margin where fp32 may take the other slope)."""
+    N, V, C = raw.shape
+    dev = raw.device
+    sd = sums_dec.to(dev)
+    mean = sd[:, :C, 0] / count
+    var = (sd[:, :C, 1] / count - mean * mean).clamp_min(0)
+    rstd = 1.0 / torch.sqrt(var + float(np.float32(eps)))
+    g = gamma.double().to(dev)[None, None]
+    b = beta.double().to(dev)[None, None]
+    y, d = raw.double(), dA.double()
+    zhat = (y - mean[:, None]) * rstd[:, None]
+    z = zhat * g + b
+    sl = float(np.float32(slope))
+    dz = torch.where(z > 0, d, d * sl)
+    # the kernel's zh = fl(fl(y - fl32(mean)) * fl32(rstd)): mean off by U32 |mean|, rstd by U32, two roundings
+    e_zh = U32 * (3 * zhat.abs() + rstd[:, None] * mean[:, None].abs()) * (1 + 4 * U32)
+    margin = g.abs() * e_zh + 2 * U32 * ((zhat * g).abs() + b.abs())
+    near = z.abs() <= margin
+    S0, S1, S2 = d.sum(1), dz.sum(1), (dz * zhat).sum(1)
+    A0, A1, A2 = d.abs().sum(1), dz.abs().sum(1), (dz * zhat).abs().sum(1)
+    gr = g * rstd[:, None]
+    dY = gr * (dz - S1[:, None] / V - zhat * S2[:, None] / V)
+    return dict(S0=S0, S1=S1, S2=S2, A0=A0, A1=A1, A2=A2, dY=dY, zhat=zhat, z=z, dz=dz, d=d, rstd=rstd, mean=mean, e_zh=e_zh,
+                near=near, gr=gr, V=V, slope=sl)
+
+
+def in_bwd_sums_bound(r, n_chain):
+    """Bounds [N, C] on the kernel's S0, S1, S2 against fp64: the fp32 chains (dZ's slope product rounds once more, the fmaf
+    chain of S2 once more for zh), zh's own error e_zh in S2, and (1 - slope) |dA| (|dA zhat| for S2) for every element near the
+    kink, where fp32 may take the other slope."""
+    kink = (1 - r["slope"]) * r["d"].abs() * r["near"]
+    e2 = (r["dz"].abs() * r["e_zh"]).sum(1)
+    b0 = U32 * n_chain * r["A0"] + FLOOR32
+    b1 = U32 * (n_chain + 1) * r["A1"] + kink.sum(1) + FLOOR32
+    b2 = U32 * (n_chain + 2) * r["A2"] + e2 + (kink * r["zhat"].abs()).sum(1) + FLOOR32
+    return b0, b1, b2
+
+
+def in_bwd_dy_bound(r, b1, b2, dtype):
+    """Bound [N, V, C] on the apply kernel's dY = gamma rstd (dZ - S1 / V - zh S2 / V) in fp32, stored in ``dtype``: the sums off
+    by b1, b2 (then rounded to fp32 after the division), zh off by e_zh, dZ rounded once, two subtractions and the product
+    of up to M = |dZ| + |S1| / V + |zh S2| / V rounded 4 times; rstd rounded to fp32 and the two products (3 U32 |dY|); the
+    stored value's rounding; near the kink (1 - slope) |dA| gamma rstd."""
+    u_out, floor = unit(dtype)
+    V = r["V"]
+    S1, S2 = r["S1"][:, None], r["S2"][:, None]
+    M = r["dz"].abs() + S1.abs() / V + (r["zhat"] * S2).abs() / V
+    et = 4 * U32 * M + (b1[:, None] + r["zhat"].abs() * b2[:, None]) / V + r["e_zh"] * (S2.abs() + b2[:, None]) / V
+    gr = r["gr"].abs()
+    kink = (1 - r["slope"]) * r["d"].abs() * r["near"]
+    return (gr * (et + kink) * (1 + 4 * U32) + 3 * U32 * r["dY"].abs()) * (1 + u_out) + u_out * r["dY"].abs() + floor
+
+
+def head_bwd_chains(vox, dtype, mfma):
+    """(du chain, dW / db chain) of dua_head_bwd.  du: fp16 MFMA path one 32x32x16 over K <= 16 classes (chain_length(16)); fp32
+    an fmaf chain of K <= 16 (+1).  dW, db: the MFMA path's waves add 32 voxels per 16x16x32 step over ceil(tiles / blocks)
+    128-voxel tiles (+ log2(32) inside), the plain kernel's threads 16 voxels of every 64-voxel tile of theirs with fmaf; a
+    4-way tree over the waves (+2); head_reduce_kernel's 16 slices of ceil(blocks / 16) partials in four chains (+2) and the
+    16 slices' atomics into the zeroed outputs (+16)."""
+    t64 = _cdiv(vox, 64)
+    blocks = min(max(t64, 1), 1024)
+    if mfma:
+        t128 = _cdiv(vox, 128)
+        g2 = min(t128, blocks)
+        main, du = _cdiv(t128, g2) + 5, chain_length(16, torch.float16)
+    else:
+        g2 = blocks
+        main, du = _cdiv(t64, g2) * 16, 17
+    return du, main + 2 + _cdiv(_cdiv(g2, 16), 4) + 2 + 16
+
+
+def deconv_bwd_chains(N, D, H, W, Cin, Cout, dtype):
+    """(dx chain, dW chain, P) of dua_deconv_k2s2_bwd.  dx: a contraction over 8 taps x Cout (chain_length).  dW: P =
+    min(ceil(768 / (8 combos)), tiles) partitions (deconv_wgrad_partitions, 64 ci x 64 co combos, 128 / 64-voxel tiles for fp16
+    / fp32); four waves take a quarter of every tile each: 2 MFMA 32x32x16 steps (+4 inside) or 8 MFMA 32x32x2 (+1 inside, +1
+    product rounding) per tile; a two-round tree over the waves (+2); deconv_wgrad_reduce_kernel's two chains of ceil(P / 2)
+    and their sum (+1); the += into the zeroed dW (+1)."""
+    combos = _cdiv(Cin, 64) * _cdiv(Cout, 64)
+    tv = 128 if dtype == torch.float16 else 64
+    total = N * _cdiv(D * H * W, tv)
+    P = max(min(_cdiv(768, 8 * combos), total), 1)
+    main = _cdiv(total, P) * (2 + 4 if dtype == torch.float16 else 8 + 2)
+    return chain_length(8 * Cout, dtype), main + 2 + _cdiv(P, 2) + 1 + 1, P
+
+
+def deconv_fold_dy(dy, D, H, W):
+    """The transposed convolution's output gradient as its backward reads it, float64 [N, 2D, 2H, 2W, C]: a replicate-padded plane
+    (dy one plane longer on an odd axis) adds into the plane it copies, axis by axis (corners reach the corner)."""
+    t = dy.double()
+    for ax, S in ((1, D), (2, H), (3, W)):
+        if t.shape[ax] == 2 * S + 1:
+            body = t.narrow(ax, 0, 2 * S).clone()
+            body.narrow(ax, 2 * S - 1, 1).add_(t.narrow(ax, 2 * S, 1))
+            t = body
+    return t
+
+
+def deconv_bwd_ref(x, dyf, w, dtype):
+    """x float64 [N, D, H, W, Cin], dyf = deconv_fold_dy [N, 2D, 2H, 2W, Cout], w [Cin, Cout, 2, 2, 2] (rounded to ``dtype`` as
+    the data-gradient packer rounds it) -> (dx, |dx| terms, squared terms) [N, D, H, W, Cin] and (dw, |dw| terms) like w."""
+    N, D, H, W, Cin = x.shape
+    Cout = dyf.shape[-1]
+    A = dyf.reshape(N, D, 2, H, 2, W, 2, Cout).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(-1, 8 * Cout)
+    wq = (w.half() if dtype == torch.float16 else w.float()).double()
+    Wm = wq.permute(2, 3, 4, 1, 0).reshape(8 * Cout, Cin)
+    dx, ax, sq = A @ Wm, A.abs() @ Wm.abs(), (A * A) @ (Wm * Wm)
+    X = x.double().reshape(-1, Cin)
+    dw = (X.t() @ A).reshape(Cin, 2, 2, 2, Cout).permute(0, 4, 1, 2, 3)
+    aw = (X.abs().t() @ A.abs()).reshape(Cin, 2, 2, 2, Cout).permute(0, 4, 1, 2, 3)
+    shp = (N, D, H, W, Cin)
+    return dx.reshape(shp), ax.reshape(shp), sq.reshape(shp), dw.contiguous(), aw.contiguous()

@@ -182,3 +182,152 @@ def test_fp16_transform_emulation_rounds_once():
     # against the exact function: within one fp16 ulp everywhere
     exact = torch.nn.functional.leaky_relu(raw * sc.double() + sh.double(), 0.1) + add.double()
     assert bool(((got - exact).abs() <= 2 ** -10 * exact.abs() + 2 ** -24).all())
+
+
+# ---- backward bounds ------------------------------------------------------------------------------------------------------------
+WG_DIMS = (8, 8, 24)          # 4x8x8 tiles: 2 x 1 x 3 per sample
+
+
+def _wgrad_case(cin=24, cin_src=17, cout=16, P=4):
+    """The fetch-once weight gradient, simulated in fp32 on fp16-rounded operands as the kernel sums it: per-tile partials,
+    each partition the tiles part, part + P, ... (walking from sample 0 into sample 1), the partitions reduced, added into dw0."""
+    g = torch.Generator().manual_seed(cin + P)
+    N = 2
+    x = torch.randn(N, *WG_DIMS, cin, generator=g).half()
+    dy = torch.randn(N, *WG_DIMS, cout, generator=g).half()
+    dw0 = torch.randn(cout, cin_src, 3, 3, 3, generator=g)
+    ref, ab = R.wgrad_ref(x, 0, cin, dy, 0, cout, cin_src=cin_src)
+    full, _ = R.wgrad_ref(x, 0, cin, dy, 0, cout)                 # every packed channel (the filter's input)
+    D, H, W = WG_DIMS
+    tiles = [(n, d, h, w) for n in range(N) for d in range(0, D, 4) for h in range(0, H, 8) for w in range(0, W, 8)]
+
+    def tile_dw(t):
+        n, d, h, w = t
+        m = torch.zeros(N, *WG_DIMS, 1, dtype=torch.float64)
+        m[n, d:d + 4, h:h + 8, w:w + 8] = 1
+        r, _ = R.wgrad_ref(x, 0, cin, (dy.double() * m).float(), 0, cout)
+        return r.float()
+    parts = []
+    for p in range(P):
+        s = torch.zeros(cout, cin, 3, 3, 3)
+        for t in tiles[p::P]:
+            s = s + tile_dw(t)
+        parts.append(s)
+    total = len(tiles)
+    return dict(x=x, dy=dy, dw0=dw0, ref=ref, ab=ab, full=full, parts=parts, cin_src=cin_src, P=P, total=total,
+                bnd=R.wgrad_bound(ref, ab, dw0, R.wgrad_fo_chain(P, total, "plain")))
+
+
+def _wgrad_got(c, parts=None, cin_src=None):
+    s = sum(c["parts"] if parts is None else parts)
+    cs = c["cin_src"] if cin_src is None else cin_src
+    out = c["dw0"].clone()
+    k = min(cs, c["cin_src"])
+    out[:, :k] += s[:, :k]
+    if cs > c["cin_src"]:              # the filter lets one channel too many through: it lands in the next row of dw
+        flat = out.view(-1, 27)
+        for co in range(s.shape[0]):
+            i = co * c["cin_src"] + c["cin_src"]
+            if i < flat.shape[0]:
+                flat[i] += s[co, c["cin_src"]].reshape(27)
+    return out.double()
+
+
+@pytest.fixture(scope="module")
+def wg():
+    return _wgrad_case()
+
+
+def test_wgrad_bound_accepts_the_kernels_summation(wg):
+    res = R.check(_wgrad_got(wg), wg["dw0"].double() + wg["ref"], wg["bnd"])
+    assert res.ratio <= 1.0, res
+
+
+def test_wgrad_bound_rejects_a_dropped_partition(wg):
+    res = R.check(_wgrad_got(wg, parts=wg["parts"][:1] + wg["parts"][2:]), wg["dw0"].double() + wg["ref"], wg["bnd"])
+    assert res.ratio > 1.0, res
+
+
+def test_wgrad_bound_rejects_a_partition_counted_twice(wg):
+    res = R.check(_wgrad_got(wg, parts=wg["parts"] + wg["parts"][2:3]), wg["dw0"].double() + wg["ref"], wg["bnd"])
+    assert res.ratio > 1.0, res
+
+
+@pytest.mark.parametrize("cin_src", [16, 18])
+def test_wgrad_bound_rejects_the_source_channel_filter_off_by_one(wg, cin_src):
+    res = R.check(_wgrad_got(wg, cin_src=cin_src), wg["dw0"].double() + wg["ref"], wg["bnd"])
+    assert res.ratio > 1.0, res
+
+
+def test_wgrad_bound_rejects_a_tap_shifted_at_the_border(wg):
+    """Tap kw = 2 reads voxel w + 1: at the last plane the kernel must read zero; here it reads the row's first voxel (wrap)."""
+    x, dy = wg["x"], wg["dy"]
+    W = WG_DIMS[2]
+    wrong = x.double()[:, :, :, 0:1]                             # what the wrapped tap reads at w = W - 1
+    extra = torch.zeros(dy.shape[-1], x.shape[-1], 3, 3, 3, dtype=torch.float64)
+    xp = torch.zeros(2, WG_DIMS[0] + 2, WG_DIMS[1] + 2, 1, x.shape[-1], dtype=torch.float64)
+    xp[:, 1:-1, 1:-1] = wrong
+    g = dy.double()[:, :, :, W - 1]
+    for kd in range(3):
+        for kh in range(3):
+            xs = xp[:, kd:kd + WG_DIMS[0], kh:kh + WG_DIMS[1], 0]
+            extra[:, :, kd, kh, 2] = g.reshape(-1, g.shape[-1]).t() @ xs.reshape(-1, x.shape[-1])
+    got = _wgrad_got(wg) + extra[:, :wg["cin_src"]]
+    res = R.check(got, wg["dw0"].double() + wg["ref"], wg["bnd"])
+    assert res.ratio > 1.0, res
+
+
+def _in_bwd_case():
+    """InstanceNorm + LeakyReLU backward simulated in the kernels' fp32 arithmetic (fp32 mean / rstd from the statistics, zh,
+    z, the slope, per-element then summed), and its fp64 reference."""
+    g = torch.Generator().manual_seed(3)
+    N, V, C = 2, 4096, 16
+    raw = (torch.randn(N, V, C, generator=g) * 1.5 + 0.3).half()
+    dA = torch.randn(N, V, C, generator=g).half()
+    gamma = torch.rand(C, generator=g) + 0.5
+    beta = torch.randn(C, generator=g) * 0.2
+    rd = raw.double()
+    sums = torch.stack([rd.sum(1), (rd * rd).sum(1)], -1)
+    r = R.in_bwd_ref(dA, raw, sums, gamma, beta, V)
+    mu, rs = r["mean"].float()[:, None], r["rstd"].float()[:, None]
+    zh = (raw.float() - mu) * rs
+    z = zh * gamma + beta
+    d = dA.float()
+    slope = torch.tensor(R.SLOPE, dtype=torch.float32)
+    return dict(r=r, zh=zh, z=z, d=d, slope=slope, gamma=gamma, rs=rs, V=V)
+
+
+def _in_bwd_sim(c, flip=None):
+    dz = torch.where(c["z"] > 0, c["d"], c["d"] * c["slope"])
+    if flip is not None:                              # one element takes the other slope
+        n, v, ch = flip
+        dz[n, v, ch] = c["d"][n, v, ch] * c["slope"] if c["z"][n, v, ch] > 0 else c["d"][n, v, ch]
+    S1, S2 = dz.double().sum(1).float(), (dz * c["zh"]).double().sum(1).float()
+    V = c["V"]
+    dY = (c["gamma"] * c["rs"] * (dz - (S1 / V)[:, None] - c["zh"] * (S2 / V)[:, None])).half()
+    return S1.double(), S2.double(), dY.double()
+
+
+def test_instnorm_backward_bound_accepts_the_kernels_arithmetic():
+    c = _in_bwd_case()
+    r = c["r"]
+    b0, b1, b2 = R.in_bwd_sums_bound(r, R.in_bwd_reduce_chain(16, c["V"], torch.float16))
+    S1, S2, dY = _in_bwd_sim(c)
+    assert R.check(S1, r["S1"], b1).ratio <= 1.0 and R.check(S2, r["S2"], b2).ratio <= 1.0
+    res = R.check(dY, r["dY"], R.in_bwd_dy_bound(r, b1, b2, torch.float16))
+    assert res.ratio <= 1.0, res
+
+
+def test_instnorm_backward_bound_rejects_a_wrong_slope_outside_the_kink_margin():
+    c = _in_bwd_case()
+    r = c["r"]
+    b0, b1, b2 = R.in_bwd_sums_bound(r, R.in_bwd_reduce_chain(16, c["V"], torch.float16))
+    # the element with the largest |dA| among those whose z lies outside the margin but within 0.05 of the kink
+    cand = (~r["near"]) & (r["z"].abs() < 0.05)
+    score = torch.where(cand, r["d"].abs(), torch.zeros_like(r["d"]))
+    k = int(torch.argmax(score))
+    flip = tuple(int(i) for i in torch.unravel_index(torch.tensor(k), score.shape))
+    S1, S2, dY = _in_bwd_sim(c, flip)
+    res = R.check(dY, r["dY"], R.in_bwd_dy_bound(r, b1, b2, torch.float16))
+    assert res.ratio > 1.0, res
+    assert tuple(res.where) == flip

@@ -803,13 +803,27 @@ def test_batched_weight_packing_equals_the_per_layer_calls():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", [32, 1, 2, 64])  # plain k loop; plain block order; one workgroup per CU; 12 waves
+@pytest.mark.parametrize("variant", [4, 8, 16,         # fetch-once form: 2, 4, 8 workgroups per CU (distinct partition counts)
+                                     256,              # three-kd form: 12 waves, LDS-DMA
+                                     256 | 128,        # ... 12 waves, register prefetch
+                                     256 | 64,         # ... 6 waves, pipelined k loop
+                                     256 | 32,         # ... 6 waves, plain k loop
+                                     256 | 1])         # ... plain block order
 def test_conv3_wgrad_launch_variants_agree(variant):
+    """Each variant reaches another kernel or launch shape than the default (fetch-once form, one workgroup per CU): 48^3 at
+    batch 2 has 864 fetch-once tiles, so none of the partition counts 128 / 256 / 512 / 864 is clamped to the same value."""
     ops = _ops()
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(variant)
-    x = torch.randn(2, 12, 16, 16, 64, generator=g, device=dev).half()
-    dy = torch.randn(2, 12, 16, 16, 64, generator=g, device=dev).half()
+    x = torch.randn(2, 48, 48, 48, 64, generator=g, device=dev).half()
+    dy = torch.randn(2, 48, 48, 48, 64, generator=g, device=dev).half()
+    import ctypes
+    from diff_unet_amos_amd import _native as nv
+
+    def ws_bytes(policy):
+        d = nv.Conv3Desc(nv.dt_code(torch.float16), 2, 48, 48, 48, 64, 64, 0, 64, 64, 0, 0, 0, 0, policy)
+        return int(nv.lib().dua_conv3d_k3_wgrad_workspace(ctypes.byref(d)))
+    assert variant & 256 or ws_bytes(variant) != ws_bytes(0)          # a fetch-once variant changes the partition count
     base = torch.zeros(64, 64, 3, 3, 3, device=dev)
     _ops().conv3d_k3_wgrad(x, 64, 0, dy, 64, 0, base)
     ops.WGRAD_POLICY = variant
