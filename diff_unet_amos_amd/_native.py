@@ -20,7 +20,9 @@ if os.environ.get("DUA_DEBUG") == "1" and os.environ.get("DUA_HIP_LIB"):
     LIB_PATH = os.environ["DUA_HIP_LIB"]
 
 F32, F16 = 0, 1
+U8 = 2                    # DUA_U8: uint8 / bool masks of the surface-distance entry points
 ERR_ARG = -22
+SURFACE_FIELDS = ("hd", "hd95", "asd", "assd", "tp", "fp", "fn", "tn", "hd95_lo", "hd95_hi", "asd_ba", "n_surface")
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -215,6 +217,11 @@ _SIGS = {
     "dua_adamw_step": (C.c_int, [C.POINTER(AdamWList), C.c_float, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
                                  C.c_int, _P]),
     "dua_adamw_advance": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_int, _P, _P]),
+    "dua_surface_scratch_bytes": (C.c_long, [C.c_int] * 4),
+    "dua_surface_masks": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int, _P, C.c_long, _P, _P]),
+    "dua_surface_edt_sq": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "dua_surface_distance_table": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
+                                   [C.c_double] * 3 + [C.c_int, _P, _P, _P, C.c_long, _P]),
 }
 
 _lib = None

@@ -1510,3 +1510,83 @@ def swin_mlp(ln2, w1, b1, w2, b2, x):
     nv.check(nv.lib().dua_swin_mlp(M, Cc, nv.ptr(ln2), nv.ptr(w1), nv.ptr(b1), nv.ptr(w2), nv.ptr(b2), nv.ptr(x), nv.stream_ptr()),
              "dua_swin_mlp")
     return x
+
+
+# ---- evaluation: surface distances (csrc/surface.hip; metric.py:314-390) ------------------------------------------------------
+
+def _surface_mask(t, name):
+    """A [..., D, H, W] device mask as (tensor, dtype code, volumes, D, H, W): fp32 or uint8 / bool (read as uint8), each
+    volume dense (a non-contiguous tensor is copied first)."""
+    assert t.is_cuda, f"{name}: libdua_hip.so entry points take device tensors"
+    assert t.dim() >= 3, f"{name}: [..., D, H, W] masks"
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype == torch.float32:
+        code = nv.F32
+    elif t.dtype == torch.uint8:
+        code = nv.U8
+    else:
+        raise TypeError(f"{name}: surface masks are float32, uint8 or bool, not {t.dtype}")
+    t = t.contiguous()
+    D, H, W = t.shape[-3:]
+    return t, code, t.numel() // max(D * H * W, 1), D, H, W
+
+
+def _spacing3(voxel_spacing):
+    if voxel_spacing is None:
+        return (1.0, 1.0, 1.0)
+    if isinstance(voxel_spacing, (int, float)):
+        return (float(voxel_spacing),) * 3
+    s = tuple(float(x) for x in voxel_spacing)
+    if len(s) == 1:
+        s = s * 3
+    if len(s) != 3:
+        raise ValueError(f"voxel_spacing: a scalar or three values (d, h, w), got {voxel_spacing!r}")
+    return s
+
+
+def surface_masks(test, reference, connectivity=1):
+    """dua_surface_masks: (surf uint8 [V, D, H, W] = border(test) in bit 0 | border(reference) in bit 1, counts int64 [V, 5] =
+    |A|, |B|, |A & B|, |border A|, |border B|), V = the product of the leading dimensions."""
+    a, ca, V, D, H, W = _surface_mask(test, "test")
+    b, cb, Vb, *ext = _surface_mask(reference, "reference")
+    assert (Vb, *ext) == (V, D, H, W), "test and reference must have the same shape"
+    surf = torch.empty((V, D, H, W), dtype=torch.uint8, device=a.device)
+    counts = torch.empty((V, 5), dtype=torch.int64, device=a.device)
+    vox = D * H * W
+    nv.check(nv.lib().dua_surface_masks(V, D, H, W, nv.ptr(a), ca, vox, nv.ptr(b), cb, vox, int(connectivity), nv.ptr(surf), vox,
+                                        nv.ptr(counts), nv.stream_ptr()), "dua_surface_masks")
+    return surf, counts
+
+
+def surface_edt_sq(seeds, voxel_spacing=None, seed_mask=1):
+    """dua_surface_edt_sq: fp64 [V, D, H, W] squared distance (offsets scaled by voxel_spacing = (d, h, w)) to the nearest voxel
+    of seeds (uint8 [..., D, H, W]) with a bit of seed_mask set; +inf in a volume without seeds."""
+    assert seeds.is_cuda and seeds.dtype in (torch.uint8, torch.bool)
+    s, _, V, D, H, W = _surface_mask(seeds, "seeds")
+    sd, sh, sw = _spacing3(voxel_spacing)
+    out = torch.empty((V, D, H, W), dtype=torch.float64, device=s.device)
+    nv.check(nv.lib().dua_surface_edt_sq(V, D, H, W, nv.ptr(s), D * H * W, int(seed_mask), sd, sh, sw, nv.ptr(out),
+                                         nv.stream_ptr()), "dua_surface_edt_sq")
+    return out
+
+
+def surface_distance_table(test, reference, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True):
+    """dua_surface_distance_table for every volume of test / reference ([..., D, H, W], same shape): (counts int64 [V, 5],
+    table fp64 [V, len(nv.SURFACE_FIELDS)] with columns nv.SURFACE_FIELDS).  No host synchronisation."""
+    a, ca, V, D, H, W = _surface_mask(test, "test")
+    b, cb, Vb, *ext = _surface_mask(reference, "reference")
+    assert (Vb, *ext) == (V, D, H, W), "test and reference must have the same shape"
+    sd, sh, sw = _spacing3(voxel_spacing)
+    L = nv.lib()
+    need = int(L.dua_surface_scratch_bytes(V, D, H, W))
+    if need < 0:
+        raise ValueError(f"surface distances: unsupported extents V={V}, D={D}, H={H}, W={W}")
+    ws = torch.empty(need, dtype=torch.uint8, device=a.device)
+    counts = torch.empty((V, 5), dtype=torch.int64, device=a.device)
+    out = torch.empty((V, len(nv.SURFACE_FIELDS)), dtype=torch.float64, device=a.device)
+    vox = D * H * W
+    nv.check(L.dua_surface_distance_table(V, D, H, W, nv.ptr(a), ca, vox, nv.ptr(b), cb, vox, int(connectivity), sd, sh, sw,
+                                          int(bool(nan_for_nonexisting)), nv.ptr(counts), nv.ptr(out), nv.ptr(ws), need,
+                                          nv.stream_ptr()), "dua_surface_distance_table")
+    return counts, out

@@ -725,6 +725,58 @@ int dua_from_channels_last(int dtype, int N, int C, long voxels, const void* src
 int dua_to_channels_last_rows(int dtype, int N, int C0, const float* src0, int C1, const float* src1, long voxels, void* dst,
                               int Cstride, void* stream);
 
+/* ---- evaluation: surface distances ---------------------------------------------------------------------------------
+ * hausdorff_distance, hausdorff_distance_95, avg_surface_distance and avg_surface_distance_symmetric of
+ * light_training/evaluation/metric.py:314-390 (medpy.metric.binary hd / hd95 / asd / assd behind the reference's wrappers),
+ * for V = N * C pairs of 3-D binary volumes [D][H][W] at once.  For one pair A (test), B (reference), spacing s = (sd, sh, sw)
+ * and connectivity k in 1..3:
+ *   border(X) = X & ~erode(X): one binary erosion with generate_binary_structure(3, k) (6, 18 or 26 neighbours and the
+ *               centre) and border_value 0, so a foreground voxel on a face of the volume is always a surface voxel;
+ *   sds(A, B) = for every voxel of border(A), the Euclidean distance (offsets scaled by s) to the nearest voxel of border(B);
+ *   hd = max(max sds(A,B), max sds(B,A)); hd95 = np.percentile(concat(sds(A,B), sds(B,A)), 95) (linear interpolation);
+ *   asd = mean sds(A,B) (directed, test -> reference); assd = (asd(A,B) + asd(B,A)) / 2;
+ *   wrapper rule: A or B empty, or A or B full -> NaN (0 with nan_for_nonexisting = 0).
+ * Masks: DUA_F32 (fp32, what binarise returns) or DUA_U8 (uint8 / bool), non-zero = foreground; volume v (= n C + c) starts
+ * vstride elements after volume v - 1 and is dense [D][H][W].  Extents 1..DUA_SURFACE_MAX_EXTENT, V <= 65535.  Spacings must
+ * be finite and > 0.  Squared distances are exact minima in fp64; every sum has a fixed order and every atomic is an integer
+ * one (two calls on the same masks agree bit for bit).  Invalid arguments: DUA_ERR_ARG, before the device is touched. */
+#define DUA_U8 2
+#define DUA_SURFACE_MAX_EXTENT 4096
+/* fields of one row of dua_surface_distance_table's out (fp64 [V][DUA_SURFACE_FIELDS]) */
+#define DUA_SURFACE_HD 0
+#define DUA_SURFACE_HD95 1
+#define DUA_SURFACE_ASD 2        /* mean sds(A, B): test -> reference */
+#define DUA_SURFACE_ASSD 3
+#define DUA_SURFACE_TP 4         /* |A & B| */
+#define DUA_SURFACE_FP 5         /* |A & ~B| */
+#define DUA_SURFACE_FN 6         /* |~A & B| */
+#define DUA_SURFACE_TN 7         /* |~A & ~B| */
+#define DUA_SURFACE_HD95_LO 8    /* the two order statistics hd95 interpolates between (floor and floor + 1 of 0.95 (n - 1)) */
+#define DUA_SURFACE_HD95_HI 9
+#define DUA_SURFACE_ASD_BA 10    /* mean sds(B, A) */
+#define DUA_SURFACE_NSURF 11     /* |border A| + |border B| */
+#define DUA_SURFACE_FIELDS 12
+
+/* Bytes of workspace dua_surface_distance_table needs (DUA_ERR_ARG for bad extents): the surface bytes, two fp64 distance
+ * volumes per pair and the per-block partial sums. */
+long dua_surface_scratch_bytes(int V, int D, int H, int W);
+/* The surface pass on its own: surf (uint8 [V][surf_vstride], WRITTEN) = border(A) in bit 0 | border(B) in bit 1 per voxel,
+ * bytes [D H W, surf_vstride) of a volume 0; counts (int64 [V][5], WRITTEN) = |A|, |B|, |A & B|, |border A|, |border B|. */
+int dua_surface_masks(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride, const void* reference,
+                      int reference_dtype, long reference_vstride, int connectivity, unsigned char* surf, long surf_vstride,
+                      unsigned long long* counts, void* stream);
+/* The exact squared distance transform on its own: out (fp64 [V][D][H][W], WRITTEN) = squared distance, offsets scaled by
+ * (sd, sh, sw), to the nearest voxel whose byte of seeds (uint8 [V][seeds_vstride]) has a bit of seed_mask set; +inf in a
+ * volume without seeds. */
+int dua_surface_edt_sq(int V, int D, int H, int W, const unsigned char* seeds, long seeds_vstride, int seed_mask, double sd,
+                       double sh, double sw, double* out, void* stream);
+/* The whole table: counts as dua_surface_masks, out (fp64 [V][DUA_SURFACE_FIELDS], WRITTEN).  workspace: at least
+ * dua_surface_scratch_bytes(V, D, H, W) bytes, 256-byte aligned. */
+int dua_surface_distance_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride,
+                               const void* reference, int reference_dtype, long reference_vstride, int connectivity, double sd,
+                               double sh, double sw, int nan_for_nonexisting, unsigned long long* counts, double* out,
+                               void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
