@@ -20,20 +20,18 @@ uses_native_kernels = True
 
 
 class _TembState:
-    """What the TwoConv blocks of one evaluation share about their timestep-embedding adds: every block reads its [N, cout]
-    rows of ONE block-major buffer (ops.temb_train_fwd) and, in backward, writes the gradient of its rows into ONE buffer
-    of the same layout; the block that ran FIRST in forward -- whose backward node can only run after every other block's,
-    since all of them consume its output -- hands that buffer to autograd as the gradient of the whole add tensor (the
-    others return None: the engine counts a node's dependencies whether or not a gradient came with them).  Nine slice
-    views would have cost nine zero-fills, copies and accumulations of a [N, 1536] tensor per step instead."""
+    """What the TwoConv blocks of one evaluation share about their timestep-embedding adds: block i (native_logits_cl's run
+    order) reads rows ``rows(add, i)`` of ONE block-major buffer (ops.temb_train_fwd) and, in backward, writes the gradient of
+    its rows into ONE buffer of the same layout; the block that ran FIRST in forward -- whose backward node can only run after
+    every other block's, since all of them consume its output -- hands that buffer to autograd as the gradient of the whole
+    add tensor (the others return None: the engine counts a node's dependencies whether or not a gradient came with them).
+    Nine slice views would have cost nine zero-fills, copies and accumulations of a [N, 1536] tensor per step instead."""
 
     def __init__(self, N, couts):
         self.N, self.couts = N, list(couts)
         self.offs = [sum(self.couts[:i]) for i in range(len(self.couts))]
         self.P = sum(self.couts)
         self.dadd = None
-        self.next = 0          # forward call counter: block i of this evaluation
-        self.written = 0
 
     def rows(self, flat, i):
         a = self.N * self.offs[i]
@@ -144,58 +142,25 @@ def _channel_sums(t, c, c_off):
     return ops.stats_channel_sums(st, c)            # decode + sum over the samples in one launch (twelve torch launches before)
 
 
-class _Conv3dK3(torch.autograd.Function):
-    """y = conv3d(x, w, b), 3x3x3 / pad 1, channels-last.  forward: dua_conv3d_k3_fwd; backward: the same kernel on
-    dy with the weights flipped and transposed (data gradient) + dua_conv3d_k3_wgrad (weight gradient)."""
-
-    @staticmethod
-    def _run(x, w, bias, cout):
-        from . import ops
-        N, D, H, W, cs = x.shape
-        wp, bp = ops.pack_conv3_weights(w, bias, x.dtype, cin_packed=cs, pad_bias=False)
-        y = torch.empty((N, D, H, W, cout), dtype=x.dtype, device=x.device)
-        stats = ops.stats_buffer(N, cout, x.device)
-        ops.conv3d_k3(x, cs, 0, wp, bp, cout, y, 0, stats, workspace=ops.splitk_ws(x.dtype, N, D, H, W, cs, cout, x.device))
-        return y
-
-    @staticmethod
-    def _dgrad(dy, w, cin_padded, packs=None):
-        """dx [.., cin_padded] = data gradient: the forward kernel on dy with W' packed straight from w (or taken from the
-        evaluation's batch-packed weights, ops.ConvPacks)."""
-        from . import ops
-        N, D, H, W, cs = dy.shape
-        wp = packs.get(w, "dgrad", cs) if packs is not None else None
-        if wp is not None:
-            bp = ops.zero_bias(w.shape[1], w.device)
-        else:
-            wp, bp = ops.pack_conv3_weights_dgrad(w, dy.dtype, cout_packed=cs)
-        dx = torch.empty((N, D, H, W, cin_padded), dtype=dy.dtype, device=dy.device)
+def _dgrad(dy, w, cin_padded, packs=None, owner=None):
+    """dx [.., cin_padded] = data gradient of a 3x3x3 / pad 1 convolution: the forward kernel on dy with W' (weights flipped
+    and transposed) packed straight from w or taken from the evaluation's batch-packed weights (ops.ConvPacks).  ``owner`` =
+    (raw, norm, sums) of the layer whose dA dx is: the launch adds that layer's InstanceNorm-backward reduce sums to ``sums``
+    instead of taking statistics of dx (ops.conv3d_k3_dgrad_reduce)."""
+    from . import ops
+    N, D, H, W, cs = dy.shape
+    wp = packs.get(w, "dgrad", cs) if packs is not None else None
+    if wp is not None:
+        bp = ops.zero_bias(w.shape[1], w.device)
+    else:
+        wp, bp = ops.pack_conv3_weights_dgrad(w, dy.dtype, cout_packed=cs)
+    dx = torch.empty((N, D, H, W, cin_padded), dtype=dy.dtype, device=dy.device)
+    if owner is not None:
+        ops.conv3d_k3_dgrad_reduce(dy, cs, wp, bp, cin_padded, dx, *owner)
+    else:
         ops.conv3d_k3(dy, cs, 0, wp, bp, cin_padded, dx, 0, ops.stats_buffer(N, cin_padded, dy.device),
                       workspace=ops.splitk_ws(dy.dtype, N, D, H, W, cs, cin_padded, dy.device))
-        return dx
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        assert x.is_contiguous() and x.shape[-1] % 8 == 0 and weight.shape[0] % 8 == 0 and weight.shape[1] <= x.shape[-1]
-        ctx.save_for_backward(x, weight)
-        return _Conv3dK3._run(x, weight.detach().float().contiguous(), bias.detach().float(), weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        from . import ops
-        x, weight = ctx.saved_tensors
-        dy = dy.contiguous()
-        cout, cin = weight.shape[:2]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _Conv3dK3._dgrad(dy, weight.detach().float().contiguous(), x.shape[-1])
-        if ctx.needs_input_grad[1]:
-            dw = ops.zeros((cout, cin, 3, 3, 3), torch.float32, x.device)
-            _wgrad(x, dy, cout, dw)
-            dw = dw.to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            db = _channel_sums(dy, cout, 0)
-        return dx, dw, db
+    return dx
 
 
 def _cl_pad(parts, dtype):
@@ -251,7 +216,7 @@ class _UpCat(torch.autograd.Function):
         assert lo.is_contiguous() and lo.shape[-1] == cin and cin % 8 == 0 and cout % 8 == 0 and cs % 8 == 0
         buf, off = _slice_of(skip)
         if buf is not skip and off == 0 and buf.shape[-1] == cs + cout:
-            cat = buf                # the skip was materialised straight into its concat buffer (_ConvNormAct, cat_extra): no copy
+            cat = buf                # the skip was materialised straight into its concat buffer (_conv_norm_act, cat_extra): no copy
         else:
             cat = torch.empty((N, D, H, W, cs + cout), dtype=skip.dtype, device=skip.device)
             cat[..., :cs].copy_(skip)
@@ -274,141 +239,134 @@ class _UpCat(torch.autograd.Function):
         return dx, (dcat[..., :cs] if ctx.needs_input_grad[1] else None), dw, db
 
 
-class _BwdLink:
-    """Hand-over between the two blocks of a TwoConv in backward: block b's data-gradient launch produces block a's dA and can take
-    the reduce pass of a's InstanceNorm backward along (ops.conv3d_k3_dgrad_reduce).  a.forward deposits what that needs; b.backward
-    (which runs first) leaves the sums and the address of the dA they belong to; a.backward uses them if that is the dA it gets."""
+def _conv_norm_act(x, weight, bias, gamma, beta, packs, fold=None, add=None, emb=None, cat_extra=0, pool=False):
+    """a = LeakyReLU(InstanceNorm(conv3d(x, w, b))) [+ add[n, c]] [+ emb] -- one MONAI Convolution block (+ the temb add / the
+    encoder embedding that follow it in TwoConv.forward / BasicUNetRDenoiser.forward): conv (raw output + statistics in its
+    epilogue) -> materialize.  ``add``: fp32 [N, cout] rows.
+    ``cat_extra`` > 0: the activation is the skip of a decoder level -- it is written into channels [0, cout) of a buffer
+    with ``cat_extra`` more channels (the half the transposed convolution fills later, _UpCat) and returned as that view:
+    torch.cat((x_e, upsampled)) (denoiser.py:190) costs no copy (226 MB moved per step at level 0 otherwise).
+    ``fold`` = (lo, deconv weight, deconv bias, skip channels): ``x`` is the concat buffer _UpCat filled from ``lo``; the
+    convolution then runs as the folded launch on (skip half of x, lo) with composed weights (dua_upconv_k3_fwd, 58 instead
+    of 196 GFLOP per sample for the upsampled half at level 0); backward is unchanged and reads x as before.
+    Returns (a, pooled or None, raw, the normalisation descriptor backward uses)."""
+    from . import ops
+    N, D, H, W, cs = x.shape
+    cout = weight.shape[0]
+    assert x.is_contiguous() and cs % 8 == 0 and cout % 8 == 0 and weight.shape[1] <= cs
+    wp = packs.get(weight.detach(), "fwd", cs) if packs is not None else None          # batch-packed at the start of the evaluation
+    if wp is not None:
+        bp = bias.detach().float().contiguous()
+    else:
+        wp, bp = ops.pack_conv3_weights(weight.detach().float().contiguous(), bias.detach().float(), x.dtype, cin_packed=cs,
+                                        pad_bias=False)
+    raw = torch.empty((N, D, H, W, cout), dtype=x.dtype, device=x.device)
+    stats = ops.stats_buffer(N, cout, x.device)
+    if fold is not None:
+        lo, wd, bd, cskip = fold
+        w_skip, wu, btab = ops.pack_upconv_weights(weight.detach().float().contiguous(), bias.detach().float(),
+                                                   wd.detach().float().contiguous(), bd.detach().float(), cskip, x.dtype)
+        ops.upconv_k3(x, cskip, 0, lo, lo.shape[-1], 0, None, w_skip, wu, btab, cout, raw, 0, stats)
+    else:
+        ops.conv3d_k3(x, cs, 0, wp, bp, cout, raw, 0, stats, workspace=ops.splitk_ws(x.dtype, N, D, H, W, cs, cout, x.device))
+    g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+    norm = ops.Norm(stats, g32, b32, D * H * W, add=add, add_stride=cout)
+    if cat_extra:
+        cat = torch.empty((N, D, H, W, cout + cat_extra), dtype=x.dtype, device=x.device)
+        act = cat[..., :cout]
+    else:
+        cat = act = torch.empty_like(raw)
+    pooled = torch.empty((N, D // 2, H // 2, W // 2, cout), dtype=x.dtype, device=x.device) if pool else None
+    ops.materialize(raw, cout, norm, cat, 0, emb=emb.detach() if emb is not None else None, pooled=pooled)
+    return act, pooled, raw, ops.Norm(stats, g32, b32, D * H * W)
 
-    def __init__(self):
-        self.raw = self.stats = self.g32 = self.b32 = self.sums = None
-        self.count = 0
-        self.da_ptr = None
+
+def _conv_norm_act_bwd(dA, dP, x, weight, raw, norm, act, packs, need_dx, need_dw, sums=None, dadd_out=None, owner=None):
+    """Backward of _conv_norm_act from dA (and dP, the pooled copy's gradient, with ``act`` the activation it was pooled
+    from): MaxPool backward -> norm/activation backward (reduce + apply; ``sums``: the reduce pass, when the launch that
+    produced dA took it along) -> data gradient (conv kernel) + weight gradient kernel.  ``dadd_out``: where the gradient of
+    the add rows goes.  ``owner`` = (raw, norm) of the layer whose activation x is: where the shape allows, the data-gradient
+    launch takes that layer's reduce sums along (ops.conv3d_k3_dgrad_reduce).
+    Returns (dx, (dw, db, dgamma, dbeta), the whole dA, the owner's sums or None)."""
+    from . import ops
+    N, D, H, W, cout = raw.shape
+    cin = x.shape[-1]
+    buf, off = _slice_of(dA) if dA is not None else (None, 0)       # a concat half's gradient is read in place
+    if act is not None and dP is not None:       # MaxPool3d(2) backward + the skip-path gradient in one pass
+        abuf, aoff = _slice_of(act)         # the activation may live in its decoder's concat buffer (cat_extra)
+        dA = buf = ops.maxpool2_bwd_add(abuf, aoff, cout, buf, off, dP.contiguous())
+        off = 0
+    dY = torch.empty_like(raw)
+    dgamma, dbeta, _ = ops.instnorm_bwd(buf, off, raw, cout, norm, dY, want_add=dadd_out is not None, dadd_out=dadd_out, sums=sums)
+    dx = dw = owner_sums = None
+    if need_dx:
+        if (owner is not None and ops.TRAIN_DGRAD_REDUCE and cin == owner[0].shape[-1]
+                and ops.conv3d_k3_dgrad_reduce_supported(dY.dtype, N, D, H, W, cout, cin)):
+            owner_sums = ops.instnorm_bwd_sums(*owner)
+        dx = _dgrad(dY, weight.detach().float().contiguous(), cin, packs,
+                    owner=(*owner, owner_sums) if owner_sums is not None else None)
+    if need_dw:
+        dw = ops.zeros(tuple(weight.shape), torch.float32, x.device)
+        _wgrad(x, dY, cout, dw)
+    db = ops.zeros((cout,), torch.float32, x.device)      # bias before InstanceNorm: sum(dY) == 0 exactly
+    return dx, (dw, db, dgamma, dbeta), dA, owner_sums
 
 
-class _ConvNormAct(torch.autograd.Function):
-    """a = LeakyReLU(InstanceNorm(conv3d(x, w, b))) [+ add[n, c]] [+ emb] -- one MONAI Convolution block (+ the temb bias /
-    the encoder embedding that follow it in TwoConv.forward / BasicUNetRDenoiser.forward), all on the HIP kernels:
-    forward  = conv (raw output + statistics in its epilogue) -> materialize;
-    backward = norm/activation backward (reduce + apply) -> data gradient (conv kernel) + weight gradient kernel."""
+class _TwoConv(torch.autograd.Function):
+    """One MONAI TwoConv block -- conv_0 [+ the temb add], conv_1 [+ the encoder embedding] (TwoConv.forward /
+    BasicUNetRDenoiser.forward), two _conv_norm_act layers -- as ONE autograd node.  Backward runs conv_1's part, then
+    conv_0's: conv_1's data gradient is conv_0's dA, and where the shape allows that launch takes the reduce pass of conv_0's
+    InstanceNorm backward along (ops.conv3d_k3_dgrad_reduce); the sums go straight into conv_0's norm backward."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, add, emb, pool=False, cat_extra=0, temb_state=None, temb_index=0, packs=None,
-                fold=None, link_out=None, link_in=None):
-        """``temb_state``: ``add`` is the block-major add buffer of the whole evaluation (_TembAdds) and this block uses rows
-        ``temb_index`` of it (_TembState); otherwise ``add`` is this block's own [N, cout] tensor or None.
-        ``cat_extra`` > 0: the activation is the skip of a decoder level -- it is written into channels [0, cout) of a buffer
-        with ``cat_extra`` more channels (the half the transposed convolution fills later, _UpCat) and returned as that view:
-        torch.cat((x_e, upsampled)) (denoiser.py:190) costs no copy (226 MB moved per step at level 0 otherwise).
-        ``fold`` = (lo, deconv weight, deconv bias, skip channels): ``x`` is the concat buffer _UpCat filled from ``lo``; the
-        FORWARD convolution then runs as the folded launch on (skip half of x, lo) with composed weights (dua_upconv_k3_fwd, 58
-        instead of 196 GFLOP per sample for the upsampled half at level 0); backward is unchanged and reads x as before."""
-        from . import ops
-        N, D, H, W, cs = x.shape
-        cout = weight.shape[0]
-        assert x.is_contiguous() and cs % 8 == 0 and cout % 8 == 0 and weight.shape[1] <= cs
-        wp = packs.get(weight.detach(), "fwd", cs) if packs is not None else None          # batch-packed at the start of the evaluation
-        if wp is not None:
-            bp = bias.detach().float().contiguous()
-        else:
-            wp, bp = ops.pack_conv3_weights(weight.detach().float().contiguous(), bias.detach().float(), x.dtype, cin_packed=cs,
-                                            pad_bias=False)
-        ctx.packs = packs
-        raw = torch.empty((N, D, H, W, cout), dtype=x.dtype, device=x.device)
-        stats = ops.stats_buffer(N, cout, x.device)
-        if fold is not None:
-            lo, wd, bd, cskip = fold
-            w_skip, wu, btab = ops.pack_upconv_weights(weight.detach().float().contiguous(), bias.detach().float(),
-                                                       wd.detach().float().contiguous(), bd.detach().float(), cskip, x.dtype)
-            ops.upconv_k3(x, cskip, 0, lo, lo.shape[-1], 0, None, w_skip, wu, btab, cout, raw, 0, stats)
-        else:
-            ops.conv3d_k3(x, cs, 0, wp, bp, cout, raw, 0, stats, workspace=ops.splitk_ws(x.dtype, N, D, H, W, cs, cout, x.device))
-        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        if add is not None and temb_state is not None:
-            a32 = temb_state.rows(add.detach(), temb_index)
-        else:
-            a32 = add.detach().float().contiguous() if add is not None else None
-        norm = ops.Norm(stats, g32, b32, D * H * W, add=a32, add_stride=cout)
-        if cat_extra:
-            cat = torch.empty((N, D, H, W, cout + cat_extra), dtype=x.dtype, device=x.device)
-            act = cat[..., :cout]
-        else:
-            cat = act = torch.empty_like(raw)
-        pooled = torch.empty((N, D // 2, H // 2, W // 2, cout), dtype=x.dtype, device=x.device) if pool else None
-        ops.materialize(raw, cout, norm, cat, 0, emb=emb.detach() if emb is not None else None, pooled=pooled)
-        ctx.save_for_backward(x, weight, raw, stats, g32, b32, act if pool else None)
-        ctx.link_out, ctx.link_in = link_out, link_in           # _BwdLink: this block's output feeds link_out's consumer / its input is link_in's
-        if link_out is not None:
-            link_out.raw, link_out.stats, link_out.g32, link_out.b32, link_out.count = raw, stats, g32, b32, D * H * W
-        ctx.has_add, ctx.has_emb, ctx.pool = add is not None, emb is not None, pool
-        ctx.temb_state, ctx.temb_index = (temb_state, temb_index) if add is not None else (None, 0)
+    def forward(ctx, x, w0, b0, g0, be0, w1, b1, g1, be1, add, emb, pool, cat_extra, temb, packs, fold):
+        """``add``: None, or the block-major add buffer of the whole evaluation (_TembAdds) with ``temb`` = (_TembState,
+        index): conv_0 adds this block's rows of it.  ``fold`` goes to conv_0, ``emb``, ``cat_extra`` and ``pool`` to conv_1
+        (_conv_norm_act).  Returns conv_1's activation, and its pooled copy when ``pool``."""
+        a0 = temb[0].rows(add.detach(), temb[1]) if add is not None else None
+        h, _, raw0, norm0 = _conv_norm_act(x, w0, b0, g0, be0, packs, fold=fold, add=a0)
+        act, pooled, raw1, norm1 = _conv_norm_act(h, w1, b1, g1, be1, packs, emb=emb, cat_extra=cat_extra, pool=pool)
+        # each layer's backward operands on ctx, not saved tensors: conv_1's are dropped as soon as its part of backward is
+        # done, as when the layers were two nodes; act is held detached, so ctx references no output of this node
+        ctx.layers = [(x, w0, raw0, norm0, None), (h, w1, raw1, norm1, act.detach() if pool else None)]
+        ctx.packs, ctx.has_emb, ctx.temb = packs, emb is not None, temb
         return (act, pooled) if pool else act
 
     @staticmethod
     def backward(ctx, dA, dP=None):
         from . import ops
-        x, weight, raw, stats, g32, b32, act = ctx.saved_tensors
-        N, D, H, W, cout = raw.shape
-        buf, off = _slice_of(dA) if dA is not None else (None, 0)       # a concat half's gradient is read in place
-        if ctx.pool and dP is not None:       # MaxPool3d(2) backward + the skip-path gradient in one pass
-            abuf, aoff = _slice_of(act)         # the activation may live in its decoder's concat buffer (cat_extra)
-            dA = buf = ops.maxpool2_bwd_add(abuf, aoff, cout, buf, off, dP.contiguous())
-            off = 0
-        norm = ops.Norm(stats, g32, b32, D * H * W)
-        sums = None
-        lo_ = ctx.link_out
-        if lo_ is not None and lo_.sums is not None and not (ctx.pool and dP is not None) and off == 0 and buf.data_ptr() == lo_.da_ptr:
-            sums = lo_.sums                 # the launch that produced dA already took this layer's reduce pass
-        dY = torch.empty_like(raw)
-        ts = ctx.temb_state
-        dadd_out = None
-        if ts is not None:
-            if ts.dadd is None:           # zero-initialised: a block whose backward never runs (its output unused) contributes nothing
-                ts.dadd = ops.zeros((ts.N * ts.P,), torch.float32, raw.device)
-            dadd_out = ts.rows(ts.dadd, ctx.temb_index)
-        dgamma, dbeta, dadd = ops.instnorm_bwd(buf, off, raw, cout, norm, dY, want_add=ctx.has_add, dadd_out=dadd_out, sums=sums)
-        if ts is not None:
-            ts.written += 1
-            # the evaluation's first block runs last in backward and hands the shared buffer on (see _TembState)
-            dadd = ts.dadd if ctx.temb_index == 0 else None
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            li = ctx.link_in
-            if (li is not None and li.raw is not None and ops.TRAIN_DGRAD_REDUCE and x.shape[-1] == li.raw.shape[-1]
-                    and ops.conv3d_k3_dgrad_reduce_supported(dY.dtype, N, D, H, W, cout, x.shape[-1])):
-                # x is the activation of the block in front: dx is its dA, and this launch takes its norm-backward sums along
-                wp = ctx.packs.get(weight.detach(), "dgrad", cout) if ctx.packs is not None else None
-                if wp is None:
-                    wp, _ = ops.pack_conv3_weights_dgrad(weight.detach().float().contiguous(), dY.dtype, cout_packed=cout)
-                dx = torch.empty((N, D, H, W, x.shape[-1]), dtype=dY.dtype, device=dY.device)
-                pnorm = ops.Norm(li.stats, li.g32, li.b32, li.count)
-                li.sums = ops.instnorm_bwd_sums(li.raw, pnorm)
-                ops.conv3d_k3_dgrad_reduce(dY, cout, wp, ops.zero_bias(x.shape[-1], x.device), x.shape[-1], dx, li.raw, pnorm, li.sums)
-                li.da_ptr = dx.data_ptr()
-            else:
-                dx = _Conv3dK3._dgrad(dY, weight.detach().float().contiguous(), x.shape[-1], ctx.packs)
-        if ctx.needs_input_grad[1]:
-            dw = ops.zeros(tuple(weight.shape), torch.float32, x.device)
-            _wgrad(x, dY, cout, dw)
-        db = ops.zeros((cout,), torch.float32, x.device)      # bias before InstanceNorm: sum(dY) == 0 exactly
-        return dx, dw, db, dgamma, dbeta, dadd, (dA if ctx.has_emb else None), None, None, None, None, None, None, None, None
+        assert ctx.layers is not None, "a TwoConv block's backward runs once (the step never retains the graph)"
+        l0, l1 = ctx.layers
+        ctx.layers = None
+        need = ctx.needs_input_grad
+        need0 = any(need[i] for i in (0, 1, 2, 3, 4, 9))      # anything in front of conv_1 takes a gradient
+        dh, g1, dA, sums = _conv_norm_act_bwd(dA, dP, *l1, ctx.packs, need0, need[5], owner=l0[2:4])
+        del l1
+        dx, g0, dadd = None, (None,) * 4, None
+        if need0:
+            dadd_out = None
+            if ctx.temb is not None:
+                ts, index = ctx.temb
+                if ts.dadd is None:       # zero-initialised: a block whose backward never runs (its output unused) contributes nothing
+                    ts.dadd = ops.zeros((ts.N * ts.P,), torch.float32, dh.device)
+                dadd_out = ts.rows(ts.dadd, index)
+                # the evaluation's first block runs last in backward and hands the shared buffer on (see _TembState)
+                dadd = ts.dadd if index == 0 else None
+            dx, g0, _, _ = _conv_norm_act_bwd(dh, None, *l0, ctx.packs, need[0], need[1], sums=sums, dadd_out=dadd_out)
+        return (dx, *g0, *g1, dadd, dA if ctx.has_emb else None) + (None,) * 5
 
 
 def _two_conv_cl(block, x, temb, emb=None, pool=False, cat_extra=0, packs=None, fold=None):
-    """``temb``: None (the encoder's blocks) or (add, state): the evaluation's block-major add buffer (_TembAdds) and its
-    _TembState; the blocks take their rows in call order."""
-    add = state = None
-    index = 0
+    """``temb``: None (the encoder's blocks) or (add, state, index): the evaluation's block-major add buffer (_TembAdds), its
+    _TembState and this block's index in it."""
+    add = ts = None
     if temb is not None:
-        add, state = temb
-        index = state.next
-        state.next += 1
+        add, state, index = temb
         assert block.temb_proj.weight.shape[0] == state.couts[index]
+        ts = (state, index)
     c0, c1 = block.conv_0, block.conv_1
-    link = _BwdLink() if torch.is_grad_enabled() else None       # conv_1's data gradient is conv_0's dA (see _BwdLink)
-    h = _ConvNormAct.apply(x, c0.conv.weight, c0.conv.bias, c0.adn.N.weight, c0.adn.N.bias, add, None, False, 0, state, index, packs,
-                           fold, link, None)
-    return _ConvNormAct.apply(h, c1.conv.weight, c1.conv.bias, c1.adn.N.weight, c1.adn.N.bias, None, emb, pool, cat_extra, None, 0,
-                              packs, None, None, link)
+    return _TwoConv.apply(x, c0.conv.weight, c0.conv.bias, c0.adn.N.weight, c0.adn.N.bias,
+                          c1.conv.weight, c1.conv.bias, c1.adn.N.weight, c1.adn.N.bias, add, emb, pool, cat_extra, ts, packs, fold)
 
 
 class _Head(torch.autograd.Function):
@@ -465,9 +423,10 @@ def native_logits_cl(net, image, x, step, dtype=torch.float16):
     _native.lib()            # fails loudly when libdua_hip.so is missing
     enc, den = net.embed_model, net.model
     from . import ops
-    # the nine denoiser blocks in the order they run: their temb_proj rows come out of one launch chain (_TembAdds)
-    blocks = [den.conv_0, den.down_1.convs, den.down_2.convs, den.down_3.convs, den.down_4.convs, den.upcat_4.convs,
-              den.upcat_3.convs, den.upcat_2.convs, den.upcat_1.convs]
+    ups = [den.upcat_4, den.upcat_3, den.upcat_2, den.upcat_1]
+    # the nine denoiser blocks in the order they run: block i adds rows i of the temb_proj outputs, which come out of one
+    # launch chain (_TembAdds)
+    blocks = [den.conv_0, den.down_1.convs, den.down_2.convs, den.down_3.convs, den.down_4.convs] + [blk.convs for blk in ups]
     # every layer's fp16 weights, forward and data-gradient layout, packed by one launch per 64 tensors; an ordinary layer's input
     # buffer has exactly its Cin channels and its output gradient exactly its Cout (the first layers -- one or seventeen input
     # channels in a padded buffer -- and fp32 plans pack per layer as before)
@@ -491,37 +450,35 @@ def native_logits_cl(net, image, x, step, dtype=torch.float16):
     tparams = [den.temb.dense[0].weight, den.temb.dense[0].bias, den.temb.dense[1].weight, den.temb.dense[1].bias]
     for b in blocks:
         tparams += [b.temb_proj.weight, b.temb_proj.bias]
-    temb = (_TembAdds.apply(step.to(torch.int64), den.temb.embedding_dim // 2, state, *tparams), state)
-    h = _cl_pad([image, x], dtype)
-    up_c = [blk.upsample.deconv.weight.shape[1] for blk in (den.upcat_1, den.upcat_2, den.upcat_3, den.upcat_4)]   # channels each
-    x0, p0 = _two_conv_cl(den.conv_0, h, temb, emb[0], True, up_c[0], packs)                                     # decoder adds to the skip
-    x1, p1 = _two_conv_cl(den.down_1.convs, p0, temb, emb[1], True, up_c[1], packs)
-    x2, p2 = _two_conv_cl(den.down_2.convs, p1, temb, emb[2], True, up_c[2], packs)
-    x3, p3 = _two_conv_cl(den.down_3.convs, p2, temb, emb[3], True, up_c[3], packs)
-    x4 = _two_conv_cl(den.down_4.convs, p3, temb, emb[4], packs=packs)
+    add = _TembAdds.apply(step.to(torch.int64), den.temb.embedding_dim // 2, state, *tparams)
 
-    def up(block, lo, skip):
-        dc = block.upsample.deconv
-        cat = _UpCat.apply(lo, skip, dc.weight, dc.bias)
+    def block(i, inp, **kw):
+        return _two_conv_cl(blocks[i], inp, (add, state, i), packs=packs, **kw)
+
+    h = _cl_pad([image, x], dtype)
+    up_c = [blk.upsample.deconv.weight.shape[1] for blk in reversed(ups)]          # channels each decoder adds to the skip
+    x0, p0 = block(0, h, emb=emb[0], pool=True, cat_extra=up_c[0])
+    x1, p1 = block(1, p0, emb=emb[1], pool=True, cat_extra=up_c[1])
+    x2, p2 = block(2, p1, emb=emb[2], pool=True, cat_extra=up_c[2])
+    x3, p3 = block(3, p2, emb=emb[3], pool=True, cat_extra=up_c[3])
+    u = block(4, p3, emb=emb[4])
+    for i, (upcat, skip) in enumerate(zip(ups, (x3, x2, x1, x0)), start=5):
+        dc = upcat.upsample.deconv
+        cat = _UpCat.apply(u, skip, dc.weight, dc.bias)
         fold = None
         N, D, H, W, cs = skip.shape
-        cout = block.convs.conv_0.conv.weight.shape[0]
+        cout = upcat.convs.conv_0.conv.weight.shape[0]
         # the forward convolution over the concat as ONE folded launch where the level has rounds of tiles to fill (level 0)
         if (ops.TRAIN_FOLD_UPCONV and dtype == torch.float16 and N * (D // 8) * (H // 8) * (W // 8) >= ops.TRAIN_FOLD_MIN_TILES
-                and D % 8 == 0 and H % 8 == 0 and W % 8 == 0 and lo.is_contiguous()
-                and ops.upconv_supported(dtype, N, D, H, W, cs, cat.shape[-1], lo.shape[-1], lo.shape[-1], cout, cout)):
-            fold = (lo.detach(), dc.weight, dc.bias, cs)
-        return _two_conv_cl(block.convs, cat, temb, packs=packs, fold=fold)
-
-    u4 = up(den.upcat_4, x4, x3)
-    u3 = up(den.upcat_3, u4, x2)
-    u2 = up(den.upcat_2, u3, x1)
-    u1 = up(den.upcat_1, u2, x0)
+                and D % 8 == 0 and H % 8 == 0 and W % 8 == 0 and u.is_contiguous()
+                and ops.upconv_supported(dtype, N, D, H, W, cs, cat.shape[-1], u.shape[-1], u.shape[-1], cout, cout)):
+            fold = (u.detach(), dc.weight, dc.bias, cs)
+        u = block(i, cat, fold=fold)
     wf = den.final_conv.weight
-    if wf.shape[0] <= ops.HEAD_MAX_K and u1.shape[-1] <= ops.HEAD_MAX_C:
-        return _Head.apply(u1, wf, den.final_conv.bias)
+    if wf.shape[0] <= ops.HEAD_MAX_K and u.shape[-1] <= ops.HEAD_MAX_C:
+        return _Head.apply(u, wf, den.final_conv.bias)
     # more classes / channels than the head kernel holds in registers: plain library GEMM
-    return u1 @ wf.reshape(wf.shape[0], -1).t().to(u1.dtype) + den.final_conv.bias.to(u1.dtype)
+    return u @ wf.reshape(wf.shape[0], -1).t().to(u.dtype) + den.final_conv.bias.to(u.dtype)
 
 
 class _NativeModule(torch.nn.Module):

@@ -1,7 +1,7 @@
 """Every backward kernel of the training step and each of its launch forms, at the geometry training runs it at, against an fp64
 reference on the exact operands it read (tests/fp64ref.py), element by element within a bound derived from the launcher's own
 arithmetic: the 3x3x3 weight gradient (fetch-once form with its two reduce routes and partition multipliers, the three-kd forms
-with and without partial sums, fp32), the data gradient as _Conv3dK3._dgrad launches it and the norm-backward-sums launch, the
+with and without partial sums, fp32), the data gradient as training._dgrad launches it and the norm-backward-sums launch, the
 InstanceNorm + LeakyReLU backward pair, the head backward and the max-pool backward.  Each case also pins the form it exercises
 (partition count, reduce route, workspace size, kernel kind), so a launcher change that moves it fails here instead of quietly
 testing another kernel."""
@@ -174,7 +174,7 @@ DGRAD_LEVELS = [(2, 96, 64, 64), (2, 48, 64, 64), (2, 24, 128, 128), (2, 12, 256
 
 @pytest.mark.parametrize("N,S,cin_f,cout_f", DGRAD_LEVELS, ids=[f"{s}^3-{a}to{b}" for (_, s, a, b) in DGRAD_LEVELS])
 def test_conv3_dgrad_launch_within_fp64_bound(N, S, cin_f, cout_f):
-    """_Conv3dK3._dgrad: pack_conv3_weights_dgrad, then conv3d_k3 on dy with ops.splitk_ws; reference = the forward reference on
+    """training._dgrad: pack_conv3_weights_dgrad, then conv3d_k3 on dy with ops.splitk_ws; reference = the forward reference on
     w.flip(2, 3, 4).transpose(0, 1) rounded to fp16, the split-K partials the finish kernel adds counted in the chain."""
     ops, nv = _ops(), _nv()
     dt = F16

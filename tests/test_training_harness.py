@@ -525,6 +525,68 @@ def test_full_size_gradients_fp16_path_vs_oracle():
                                final=(1e-3, 0.9999))
 
 
+@pytest.mark.gpu
+def test_two_conv_block_hands_conv_0_its_norm_backward_sums(monkeypatch):
+    """training._TwoConv runs a TwoConv block's backward as one node: conv_1's data-gradient launch writes conv_0's dA and, where
+    ops.conv3d_k3_dgrad_reduce_supported allows, takes the reduce sums of conv_0's InstanceNorm backward along, which conv_0's
+    norm backward then uses.  One fp16 forward + backward at 96^3: that launch runs once per qualifying block (none falls back
+    to the separate reduce pass unnoticed), and every parameter gradient agrees with the same step where the reduce is its own
+    pass (ops.TRAIN_DGRAD_REDUCE = False).  The launch's dx is bit-identical to the plain launch and its sums agree to 1e-5
+    (test_data_gradient_launch_takes_the_norm_backward_sums_along): downstream, the sums move dY by fp16 roundings only, so the
+    whole gradient agrees within that test's 1e-4 and every tensor keeps its direction."""
+    from diff_unet_amos_amd import ops
+    from diff_unet_amos_amd.training import native_logits_cl, _SegLoss
+    dev = torch.device("cuda:0")
+    torch.manual_seed(5)
+    net = DiffUNet(in_channels=1, out_channels=16).to(dev)
+    N, S = 1, 96
+    g = torch.Generator().manual_seed(45)
+    image = torch.rand(N, 1, S, S, S, generator=g).to(dev)
+    labels = (torch.rand(N, 16, S, S, S, generator=g) > 0.8).float().to(dev)
+    x_t = torch.randn(N, 16, S, S, S, generator=g).to(dev)
+    t = torch.tensor([417], device=dev)
+    enc, den = net.embed_model, net.model
+    # every TwoConv block with the extent of its level; its conv_1's data gradient maps dy [.., cout] to dx [.., cin]
+    blocks = [(enc.conv_0, S)] + [(d.convs, S >> (k + 1)) for k, d in enumerate(enc.down)] + [(den.conv_0, S)]
+    blocks += [(getattr(den, f"down_{k}").convs, S >> k) for k in range(1, 5)]
+    blocks += [(getattr(den, f"upcat_{k}").convs, S >> (k - 1)) for k in range(1, 5)]
+    assert len(blocks) == 14
+    want = sum(ops.conv3d_k3_dgrad_reduce_supported(torch.float16, N, s, s, s, *b.conv_1.conv.weight.shape[:2]) for b, s in blocks)
+    assert want > 0
+    calls = []
+    real = ops.conv3d_k3_dgrad_reduce
+    monkeypatch.setattr(ops, "conv3d_k3_dgrad_reduce", lambda *a, **k: (calls.append(tuple(a[0].shape)), real(*a, **k))[1])
+
+    def step(reduce):
+        monkeypatch.setattr(ops, "TRAIN_DGRAD_REDUCE", reduce)
+        net.zero_grad(set_to_none=True)
+        calls.clear()
+        (_SegLoss.apply(native_logits_cl(net, image, x_t, t, torch.float16), labels) * 4096.0).backward()
+        return len(calls), {k: p.grad.detach().double() for k, p in net.named_parameters()}
+
+    n_fused, fused = step(True)
+    n_sep, sep = step(False)
+    assert n_fused == want and n_sep == 0, (n_fused, want, n_sep)
+    num = den = 0.0
+    seen = []
+    for k, b in sep.items():
+        d = fused[k] - b
+        num += float((d ** 2).sum()); den += float((b ** 2).sum())
+        if float(b.norm()) > 0:             # the Conv3d biases in front of an InstanceNorm: exact zeros either way
+            seen.append((float(d.norm() / b.norm()), float((fused[k] * b).sum() / (fused[k].norm() * b.norm())), k))
+        else:
+            assert torch.equal(fused[k], b), k
+    seen.sort(reverse=True)
+    rel = (num / den) ** 0.5
+    print(f"reduce in the data-gradient launch vs its own pass: whole-gradient relative L2 {rel:.2e}; per tensor (relative L2, "
+          "cosine): " + ", ".join(f"{k} {r:.2e} {c:.6f}" for r, c, k in seen[:4]))
+    # measured: 2.7e-5 whole; per tensor at most 1.0e-2 / cosine 0.99995 (the 6^3 and 12^3 levels, which fp16 roundings of
+    # dY reach in proportion to their small gradients).  1e-4 is the kernel test's relative bound on parameter gradients.
+    assert rel < 1e-4, rel
+    for r, c, k in seen:
+        assert r < 5e-2 and c > 0.999, (k, r, c)
+
+
 def _real_bias_gradient(k):
     """The biases whose gradient is real although their names end in "conv.bias": the head's and the four transposed
     convolutions' (the Conv3d biases in front of an InstanceNorm are the ones with a zero true gradient)."""
