@@ -132,6 +132,23 @@ class AdamWList(C.Structure):
     _fields_ = [("count", C.c_int), ("numel", C.c_long * ADAMW_MAX_TENSORS), ("p", C.c_void_p * ADAMW_MAX_TENSORS),
                 ("g", C.c_void_p * ADAMW_MAX_TENSORS), ("m", C.c_void_p * ADAMW_MAX_TENSORS), ("v", C.c_void_p * ADAMW_MAX_TENSORS)]
 
+class AugVolume(C.Structure):
+    """dua_aug_volume: one 64-byte row of the device table of volumes."""
+    _fields_ = [("image", C.c_void_p), ("label", C.c_void_p), ("fg_prefix", C.c_void_p), ("bg_prefix", C.c_void_p),
+                ("D", C.c_int), ("H", C.c_int), ("W", C.c_int), ("nchunks", C.c_int), ("fg_count", C.c_uint),
+                ("bg_count", C.c_uint), ("image_threshold", C.c_float), ("reserved", C.c_int)]
+
+
+class AugConfig(C.Structure):
+    """dua_aug_config."""
+    _fields_ = [("roi", C.c_int * 3), ("max_k", C.c_int), ("pos_fraction", C.c_float), ("flip_prob", C.c_float),
+                ("rot90_prob", C.c_float), ("scale_prob", C.c_float), ("scale_factors", C.c_float), ("shift_prob", C.c_float),
+                ("shift_offsets", C.c_float), ("reserved", C.c_int)]
+
+
+AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
+AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
+
 _P = C.c_void_p
 ABI_VERSION = 8          # DUA_ABI_VERSION of include/dua_hip.h this binding was written against
 
@@ -222,6 +239,10 @@ _SIGS = {
     "dua_surface_edt_sq": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P]),
     "dua_surface_distance_table": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
                                    [C.c_double] * 3 + [C.c_int, _P, _P, _P, C.c_long, _P]),
+    "dua_aug_count_candidates": (C.c_int, [_P, _P, C.c_long, C.c_float, _P, _P]),
+    "dua_aug_draw": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P,
+                               _P]),
+    "dua_aug_apply": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,191 @@
+"""Augmented training batches produced on the device from cached volumes.
+
+The reference builds a batch on the host: MONAI's RandCropByPosNegLabeld, three RandFlipd, RandRotate90d,
+RandScaleIntensityd and RandShiftIntensityd (utils.py:143-160), then Engine.convert_labels (engine.py:157-165) expands the
+label map into one-hot channels.  Here the volumes the reference caches (after its deterministic transforms) live in device
+memory, and two launches per batch (csrc/augment.hip) write exactly the two tensors ``NativeConvTrainer.step`` takes::
+
+    producer = DeviceBatchProducer([DeviceVolume(image, label) for image, label in cases])
+    images, labels = producer.next(ids)          # no host-to-device copy of voxels, no host synchronisation
+    trainer.step(images, labels)
+
+What the random words decide and how the patch is transformed is fixed in include/dua_hip.h ("training input"), not by
+MONAI's source; tests/augment_ref.py restates it independently.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _native as nv
+from . import ops
+
+PARAM_COLUMNS = ("volume", "start_d", "start_h", "start_w", "flip_bits", "k", "scale", "shift")
+
+
+def split_params(params):
+    """``params`` (int32 [B, 8]) as (int32 [B, 6]: volume, start_d, start_h, start_w, flip_bits, k; fp32 [B, 2]: scale, shift)."""
+    assert params.dtype == torch.int32 and params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS
+    return params[:, :nv.AUG_SCALE], params[:, nv.AUG_SCALE:].contiguous().view(torch.float32)
+
+
+def pack_params(ints, floats, device=None):
+    """The inverse of ``split_params``: a params tensor from [B, 6] integers and [B, 2] floats (hand-built or logged rows)."""
+    ints = torch.as_tensor(ints, dtype=torch.int32).reshape(-1, nv.AUG_SCALE)
+    floats = torch.as_tensor(floats, dtype=torch.float32).reshape(-1, nv.AUG_PARAM_WORDS - nv.AUG_SCALE)
+    if ints.shape[0] != floats.shape[0]:
+        raise ValueError("pack_params: as many rows of floats as of integers")
+    out = torch.cat([ints.cpu(), floats.cpu().contiguous().view(torch.int32)], dim=1).contiguous()
+    return out.to(device) if device is not None else out
+
+
+class DeviceVolume:
+    """One cached case on the device: ``image`` fp32 [D, H, W] (or [1, D, H, W]) and ``label`` uint8 [D, H, W] of class ids,
+    with the candidate sets of RandCropByPosNegLabel counted once (foreground = label > 0; background = label == 0 and
+    image > image_threshold) and their per-chunk prefix tables left on the device."""
+
+    def __init__(self, image, label, image_threshold=0.0, device="cuda"):
+        if not (torch.is_tensor(image) and torch.is_tensor(label)):
+            raise ValueError("DeviceVolume: image and label are tensors")
+        if image.dim() == 4 and image.shape[0] == 1:
+            image = image[0]
+        if label.dim() == 4 and label.shape[0] == 1:
+            label = label[0]
+        if image.dtype != torch.float32 or label.dtype != torch.uint8:
+            raise ValueError(f"DeviceVolume: image must be float32 and label uint8, got {image.dtype} and {label.dtype}")
+        if image.dim() != 3 or image.shape != label.shape or image.numel() == 0:
+            raise ValueError(f"DeviceVolume: image and label are [D, H, W] of one shape, got {tuple(image.shape)} and "
+                             f"{tuple(label.shape)}")
+        if image.numel() >= 2 ** 31:
+            raise ValueError("DeviceVolume: a volume holds fewer than 2^31 voxels")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"DeviceVolume: a GPU device, not {device}")
+        self.image = image.to(device).contiguous()
+        self.label = label.to(device).contiguous()
+        self.image_threshold = float(image_threshold)
+        self.prefix = ops.aug_count_candidates(self.image, self.label, self.image_threshold)
+        totals = self.prefix[:, -1].tolist()                  # the one host read, at construction
+        self.fg_count, self.bg_count = int(totals[0]), int(totals[1])
+        if self.fg_count == 0 and self.bg_count == 0:
+            raise ValueError("DeviceVolume: no crop centre: the label map has no foreground and no voxel of the image is above "
+                             f"image_threshold = {self.image_threshold}")
+
+    @classmethod
+    def from_hu(cls, image_hu, label, a_min=-175.0, a_max=250.0, image_threshold=0.0, device="cuda"):
+        """ScaleIntensityRanged(a_min, a_max, b_min=0, b_max=1, clip=True) of the reference's deterministic transforms, applied
+        once with torch operators, then ``DeviceVolume``."""
+        x = torch.as_tensor(image_hu).to(device=device, dtype=torch.float32)
+        x = ((x - a_min) / (a_max - a_min)).clamp_(0.0, 1.0)
+        return cls(x, label, image_threshold=image_threshold, device=device)
+
+    @property
+    def shape(self):
+        return tuple(self.image.shape)
+
+    @property
+    def device(self):
+        return self.image.device
+
+    def table_row(self):
+        D, H, W = self.shape
+        n = self.prefix.shape[1]
+        return nv.AugVolume(self.image.data_ptr(), self.label.data_ptr(), self.prefix.data_ptr(), self.prefix.data_ptr() + 4 * n,
+                            D, H, W, n - 1, self.fg_count, self.bg_count, self.image_threshold, 0)
+
+
+class DeviceBatchProducer:
+    """Random patches of ``volumes`` as training batches: ``next(volume_ids)`` returns ``images`` fp32 [B, 1, *roi] and
+    ``labels`` fp32 [B, len(class_ids), *roi] (one-hot of ``class_ids``), NCDHW contiguous, in two launches with no host read.
+    Deterministic for a given (seed, call counter, volume_ids); the call counter is a 64-bit device word the draw launch
+    itself advances, so a captured ``next`` produces a new batch on every replay."""
+
+    def __init__(self, volumes, roi=(96, 96, 96), class_ids=range(16), pos=1, neg=1, flip_prob=0.1, rot90_prob=0.1, max_k=3,
+                 scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0):
+        volumes = list(volumes)
+        if not volumes or not all(isinstance(v, DeviceVolume) for v in volumes):
+            raise ValueError("DeviceBatchProducer: a non-empty list of DeviceVolume")
+        self.device = volumes[0].device
+        if any(v.device != self.device for v in volumes):
+            raise ValueError("DeviceBatchProducer: every volume on one device")
+        roi = tuple(int(r) for r in roi)
+        if len(roi) != 3 or min(roi) < 1:
+            raise ValueError(f"DeviceBatchProducer: roi is three positive extents, got {roi}")
+        for i, v in enumerate(volumes):
+            if any(s < r for s, r in zip(v.shape, roi)):
+                raise ValueError(f"DeviceBatchProducer: volume {i} of shape {v.shape} is smaller than roi {roi}")
+        class_ids = [int(c) for c in class_ids]
+        if not 1 <= len(class_ids) <= nv.AUG_MAX_CLASSES:
+            raise ValueError(f"DeviceBatchProducer: 1 .. {nv.AUG_MAX_CLASSES} class ids, got {len(class_ids)}")
+        if any(c < 0 or c > 255 for c in class_ids):
+            raise ValueError("DeviceBatchProducer: class ids are values of a uint8 label map (0 .. 255)")
+        probs = dict(flip_prob=flip_prob, rot90_prob=rot90_prob, scale_prob=scale_prob, shift_prob=shift_prob)
+        for name, p in probs.items():
+            if not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"DeviceBatchProducer: {name} is a probability, got {p}")
+        if float(pos) < 0 or float(neg) < 0 or float(pos) + float(neg) <= 0:
+            raise ValueError("DeviceBatchProducer: pos and neg are non-negative and not both zero")
+        if float(scale_factors) < 0 or float(shift_offsets) < 0:
+            raise ValueError("DeviceBatchProducer: scale_factors and shift_offsets are non-negative half-widths")
+        if int(max_k) not in (1, 2, 3):
+            raise ValueError(f"DeviceBatchProducer: max_k is 1, 2 or 3, got {max_k}")
+        if float(rot90_prob) > 0 and roi[0] != roi[1]:
+            raise ValueError(f"DeviceBatchProducer: the rotation is in the plane of the first two axes and needs roi[0] == roi[1] "
+                             f"(roi = {roi}); pass rot90_prob=0")
+        self.volumes, self.roi, self.class_ids, self.seed = volumes, roi, tuple(class_ids), int(seed)
+        self.cfg = nv.AugConfig((C.c_int * 3)(*roi), int(max_k), float(pos) / (float(pos) + float(neg)), float(flip_prob),
+                                float(rot90_prob), float(scale_prob), float(scale_factors), float(shift_prob),
+                                float(shift_offsets), 0)
+        rows = (nv.AugVolume * len(volumes))(*[v.table_row() for v in volumes])
+        self.table = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).reshape(len(volumes), -1).to(self.device)
+        self.class_table = torch.tensor(class_ids, dtype=torch.uint8).to(self.device)
+        self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    @property
+    def counter(self):
+        """The call counter the next ``draw`` will use (reads the device word: a host synchronisation)."""
+        return int(self._counter.item()) & (2 ** 64 - 1)
+
+    @property
+    def status(self):
+        """Non-zero once any launch met a row it had to skip: a volume id outside the table, or a params row that would read
+        outside its volume (reads the device word: a host synchronisation)."""
+        return int(self._status.item())
+
+    def _ids(self, volume_ids):
+        if torch.is_tensor(volume_ids):
+            if not volume_ids.is_cuda:
+                volume_ids = volume_ids.tolist()
+            else:
+                assert volume_ids.dtype == torch.int32 and volume_ids.dim() == 1 and volume_ids.numel() >= 1 and \
+                    volume_ids.device == self.device and volume_ids.is_contiguous(), \
+                    "volume_ids: a host sequence, or a contiguous int32 [B] tensor on the producer's device"
+                return volume_ids
+        ids = [int(i) for i in volume_ids]
+        if not ids or any(i < 0 or i >= len(self.volumes) for i in ids):
+            raise ValueError(f"volume_ids: at least one id, each in [0, {len(self.volumes)})")
+        return torch.tensor(ids, dtype=torch.int32).to(self.device)
+
+    def draw(self, volume_ids, counter=None):
+        """The random decisions of one batch as ``params`` (int32 [B, 8] on the device; ``split_params`` names the columns).
+        ``counter=None`` uses and advances the producer's device-resident call counter; an integer is used for this call only."""
+        ids = self._ids(volume_ids)
+        params = torch.empty((ids.numel(), nv.AUG_PARAM_WORDS), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter)
+
+    def apply(self, params, out_images=None, out_labels=None):
+        """The batch ``params`` describes: (images fp32 [B, 1, *roi], labels fp32 [B, len(class_ids), *roi])."""
+        assert torch.is_tensor(params) and params.is_cuda and params.device == self.device, "params: a tensor on the producer's device"
+        B = params.shape[0]
+        if out_images is None:
+            out_images = torch.empty((B, 1) + self.roi, dtype=torch.float32, device=self.device)
+        if out_labels is None:
+            out_labels = torch.empty((B, len(self.class_ids)) + self.roi, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            return ops.aug_apply(self.table, params, self.roi, self.class_table, out_images, out_labels, self._status)
+
+    def next(self, volume_ids, out_images=None, out_labels=None):
+        return self.apply(self.draw(volume_ids), out_images, out_labels)

@@ -1590,3 +1590,68 @@ def surface_distance_table(test, reference, voxel_spacing=None, connectivity=1, 
                                           int(bool(nan_for_nonexisting)), nv.ptr(counts), nv.ptr(out), nv.ptr(ws), need,
                                           nv.stream_ptr()), "dua_surface_distance_table")
     return counts, out
+
+
+# ---- training input: augmented batches from device-resident volumes (csrc/augment.hip; utils.py:143-160, engine.py:157-165) ----
+
+def _i32c(t, name):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), f"{name}: contiguous int32 device tensor"
+
+
+def _u8c(t, name):
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), f"{name}: contiguous uint8 device tensor"
+
+
+def aug_count_candidates(image, label, image_threshold=0.0):
+    """dua_aug_count_candidates: int32 [2, nchunks + 1] exclusive prefix tables of the per-chunk candidate counts of one volume
+    (row 0 foreground = label > 0, row 1 background = label == 0 and image > image_threshold; the last entry is the total)."""
+    _f32c(image, "image"); _u8c(label, "label")
+    assert image.dim() == 3 and image.shape == label.shape and image.device == label.device, "image / label: [D, H, W], same device"
+    vox = image.numel()
+    assert 0 < vox < 2 ** 31, "a volume holds fewer than 2^31 voxels"
+    prefix = torch.empty((2, -(-vox // nv.AUG_CHUNK) + 1), dtype=torch.int32, device=image.device)
+    with torch.cuda.device(image.device):
+        nv.check(nv.lib().dua_aug_count_candidates(nv.ptr(image), nv.ptr(label), vox, float(image_threshold), nv.ptr(prefix),
+                                                   nv.stream_ptr()), "dua_aug_count_candidates")
+    return prefix
+
+
+def _aug_table(table, name="table"):
+    _u8c(table, name)
+    assert table.dim() == 2 and table.shape[1] == C.sizeof(nv.AugVolume) and table.shape[0] >= 1, f"{name}: uint8 [volumes, 64]"
+    return table.shape[0]
+
+
+def aug_draw(table, ids, cfg, seed, counter, params, status, counter_value=None):
+    """dua_aug_draw: one row of ``params`` (int32 [B, 8]) per entry of ``ids`` (int32 [B]); ``counter`` (int64 [1]) is the
+    device-resident call counter the launch reads and advances, unless ``counter_value`` overrides it for this call."""
+    nvol = _aug_table(table)
+    _i32c(ids, "volume_ids"); _i32c(params, "params"); _i32c(status, "status")
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1, "counter: int64 [1] device tensor"
+    B = ids.numel()
+    assert ids.dim() == 1 and B >= 1 and tuple(params.shape) == (B, nv.AUG_PARAM_WORDS) and status.numel() == 1
+    assert all(t.device == table.device for t in (ids, params, status, counter)), "every tensor on the volumes' device"
+    assert isinstance(cfg, nv.AugConfig)
+    use = counter_value is not None
+    nv.check(nv.lib().dua_aug_draw(nv.ptr(table), nvol, nv.ptr(ids), B, C.byref(cfg), int(seed) & (2 ** 64 - 1), nv.ptr(counter),
+                                   int(use), (int(counter_value) & (2 ** 64 - 1)) if use else 0, nv.ptr(params), nv.ptr(status),
+                                   nv.stream_ptr()), "dua_aug_draw")
+    return params
+
+
+def aug_apply(table, params, roi, class_ids, images, labels, status):
+    """dua_aug_apply: images fp32 [B, 1, *roi] and labels fp32 [B, C, *roi] (both WRITTEN) from ``params`` (int32 [B, 8]);
+    ``class_ids``: uint8 [C] device tensor."""
+    nvol = _aug_table(table)
+    _i32c(params, "params"); _i32c(status, "status"); _u8c(class_ids, "class_ids")
+    _f32c(images, "images"); _f32c(labels, "labels")
+    B, Cn = params.shape[0], class_ids.numel()
+    assert params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS and B >= 1 and status.numel() == 1
+    assert 1 <= Cn <= nv.AUG_MAX_CLASSES, f"1 .. {nv.AUG_MAX_CLASSES} classes"
+    rd, rh, rw = (int(r) for r in roi)
+    assert tuple(images.shape) == (B, 1, rd, rh, rw), f"images: [{B}, 1, {rd}, {rh}, {rw}], got {tuple(images.shape)}"
+    assert tuple(labels.shape) == (B, Cn, rd, rh, rw), f"labels: [{B}, {Cn}, {rd}, {rh}, {rw}], got {tuple(labels.shape)}"
+    assert all(t.device == table.device for t in (params, status, class_ids, images, labels)), "every tensor on the volumes' device"
+    nv.check(nv.lib().dua_aug_apply(nv.ptr(table), nvol, nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
+                                    nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply")
+    return images, labels

@@ -777,6 +777,86 @@ int dua_surface_distance_table(int V, int D, int H, int W, const void* test, int
                                double sh, double sw, int nan_for_nonexisting, unsigned long long* counts, double* out,
                                void* workspace, long workspace_bytes, void* stream);
 
+/* ---- training input: augmented batches from device-resident volumes ------------------------------------------------
+ * The random tail of the reference's training transforms (utils.py:143-160: RandCropByPosNegLabeld, three RandFlipd,
+ * RandRotate90d, RandScaleIntensityd, RandShiftIntensityd) and the one-hot expansion of Engine.convert_labels
+ * (engine.py:157-165), for volumes that already went through the deterministic transforms and sit in device memory:
+ * image fp32 [D][H][W], label uint8 [D][H][W] of class ids, D H W < 2^31.  Two launches per batch (dua_aug_draw, then
+ * dua_aug_apply), no host read, capturable.  The semantics are fixed HERE (MONAI is not a dependency):
+ *
+ * Candidate sets of a volume (dua_aug_count_candidates): foreground = label > 0; background = label == 0 and image >
+ * image_threshold; each ordered by ascending linear voxel index (d H + h) W + w.  prefix (WRITTEN) = unsigned
+ * [2][nchunks + 1], nchunks = ceil(D H W / DUA_AUG_CHUNK): row 0 foreground, row 1 background; entry c = number of
+ * candidates in chunks [0, c) (chunk c = linear indices [c DUA_AUG_CHUNK, (c + 1) DUA_AUG_CHUNK)), entry nchunks = the total.
+ *
+ * dua_aug_draw, one params row per sample b (volume = ids[b]).  Random words: Philox4x32-10, key = (seed lo, seed hi),
+ * counter = (call counter lo, call counter hi, b, j); block j yields words j.0 .. j.3:
+ *   0.0 set choice   0.1 candidate index   0.2 flip axis 0   0.3 flip axis 1
+ *   1.0 flip axis 2  1.1 rotation event    1.2 rotation k    1.3 scale event
+ *   2.0 scale value  2.1 shift event       2.2 shift value   2.3 unused
+ * (every word keeps its role whether or not the event before it happened).  With x a 32-bit word:
+ *   integer in [0, n): mulhi(x, n) = (x * n) >> 32;   u(x) = (x >> 8) * 2^-24 (exact in fp32);   event of probability p
+ *   (fp32): u(x) < p;
+ *   set: foreground iff u(0.0) < pos_fraction (= fp32(pos / (pos + neg))), or the only non-empty set;
+ *   centre = candidate number mulhi(0.1, count) of that set;   start_a = clamp(centre_a - roi_a / 2, 0, size_a - roi_a);
+ *   flip bit a (a = 0, 1, 2) iff u < flip_prob;   k = 1 + mulhi(1.2, max_k) iff u(1.1) < rot90_prob, else 0;
+ *   scale = fadd(fmul(2 scale_factors, u(2.0)), -scale_factors) iff u(1.3) < scale_prob, else 0;
+ *   shift = fadd(fmul(2 shift_offsets, u(2.2)), -shift_offsets) iff u(2.1) < shift_prob, else 0   (no contraction).
+ * Call counter: use_counter == 0: the 64-bit word *counter is read by every sample and then advanced by one (one lane, after
+ * a workgroup barrier; all samples of a call are drawn by ONE workgroup, a wave each, for that reason), so a captured launch
+ * moves on with every replay; use_counter != 0: counter_value is used and *counter is left alone.
+ *
+ * params (int [B][DUA_AUG_PARAM_WORDS]): DUA_AUG_VOLUME, _START_D, _START_H, _START_W, _FLIP (bit a = flip axis a), _K as
+ * int32; _SCALE and _SHIFT as the bits of an fp32.  A sample whose id is outside [0, nvol) gets volume -1.
+ *
+ * dua_aug_apply: with p = image[start_d : start_d + roi_d, start_h : .., start_w : ..] of the row's volume (and the same
+ * window of the label map) the outputs are, in torch terms,
+ *   for a in (0, 1, 2): if flip bit a: p = p.flip(a)
+ *   p = torch.rot90(p, k, (0, 1))
+ *   images[b, 0] = (p * (1 + scale)) + shift            (fp32: one add, one multiply, one add, each rounded)
+ *   labels[b, c] = (label_p == class_ids[c]) ? 1 : 0    (fp32 [B][C][roi], C <= DUA_AUG_MAX_CLASSES)
+ * both NCDHW contiguous.  The rotation is in the (d, h) plane, so rows along w stay rows (reversed by flip bit 2): every
+ * (flip, k) combination reads and writes whole rows, 16 bytes per lane when roi_w is a multiple of 4 (4 bytes otherwise), and
+ * one pass over the label window emits all C planes.  A row that would read outside its volume (volume, start, k or flip out
+ * of range; odd k with roi_d != roi_h) is skipped -- its outputs are left as they were -- and *status (int, may be NULL) is
+ * set to 1; dua_aug_draw sets it likewise for an id outside the table.  The caller zeroes status. */
+#define DUA_AUG_CHUNK 1024
+#define DUA_AUG_MAX_CLASSES 64
+#define DUA_AUG_VOLUME 0
+#define DUA_AUG_START_D 1
+#define DUA_AUG_START_H 2
+#define DUA_AUG_START_W 3
+#define DUA_AUG_FLIP 4
+#define DUA_AUG_K 5
+#define DUA_AUG_SCALE 6
+#define DUA_AUG_SHIFT 7
+#define DUA_AUG_PARAM_WORDS 8
+typedef struct {                 /* one row of the device table of volumes (64 bytes) */
+  const float* image;            /* fp32 [D][H][W] */
+  const unsigned char* label;    /* uint8 [D][H][W] */
+  const unsigned* fg_prefix;     /* row 0 of dua_aug_count_candidates' prefix */
+  const unsigned* bg_prefix;     /* row 1 */
+  int D, H, W, nchunks;
+  unsigned fg_count, bg_count;   /* the totals (at least one is non-zero) */
+  float image_threshold;
+  int reserved;
+} dua_aug_volume;
+typedef struct {
+  int roi[3];
+  int max_k;                     /* 1..3 */
+  float pos_fraction, flip_prob, rot90_prob, scale_prob, scale_factors, shift_prob, shift_offsets;
+  int reserved;
+} dua_aug_config;
+
+int dua_aug_count_candidates(const float* image, const unsigned char* label, long voxels, float image_threshold,
+                             unsigned* prefix, void* stream);
+int dua_aug_draw(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                 unsigned long long seed, unsigned long long* counter, int use_counter, unsigned long long counter_value,
+                 int* params, int* status, void* stream);
+/* class_ids: DEVICE uint8 [C] */
+int dua_aug_apply(const dua_aug_volume* table, int nvol, const int* params, int B, int roi_d, int roi_h, int roi_w,
+                  const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

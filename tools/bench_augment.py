@@ -1,0 +1,175 @@
+"""Time DeviceBatchProducer.next (csrc/augment.hip) against a torch-operator restatement of the same contract.
+
+    python tools/bench_augment.py [--repeats 1000] [--warmup 20] [--rounds 7] [--with-step] [--out profiles/augment_bench.json]
+
+For B in {1, 2, 10} at roi 96^3 and 16 classes over eight synthetic volumes of about 200 x 160 x 160 resident on the device:
+``next`` into preallocated outputs, and the torch restatement a user would otherwise write (slice, flip, rot90, the two
+intensity operations, a stacked == for the one-hot) from the same params on the same device in the same process.  The two are
+timed in alternating rounds (``--rounds`` of ``--repeats`` calls each, device events around a whole round, after warm-up of
+both); the statistic is the median round, the spread its min .. max.  The restatement gets its params from the host (the
+producer's own rows, read back before the timed window), as a torch user's would be.  Achieved write bandwidth = the bytes
+the outputs hold, 4 (1 + C) per voxel, over the median call time; ``apply`` alone is timed the same way.  ``--with-step``
+adds one training step of NativeConvTrainer (graph mode, fp16, batch 2, 96^3, 16 classes: BASELINE config 4) on synthetic
+inputs.  One JSON line at the end, also written to ``--out``.
+"""
+import argparse
+import json
+import os
+import socket
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from diff_unet_amos_amd import augment  # noqa: E402
+
+DEV = "cuda:0"
+ROI, CLASSES = (96, 96, 96), 16
+
+
+def volumes(n):
+    out = []
+    for i in range(n):
+        g = torch.Generator().manual_seed(100 + i)
+        shape = (200 + 4 * (i % 3), 160 + 3 * (i % 4), 160 + 5 * (i % 2))
+        coarse = torch.randint(0, CLASSES * 3, tuple(-(-s // 8) for s in shape), generator=g)
+        coarse = torch.where(coarse < CLASSES, coarse, torch.zeros_like(coarse))
+        label = coarse.repeat_interleave(8, 0).repeat_interleave(8, 1).repeat_interleave(8, 2)
+        label = label[:shape[0], :shape[1], :shape[2]].to(torch.uint8).contiguous()
+        out.append(augment.DeviceVolume(torch.rand(shape, generator=g) - 0.3, label, device=DEV))
+    return out
+
+
+def torch_next(vols, rows, class_ids, out_images, out_labels):
+    """The contract of dua_aug_apply in torch operators, one sample at a time, from host rows."""
+    for b, (vid, sd, sh, sw, flip, k, scale, shift) in enumerate(rows):
+        v = vols[vid]
+        win = (slice(sd, sd + ROI[0]), slice(sh, sh + ROI[1]), slice(sw, sw + ROI[2]))
+        p, q = v.image[win], v.label[win]
+        dims = [a for a in (0, 1, 2) if flip >> a & 1]
+        if dims:
+            p, q = p.flip(dims), q.flip(dims)
+        if k:
+            p, q = torch.rot90(p, k, (0, 1)), torch.rot90(q, k, (0, 1))
+        out_images[b, 0] = p * (1.0 + scale) + shift
+        torch.eq(q[None], class_ids, out=out_labels[b])
+    return out_images, out_labels
+
+
+def timed_rounds(fns, repeats, rounds):
+    """Alternating rounds of ``repeats`` calls of each function; per-call milliseconds of every round, per function."""
+    ms = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(repeats):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[i].append(e0.elapsed_time(e1) / repeats)
+    return ms
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms)}
+
+
+def train_step_ms(warmup, steps):
+    from diff_unet_amos_amd.diff_unet import DiffUNet
+    from diff_unet_amos_amd.training import NativeConvTrainer
+    torch.manual_seed(0)
+    net = DiffUNet(in_channels=1, out_channels=CLASSES).to(DEV)
+    tr = NativeConvTrainer(net, graph=True)
+    g = torch.Generator().manual_seed(1)
+    image = torch.rand(2, 1, *ROI, generator=g).to(DEV)
+    labels = (torch.rand(2, CLASSES, *ROI, generator=g) > 0.8).float().to(DEV)
+    for _ in range(warmup):
+        tr.step(image, labels)
+    torch.cuda.synchronize()
+    per = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tr.step(image, labels)
+        e1.record()
+        e1.synchronize()
+        per.append(e0.elapsed_time(e1))
+    return summary(per)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=1000)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--volumes", type=int, default=8)
+    ap.add_argument("--with-step", action="store_true")
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_augment.py measures on the GPU; none is visible")
+    vols = volumes(args.volumes)
+    prod = augment.DeviceBatchProducer(vols, roi=ROI, class_ids=range(CLASSES), seed=1)
+    class_ids = torch.arange(CLASSES, dtype=torch.uint8, device=DEV).view(-1, 1, 1, 1)
+    result = {"metric": "augment_next_time", "unit": "ms", "box": socket.gethostname(), "device": torch.cuda.get_device_name(0),
+              "roi": ROI, "classes": CLASSES, "repeats": args.repeats, "rounds": args.rounds, "batches": {}}
+    for B in (1, 2, 10):
+        ids = torch.tensor([i % len(vols) for i in range(B)], dtype=torch.int32, device=DEV)
+        out_images = torch.empty((B, 1) + ROI, device=DEV)
+        out_labels = torch.empty((B, CLASSES) + ROI, device=DEV)
+        ref_images, ref_labels = torch.empty_like(out_images), torch.empty(out_labels.shape, dtype=torch.bool, device=DEV)
+        ref_float = torch.empty_like(out_labels)
+        # rows with every kind of transform in them (the default probabilities leave most samples untouched)
+        busy = augment.DeviceBatchProducer(vols, roi=ROI, class_ids=range(CLASSES), flip_prob=0.5, rot90_prob=0.5, scale_prob=0.5,
+                                           seed=2)
+        params = busy.draw(ids)
+        ints, floats = augment.split_params(params.cpu())
+        rows = [tuple(i) + tuple(f) for i, f in zip(ints.tolist(), floats.tolist())]
+
+        def torch_fn():
+            torch_next(vols, rows, class_ids, ref_images, ref_labels)
+            ref_float.copy_(ref_labels)                      # the trainer takes fp32 one-hot channels
+
+        def next_fn():
+            prod.next(ids, out_images, out_labels)
+
+        def apply_fn():
+            busy.apply(params, out_images, out_labels)
+
+        # same tensors from both before anything is timed
+        apply_fn(); torch_fn()
+        same = bool(torch.equal(out_images, ref_images)) and bool(torch.equal(out_labels, ref_float))
+        for _ in range(args.warmup):
+            next_fn(); apply_fn(); torch_fn()
+        torch.cuda.synchronize()
+        ms_next, ms_apply, ms_torch = timed_rounds((next_fn, apply_fn, torch_fn), args.repeats, args.rounds)
+        nbytes = 4 * (1 + CLASSES) * B * ROI[0] * ROI[1] * ROI[2]
+        entry = {"next": summary(ms_next), "apply": summary(ms_apply), "torch_restatement": summary(ms_torch),
+                 "outputs_equal_torch": same, "bytes_written": nbytes,
+                 "next_write_GBps": nbytes / (statistics.median(ms_next) * 1e-3) / 1e9,
+                 "apply_write_GBps": nbytes / (statistics.median(ms_apply) * 1e-3) / 1e9,
+                 "torch_over_next": statistics.median(ms_torch) / statistics.median(ms_next)}
+        result["batches"][str(B)] = entry
+        print(f"B={B}: next {entry['next']['median_ms']:.4f} ms ({entry['next']['min_ms']:.4f} .. {entry['next']['max_ms']:.4f}), "
+              f"apply alone {entry['apply']['median_ms']:.4f} ms = {entry['apply_write_GBps']:.0f} GB/s written, torch restatement "
+              f"{entry['torch_restatement']['median_ms']:.4f} ms ({entry['torch_restatement']['min_ms']:.4f} .. "
+              f"{entry['torch_restatement']['max_ms']:.4f}) = {entry['torch_over_next']:.1f}x; outputs equal: {same}", flush=True)
+    assert prod.status == 0
+    if args.with_step:
+        result["train_step"] = train_step_ms(5, 20)
+        result["next_B2_share_of_step"] = result["batches"]["2"]["next"]["median_ms"] / result["train_step"]["median_ms"]
+        print(f"training step (graph, fp16, batch 2): {result['train_step']['median_ms']:.2f} ms; next at B=2 is "
+              f"{100 * result['next_B2_share_of_step']:.2f} % of it", flush=True)
+    result["value"] = result["batches"]["2"]["next"]["median_ms"]
+    line = json.dumps(result)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
