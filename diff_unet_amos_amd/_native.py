@@ -146,6 +146,11 @@ class AugConfig(C.Structure):
                 ("shift_offsets", C.c_float), ("reserved", C.c_int)]
 
 
+class AugSmoothing(C.Structure):
+    """dua_aug_smoothing."""
+    _fields_ = [("alpha", C.c_float), ("order", C.c_float), ("epsilon", C.c_float), ("max_value", C.c_float)]
+
+
 AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
 
@@ -243,6 +248,9 @@ _SIGS = {
     "dua_aug_draw": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P,
                                _P]),
     "dua_aug_apply": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    "dua_aug_class_centroids": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dua_aug_apply_smoothed": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         _P, C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -11,10 +11,22 @@ memory, and two launches per batch (csrc/augment.hip) write exactly the two tens
 
 What the random words decide and how the patch is transformed is fixed in include/dua_hip.h ("training input"), not by
 MONAI's source; tests/augment_ref.py restates it independently.
+
+The reference's second label form, centroid-distance label smoothing (dataset/cache_dataset.py:105-153, ``label_smoothing:
+true``), comes from the same two launches: the cached case stays a uint8 label map plus three floats per class, and the
+smoothed channels are evaluated where the patch is written::
+
+    volumes = [DeviceVolume(image, label, num_classes=14) for image, label in cases]
+    producer = DeviceBatchProducer(volumes, class_ids=range(1, 14), smoothing=LabelSmoothing())
+
+``class_ids=range(1, K)`` is the reference's ``labels[:, 1:]`` for training (engine.py:159-160).  tests/label_smoothing_ref.py
+restates the definition; tests/golden/label_smoothing_golden.npz holds the reference's own outputs.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import math
 
 import torch
 
@@ -40,12 +52,45 @@ def pack_params(ints, floats, device=None):
     return out.to(device) if device is not None else out
 
 
+@dataclasses.dataclass(frozen=True)
+class LabelSmoothing:
+    """Centroid-distance label smoothing (dataset/cache_dataset.py:105-153, the ``rational`` form): channel k of a voxel at
+    distance d from the centroid of class k holds ``| [label == k] - alpha / (d ** order + epsilon) |``; the defaults are the
+    reference's (utils.py:112-113, cache_dataset.py:43-47).
+
+    The value is unbounded near a centroid, as it is in the reference: a class of one voxel has d = 0 there and the value is
+    ``|1 - alpha / epsilon|``, 3e5 with the defaults.  ``max_value=None`` keeps that; a number clamps every channel from above
+    and changes nothing else.  Pass one when training with fp16 activations (``NativeConvTrainer``'s default): ``2 * label - 1``
+    leaves the fp16 range above 32 752."""
+    alpha: float = 0.3
+    order: float = 1.0
+    epsilon: float = 1e-6
+    max_value: float | None = None
+
+    def __post_init__(self):
+        if not (math.isfinite(self.alpha) and self.alpha >= 0):
+            raise ValueError(f"LabelSmoothing: alpha is finite and not negative, got {self.alpha}")
+        if not (math.isfinite(self.order) and self.order > 0):
+            raise ValueError(f"LabelSmoothing: order is finite and positive, got {self.order}")
+        if not (math.isfinite(self.epsilon) and self.epsilon >= 2.0 ** -126):
+            raise ValueError(f"LabelSmoothing: epsilon is a positive normal fp32 number, got {self.epsilon}")
+        if self.max_value is not None and not self.max_value > 0:
+            raise ValueError(f"LabelSmoothing: max_value is None or positive, got {self.max_value}")
+
+    def native(self):
+        return nv.AugSmoothing(self.alpha, self.order, self.epsilon, math.inf if self.max_value is None else self.max_value)
+
+
 class DeviceVolume:
     """One cached case on the device: ``image`` fp32 [D, H, W] (or [1, D, H, W]) and ``label`` uint8 [D, H, W] of class ids,
     with the candidate sets of RandCropByPosNegLabel counted once (foreground = label > 0; background = label == 0 and
-    image > image_threshold) and their per-chunk prefix tables left on the device."""
+    image > image_threshold) and their per-chunk prefix tables left on the device.
 
-    def __init__(self, image, label, image_threshold=0.0, device="cuda"):
+    ``num_classes`` (background included) also computes, once, what label smoothing needs: ``centroids`` fp32 [K, 3] (the mean
+    index of every class, zeros for an absent one, as in the reference), ``class_counts`` int64 [K] and ``class_sums`` int64
+    [K, 3], all on the device.  A label map that holds an id >= num_classes is refused."""
+
+    def __init__(self, image, label, image_threshold=0.0, device="cuda", num_classes=None):
         if not (torch.is_tensor(image) and torch.is_tensor(label)):
             raise ValueError("DeviceVolume: image and label are tensors")
         if image.dim() == 4 and image.shape[0] == 1:
@@ -59,6 +104,10 @@ class DeviceVolume:
                              f"{tuple(label.shape)}")
         if image.numel() >= 2 ** 31:
             raise ValueError("DeviceVolume: a volume holds fewer than 2^31 voxels")
+        if num_classes is not None and not 1 <= int(num_classes) <= 256:
+            raise ValueError(f"DeviceVolume: num_classes counts the ids of a uint8 label map (1 .. 256), got {num_classes}")
+        if num_classes is not None and max(image.shape) > 2 ** 24:
+            raise ValueError("DeviceVolume: label smoothing takes voxel indices in fp32: extents up to 2^24")
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError(f"DeviceVolume: a GPU device, not {device}")
@@ -66,19 +115,28 @@ class DeviceVolume:
         self.label = label.to(device).contiguous()
         self.image_threshold = float(image_threshold)
         self.prefix = ops.aug_count_candidates(self.image, self.label, self.image_threshold)
-        totals = self.prefix[:, -1].tolist()                  # the one host read, at construction
+        self.num_classes = None if num_classes is None else int(num_classes)
+        self.centroids = self.class_counts = self.class_sums = None
+        totals = self.prefix[:, -1].to(torch.int64)
+        if self.num_classes is not None:
+            sums, self.centroids = ops.aug_class_centroids(self.label, self.num_classes)
+            self.class_counts, self.class_sums = sums[:self.num_classes, 0], sums[:self.num_classes, 1:]
+            totals = torch.cat([totals, sums[self.num_classes, :1]])
+        totals = totals.tolist()                              # the one host read, at construction
         self.fg_count, self.bg_count = int(totals[0]), int(totals[1])
+        if self.num_classes is not None and totals[2] != 0:
+            raise ValueError(f"DeviceVolume: {totals[2]} voxels of the label map hold an id >= num_classes = {self.num_classes}")
         if self.fg_count == 0 and self.bg_count == 0:
             raise ValueError("DeviceVolume: no crop centre: the label map has no foreground and no voxel of the image is above "
                              f"image_threshold = {self.image_threshold}")
 
     @classmethod
-    def from_hu(cls, image_hu, label, a_min=-175.0, a_max=250.0, image_threshold=0.0, device="cuda"):
+    def from_hu(cls, image_hu, label, a_min=-175.0, a_max=250.0, image_threshold=0.0, device="cuda", num_classes=None):
         """ScaleIntensityRanged(a_min, a_max, b_min=0, b_max=1, clip=True) of the reference's deterministic transforms, applied
         once with torch operators, then ``DeviceVolume``."""
         x = torch.as_tensor(image_hu).to(device=device, dtype=torch.float32)
         x = ((x - a_min) / (a_max - a_min)).clamp_(0.0, 1.0)
-        return cls(x, label, image_threshold=image_threshold, device=device)
+        return cls(x, label, image_threshold=image_threshold, device=device, num_classes=num_classes)
 
     @property
     def shape(self):
@@ -99,10 +157,15 @@ class DeviceBatchProducer:
     """Random patches of ``volumes`` as training batches: ``next(volume_ids)`` returns ``images`` fp32 [B, 1, *roi] and
     ``labels`` fp32 [B, len(class_ids), *roi] (one-hot of ``class_ids``), NCDHW contiguous, in two launches with no host read.
     Deterministic for a given (seed, call counter, volume_ids); the call counter is a 64-bit device word the draw launch
-    itself advances, so a captured ``next`` produces a new batch on every replay."""
+    itself advances, so a captured ``next`` produces a new batch on every replay.
+
+    ``smoothing`` (a ``LabelSmoothing``) makes ``labels`` the centroid-distance smoothed channels of ``class_ids`` instead of
+    the one-hot ones: same launches, same ``params``, and ``apply`` of a logged row reproduces the smoothed batch.  Every volume
+    then needs ``num_classes`` (one value for all).  ``class_ids=range(1, K)`` gives the channels the reference trains on
+    (``labels[:, 1:]``, engine.py:159-160).  Crop centres come from the hard label map either way."""
 
     def __init__(self, volumes, roi=(96, 96, 96), class_ids=range(16), pos=1, neg=1, flip_prob=0.1, rot90_prob=0.1, max_k=3,
-                 scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0):
+                 scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0, smoothing=None):
         volumes = list(volumes)
         if not volumes or not all(isinstance(v, DeviceVolume) for v in volumes):
             raise ValueError("DeviceBatchProducer: a non-empty list of DeviceVolume")
@@ -133,6 +196,20 @@ class DeviceBatchProducer:
         if float(rot90_prob) > 0 and roi[0] != roi[1]:
             raise ValueError(f"DeviceBatchProducer: the rotation is in the plane of the first two axes and needs roi[0] == roi[1] "
                              f"(roi = {roi}); pass rot90_prob=0")
+        if smoothing is not None:
+            if not isinstance(smoothing, LabelSmoothing):
+                raise ValueError("DeviceBatchProducer: smoothing is a LabelSmoothing or None")
+            missing = [i for i, v in enumerate(volumes) if v.centroids is None]
+            if missing:
+                raise ValueError(f"DeviceBatchProducer: smoothing needs class centroids, volumes {missing} were built without "
+                                 "num_classes")
+            if len({v.num_classes for v in volumes}) != 1:
+                raise ValueError("DeviceBatchProducer: smoothing needs one num_classes for every volume, got "
+                                 f"{sorted({v.num_classes for v in volumes})}")
+            if max(class_ids) >= volumes[0].num_classes:
+                raise ValueError(f"DeviceBatchProducer: class id {max(class_ids)} has no centroid (num_classes = "
+                                 f"{volumes[0].num_classes})")
+        self.smoothing = smoothing
         self.volumes, self.roi, self.class_ids, self.seed = volumes, roi, tuple(class_ids), int(seed)
         self.cfg = nv.AugConfig((C.c_int * 3)(*roi), int(max_k), float(pos) / (float(pos) + float(neg)), float(flip_prob),
                                 float(rot90_prob), float(scale_prob), float(scale_factors), float(shift_prob),
@@ -142,6 +219,9 @@ class DeviceBatchProducer:
         self.class_table = torch.tensor(class_ids, dtype=torch.uint8).to(self.device)
         self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if smoothing is not None:
+            self.centroids = torch.stack([v.centroids for v in volumes]).contiguous()       # fp32 [volumes, num_classes, 3]
+            self._smoothing = smoothing.native()
 
     @property
     def counter(self):
@@ -177,7 +257,8 @@ class DeviceBatchProducer:
             return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter)
 
     def apply(self, params, out_images=None, out_labels=None):
-        """The batch ``params`` describes: (images fp32 [B, 1, *roi], labels fp32 [B, len(class_ids), *roi])."""
+        """The batch ``params`` describes: (images fp32 [B, 1, *roi], labels fp32 [B, len(class_ids), *roi]); the labels are
+        one-hot, or smoothed when the producer was built with ``smoothing``."""
         assert torch.is_tensor(params) and params.is_cuda and params.device == self.device, "params: a tensor on the producer's device"
         B = params.shape[0]
         if out_images is None:
@@ -185,6 +266,9 @@ class DeviceBatchProducer:
         if out_labels is None:
             out_labels = torch.empty((B, len(self.class_ids)) + self.roi, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
+            if self.smoothing is not None:
+                return ops.aug_apply_smoothed(self.table, self.centroids, self._smoothing, params, self.roi, self.class_table,
+                                              out_images, out_labels, self._status)
             return ops.aug_apply(self.table, params, self.roi, self.class_table, out_images, out_labels, self._status)
 
     def next(self, volume_ids, out_images=None, out_labels=None):

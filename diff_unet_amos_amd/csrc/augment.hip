@@ -15,6 +15,12 @@
 //            plane, so an output row along w is always one source row, forwards or backwards: a lane owns 4 consecutive
 //            output voxels, reads their 4 floats and 4 label bytes and writes one 16-byte store into the image plane and
 //            into each of the C label planes; a wave-instruction covers 1 KiB of one plane.
+//   centroids : once per volume, for label smoothing (dataset/cache_dataset.py:105-153).  One pass over the label map, 16 bytes
+//            per thread and step; count and index sums per class as 64-bit integers, LDS atomics inside a workgroup, one
+//            global integer atomic per class and workgroup: exact, so identical between runs.  A finish launch divides in fp64.
+//   smoothed apply : the apply kernel with another body for the label planes (template parameter MODE): the same index code
+//            gives the source index of a lane's 4 voxels, the centroids of the row's volume sit in LDS (one broadcast read per
+//            channel), and a channel costs 4 x (sub, fma, sqrt, add, rcp, mul, sub, min) before its 16-byte store.
 // -ffp-contract=off (csrc/Makefile) keeps the three fp32 operations of the intensity transform, and the two of each drawn
 // value, separately rounded; the pragma below says so for this file whatever the command line.
 #include "common.hpp"
@@ -184,14 +190,26 @@ template <int V> struct OutVec;
 template <> struct OutVec<4> { using T = f32x4; };
 template <> struct OutVec<1> { using T = float; };
 
-// V output voxels per lane (4: roi_w is a multiple of 4, so a group never crosses a row and every store is 16-byte aligned)
-template <int V>
+// what the smoothed forms need beyond the one-hot apply (unused by SMOOTH_NONE)
+struct AugSmooth {
+  const float* centroids;                                 // fp32 [nvol][K][3]
+  int K;
+  float alpha, order, epsilon, max_value;
+};
+enum { SMOOTH_NONE = 0, SMOOTH_ORDER1 = 1, SMOOTH_POW = 2 };
+
+// V output voxels per lane (4: roi_w is a multiple of 4, so a group never crosses a row and every store is 16-byte aligned).
+// MODE: what a label plane holds -- SMOOTH_NONE: the one-hot channel; SMOOTH_ORDER1 / SMOOTH_POW: the centroid-distance
+// smoothed channel (order == 1 without pow), evaluated at the source index that the index code, shared by all, finds.
+template <int V, int MODE>
 __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_volume* __restrict__ table, int nvol,
                                                                const int* __restrict__ params, int Rd, int Rh, int Rw,
                                                                const unsigned char* __restrict__ class_ids, int C,
                                                                float* __restrict__ images, float* __restrict__ labels,
-                                                               int* status) {
+                                                               int* status, AugSmooth sm) {
   using Vec = typename OutVec<V>::T;
+  __shared__ float cen[MODE == SMOOTH_NONE ? 1 : DUA_AUG_MAX_CLASSES][4];      // centroid of class_ids[ch] in the row's volume
+  __shared__ int bad_id;
   const int b = blockIdx.y;
   const int* row = params + (long)b * DUA_AUG_PARAM_WORDS;
   const int vid = row[DUA_AUG_VOLUME], sd0 = row[DUA_AUG_START_D], sh0 = row[DUA_AUG_START_H], sw0 = row[DUA_AUG_START_W];
@@ -205,6 +223,24 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
   if (!ok) {                                              // block-uniform: nothing is read, nothing is written
     if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
     return;
+  }
+  if constexpr (MODE != SMOOTH_NONE) {
+    if (threadIdx.x == 0) bad_id = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < C) {                           // C <= DUA_AUG_MAX_CLASSES < AUG_THREADS
+      const int id = class_ids[threadIdx.x];
+      if (id < sm.K) {
+        const float* c3 = sm.centroids + ((long)vid * sm.K + id) * 3;
+        cen[threadIdx.x][0] = c3[0]; cen[threadIdx.x][1] = c3[1]; cen[threadIdx.x][2] = c3[2];
+      } else {
+        bad_id = 1;
+      }
+    }
+    __syncthreads();
+    if (bad_id) {                                         // block-uniform again: a class id without a centroid row
+      if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
+      return;
+    }
   }
   const long vox = (long)Rd * Rh * Rw;
   const unsigned o = (blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x) * V;   // first output voxel of this lane (vox < 2^31)
@@ -242,18 +278,111 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
   }
   *reinterpret_cast<Vec*>(images + (long)b * vox + o) = v;
   float* lab = labels + (long)b * C * vox + o;
+  if constexpr (MODE == SMOOTH_NONE) {
 #pragma unroll 4
-  for (int ch = 0; ch < C; ++ch) {
-    const unsigned char id = class_ids[ch];
-    Vec m;
-    if constexpr (V == 4) {
+    for (int ch = 0; ch < C; ++ch) {
+      const unsigned char id = class_ids[ch];
+      Vec m;
+      if constexpr (V == 4) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = lb[e] == id ? 1.f : 0.f;
-    } else {
-      m = lb[0] == id ? 1.f : 0.f;
+        for (int e = 0; e < 4; ++e) m[e] = lb[e] == id ? 1.f : 0.f;
+      } else {
+        m = lb[0] == id ? 1.f : 0.f;
+      }
+      *reinterpret_cast<Vec*>(lab + (long)ch * vox) = m;
     }
-    *reinterpret_cast<Vec*>(lab + (long)ch * vox) = m;
+  } else {
+    // the source index of the lane's voxels is (sd0 + a, sh0 + c, sw0 + sw_e); fp32 holds it exactly for extents up to 2^24
+    const float fd = (float)(sd0 + a), fh = (float)(sh0 + c);
+    float fx[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) fx[e] = (float)(sw0 + (fw ? Rw - 1 - (ow + e) : ow + e));
+#pragma unroll 2
+    for (int ch = 0; ch < C; ++ch) {
+      const unsigned char id = class_ids[ch];
+      const float dd = fd - cen[ch][0], dh = fh - cen[ch][1], cw = cen[ch][2];
+      const float t = dd * dd + dh * dh;
+      float m[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const float dw = fx[e] - cw;
+        const float dist = __builtin_amdgcn_sqrtf(__builtin_fmaf(dw, dw, t));
+        const float p = MODE == SMOOTH_POW ? powf(dist, sm.order) : dist;
+        const float s = __builtin_amdgcn_rcpf(p + sm.epsilon) * sm.alpha;
+        m[e] = fminf(fabsf((lb[e] == id ? 1.f : 0.f) - s), sm.max_value);
+      }
+      if constexpr (V == 4) {
+        Vec mv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mv[e] = m[e];
+        *reinterpret_cast<Vec*>(lab + (long)ch * vox) = mv;
+      } else {
+        *(lab + (long)ch * vox) = m[0];
+      }
+    }
   }
+}
+
+constexpr int CEN_THREADS = 256;
+constexpr int CEN_RUN = 16;                               // label bytes per thread and step: one 16-byte load
+constexpr int CEN_MAX_BLOCKS = 2048;
+constexpr int CEN_MAX_CLASSES = 256;                      // every value of a uint8 label map
+
+// sums[k] += (count, sum d, sum h, sum w) of the voxels of class k (row K: ids >= K).  A thread takes 16 consecutive voxels and
+// adds to the workgroup's LDS table once per run of equal ids (label maps are piecewise constant: mostly one run); the
+// workgroup adds its non-zero entries to the global table once.  64-bit integer atomics at both levels: the sums are exact
+// and do not depend on the order of arrival.
+__global__ void __launch_bounds__(CEN_THREADS) aug_class_sums_kernel(const unsigned char* __restrict__ label, long voxels, int H,
+                                                                    int W, int K, unsigned long long* __restrict__ sums) {
+  __shared__ unsigned long long part[(CEN_MAX_CLASSES + 1) * 4];
+  for (int i = threadIdx.x; i < (K + 1) * 4; i += CEN_THREADS) part[i] = 0;
+  __syncthreads();
+  const long groups = (voxels + CEN_RUN - 1) / CEN_RUN;
+  for (long g = (long)blockIdx.x * CEN_THREADS + threadIdx.x; g < groups; g += (long)gridDim.x * CEN_THREADS) {
+    const long i0 = g * CEN_RUN;
+    const int n = (int)min((long)CEN_RUN, voxels - i0);
+    unsigned char lb[CEN_RUN];
+    if (n == CEN_RUN) {                                   // label is 16-byte aligned (checked by the launcher)
+      const uint4 q = *reinterpret_cast<const uint4*>(label + i0);
+      const unsigned wd[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < CEN_RUN; ++e) lb[e] = (unsigned char)(wd[e >> 2] >> (8 * (e & 3)));
+    } else {
+#pragma unroll
+      for (int e = 0; e < CEN_RUN; ++e) lb[e] = e < n ? label[i0 + e] : 0;
+    }
+    const unsigned line = (unsigned)i0 / (unsigned)W;     // voxels < 2^31
+    int w = (int)((unsigned)i0 - line * (unsigned)W), d = (int)(line / (unsigned)H), h = (int)(line - (unsigned)d * (unsigned)H);
+    int cur = min((int)lb[0], K);
+    unsigned long long cnt = 0, sd = 0, sh = 0, sw = 0;
+#pragma unroll
+    for (int e = 0; e < CEN_RUN; ++e) {
+      if (e < n) {
+        const int id = min((int)lb[e], K);
+        if (id != cur) {
+          atomicAdd(&part[cur * 4 + 0], cnt); atomicAdd(&part[cur * 4 + 1], sd);
+          atomicAdd(&part[cur * 4 + 2], sh); atomicAdd(&part[cur * 4 + 3], sw);
+          cur = id; cnt = sd = sh = sw = 0;
+        }
+        cnt += 1; sd += (unsigned)d; sh += (unsigned)h; sw += (unsigned)w;
+        if (++w == W) { w = 0; if (++h == H) { h = 0; ++d; } }
+      }
+    }
+    atomicAdd(&part[cur * 4 + 0], cnt); atomicAdd(&part[cur * 4 + 1], sd);
+    atomicAdd(&part[cur * 4 + 2], sh); atomicAdd(&part[cur * 4 + 3], sw);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < (K + 1) * 4; i += CEN_THREADS)
+    if (part[i]) atomicAdd(&sums[i], part[i]);
+}
+
+// centroids[k] = fp32(sum / count), the division in fp64 on exact operands (below 2^53); zeros for an absent class
+__global__ void aug_centroid_finish_kernel(int K, const unsigned long long* __restrict__ sums, float* __restrict__ centroids) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= K) return;
+  const unsigned long long n = sums[k * 4];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) centroids[k * 3 + j] = n ? (float)((double)sums[k * 4 + 1 + j] / (double)n) : 0.f;
 }
 
 static bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }
@@ -301,13 +430,63 @@ int dua_aug_apply(const dua_aug_volume* table, int nvol, const int* params, int 
   const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
   if (wide) {
     const dim3 grid((unsigned)((vox / 4 + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-    hipLaunchKernelGGL(dua::aug_apply_kernel<4>, grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, roi_d, roi_h, roi_w,
-                       class_ids, C, images, labels, status);
+    hipLaunchKernelGGL((dua::aug_apply_kernel<4, dua::SMOOTH_NONE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params,
+                       roi_d, roi_h, roi_w, class_ids, C, images, labels, status, dua::AugSmooth{});
   } else {
     const dim3 grid((unsigned)((vox + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-    hipLaunchKernelGGL(dua::aug_apply_kernel<1>, grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, roi_d, roi_h, roi_w,
-                       class_ids, C, images, labels, status);
+    hipLaunchKernelGGL((dua::aug_apply_kernel<1, dua::SMOOTH_NONE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params,
+                       roi_d, roi_h, roi_w, class_ids, C, images, labels, status, dua::AugSmooth{});
   }
+  return (int)hipGetLastError();
+}
+
+int dua_aug_class_centroids(const unsigned char* label, int D, int H, int W, int num_classes, unsigned long long* sums,
+                            float* centroids, void* stream) {
+  if (!label || ((size_t)label & 15) || D < 1 || H < 1 || W < 1 || num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES ||
+      !sums || !centroids)
+    return DUA_ERR_ARG;
+  const long voxels = (long)D * H * W;                    // three factors below 2^31: cannot wrap before the test below
+  const long longest = D > H ? (D > W ? D : W) : (H > W ? H : W);
+  if ((long)D * H >= (1L << 31) || voxels >= (1L << 31) || voxels * longest >= (1L << 53)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(sums, 0, sizeof(unsigned long long) * 4 * (num_classes + 1), s);
+  if (e != hipSuccess) return (int)e;
+  const long per_block = (long)dua::CEN_RUN * dua::CEN_THREADS;
+  const long blocks = (voxels + per_block - 1) / per_block;
+  hipLaunchKernelGGL(dua::aug_class_sums_kernel, dim3((unsigned)(blocks < dua::CEN_MAX_BLOCKS ? blocks : dua::CEN_MAX_BLOCKS)),
+                     dim3(dua::CEN_THREADS), 0, s, label, voxels, H, W, num_classes, sums);
+  hipLaunchKernelGGL(dua::aug_centroid_finish_kernel, dim3((num_classes + 63) / 64), dim3(64), 0, s, num_classes, sums, centroids);
+  return (int)hipGetLastError();
+}
+
+int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
+                           const dua_aug_smoothing* smoothing, const int* params, int B, int roi_d, int roi_h, int roi_w,
+                           const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream) {
+  if (!table || nvol < 1 || !params || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 || !class_ids || C < 1 ||
+      C > DUA_AUG_MAX_CLASSES || !images || !labels || !centroids || num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES ||
+      !smoothing)
+    return DUA_ERR_ARG;
+  const dua_aug_smoothing p = *smoothing;
+  // every comparison is false for a NaN.  epsilon is a normal number, so that 1 / (dist^order + epsilon) stays finite and
+  // alpha = 0 gives exactly 0
+  if (!(p.alpha >= 0.f && p.alpha <= 3.0e38f) || !(p.order > 0.f && p.order <= 3.0e38f) ||
+      !(p.epsilon >= 1.17549435e-38f && p.epsilon <= 3.0e38f) || !(p.max_value > 0.f))
+    return DUA_ERR_ARG;
+  const long vox = (long)roi_d * roi_h * roi_w;
+  if (vox >= (1L << 31)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const dua::AugSmooth sm{centroids, num_classes, p.alpha, p.order, p.epsilon, p.max_value};
+  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
+  const bool pw = p.order != 1.f;
+  const dim3 grid((unsigned)(((wide ? vox / 4 : vox) + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
+#define DUA_AUG_SMOOTHED(V, MODE)                                                                                              \
+  hipLaunchKernelGGL((dua::aug_apply_kernel<V, MODE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, roi_d, roi_h, \
+                     roi_w, class_ids, C, images, labels, status, sm)
+  if (wide && !pw) DUA_AUG_SMOOTHED(4, dua::SMOOTH_ORDER1);
+  else if (wide) DUA_AUG_SMOOTHED(4, dua::SMOOTH_POW);
+  else if (!pw) DUA_AUG_SMOOTHED(1, dua::SMOOTH_ORDER1);
+  else DUA_AUG_SMOOTHED(1, dua::SMOOTH_POW);
+#undef DUA_AUG_SMOOTHED
   return (int)hipGetLastError();
 }
 

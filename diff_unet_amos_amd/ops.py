@@ -1655,3 +1655,43 @@ def aug_apply(table, params, roi, class_ids, images, labels, status):
     nv.check(nv.lib().dua_aug_apply(nv.ptr(table), nvol, nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
                                     nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply")
     return images, labels
+
+
+# ---- centroid-distance label smoothing of the training input (csrc/augment.hip; dataset/cache_dataset.py:105-153) ----
+
+def aug_class_centroids(label, num_classes):
+    """dua_aug_class_centroids: (sums int64 [num_classes + 1, 4] = voxel count and the sums of d, h, w per class, the last row
+    for ids >= num_classes; centroids fp32 [num_classes, 3], zeros for an absent class) of a uint8 [D, H, W] label map."""
+    _u8c(label, "label")
+    K = int(num_classes)
+    assert label.dim() == 3 and 0 < label.numel() < 2 ** 31, "label: [D, H, W] of fewer than 2^31 voxels"
+    assert 1 <= K <= 256, "num_classes: 1 .. 256"
+    D, H, W = label.shape
+    sums = torch.empty((K + 1, 4), dtype=torch.int64, device=label.device)
+    centroids = torch.empty((K, 3), dtype=torch.float32, device=label.device)
+    with torch.cuda.device(label.device):
+        nv.check(nv.lib().dua_aug_class_centroids(nv.ptr(label), D, H, W, K, nv.ptr(sums), nv.ptr(centroids), nv.stream_ptr()),
+                 "dua_aug_class_centroids")
+    return sums, centroids
+
+
+def aug_apply_smoothed(table, centroids, smoothing, params, roi, class_ids, images, labels, status):
+    """dua_aug_apply_smoothed: ``aug_apply`` with centroid-distance smoothed label channels; ``centroids`` fp32
+    [volumes, num_classes, 3], ``smoothing`` an ``nv.AugSmoothing``."""
+    nvol = _aug_table(table)
+    _i32c(params, "params"); _i32c(status, "status"); _u8c(class_ids, "class_ids")
+    _f32c(images, "images"); _f32c(labels, "labels"); _f32c(centroids, "centroids")
+    B, Cn = params.shape[0], class_ids.numel()
+    assert params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS and B >= 1 and status.numel() == 1
+    assert 1 <= Cn <= nv.AUG_MAX_CLASSES, f"1 .. {nv.AUG_MAX_CLASSES} classes"
+    assert centroids.dim() == 3 and centroids.shape[0] == nvol and centroids.shape[2] == 3, "centroids: [volumes, num_classes, 3]"
+    assert isinstance(smoothing, nv.AugSmoothing)
+    rd, rh, rw = (int(r) for r in roi)
+    assert tuple(images.shape) == (B, 1, rd, rh, rw), f"images: [{B}, 1, {rd}, {rh}, {rw}], got {tuple(images.shape)}"
+    assert tuple(labels.shape) == (B, Cn, rd, rh, rw), f"labels: [{B}, {Cn}, {rd}, {rh}, {rw}], got {tuple(labels.shape)}"
+    assert all(t.device == table.device for t in (params, status, class_ids, images, labels, centroids)), \
+        "every tensor on the volumes' device"
+    nv.check(nv.lib().dua_aug_apply_smoothed(nv.ptr(table), nvol, nv.ptr(centroids), centroids.shape[1], C.byref(smoothing),
+                                             nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
+                                             nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply_smoothed")
+    return images, labels

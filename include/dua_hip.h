@@ -857,6 +857,43 @@ int dua_aug_draw(const dua_aug_volume* table, int nvol, const int* ids, int B, c
 int dua_aug_apply(const dua_aug_volume* table, int nvol, const int* params, int B, int roi_d, int roi_h, int roi_w,
                   const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream);
 
+/* ---- training input: centroid-distance label smoothing --------------------------------------------------------------
+ * The reference's second label form (dataset/cache_dataset.py:105-153, `label_smoothing: true`): there a float tensor with
+ * one channel per class, computed once per case on the whole volume and cached (4 K bytes per voxel).  Here the cached case
+ * stays one byte per voxel plus 3 floats per class, and the smoothed value is evaluated where a patch is written: cropping,
+ * flipping and rotating only move voxels, so a patch of the smoothed field is the field at the patch's source indices.
+ *
+ * For a label map L of extents (D, H, W) with ids in [0, K), K = num_classes (background included):
+ *   centroid[k] = mean index (d, h, w) of the voxels with L == k; (0, 0, 0) when class k is absent (as the reference leaves it)
+ *   dist[k][v]  = || index(v) - centroid[k] ||_2
+ *   out[k][v]   = min(| [L(v) == k] - alpha / (dist[k][v] ^ order + epsilon) |, max_value)
+ * The reference has no max_value (pass +inf): out is unbounded near a centroid -- a one-voxel class has dist = 0 at its voxel
+ * and out = |1 - alpha / epsilon| there, 3e5 with the defaults (alpha 0.3, order 1, epsilon 1e-6).
+ *
+ * dua_aug_class_centroids, once per volume: one pass over the label map.  sums (WRITTEN, the call zeroes it first) = 64-bit
+ * unsigned [num_classes + 1][4]: voxel count and the sums of d, of h and of w per class; row num_classes collects the voxels
+ * whose id is >= num_classes (a caller that finds a count there refuses the volume).  Integer sums, integer atomics: the
+ * result does not depend on the order of arrival and is identical between runs.  centroids (WRITTEN) = fp32 [num_classes][3]:
+ * sum / count divided in fp64 (exact operands: D H W max(D, H, W) < 2^53 is required) and rounded to fp32; zeros for count 0.
+ * label must be 16-byte aligned.
+ *
+ * dua_aug_apply_smoothed: dua_aug_apply with
+ *   labels[b, c] = out[class_ids[c]] of the row's volume at the source index of each output voxel
+ * and images, the params rows, the skipping of rows and *status exactly as there.  centroids = fp32 [nvol][num_classes][3],
+ * volume v of the table at row v.  fp32 arithmetic: dist = sqrt(fma(dw, dw, dd dd + dh dh)) with the differences taken
+ * against the fp32 centroid, r = 1 / (dist ^ order + epsilon), out = min(|onehot - r alpha|, max_value); square root and
+ * reciprocal are the hardware's (1 ulp); order == 1 takes no pow.  alpha == 0 gives the bits of dua_aug_apply.  A class id
+ * >= num_classes in class_ids makes the launch write nothing and set *status.
+ * Arguments: alpha >= 0, order > 0, epsilon a normal fp32 > 0, max_value > 0 (+inf = none), all finite but max_value. */
+typedef struct {
+  float alpha, order, epsilon, max_value;
+} dua_aug_smoothing;
+int dua_aug_class_centroids(const unsigned char* label, int D, int H, int W, int num_classes, unsigned long long* sums,
+                            float* centroids, void* stream);
+int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
+                           const dua_aug_smoothing* smoothing, const int* params, int B, int roi_d, int roi_h, int roi_w,
+                           const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,18 @@ producer's own rows, read back before the timed window), as a torch user's would
 the outputs hold, 4 (1 + C) per voxel, over the median call time; ``apply`` alone is timed the same way.  ``--with-step``
 adds one training step of NativeConvTrainer (graph mode, fp16, batch 2, 96^3, 16 classes: BASELINE config 4) on synthetic
 inputs.  One JSON line at the end, also written to ``--out``.
+
+    python tools/bench_augment.py --smoothing [--onehot-lib other/libdua_hip.so] [--rounds 21] [--repeats 200]
+
+``--smoothing`` times, instead, the centroid-distance smoothed ``apply`` next to the one-hot ``apply`` at B = 2, roi 96^3 and
+C = 13 and 15 channels (``class_ids = range(1, K)``, K = 14 and 16), same params, same outputs, alternating rounds in one
+process.  The one-hot side is ``dua_aug_apply`` of ``--onehot-lib`` (default: the library ``DUA_HIP_LIB`` names, else the
+package's own), loaded next to the package's library, so that the smoothed kernel of this tree is measured against the one-hot
+kernel of another build.  Both write the same bytes, 4 (1 + C) per voxel.  It also times the once-per-volume centroid pass
+(``dua_aug_class_centroids``) next to ``dua_aug_count_candidates`` on a 512 x 512 x 150 label map.
 """
 import argparse
+import ctypes
 import json
 import os
 import socket
@@ -29,16 +39,20 @@ DEV = "cuda:0"
 ROI, CLASSES = (96, 96, 96), 16
 
 
-def volumes(n):
+def block_labels(shape, classes, g):
+    coarse = torch.randint(0, classes * 3, tuple(-(-s // 8) for s in shape), generator=g)
+    coarse = torch.where(coarse < classes, coarse, torch.zeros_like(coarse))
+    label = coarse.repeat_interleave(8, 0).repeat_interleave(8, 1).repeat_interleave(8, 2)
+    return label[:shape[0], :shape[1], :shape[2]].to(torch.uint8).contiguous()
+
+
+def volumes(n, classes=CLASSES, num_classes=None):
     out = []
     for i in range(n):
         g = torch.Generator().manual_seed(100 + i)
         shape = (200 + 4 * (i % 3), 160 + 3 * (i % 4), 160 + 5 * (i % 2))
-        coarse = torch.randint(0, CLASSES * 3, tuple(-(-s // 8) for s in shape), generator=g)
-        coarse = torch.where(coarse < CLASSES, coarse, torch.zeros_like(coarse))
-        label = coarse.repeat_interleave(8, 0).repeat_interleave(8, 1).repeat_interleave(8, 2)
-        label = label[:shape[0], :shape[1], :shape[2]].to(torch.uint8).contiguous()
-        out.append(augment.DeviceVolume(torch.rand(shape, generator=g) - 0.3, label, device=DEV))
+        label = block_labels(shape, classes, g)
+        out.append(augment.DeviceVolume(torch.rand(shape, generator=g) - 0.3, label, device=DEV, num_classes=num_classes))
     return out
 
 
@@ -100,6 +114,67 @@ def train_step_ms(warmup, steps):
     return summary(per)
 
 
+def smoothing_bench(args):
+    from diff_unet_amos_amd import _native as nv
+    from diff_unet_amos_amd import ops
+    path = args.onehot_lib or os.environ.get("DUA_HIP_LIB") or nv.LIB_PATH
+    other = ctypes.CDLL(path)
+    other.dua_aug_apply.restype, other.dua_aug_apply.argtypes = nv._SIGS["dua_aug_apply"]
+    B = 2
+    result = {"metric": "augment_smoothed_apply_time", "unit": "ms", "box": socket.gethostname(),
+              "device": torch.cuda.get_device_name(0), "roi": ROI, "B": B, "repeats": args.repeats, "rounds": args.rounds,
+              "onehot_lib": os.path.relpath(path), "channels": {}}
+    for K in (14, 16):
+        vols = volumes(args.volumes, classes=K, num_classes=K)
+        ids = torch.tensor([i % len(vols) for i in range(B)], dtype=torch.int32, device=DEV)
+        kw = dict(roi=ROI, class_ids=range(1, K), flip_prob=0.5, rot90_prob=0.5, scale_prob=0.5, seed=2)
+        hard, soft = augment.DeviceBatchProducer(vols, **kw), augment.DeviceBatchProducer(vols, smoothing=augment.LabelSmoothing(), **kw)
+        params = hard.draw(ids)
+        out_images = torch.empty((B, 1) + ROI, device=DEV)
+        out_labels = torch.empty((B, K - 1) + ROI, device=DEV)
+
+        def onehot_fn():
+            nv.check(other.dua_aug_apply(nv.ptr(hard.table), len(vols), nv.ptr(params), B, *ROI, nv.ptr(hard.class_table), K - 1,
+                                         nv.ptr(out_images), nv.ptr(out_labels), nv.ptr(hard._status), nv.stream_ptr()), "dua_aug_apply")
+
+        def smoothed_fn():
+            soft.apply(params, out_images, out_labels)
+
+        onehot_fn()
+        same = bool(torch.equal(out_labels, hard.apply(params)[1]))          # the other build writes this build's one-hot bits
+        for _ in range(args.warmup):
+            onehot_fn(); smoothed_fn()
+        torch.cuda.synchronize()
+        ms_hard, ms_soft = timed_rounds((onehot_fn, smoothed_fn), args.repeats, args.rounds)
+        nbytes = 4 * K * B * ROI[0] * ROI[1] * ROI[2]
+        entry = {"onehot_apply": summary(ms_hard), "smoothed_apply": summary(ms_soft), "bytes_written": nbytes,
+                 "onehot_equal_between_builds": same,
+                 "onehot_write_GBps": nbytes / (statistics.median(ms_hard) * 1e-3) / 1e9,
+                 "smoothed_write_GBps": nbytes / (statistics.median(ms_soft) * 1e-3) / 1e9,
+                 "smoothed_over_onehot": statistics.median(ms_soft) / statistics.median(ms_hard)}
+        result["channels"][str(K - 1)] = entry
+        print(f"C={K - 1}: one-hot apply {entry['onehot_apply']['median_ms']:.4f} ms = {entry['onehot_write_GBps']:.0f} GB/s, smoothed "
+              f"apply {entry['smoothed_apply']['median_ms']:.4f} ms ({entry['smoothed_apply']['min_ms']:.4f} .. "
+              f"{entry['smoothed_apply']['max_ms']:.4f}) = {entry['smoothed_write_GBps']:.0f} GB/s: ratio "
+              f"{entry['smoothed_over_onehot']:.3f}; one-hot bits equal between builds: {same}", flush=True)
+        assert hard.status == 0 and soft.status == 0
+        del vols, hard, soft
+    # once per case: the centroid pass next to the candidate count, on a label map of the size of a BTCV scan
+    g = torch.Generator().manual_seed(7)
+    shape = (150, 512, 512)
+    label = block_labels(shape, 14, g).to(DEV)
+    image = (torch.rand(shape, generator=g) - 0.3).to(DEV)
+    fns = (lambda: ops.aug_class_centroids(label, 14), lambda: ops.aug_count_candidates(image, label, 0.0))
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ms_cen, ms_cnt = timed_rounds(fns, 20, args.rounds)
+    result["per_volume"] = {"shape": shape, "class_centroids": summary(ms_cen), "count_candidates": summary(ms_cnt)}
+    print(f"{shape}: class centroids {statistics.median(ms_cen):.4f} ms, candidate count {statistics.median(ms_cnt):.4f} ms", flush=True)
+    result["value"] = result["channels"]["15"]["smoothed_apply"]["median_ms"]
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=1000)
@@ -108,9 +183,18 @@ def main():
     ap.add_argument("--volumes", type=int, default=8)
     ap.add_argument("--with-step", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--smoothing", action="store_true", help="smoothed apply next to the one-hot apply, and the centroid pass")
+    ap.add_argument("--onehot-lib", default="", help="with --smoothing: the build whose dua_aug_apply is the one-hot side")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_augment.py measures on the GPU; none is visible")
+    if args.smoothing:
+        line = json.dumps(smoothing_bench(args))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     vols = volumes(args.volumes)
     prod = augment.DeviceBatchProducer(vols, roi=ROI, class_ids=range(CLASSES), seed=1)
     class_ids = torch.arange(CLASSES, dtype=torch.uint8, device=DEV).view(-1, 1, 1, 1)
