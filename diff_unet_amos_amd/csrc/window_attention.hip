@@ -29,6 +29,10 @@
 // 128 contiguous bytes per key.  The shifted-window mask can instead be given as what compute_mask builds it from: one
 // region id per token of every window ([windows per image][tokens], uint8; attention.py:135-157) -- 343 bytes per window
 // instead of 343 x 343 floats (161 MB per image at 48^3 tokens); the kernel adds -100 where the ids of query and key differ.
+// Precision: T = float changes the LOADS and the STORE only.  q, k and v are rounded to fp16 on load (load8) and the
+// probabilities are rounded to fp16 before the second product -- both products run on the fp16 MFMA in either instantiation;
+// accumulation is fp32.  The fp32 form is therefore accurate to about 2^-11 of the spread of v under the softmax weights, not
+// to an fp32 rounding (tests/swin_fp64ref.py derives the bound).
 #include "common.hpp"
 #include "../../include/dua_hip.h"
 

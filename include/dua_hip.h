@@ -652,7 +652,11 @@ int dua_instnorm_stats(int dtype, int N, long voxels, int C, const void* x, int 
  *            per sample, `samples` grid rows)                                            conv3 + norm3 statistics
  *   RESIDUAL x[token][n] += out + bias on the fp32 stream                                x + mlp(norm2(x)), transformer.py:477-480
  *   SCATTER  token = window order: x[voxel(token)] += out + bias, ln_out[voxel] = LayerNorm(x)*gamma+beta; padding tokens
- *            dropped (window_reverse, roll back, crop, shortcut add, norm2: transformer.py:417-434, 475-476) */
+ *            dropped (window_reverse, roll back, crop, shortcut add, norm2: transformer.py:417-434, 475-476); N = 48, 96 or 192.
+ * Every mode keeps the weights (32 ceil(N / 32) rows of 2 K bytes, padded) and one 128-token tile (the wider of the fp16 input
+ * chunk and the output tile, fp32 for RESIDUAL / SCATTER) in LDS; a launch that needs more than 160 KiB returns DUA_ERR_ARG.
+ * This excludes SCATTER with K = N = 192 (177 168 bytes): at that width use dua_token_linear PLAIN +
+ * dua_window_scatter_add_norm.  SCATTER with N = 192 and K <= 152 fits. */
 #define DUA_TOKLIN_PLAIN 0
 #define DUA_TOKLIN_GELU 1
 #define DUA_TOKLIN_STATS 2
