@@ -152,6 +152,7 @@ class AugSmoothing(C.Structure):
 
 
 AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
+BLEND_MAX_CLASSES = 64   # DUA_BLEND_MAX_CLASSES
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
 
 _P = C.c_void_p
@@ -251,6 +252,8 @@ _SIGS = {
     "dua_aug_class_centroids": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dua_aug_apply_smoothed": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _P, C.c_int, _P, _P, _P, _P]),
+    "dua_blend_accumulate": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 + [_P, _P]),
+    "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,246 @@
+// Streamed sliding-window blend (Engine.infer, engine.py:167-182; Tester, test.py:119-159; metric.py:37-49): window outputs
+// are added into a device-resident fp32 sum volume as soon as a predictor call returns, and one pass afterwards divides by the
+// window count, crops the padding away, binarises and tallies Dice.  The contract is written down in include/dua_hip.h; this
+// file only says how it is computed.
+//
+//   accumulate : ONE GRID PER WINDOW, enqueued in window-index order inside the call.  Windows of one predictor call overlap
+//            each other (scan interval 19 at roi 96, overlap 0.8), so two windows' additions into one voxel need an order; the
+//            stream gives it, no atomics, and every voxel sees the fp32 additions of a slice-add per window in index order.
+//            A kernel boundary costs 1.5-2 us against >= 30 us of traffic for a 16 x 96^3 window (window read, volume read,
+//            volume written: 170 MB), and a call holds sw_batch_size (1..4) windows.
+//            The volume side is the read-modify-write side, so the lanes are laid along the VOLUME's 16-byte groups: a window
+//            row starts `shift` = (element offset of its first voxel) mod 4 elements into a group, lane g of a row owns group g
+//            and does one aligned 16-byte load and store there; the two groups a row only partly covers are done by element.
+//            The window side is read at whatever alignment that leaves it (one 16-byte load when shift == 0 and the row is
+//            aligned, four dword loads otherwise: reads of one cache line by neighbouring lanes).  A volume whose base is not
+//            16-byte aligned takes the one-element-per-lane form.
+//            Every lane reads the table row (a wave-uniform load) and clamps it into the volume before forming an address.
+//   finish : grid = (blocks, B C): a workgroup stays inside one channel plane, so its Dice tallies are three counters.  When
+//            nothing is cropped and a plane is a multiple of 4 voxels, a lane takes 4 consecutive voxels (16-byte load of the
+//            sums, 16-byte store of q, 4-byte store of the mask, 16- or 4-byte load of the labels); otherwise one voxel.
+//            Counters: per lane -> wave shuffle -> LDS -> one 64-bit integer atomic per counter and workgroup.
+#include "common.hpp"
+#include "../../include/dua_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace dua {
+
+constexpr int BLEND_THREADS = 256;
+constexpr int BLEND_FINISH_BLOCKS = 256;      // per channel plane; grid-stride beyond
+
+enum { LABELS_NONE = 0, LABELS_ONEHOT_F32 = 1, LABELS_ONEHOT_U8 = 2, LABELS_MAP_U8 = 3 };
+
+__device__ __forceinline__ int clamp_flag(int v, int hi, bool& bad) {       // into [0, hi]
+  if (v < 0) { bad = true; return 0; }
+  if (v > hi) { bad = true; return hi; }
+  return v;
+}
+
+__device__ __forceinline__ f32x4 load4(const float* p) {
+  if (((size_t)p & 15) == 0) return *reinterpret_cast<const f32x4*>(p);
+  return f32x4{p[0], p[1], p[2], p[3]};
+}
+__device__ __forceinline__ f32x4 load4(const f16* p) {
+  if (((size_t)p & 7) == 0) {
+    const f16x4 v = *reinterpret_cast<const f16x4*>(p);
+    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+  }
+  return f32x4{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
+}
+
+// one window [C][rd][rh][rw] at `win`, its position in `row` (b, d, h, w); grid = (ceil(rh G / threads), rd, C)
+template <typename T, bool WIDE>
+__global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T* __restrict__ win, const int* __restrict__ row,
+                                                                         float* __restrict__ sum, int B, int C, int rd, int rh,
+                                                                         int rw, int Dp, int Hp, int Wp, int G, int* err) {
+  bool bad = false;
+  const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
+            w = clamp_flag(row[3], Wp - rw, bad);
+  if (bad && err && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *err = 1;
+  const int c = blockIdx.z, z = blockIdx.y;
+  const int it = blockIdx.x * BLEND_THREADS + threadIdx.x;
+  if (it >= rh * G) return;
+  const int y = it / G, g = it - y * G;
+  const long vrow = ((((long)b * C + c) * Dp + (d + z)) * Hp + (h + y)) * Wp + w;      // volume element of the row's x = 0
+  const T* wrow = win + (((long)c * rd + z) * rh + y) * rw;
+  if (WIDE) {
+    const int shift = (int)(vrow & 3);
+    const int x0 = 4 * g - shift;                   // window x of the group's first element
+    if (x0 >= rw) return;
+    float* vp = sum + (vrow + x0);                  // 16-byte aligned
+    if (x0 >= 0 && x0 + 4 <= rw) {
+      f32x4 v = *reinterpret_cast<f32x4*>(vp);
+      const f32x4 o = load4(wrow + x0);
+      v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3];
+      *reinterpret_cast<f32x4*>(vp) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        if (x >= 0 && x < rw) vp[j] += (float)wrow[x];
+      }
+    }
+  } else {
+    if (g < rw) sum[vrow + g] += (float)wrow[g];
+  }
+}
+
+__device__ __forceinline__ bool sigmoid_above_half(float q) { return 1.f / (1.f + expf(-q)) > 0.5f; }
+
+template <int VEC>
+__global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float* __restrict__ sum, int C, int Dp, int Hp, int Wp,
+                                                                     const int* __restrict__ nd, const int* __restrict__ nh,
+                                                                     const int* __restrict__ nw, int od, int oh, int ow, int D,
+                                                                     int H, int W, float* __restrict__ q_out,
+                                                                     unsigned char* __restrict__ mask_out,
+                                                                     const void* __restrict__ labels, int label_kind,
+                                                                     unsigned long long* __restrict__ tallies) {
+  __shared__ unsigned part[3][BLEND_THREADS / 64];
+  const int plane = blockIdx.y, c = plane % C, b = plane / C;
+  const long V = (long)D * H * W;
+  const long obase = (long)plane * V;                         // q, mask and one-hot labels: [B][C][D][H][W]
+  const long lbase = label_kind == LABELS_MAP_U8 ? (long)b * V : obase;
+  const float* lf = reinterpret_cast<const float*>(labels);
+  const unsigned char* lu = reinterpret_cast<const unsigned char*>(labels);
+  unsigned t_and = 0, t_a = 0, t_b = 0;
+  for (long i = ((long)blockIdx.x * BLEND_THREADS + threadIdx.x) * VEC; i < V; i += (long)gridDim.x * BLEND_THREADS * VEC) {
+    int x = (int)(i % W);
+    const long r = i / W;
+    int y = (int)(r % H), z = (int)(r / H);
+    float s[VEC];
+    bool lab[VEC] = {};
+    if constexpr (VEC == 4) {                                 // nothing cropped: the sum plane has the output's layout
+      const f32x4 v = *reinterpret_cast<const f32x4*>(sum + obase + i);
+      s[0] = v[0]; s[1] = v[1]; s[2] = v[2]; s[3] = v[3];
+      if (label_kind == LABELS_ONEHOT_F32) {
+        const f32x4 l = *reinterpret_cast<const f32x4*>(lf + lbase + i);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) lab[j] = l[j] != 0.f;
+      } else if (label_kind != LABELS_NONE) {
+        const unsigned l = *reinterpret_cast<const unsigned*>(lu + lbase + i);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const unsigned byte = (l >> (8 * j)) & 255u;
+          lab[j] = label_kind == LABELS_MAP_U8 ? byte == (unsigned)c : byte != 0;
+        }
+      }
+    } else {
+      s[0] = sum[(((long)plane * Dp + (od + z)) * Hp + (oh + y)) * Wp + (ow + x)];
+      if (label_kind == LABELS_ONEHOT_F32) lab[0] = lf[lbase + i] != 0.f;
+      else if (label_kind == LABELS_ONEHOT_U8) lab[0] = lu[lbase + i] != 0;
+      else if (label_kind == LABELS_MAP_U8) lab[0] = lu[lbase + i] == (unsigned)c;
+    }
+    float q[VEC];
+    unsigned m = 0;
+    int ndh = nd[od + z] * nh[oh + y];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      q[j] = s[j] / (float)(ndh * nw[ow + x]);
+      const bool a = sigmoid_above_half(q[j]);
+      m |= (unsigned)a << (8 * j);
+      if (label_kind != LABELS_NONE) {
+        t_a += a;
+        t_b += lab[j];
+        t_and += a && lab[j];
+      }
+      if (j + 1 < VEC && ++x == W) {                          // the next voxel starts a row
+        x = 0;
+        if (++y == H) { y = 0; ++z; }
+        ndh = nd[od + z] * nh[oh + y];
+      }
+    }
+    if constexpr (VEC == 4) {
+      if (q_out) *reinterpret_cast<f32x4*>(q_out + obase + i) = f32x4{q[0], q[1], q[2], q[3]};
+      if (mask_out) *reinterpret_cast<unsigned*>(mask_out + obase + i) = m;
+    } else {
+      if (q_out) q_out[obase + i] = q[0];
+      if (mask_out) mask_out[obase + i] = (unsigned char)m;
+    }
+  }
+  if (label_kind == LABELS_NONE) return;                      // uniform over the grid
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    t_and += __shfl_down(t_and, off, 64);
+    t_a += __shfl_down(t_a, off, 64);
+    t_b += __shfl_down(t_b, off, 64);
+  }
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) { part[0][tid >> 6] = t_and; part[1][tid >> 6] = t_a; part[2][tid >> 6] = t_b; }
+  __syncthreads();
+  if (tid < 3) {
+    unsigned long long v = 0;
+#pragma unroll
+    for (int k = 0; k < BLEND_THREADS / 64; ++k) v += part[tid][k];
+    if (v) atomicAdd(&tallies[c * 3 + tid], v);
+  }
+}
+
+}  // namespace dua
+
+int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
+                         int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
+                         void* stream) {
+  if ((dtype != DUA_F32 && dtype != DUA_F16) || nb < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || !windows || !table || !sum)
+    return DUA_ERR_ARG;
+  if (rd < 1 || rh < 1 || rw < 1 || B < 1 || Dp < rd || Hp < rh || Wp < rw || rd > 65535) return DUA_ERR_ARG;
+  if (table_rows < 1 || table_off < 0 || table_stride < 1 || (long)table_off + (long)(nb - 1) * table_stride >= table_rows)
+    return DUA_ERR_ARG;
+  if ((long)Dp * Hp * Wp >= (1L << 31) || (long)rd * rh * rw >= (1L << 31)) return DUA_ERR_ARG;
+  if (((size_t)windows & (dtype == DUA_F16 ? 1 : 3)) || ((size_t)sum & 3) || ((size_t)table & 3)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = ((size_t)sum & 15) == 0;
+  const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
+  const dim3 grid((unsigned)(((long)rh * G + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS), rd, C);
+  const long wvox = (long)C * rd * rh * rw;
+  for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
+    const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
+#define DUA_BLEND_ACC(T, WIDE)                                                                                              \
+  hipLaunchKernelGGL((dua::blend_accumulate_kernel<T, WIDE>), grid, dim3(dua::BLEND_THREADS), 0, s,                         \
+                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, B, C, rd, rh, rw, Dp, Hp, Wp, G, err_word)
+    if (dtype == DUA_F32) { if (wide) DUA_BLEND_ACC(float, true); else DUA_BLEND_ACC(float, false); }
+    else { if (wide) DUA_BLEND_ACC(dua::f16, true); else DUA_BLEND_ACC(dua::f16, false); }
+#undef DUA_BLEND_ACC
+  }
+  return (int)hipGetLastError();
+}
+
+int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw, int od,
+                     int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
+                     int labels_dtype, int label_map, unsigned long long* tallies, void* stream) {
+  if (!sum || !nd || !nh || !nw || B < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || (long)B * C > 65535) return DUA_ERR_ARG;
+  if (D < 1 || H < 1 || W < 1 || od < 0 || oh < 0 || ow < 0 || od > Dp - D || oh > Hp - H || ow > Wp - W) return DUA_ERR_ARG;
+  if ((long)Dp * Hp * Wp >= (1L << 31)) return DUA_ERR_ARG;
+  if (!q_out && !mask_out && !tallies) return DUA_ERR_ARG;
+  if ((labels != nullptr) != (tallies != nullptr)) return DUA_ERR_ARG;
+  int kind = dua::LABELS_NONE;
+  if (labels) {
+    if (label_map) {
+      if (labels_dtype != DUA_U8) return DUA_ERR_ARG;
+      kind = dua::LABELS_MAP_U8;
+    } else if (labels_dtype == DUA_F32) kind = dua::LABELS_ONEHOT_F32;
+    else if (labels_dtype == DUA_U8) kind = dua::LABELS_ONEHOT_U8;
+    else return DUA_ERR_ARG;
+  }
+  if (((size_t)sum & 3) || ((size_t)q_out & 3) || (kind == dua::LABELS_ONEHOT_F32 && ((size_t)labels & 3)) || ((size_t)tallies & 7))
+    return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (tallies) {
+    const hipError_t e = hipMemsetAsync(tallies, 0, sizeof(unsigned long long) * 3 * C, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const long V = (long)D * H * W;
+  const bool wide = D == Dp && H == Hp && W == Wp && V % 4 == 0 && ((size_t)sum & 15) == 0 && ((size_t)q_out & 15) == 0 &&
+                    ((size_t)mask_out & 3) == 0 && ((size_t)labels & (kind == dua::LABELS_ONEHOT_F32 ? 15 : 3)) == 0;
+  const long items = wide ? V / 4 : V;
+  long blocks = (items + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS;
+  if (blocks > dua::BLEND_FINISH_BLOCKS) blocks = dua::BLEND_FINISH_BLOCKS;
+  const dim3 grid((unsigned)blocks, (unsigned)(B * C));
+  if (wide)
+    hipLaunchKernelGGL(dua::blend_finish_kernel<4>, grid, dim3(dua::BLEND_THREADS), 0, s, sum, C, Dp, Hp, Wp, nd, nh, nw, od, oh, ow,
+                       D, H, W, q_out, mask_out, labels, kind, tallies);
+  else
+    hipLaunchKernelGGL(dua::blend_finish_kernel<1>, grid, dim3(dua::BLEND_THREADS), 0, s, sum, C, Dp, Hp, Wp, nd, nh, nw, od, oh, ow,
+                       D, H, W, q_out, mask_out, labels, kind, tallies);
+  return (int)hipGetLastError();
+}

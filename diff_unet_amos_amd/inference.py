@@ -15,6 +15,11 @@ Windows are independent units (each gets its own encoder pass and its own x_T,
 models/diffusion/diffusion.py:88-100), so the multi-GPU form shards them with no data-path
 collective until the end: rank r runs windows r, r+W, r+2W, ...; one all-gather (RCCL over xGMI on a
 GPU node) of the per-window outputs; every rank then blends identically.
+
+The streamed form (streamed_sliding_window_inference, evaluate_volume; csrc/blend.hip) keeps no list of window outputs: each
+predictor call's outputs are added into a device-resident fp32 sum volume at once, the window count is derived from the plan
+(the window grid is a dense product, so the count is a product of three per-axis vectors), one pass divides, crops,
+binarises and tallies Dice, and the multi-GPU form all-reduces the per-rank sum volumes instead of gathering windows.
 """
 from __future__ import annotations
 
@@ -65,6 +70,40 @@ def _plan(inputs, roi_size, overlap):
         pad.extend([half, diff - half])
     starts = dense_window_starts(padded, roi, _scan_interval(padded, roi, overlap))
     return spatial, roi, padded, pad, starts
+
+
+def coverage_counts(padded, roi, starts):
+    """Per-axis window coverage of a plan: three lists, ``n_axis[i]`` = the number of starts ``s`` of that axis with
+    ``s <= i < s + roi``.  ``starts`` is the dense product ``_plan`` returns, so the number of windows over voxel (z, y, x) --
+    the count map ``_blend`` accumulates -- is ``n_d[z] * n_h[y] * n_w[x]``."""
+    per_axis = [sorted({s[k] for s in starts}) for k in range(3)]
+    assert len(per_axis[0]) * len(per_axis[1]) * len(per_axis[2]) == len(starts), "window starts are not a dense product"
+    out = []
+    for k in range(3):
+        n = [0] * int(padded[k])
+        for s in per_axis[k]:
+            for i in range(s, s + int(roi[k])):
+                n[i] += 1
+        out.append(n)
+    return out
+
+
+def window_table(starts, batch, device=None):
+    """The plan as the int32 table dua_blend_accumulate reads: row ``idx`` = (b, d, h, w) of window ``idx`` = b * len(starts) + k,
+    i.e. ``len(starts) * batch`` rows in window-index order.  Built once per plan (on ``device`` when given)."""
+    rows = [(b, d, h, w) for b in range(int(batch)) for (d, h, w) in starts]
+    t = torch.tensor(rows, dtype=torch.int32).view(-1, 4)
+    return t if device is None else t.to(device)
+
+
+def blend_traffic_bytes(windows_total, channels, roi, batch, padded, world, window_itemsize=4):
+    """Derived (not measured) bytes every rank receives in the two multi-GPU forms: ``gathered`` = the flat tensor
+    all_gather_into_tensor fills, world * ceil(windows / world) window outputs of ``window_itemsize`` bytes per element;
+    ``reduced`` = the fp32 sum volume one all_reduce combines."""
+    per_rank = -(-int(windows_total) // int(world))
+    window = int(channels) * int(roi[0]) * int(roi[1]) * int(roi[2]) * int(window_itemsize)
+    volume = int(batch) * int(channels) * int(padded[0]) * int(padded[1]) * int(padded[2]) * 4
+    return {"gathered": int(world) * per_rank * window, "reduced": volume}
 
 
 def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial, device, dtype):
@@ -164,6 +203,99 @@ def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_si
     return _blend(results, inputs.shape[0], local.shape[1], padded, roi, starts, pad, spatial, local.device, torch.float32)
 
 
+def _need_device(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} runs on an MI355X (device 'cuda'); there is no CPU path in this package")
+
+
+def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype, timings, kwargs):
+    """The sum volume fp32 [B, C, *padded] of this plan (all-reduced over ``group`` when given) and what the finish pass needs:
+    (sum volume, coverage vectors on the device, crop offsets, spatial)."""
+    from . import ops
+    spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
+    world, rank = 1, 0
+    if group is not None:
+        import torch.distributed as dist
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+    dev = inputs.device
+    x = F.pad(inputs, pad=pad, mode="constant", value=0.0) if any(pad) else inputs      # no copy of a volume that needs none
+    batch = inputs.shape[0]
+    nwin, total = len(starts), len(starts) * batch
+    table = window_table(starts, batch, dev)
+    err = ops.zeros((1,), torch.int32, dev)
+    mine = list(range(rank, total, world))
+    # one process: the calls of sliding_window_inference; ranks of a group: those of sharded_sliding_window_inference
+    sizes = [min(sw_batch_size, total - g) for g in range(0, total, sw_batch_size)] if group is None else \
+        balanced_batches(len(mine), sw_batch_size)
+    acc = None
+    g = 0
+    for nb in sizes:
+        idxs = mine[g:g + nb]
+        seg = predictor(torch.cat([_window(x, i, nwin, starts, roi) for i in idxs]), **kwargs)
+        if acc is None:
+            acc = ops.zeros((batch, seg.shape[1], *padded), torch.float32, dev)
+        if gather_dtype is not None:
+            seg = seg.to(gather_dtype)
+        ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
+        g += nb
+        del seg
+    if acc is None:          # more ranks than windows: still take part in the collective
+        probe = predictor(_window(x, 0, nwin, starts, roi), **kwargs)
+        acc = ops.zeros((batch, probe.shape[1], *padded), torch.float32, dev)
+    if group is not None:
+        import torch.distributed as dist
+        if timings is not None:
+            import time
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+        dist.all_reduce(acc, group=group)
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["all_reduce_s"] = timings.get("all_reduce_s", 0.0) + time.perf_counter() - t0
+            timings["reduced_bytes"] = acc.numel() * acc.element_size()
+    if int(err.item()):
+        raise RuntimeError("streamed blend: a window position of the plan lies outside the padded volume")
+    coverage = [torch.tensor(n, dtype=torch.int32).to(dev) for n in coverage_counts(padded, roi, starts)]
+    crop_lo = tuple(pad[2 * (2 - k)] for k in range(3))
+    return acc, coverage, crop_lo, spatial
+
+
+def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
+                                      overlap: float = 0.25, group=None, gather_dtype: torch.dtype = None,
+                                      timings: dict = None, **kwargs) -> torch.Tensor:
+    """The volume ``sliding_window_inference`` returns -- same plan, padding, window order and predictor calls -- without the list
+    of window outputs: every call's outputs are added into a device-resident fp32 sum volume at once (dua_blend_accumulate:
+    the fp32 additions of ``_blend`` in the same order), and one pass divides by the window count derived from the plan and
+    crops (dua_blend_finish).  ``group=None``: one process.  With a group, each rank adds its round-robin windows (dealt in
+    ``balanced_batches`` calls, as ``sharded_sliding_window_inference`` does) into its own sum volume and ONE all_reduce of the
+    fp32 volumes follows; ``timings`` accumulates its wall time under "all_reduce_s" and records "reduced_bytes";
+    ``gather_dtype`` only narrows the window tensor handed to the accumulate call.  Device tensors only."""
+    from . import ops
+    _need_device(inputs, "streamed_sliding_window_inference")
+    acc, coverage, crop_lo, spatial = _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype,
+                                                    timings, kwargs)
+    return ops.blend_finish(acc, coverage, crop_lo, spatial, want_q=True)[0]
+
+
+def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
+                    overlap: float = 0.25, distributed: bool = False, group=None):
+    """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
+    [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
+    written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
+    set) or a uint8 label map [B, D, H, W] (class c = channel c).  ``distributed``: shard the windows over the ranks of
+    ``group`` (default: the world) and all-reduce the sum volumes."""
+    from . import ops
+    _need_device(image, "evaluate_volume")
+    if distributed and group is None:
+        import torch.distributed as dist
+        group = dist.group.WORLD
+    with torch.no_grad():
+        acc, coverage, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
+                                                        None, None, dict(pred_type="ddim_sample"))
+        _, mask, tallies = ops.blend_finish(acc, coverage, crop_lo, spatial, want_mask=True, labels=labels)
+    return mask, (ops.dice_from_tallies(tallies) if tallies is not None else None)
+
+
 def binarise(outputs: torch.Tensor) -> torch.Tensor:
     """engine.py:179-180."""
     return (torch.sigmoid(outputs) > 0.5).float()
@@ -180,8 +312,11 @@ def dice_per_class(outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 
 def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
-          distributed: bool = False, group=None) -> torch.Tensor:
-    """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5."""
+          distributed: bool = False, group=None, streaming: bool = False) -> torch.Tensor:
+    """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
+    ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume)."""
+    if streaming:
+        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group)[0].float()
     fn = sharded_sliding_window_inference if distributed else sliding_window_inference
     kw = dict(group=group) if distributed else {}
     with torch.no_grad():

@@ -1695,3 +1695,74 @@ def aug_apply_smoothed(table, centroids, smoothing, params, roi, class_ids, imag
                                              nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
                                              nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply_smoothed")
     return images, labels
+
+
+# ---- evaluation: streamed sliding-window blend (csrc/blend.hip; engine.py:173-180, metric.py:37-49) ----
+
+def blend_accumulate(sum_volume, windows, table, table_off, table_stride=1, err=None):
+    """dua_blend_accumulate: ``sum_volume`` (fp32 [B, C, Dp, Hp, Wp]) += the ``windows`` ([nb, C, rd, rh, rw], fp32 or fp16) at the
+    positions rows ``table_off + k * table_stride`` of ``table`` (int32 [rows, 4] of (b, d, h, w)) give, in the order of k.
+    ``err`` (int32 [1], zeroed by the caller) is set to 1 by a row that had to be clamped into the volume."""
+    _f32c(sum_volume, "sum_volume"); _i32c(table, "table")
+    assert windows.is_cuda and windows.is_contiguous() and windows.dim() == 5, "windows: contiguous [nb, C, rd, rh, rw] device tensor"
+    assert sum_volume.dim() == 5 and table.dim() == 2 and table.shape[1] == 4, "sum_volume: [B, C, Dp, Hp, Wp]; table: int32 [rows, 4]"
+    assert windows.device == sum_volume.device == table.device, "every tensor on one device"
+    if err is not None:
+        _i32c(err, "err")
+        assert err.numel() == 1 and err.device == sum_volume.device
+    nb, Cn, rd, rh, rw = windows.shape
+    B, Cs, Dp, Hp, Wp = sum_volume.shape
+    assert Cn == Cs, f"windows have {Cn} channels, the sum volume {Cs}"
+    with torch.cuda.device(sum_volume.device):
+        nv.check(nv.lib().dua_blend_accumulate(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows), nv.ptr(table),
+                                               table.shape[0], int(table_off), int(table_stride), nv.ptr(sum_volume), B, Dp, Hp, Wp,
+                                               nv.ptr(err), nv.stream_ptr()), "dua_blend_accumulate")
+    return sum_volume
+
+
+def blend_finish(sum_volume, coverage, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
+    """dua_blend_finish on the crop ``crop_lo`` .. ``crop_lo + spatial`` of ``sum_volume``: (q fp32 [B, C, *spatial] or None, mask
+    uint8 [B, C, *spatial] or None, tallies int64 [C, 3] = (|A & B|, |A|, |B|) or None).  ``coverage``: the three int32 device
+    vectors [Dp], [Hp], [Wp] whose product is the window count.  ``labels``: one-hot [B, C, *spatial] (fp32, uint8 or bool) or
+    a uint8 label map [B, *spatial] (class c = channel c)."""
+    _f32c(sum_volume, "sum_volume")
+    assert sum_volume.dim() == 5, "sum_volume: [B, C, Dp, Hp, Wp]"
+    B, Cn, Dp, Hp, Wp = sum_volume.shape
+    dev = sum_volume.device
+    nd, nh, nw = coverage
+    for t, n, name in ((nd, Dp, "nd"), (nh, Hp, "nh"), (nw, Wp, "nw")):
+        _i32c(t, name)
+        assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: int32 [{n}] on the volume's device"
+    od, oh, ow = (int(v) for v in crop_lo)
+    D, H, W = (int(v) for v in spatial)
+    code, is_map = nv.F32, 0
+    if labels is not None:
+        assert labels.is_cuda and labels.device == dev, "labels: on the volume's device"
+        if labels.dtype == torch.bool:
+            labels = labels.view(torch.uint8)
+        labels = labels.contiguous()
+        if labels.dim() == 4:
+            if labels.dtype != torch.uint8:
+                raise TypeError(f"labels: a label map is uint8, not {labels.dtype}")
+            assert tuple(labels.shape) == (B, D, H, W), f"label map: [{B}, {D}, {H}, {W}], got {tuple(labels.shape)}"
+            code, is_map = nv.U8, 1
+        else:
+            if labels.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(f"labels: one-hot labels are float32, uint8 or bool, not {labels.dtype}")
+            assert tuple(labels.shape) == (B, Cn, D, H, W), f"one-hot labels: [{B}, {Cn}, {D}, {H}, {W}], got {tuple(labels.shape)}"
+            code = nv.F32 if labels.dtype == torch.float32 else nv.U8
+    q = torch.empty((B, Cn, D, H, W), dtype=torch.float32, device=dev) if want_q else None
+    mask = torch.empty((B, Cn, D, H, W), dtype=torch.uint8, device=dev) if want_mask else None
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if labels is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_blend_finish(nv.ptr(sum_volume), B, Cn, Dp, Hp, Wp, nv.ptr(nd), nv.ptr(nh), nv.ptr(nw), od, oh, ow, D, H, W,
+                                           nv.ptr(q), nv.ptr(mask), nv.ptr(labels), code, is_map, nv.ptr(tallies), nv.stream_ptr()),
+                 "dua_blend_finish")
+    return q, mask, tallies
+
+
+def dice_from_tallies(tallies):
+    """The dice_per_class rule (metric.py:37-49) on dua_blend_finish's counts: 2 |A & B| / (|A| + |B|), 0 when both are empty;
+    fp64 [C] on the tallies' device, no host read."""
+    inter, denom = tallies[:, 0].double(), tallies[:, 1].double() + tallies[:, 2].double()
+    return torch.where(denom > 0, 2.0 * inter / denom.clamp(min=1), torch.zeros_like(denom))

@@ -898,6 +898,44 @@ int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* c
                            const dua_aug_smoothing* smoothing, const int* params, int B, int roi_d, int roi_h, int roi_w,
                            const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream);
 
+/* ---- evaluation: streamed sliding-window blend ----------------------------------------------------------------------
+ * The blend of monai.inferers.sliding_window_inference as Engine.infer calls it (engine.py:173-177; Tester, test.py:119-159:
+ * constant importance map, sum / count), the binarisation that follows it (engine.py:179-180) and the three voxel counts of
+ * the Dice metric (metric.py:37-49), without a list of window outputs: a window is added into a resident sum volume when its
+ * predictor call returns, and the window count is not accumulated but derived from the plan -- the window grid is a dense
+ * product of per-axis starts, so count(z, y, x) = nd[z] nh[y] nw[x] with n_axis[i] = the number of starts s of that axis with
+ * s <= i < s + roi.
+ *
+ * dua_blend_accumulate: windows = nb window outputs [nb][C][rd][rh][rw], DUA_F32 or DUA_F16; sum = fp32 [B][C][Dp][Hp][Wp]
+ * (UPDATED); table = DEVICE int32 [table_rows][4] of window positions (b, d, h, w), uploaded once per plan.  Window k of the
+ * call takes row table_off + k table_stride (stride 1: consecutive windows; stride W: the windows of one rank of W) and
+ *   sum[b, :, d : d + rd, h : h + rh, w : w + rw] += (fp32) windows[k]
+ * for k = 0 .. nb - 1 IN THAT ORDER: windows of one call may overlap, and every voxel receives the fp32 additions a slice-add
+ * per window in index order performs (bit-equal, identical between runs).  No atomic touches the volume.  A row outside the
+ * volume (b outside [0, B), a start below 0 or above extent - roi) is clamped into it -- no wild access -- and *err_word
+ * (int, may be NULL; the caller zeroes it) is set to 1.  C <= DUA_BLEND_MAX_CLASSES, rd <= 65535, a (b, c) plane of the
+ * volume and a window hold fewer than 2^31 voxels.  16-byte accesses on the volume side when sum is 16-byte aligned, whatever
+ * the window starts are.
+ *
+ * dua_blend_finish: one pass over the cropped volume [od, od + D) x [oh, oh + H) x [ow, ow + W) of sum.  Per voxel
+ *   q = sum / (float)(nd[od + z] nh[oh + y] nw[ow + x])        (IEEE fp32 division; nd, nh, nw: DEVICE int32 [Dp], [Hp], [Wp])
+ * and any subset of (a NULL pointer leaves one out; at least one is given):
+ *   q_out    fp32  [B][C][D][H][W] = q
+ *   mask_out uint8 [B][C][D][H][W] = 1 / (1 + expf(-q)) > 0.5 ? 1 : 0          (fp32; 0 for q == 0)
+ *   tallies  64-bit unsigned [C][3] (WRITTEN, the call zeroes it first) = |A & B|, |A|, |B| over batch and space, A = the
+ *            mask, B = labels; given exactly when labels is.
+ * labels: label_map == 0: one-hot [B][C][D][H][W], DUA_F32 or DUA_U8, non-zero = set; label_map != 0: DUA_U8 [B][D][H][W] of
+ * class ids, class c = channel c.  Integer counters, one integer atomic per counter and workgroup: exact and independent of
+ * the order of arrival.  Dice = 2 |A & B| / (|A| + |B|), 0 when both are empty, is the caller's division.
+ * C <= DUA_BLEND_MAX_CLASSES, B C <= 65535.  Invalid arguments: DUA_ERR_ARG, before the device is touched. */
+#define DUA_BLEND_MAX_CLASSES 64
+int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
+                         int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
+                         void* stream);
+int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw, int od,
+                     int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
+                     int labels_dtype, int label_map, unsigned long long* tallies, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,120 @@
+"""Time the whole-volume blend of sliding-window inference, streamed (csrc/blend.hip) against list-and-blend, predictor excluded.
+
+    python tools/bench_blend.py [--volume 240 240 180] [--channels 16] [--roi 96] [--overlap 0.8] [--sw-batch 4]
+                                [--repeats 5] [--warmup 2]
+
+A stub predictor hands out preallocated window outputs (a pool of --sw-batch random fp32 windows, reused by every call), so
+only the blend is timed.  Per repeat, alternating the two forms, between device synchronisations:
+  streamed : one dua_blend_accumulate per predictor call into the fp32 sum volume, then one dua_blend_finish that writes the
+             uint8 mask and the Dice tallies against one-hot fp32 labels (inference.evaluate_volume without the predictor);
+  listed   : inference._blend on the list of (index, window) pairs + binarise + dice_per_class on the same windows and labels.
+The two masks are compared outside |q| <= 2^-20 and the Dice vectors printed.  Peak device memory (max_memory_allocated above
+what is resident before the call: pool, labels, table) is reported for both; the listed form's figure does NOT contain the
+list of window outputs a real predictor would leave (the pool is shared) -- that list is printed as derived bytes.  Bytes
+moved by the streamed form are computed from the shapes.  The last lines are the derived (not measured) bytes a rank receives
+in the gather and in the all-reduce form for 2, 4 and 8 ranks."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from diff_unet_amos_amd import ops  # noqa: E402
+from diff_unet_amos_amd.inference import (_blend, _plan, binarise, blend_traffic_bytes, coverage_counts, dice_per_class,  # noqa: E402
+                                          window_table)
+
+
+def clocks():
+    """Whatever this box reports about the device clock, read-only."""
+    try:
+        return f"{torch.cuda.clock_rate()} MHz (torch.cuda.clock_rate)"
+    except Exception:       # noqa: BLE001 -- no management library: say so
+        return "not available"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--volume", type=int, nargs=3, default=[240, 240, 180])
+    ap.add_argument("--channels", type=int, default=16)
+    ap.add_argument("--roi", type=int, default=96)
+    ap.add_argument("--overlap", type=float, default=0.8)
+    ap.add_argument("--sw-batch", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_blend.py measures on an MI355X; no GPU here")
+    dev = torch.device("cuda", 0)
+    Cn, roi = args.channels, (args.roi,) * 3
+    probe = torch.empty(1, 1, *args.volume, device="meta")
+    spatial, roi, padded, pad, starts = _plan(probe, roi, args.overlap)
+    nwin = len(starts)
+    g = torch.Generator(device=dev).manual_seed(0)
+    pool = torch.randn(args.sw_batch, Cn, *roi, generator=g, device=dev)
+    labels = (torch.rand(1, Cn, *spatial, generator=g, device=dev) > 0.6).float()
+    table = window_table(starts, 1, dev)
+    cov = [torch.tensor(n, dtype=torch.int32, device=dev) for n in coverage_counts(padded, roi, starts)]
+    crop_lo = tuple(pad[2 * (2 - k)] for k in range(3))
+    calls = [(g0, min(args.sw_batch, nwin - g0)) for g0 in range(0, nwin, args.sw_batch)]
+    listed_windows = [(g0 + k, pool[k:k + 1]) for g0, nb in calls for k in range(nb)]
+
+    def streamed():
+        acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
+        for g0, nb in calls:
+            ops.blend_accumulate(acc, pool[:nb], table, g0)
+        _, mask, tallies = ops.blend_finish(acc, cov, crop_lo, spatial, want_mask=True, labels=labels)
+        return mask, ops.dice_from_tallies(tallies)
+
+    def listed():
+        q = _blend(listed_windows, 1, Cn, padded, roi, starts, pad, spatial, dev, torch.float32)
+        mask = binarise(q)
+        return mask, dice_per_class(mask, labels), q
+
+    def run(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, torch.cuda.max_memory_allocated(dev) - base, out
+
+    for _ in range(args.warmup):
+        run(streamed); run(listed)
+    ts, tl, ps, pl = [], [], [], []
+    for _ in range(args.repeats):                                  # alternate the two forms
+        t, p, (mask_s, dice_s) = run(streamed)
+        ts.append(t); ps.append(p)
+        t, p, (mask_l, dice_l, q) = run(listed)
+        tl.append(t); pl.append(p)
+    outside = q.abs() > 2.0 ** -20
+    agree = bool(torch.equal(mask_s.float()[outside], mask_l[outside]))
+    window_bytes = Cn * roi[0] * roi[1] * roi[2] * 4
+    volume_bytes = Cn * padded[0] * padded[1] * padded[2] * 4
+    out_vox = Cn * spatial[0] * spatial[1] * spatial[2]
+    moved = nwin * 3 * window_bytes + volume_bytes + volume_bytes + out_vox * (1 + 4)       # accumulate; zero fill; finish
+    med_s, med_l = statistics.median(ts), statistics.median(tl)
+    print(json.dumps({
+        "plan": {"volume": list(spatial), "padded": list(padded), "channels": Cn, "roi": list(roi), "overlap": args.overlap,
+                 "windows": nwin, "sw_batch": args.sw_batch, "calls": len(calls)},
+        "clocks": clocks(), "device": torch.cuda.get_device_name(dev), "warmup": args.warmup, "repeats": args.repeats,
+        "streamed_seconds": {"median": med_s, "min": min(ts), "max": max(ts)},
+        "listed_seconds": {"median": med_l, "min": min(tl), "max": max(tl)},
+        "streamed_peak_bytes": max(ps), "listed_peak_bytes": max(pl),
+        "listed_window_list_bytes_derived": nwin * window_bytes,
+        "streamed_bytes_moved_derived": moved, "streamed_bytes_per_second": moved / med_s,
+        "masks_agree_outside_band": agree, "voxels_in_band": int((~outside).sum()),
+        "dice_streamed": [round(float(v), 6) for v in dice_s.tolist()], "dice_listed": [round(float(v), 6) for v in dice_l.tolist()],
+    }))
+    for world in (2, 4, 8):
+        b = blend_traffic_bytes(nwin, Cn, roi, 1, padded, world)
+        print(json.dumps({"ranks": world, "gathered_bytes_per_rank_derived": b["gathered"], "reduced_bytes_per_rank_derived": b["reduced"]}))
+
+
+if __name__ == "__main__":
+    main()
