@@ -578,6 +578,9 @@ static int tail_entry(const dua_tail_desc* d, const void* raw, const dua_in_norm
     else hipLaunchKernelGGL(dua::final_conv_sampler_mfma_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
   }
+  // the VALU form keeps [K/4][CX][4] weights + scale / shift / add in dynamic LDS and does not raise the 64 KB default
+  // (no entry in prepare.hip): CX = 32 with K > 464 cannot launch
+  if ((size_t)(d->CX + 3) * d->K * sizeof(float) > 65536) return DUA_ERR_ARG;
   if (d->dtype == DUA_F16) return dua::dispatch_tail<dua::f16>(d, a, (hipStream_t)stream);
   if (d->dtype == DUA_F32) return dua::dispatch_tail<float>(d, a, (hipStream_t)stream);
   return DUA_ERR_ARG;

@@ -454,7 +454,8 @@ typedef struct {
   int dtype;
   int N;
   long voxels;
-  int K, raw_stride;       /* channels of the last decoder block, channel stride of raw */
+  int K, raw_stride;       /* channels of the last decoder block (a multiple of 8, <= 512; the form without matrix cores keeps
+                              (CX + 3) * K floats in 64 KB of LDS: CX = 32 takes K <= 464), channel stride of raw */
   int C, CX;               /* classes; channel stride of the fp32 sampler state (8/16/24/32) */
   int mode;                /* DUA_MODE_* */
   int xin_stride;          /* channel stride of xin (x_{t-1} goes to channels [0, C)) */

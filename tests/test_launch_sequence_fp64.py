@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import fp64ref as R
+import sampler_fp64ref as T
 
 pytestmark = pytest.mark.gpu
 
@@ -285,14 +286,10 @@ class _Checker:
         sc, sh, _ = self._consts(norm, N)
         pts = self._pts("head", N, (D, H, W))
         n = pts[:, 0]
-        t = R.tail_transform(R.gather_points(rs, pts, 0, K), sc[n], sh[n])
-        wfd, bfd = wf.cpu().double(), bf.cpu().double()
-        ref, ab, sq = R.contract(t, wfd.t())
-        ref, ab = ref + bfd, ab + bfd.abs()
         # fp16 plans: each fp32 operand is carried as an fp16 pair (hi + lo, csrc/sampler.hip), the lo x lo product dropped:
-        # 3 * 2^-22 of every product
-        split = 3 * 2.0 ** -22 * ab if self.dt == torch.float16 else 0.0
-        bnd = R.bound(ref, ab, sq, K + 1, torch.float32, emulated_in=torch.float32, extra=split)
+        # 3 * 2^-22 of every product (tests/sampler_fp64ref.py)
+        ref, ab, sq, _ = T.tail_logits_ref(R.gather_points(rs, pts, 0, K), sc[n], sh[n], wf, bf)
+        bnd = T.tail_logits_bound(ref, ab, sq, K, split=self.dt == torch.float16)
         p = pts.to(logits.device)
         got = logits[p[:, 0], :, p[:, 1], p[:, 2], p[:, 3]].cpu()
         self._row("head", "tail", False, f"{N}x{D}x{H}x{W} {K}->{num_classes}", len(pts), R.check(got, ref, bnd, pts))

@@ -7,6 +7,7 @@ mkdir -p "$out"
 ulimit -c unlimited 2>/dev/null
 export PYTHONFAULTHANDLER=1
 # the limit: the whole suite takes 308 s on one MI355X, tests/test_loss_fp64.py 7 s of it
+# with tests/test_sampler_fp64.py (14 s): 337 s
 timeout -k 10 1100 python -X faulthandler -m pytest tests -m gpu -x -q "$@" > "$out/tests.log" 2>&1
 rc=$?
 tail -n 5 "$out/tests.log"
