@@ -42,6 +42,23 @@ class InNorm(C.Structure):
                 ("slope", C.c_float)]
 
 
+class Conv3Form(C.Structure):
+    """dua_conv3_form: the launch form of a 3x3x3 convolution (dua_conv3d_k3_form)."""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "tile_depth", "ksplit", "units_per_split", "finish", "grid_x", "grid_y", "grid_z",
+                                       "lds_bytes", "lds_limit")] + [("workspace_needed", C.c_long)]
+
+
+class DeconvForm(C.Structure):
+    """dua_deconv_form (dua_deconv_k2s2_form)."""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "tile_voxels", "grid_x", "grid_y", "grid_z", "lds_bytes", "lds_limit")]
+
+
+# dua_conv3_form.kernel (DUA_CONV3_*) and dua_deconv_form.kernel (DUA_DECONV_*)
+(CONV3_FIRST, CONV3_TAP0, CONV3_TAP1, CONV3_WIDE, CONV3_WIDE_BWD, CONV3_WIDE_PT, CONV3_V2_4, CONV3_V2_4_HALF, CONV3_V2_4_KD,
+ CONV3_V2_2, CONV3_V2_2_KD) = range(11)
+DECONV_ONE_TAP, DECONV_KSPLIT, DECONV_ALLTAPS_128, DECONV_ALLTAPS_256 = range(4)
+
+
 class UpConvDesc(C.Structure):
     """dua_upconv_desc."""
     _fields_ = [(n, C.c_int) for n in ("dtype", "N", "D", "H", "W", "Cskip", "Cskip_stride", "Cskip_off", "Cu", "Cu_stride", "Cu_off",
@@ -197,6 +214,8 @@ _SIGS = {
     "dua_conv3d_k3_workspace": (C.c_long, [C.POINTER(Conv3Desc)]),
     "dua_conv3d_k3_kernel_kind": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_int]),
     "dua_deconv_k2s2_kernel_kind": (C.c_int, [C.POINTER(Conv3Desc)]),
+    "dua_conv3d_k3_form": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_long, C.c_int, C.POINTER(Conv3Form)]),
+    "dua_deconv_k2s2_form": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DeconvForm)]),
     "dua_conv3d_k3_fwd": (C.c_int, [C.POINTER(Conv3Desc), _P, _P, _P, C.POINTER(InNorm), _P, _P, _P, C.c_long, _P]),
     "dua_upconv_k3_supported": (C.c_int, [C.POINTER(UpConvDesc)]),
     "dua_pack_upconv_weights": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),

@@ -1,6 +1,7 @@
 // Launch arguments shared by the conv3d_k3 kernel variants.
 #pragma once
 #include "common.hpp"
+#include "conv3_form.hpp"
 
 namespace dua {
 
@@ -26,9 +27,7 @@ struct Conv3Args {
 };
 
 // conv3d_wide.hip: the 8-accumulator form (8x8x8 tiles) for fp16 layers with >= 1024 tiles of 4x8x8; D, H, W multiples of 8,
-// Cin a multiple of 16.
-// persistent (policies 8 / 9, A/B only): workgroups walk tiles (conv3d_k3_wide_pt_kernel); false = one tile per workgroup (shipped)
-int launch_conv3_wide(Conv3Args a, int D, hipStream_t s, bool persistent, int stagger = 0);
-bool conv3_wide_takes_bwd_sums(const Conv3Args& a);     // the shipped one-tile-per-workgroup form, 64-wide output tiles
+// Cin a multiple of 16.  `a` and `f` as conv3_form decided them: DUA_CONV3_WIDE (shipped), _WIDE_BWD or _WIDE_PT (A/B only).
+int launch_conv3_wide(Conv3Args a, const Conv3Form& f, hipStream_t s);
 
 }  // namespace dua

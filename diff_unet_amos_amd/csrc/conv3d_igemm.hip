@@ -24,26 +24,6 @@
 
 namespace dua {
 
-namespace c3 {
-constexpr int TD = 4, TH = 8, TW = 8;
-constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;
-constexpr int KG = 4;                      // k-groups (16 B) per chunk
-constexpr int VS = KG * 16;                // 64 B per halo voxel per chunk
-constexpr int RS = HW * VS + 16;           // 656: halo row stride, padded (bank-conflict free)
-constexpr int PS = HH * RS;                // 6560: halo plane stride
-constexpr int HALO_BYTES = HD * PS;        // 39360
-constexpr int BN = 64;                     // output channels per workgroup
-}  // namespace c3
-
-// launch form of a call (dua_conv3_desc.policy, low byte): 0 = auto (split-K for small layers, 2x8x8 tiles for mid-size ones,
-// both in the kd-plane form; the wide-tile form where there are tiles to spare); 2 forces 4x8x8 tiles without split-K, 3 forces
-// 2x8x8 (slab form), 6 = the automatic policy with the slab form everywhere, 7 = without the wide-tile form
-static inline int conv_variant_of(const dua_conv3_desc* d) { return d->policy & 0xff; }
-static inline bool conv_policy_ok(const dua_conv3_desc* d) {
-  const int v = d->policy & 0xff;
-  return (d->policy & ~(0xff | DUA_POLICY_NO_FINISH)) == 0 && (v == 0 || v == 2 || v == 3 || v == 6 || v == 7 || v == 8 || v == 9);
-}
-
 #ifdef DUA_ABLATE
 extern int g_wgrad_abl;
 #endif
@@ -55,12 +35,6 @@ extern int g_wgrad_abl;
 // (transformed) to LDS between two barriers.  Operand fragments of k-step t+1 are read from LDS while
 // the MFMAs of step t issue.  One barrier per slab; nothing waits on a global load that was not issued
 // a full MFMA phase earlier.
-namespace c3v2 {
-using namespace c3;
-constexpr int SLAB = 3 * KG * BN * 16;             // 12288
-constexpr int LDS_MAIN = HALO_BYTES + 2 * SLAB;    // 63936
-}  // namespace c3v2
-
 __device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
@@ -523,20 +497,7 @@ __global__ __launch_bounds__(256, BIG ? 1 : 2) void conv3d_k3_v2_kernel(Conv3Arg
 // MFMAs per wave with no barrier between them, epilogue.  Two workgroups per CU (79.5 KB of LDS each) overlap one's
 // epilogue with the other's MFMAs.
 //
-// Halo image: 32 B per voxel (the 16 ordinary channels; the image channel goes to an fp16 array of its own), 12 voxel slots
-// per row (10 used), and the two 16-byte halves of a voxel swapped on odd halo rows: with that the four 16-lane groups of
-// every ds_read_b128 fragment read cover all 64 banks once (rows r>>3 = 0..3 of a 32-voxel block land on 16-byte slots
-// {0,2,4,6}+8k / {1,3,5,7}+8k).
-namespace c3f {
-using namespace c3;
-constexpr int VSF = 32, RSF = 12 * VSF, PSF = HH * RSF;      // 384-byte rows, 3840-byte planes
-constexpr int HALO_F = HD * PSF;                              // 23040
-constexpr int WRES = 27 * 2 * BN * 16;                        // 55296: [tap][k-half][64 couts][16 B]
-constexpr int IMG_F = 1216;                                   // 600 fp16 of the image halo (+ pad)
-constexpr int LDS_F = WRES + HALO_F + IMG_F;                  // 79552: two workgroups per CU
-constexpr int NV = HD * HH * HW;                              // 600 halo voxels
-}  // namespace c3f
-
+// Halo image layout and LDS budget: namespace c3f, conv3_form.hpp
 __global__ __launch_bounds__(256, 2) void conv3d_k3_first_kernel(Conv3Args a, int items) {
   using namespace c3f;
   using T = f16;
@@ -916,61 +877,36 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
 }
 
 
-static inline void choose_split(int base_wgs, int units, int* ksplit, int* ups, int target = 320, int max_base = 64) {
-  *ksplit = 1; *ups = units;
-  if (base_wgs > max_base || units <= 1) return;  // 24^3 and up: the partial-tile round trip costs more than it buys
-  int want = target == 320 ? (320 + base_wgs - 1) / base_wgs : target / base_wgs;   // ~one workgroup per CU, each keeping >= a few units of work
-  if (want < 1) want = 1;
-  if (want > units) want = units;
-  *ups = (units + want - 1) / want;
-  *ksplit = (units + *ups - 1) / *ups;
-}
-
-// A background launch (dua_conv3_desc.background) runs on a second stream UNDER other launches: it asks for enough
-// extra LDS that only ONE of its workgroups fits a CU, so that every CU keeps 64 KB and half its wave slots free for the
-// main stream's workgroups (two of them per CU leave no room: the co-running launches then wait for retiring workgroups).
-constexpr int PARTIAL_LDS_PAD = 36 * 1024;
-
-// Kernels of this file that ask for more than 64 KB of dynamic LDS (raised once per device by ensure_prepared(), common.hpp)
+// Kernels of this file that ask for more than 64 KB of dynamic LDS (raised once per device by ensure_prepared(), common.hpp);
+// the limits are conv3_lds_limit(), which the forms report beside the bytes they ask for
 static const LdsAttr kConvLdsAttrs[] = {
-    {(const void*)conv3d_k3_v2_kernel<f16, 4>, c3v2::LDS_MAIN + 3 * 4 * 1024 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_v2_kernel<float, 4>, c3v2::LDS_MAIN + 3 * 4 * 1024 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_v2_kernel<f16, 4, 1>, c3v2::LDS_MAIN + 4096 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_v2_kernel<f16, 4, 0>, c3v2::LDS_MAIN + 4096 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_v2_kernel<f16, 4, 2, true>, c3v2::LDS_MAIN + 3 * 4 * 1024 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_first_kernel, c3f::LDS_F + 2048 + PARTIAL_LDS_PAD},
-    {(const void*)conv3d_k3_v2_kernel<f16, 2>, c3v2::LDS_MAIN + 3 * 4 * 1024},
-    {(const void*)conv3d_k3_v2_kernel<float, 2>, c3v2::LDS_MAIN + 3 * 4 * 1024},
-    {(const void*)conv3d_k3_v2_kernel<f16, 4, 2, false, true>, 160 * 1024},
-    {(const void*)conv3d_k3_v2_kernel<float, 4, 2, false, true>, 160 * 1024},
-    {(const void*)conv3d_k3_v2_kernel<f16, 2, 2, false, true>, 160 * 1024},
-    {(const void*)conv3d_k3_v2_kernel<float, 2, 2, false, true>, 160 * 1024},
+    {(const void*)conv3d_k3_v2_kernel<f16, 4>, conv3_lds_limit(DUA_CONV3_V2_4)},
+    {(const void*)conv3d_k3_v2_kernel<float, 4>, conv3_lds_limit(DUA_CONV3_V2_4)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 4, 1>, conv3_lds_limit(DUA_CONV3_TAP1)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 4, 0>, conv3_lds_limit(DUA_CONV3_TAP0)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 4, 2, true>, conv3_lds_limit(DUA_CONV3_V2_4_HALF)},
+    {(const void*)conv3d_k3_first_kernel, conv3_lds_limit(DUA_CONV3_FIRST)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 2>, conv3_lds_limit(DUA_CONV3_V2_2)},
+    {(const void*)conv3d_k3_v2_kernel<float, 2>, conv3_lds_limit(DUA_CONV3_V2_2)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 4, 2, false, true>, conv3_lds_limit(DUA_CONV3_V2_4_KD)},
+    {(const void*)conv3d_k3_v2_kernel<float, 4, 2, false, true>, conv3_lds_limit(DUA_CONV3_V2_4_KD)},
+    {(const void*)conv3d_k3_v2_kernel<f16, 2, 2, false, true>, conv3_lds_limit(DUA_CONV3_V2_2_KD)},
+    {(const void*)conv3d_k3_v2_kernel<float, 2, 2, false, true>, conv3_lds_limit(DUA_CONV3_V2_2_KD)},
 };
 static const LdsAttrs kConvLdsReg(kConvLdsAttrs);
-
-// Which kernel a launch takes (also exported: dua_conv3d_k3_kernel_kind): 1 = the resident-weight first-layer kernel, 2 = the
-// wide-tile form, 0 = conv3d_k3_v2_kernel in one of its launch shapes.
-static int conv3_kernel_kind(const dua_conv3_desc* d, bool fused) {
-  const int g_conv_variant = conv_variant_of(d);
-  if (d->dtype != DUA_F16) return 0;
-  if (d->tap_channel_plus1 > 0) return (d->tap_channel_plus1 == 17 && g_conv_variant == 0) ? 1 : 0;
-  const long tiles = (long)((d->D + 3) / 4) * ((d->H + 7) / 8) * ((d->W + 7) / 8) * ((d->Cout + c3::BN - 1) / c3::BN) * d->N;
-  const long vox = (long)d->D * d->H * d->W;
-  if ((g_conv_variant == 0 || g_conv_variant == 8 || g_conv_variant == 9) && !d->background && tiles >= 1024 && d->D % 8 == 0 && d->H % 8 == 0 && d->W % 8 == 0 &&
-      d->Cin % 16 == 0 && d->Cin <= (fused ? 256 : 384) && vox * d->Cin_stride < 0x7fffffffL)
-    return 2;
-  return 0;
-}
 
 // the owner of a data-gradient launch's output (dua_conv3d_k3_dgrad_reduce)
 struct BwdSums { const void* raw; int stride, off; const dua_in_norm* in; double* sums; };
 
+// One launch as conv3_form (conv3_form.hpp) decides it, and the split-K finish launch behind it if the form says so.
 template <typename T>
 static int launch_conv3(const dua_conv3_desc* d, const void* x, const void* w, const float* bias,
                         const dua_in_norm* in, void* y, stat_t* stats, float* ws, long ws_bytes, hipStream_t s,
                         const BwdSums* bw = nullptr) {
-  using namespace c3;
-  constexpr int CK = KG * Elem<T>::EPG;
+  const int prepared = ensure_prepared();
+  Conv3Form f;
+  if (int e = conv3_form(d, in && in->stats, bw != nullptr, ws ? ws_bytes : 0, prepared ? 0 : device_cus(), &f)) return e;   // argument errors first
+  if (prepared) return prepared;
   Conv3Args a;
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = stats;
   a.bw_raw = nullptr; a.bw_stride = a.bw_off = 0; a.bw_xf = make_xform(nullptr, d->Cout); a.bw_sums = nullptr;
@@ -981,99 +917,37 @@ static int launch_conv3(const dua_conv3_desc* d, const void* x, const void* w, c
   a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cin_stride = d->Cin_stride; a.Cin_off = d->Cin_off;
   a.Cout = d->Cout; a.Cout_stride = d->Cout_stride; a.Cout_off = d->Cout_off;
-  a.nchunks = (d->Cin + CK - 1) / CK;
-  const int td = (d->D + TD - 1) / TD;
-  a.tiles_h = (d->H + TH - 1) / TH; a.tiles_w = (d->W + TW - 1) / TW;
-  a.ntiles = td * a.tiles_h * a.tiles_w;
-  const int nct = (d->Cout + BN - 1) / BN;
-  a.cout_pad = nct * BN;
-  a.ksplit = 1; a.units_per_split = a.nchunks * 3; a.part = nullptr; a.tap_ch = -1;
+  a.nchunks = f.nchunks; a.ntiles = f.ntiles; a.tiles_h = f.tiles_h; a.tiles_w = f.tiles_w; a.cout_pad = f.cout_pad;
+  a.ksplit = f.ksplit; a.units_per_split = f.units_per_split; a.part = f.ksplit > 1 ? ws : nullptr; a.tap_ch = f.tap_ch;
   a.in_blk = d->layout & DUA_IN_BLOCKED ? 1 : 0; a.out_blk = d->layout & DUA_OUT_BLOCKED ? 1 : 0;
-  if (a.nchunks * CK > 1024 || !conv_policy_ok(d)) return DUA_ERR_ARG;
-  const int g_conv_variant = conv_variant_of(d);
-  const int kind = conv3_kernel_kind(d, in && in->stats);
-  // 16-channel-blocked buffers: read by the wide-tile form only, written by it and by the first-layer kernel only
-  if ((a.in_blk && kind != 2) || (a.out_blk && kind == 0)) return DUA_ERR_ARG;
-  if ((a.in_blk && (d->Cin_off % 16 || d->Cin_stride % 16)) || (a.out_blk && (d->Cout_off % 16 || d->Cout_stride % 16))) return DUA_ERR_ARG;
-  const int xf_bytes = in && in->stats ? 3 * 4 * a.nchunks * CK : 0;
-  if (int e = ensure_prepared()) return e;
-  const long vox = (long)d->D * d->H * d->W;
-  const int bg_pad = d->background ? PARTIAL_LDS_PAD : 0;     // one workgroup per CU, see PARTIAL_LDS_PAD
-  if (d->tap_channel_plus1 > 0) {
-    // single-channel tap form (see the kernel): fp16, one Cin chunk, no fused input transform, 16 * NKS ordinary
-    // channels in front of the tap channel, zero padding behind it; weights from dua_pack_conv3_weights_tap
-    a.tap_ch = d->tap_channel_plus1 - 1;
-    if constexpr (sizeof(T) != 2) return DUA_ERR_ARG;
-    else {
-      if (a.nchunks != 1 || (in && in->stats) || (a.tap_ch != 0 && a.tap_ch != 16) || d->Cin != a.tap_ch + 8) return DUA_ERR_ARG;
-      dim3 grid(a.ntiles, nct, d->N);
-      if (kind == 1) {
-        // resident-weight form: two persistent workgroups per CU walk the (sample, tile) items; a background launch takes one
-        // per CU (and the LDS pad that keeps a second one off the CU)
-        const int cus = device_cus();
-        if (cus <= 0) return DUA_ERR_ARG;
-        const int items = a.ntiles * d->N;
-        const int wgs = std::max(1, (bg_pad ? 1 : 2) * cus / nct);
-        hipLaunchKernelGGL(conv3d_k3_first_kernel, dim3(std::min(items, wgs), nct, 1), dim3(256), c3f::LDS_F + 2048 + bg_pad, s, a, items);
-        return (int)hipGetLastError();
-      }
-      if (a.tap_ch == 16) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 1>), grid, dim3(256), c3v2::LDS_MAIN + 4096 + bg_pad, s, a);
-      else hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 0>), grid, dim3(256), c3v2::LDS_MAIN + 4096 + bg_pad, s, a);
-      return (int)hipGetLastError();
-    }
+  const dim3 grid(f.grid_x, f.grid_y, f.grid_z), block(256);
+  const int lds = f.lds_bytes;
+  constexpr bool F16 = sizeof(T) == 2;                     // the first-layer and tap kernels exist in fp16 only (conv3_form never gives them to fp32)
+  switch (f.kernel) {
+    case DUA_CONV3_FIRST: if constexpr (F16) hipLaunchKernelGGL(conv3d_k3_first_kernel, grid, block, lds, s, a, f.items); break;
+    case DUA_CONV3_TAP0: if constexpr (F16) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 0>), grid, block, lds, s, a); break;
+    case DUA_CONV3_TAP1: if constexpr (F16) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 1>), grid, block, lds, s, a); break;
+    case DUA_CONV3_WIDE: case DUA_CONV3_WIDE_BWD: case DUA_CONV3_WIDE_PT: return launch_conv3_wide(a, f, s);
+    case DUA_CONV3_V2_4: hipLaunchKernelGGL(conv3d_k3_v2_kernel<T>, grid, block, lds, s, a); break;
+    case DUA_CONV3_V2_4_HALF: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, true>), grid, block, lds, s, a); break;
+    case DUA_CONV3_V2_4_KD: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, false, true>), grid, block, lds, s, a); break;
+    case DUA_CONV3_V2_2: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 2>), grid, block, lds, s, a); break;
+    case DUA_CONV3_V2_2_KD: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 2, 2, false, true>), grid, block, lds, s, a); break;
+    default: return DUA_ERR_ARG;
   }
-  // wide-tile form (conv3d_wide.hip): fp16 layers with tiles to spare (96^3); variant 7 keeps them on the 4x8x8 kernel (A/B)
-  if constexpr (sizeof(T) == 2) {
-    // 8: persistent workgroups with the accumulators held by name (round 5, conv3d_k3_wide_pt_kernel), 9: the same with the
-    // odd-slot workgroup of a CU starting two sleeps late -- both measured 1.5-2.5 % SLOWER than one tile per workgroup
-    // (profiles/r5_conv_wide_persistent_named_acc_ab.txt) and kept for that A/B only
-    if (kind == 2) return launch_conv3_wide(a, d->D, s, g_conv_variant >= 8, g_conv_variant == 9 ? 2 : 0);
-  }
-  if (bw) return DUA_ERR_ARG;                                  // only the wide-tile form has the backward-sums epilogue
-  const bool autop = g_conv_variant == 0 || g_conv_variant == 2 || g_conv_variant == 6 || g_conv_variant == 7 || g_conv_variant >= 8;       // the automatic policy; 6 = without the kd-plane form, 7 = without the wide-tile form (A/B)
-  const bool big = g_conv_variant == 0 || g_conv_variant == 2 || g_conv_variant == 7 || g_conv_variant >= 8;          // kd-plane form for the layers that cannot put two workgroups on every CU
-  if (ws != nullptr && autop) {
-    int ks, ups;
-    if (g_conv_variant == 2) choose_split(a.ntiles * nct * d->N, a.nchunks * 3, &ks, &ups, 512, 256);    // A/B: K split up to 256 base workgroups
-    else choose_split(a.ntiles * nct * d->N, a.nchunks * 3, &ks, &ups, big ? 256 : 320);
-    if (ks > 1 && (long)ks * d->N * vox * a.cout_pad * 4 <= ws_bytes) { a.ksplit = ks; a.units_per_split = ups; a.part = ws; }
-  }
-  // 24^3-sized layers (too few 4x8x8 tiles for 256 CUs, too big for split-K to pay): 2x8x8 tiles, twice the workgroups
-  if (a.ksplit == 1 && ((autop && a.ntiles * nct * d->N < 200 && a.ntiles * nct * d->N > 64) || g_conv_variant == 3)) {
-    const int td2 = (d->D + 1) / 2;
-    a.ntiles = td2 * a.tiles_h * a.tiles_w;
-    dim3 grid2(a.ntiles, nct, d->N);
-    constexpr int LDS2 = 4 * c3::HH * c3::RS + 2 * c3v2::SLAB;
-    // the kd-plane form (nine slabs resident: one workgroup per CU) only while every workgroup has a CU of its own; with more of
-    // them (12^3 at batch 4: 384) two slab-pipeline workgroups per CU are faster (64.3 vs 79.8 us on 256 -> 256, tools/bench_conv.py)
-    const bool big2 = big && (long)a.ntiles * nct * d->N <= 256;
-    if (big2) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 2, 2, false, true>), grid2, dim3(256), 4 * c3::HH * c3::RS + 9 * c3v2::SLAB + xf_bytes, s, a);
-    else hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 2>), grid2, dim3(256), LDS2 + xf_bytes, s, a);
-    return (int)hipGetLastError();
-  }
-  dim3 grid(a.ntiles, nct, d->N * a.ksplit);
-  if (a.ksplit > 1) {
-    if (big) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, false, true>), grid, dim3(256), c3::HALO_BYTES + 9 * c3v2::SLAB + xf_bytes, s, a);
-    else hipLaunchKernelGGL(conv3d_k3_v2_kernel<T>, grid, dim3(256), c3v2::LDS_MAIN + xf_bytes, s, a);
-    if (d->policy & DUA_POLICY_NO_FINISH) return (int)hipGetLastError();
-    const int G = a.cout_pad / 4 > 256 ? 256 : a.cout_pad / 4;       // channel groups handled per block pass
-    if (a.cout_pad / 4 > 256) return DUA_ERR_ARG;
-    const int VL = 256 / G;
-    int ITER = 8;
-    while (ITER > 1 && (vox + (long)VL * ITER - 1) / ((long)VL * ITER) < 128) ITER >>= 1;   // >= ~128 blocks; every block ends with
-                                                                                            // 16 atomic instructions (measured: 432
-                                                                                            // blocks 14.8 us, 216 blocks 10.9 us at 12^3)
-    dim3 fgrid((unsigned)((vox + (long)VL * ITER - 1) / ((long)VL * ITER)), d->N);
-    hipLaunchKernelGGL(splitk_finish_kernel<T>, fgrid, dim3(256), 0, s, (const float*)ws, a.ksplit, d->N, vox, a.cout_pad,
-                       d->Cout, bias, (T*)y, d->Cout_stride, d->Cout_off, stats, G, VL, ITER);
-    return (int)hipGetLastError();
-  }
-  if (sizeof(T) == 2 && d->Cin - (a.nchunks - 1) * CK <= CK / 2)       // e.g. Cin = 48: the last chunk is half padding
-    hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, true>), grid, dim3(256), c3v2::LDS_MAIN + xf_bytes + bg_pad, s, a);
-  else
-    hipLaunchKernelGGL(conv3d_k3_v2_kernel<T>, grid, dim3(256), c3v2::LDS_MAIN + xf_bytes + bg_pad, s, a);
+  if (f.finish)
+    hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3(f.fin_grid_x, f.fin_grid_y), block, 0, s, (const float*)ws, a.ksplit, d->N,
+                       (long)d->D * d->H * d->W, a.cout_pad, d->Cout, bias, (T*)y, d->Cout_stride, d->Cout_off, stats, f.fin_G, f.fin_VL,
+                       f.fin_ITER);
   return (int)hipGetLastError();
 }
+
+// the form for the current device, or for `cus` compute units without touching it
+static int form_for(const dua_conv3_desc* d, bool fused, bool backward_sums, long workspace_bytes, int cus, Conv3Form* f) {
+  if (cus <= 0 && ensure_prepared() == 0) cus = device_cus();
+  return conv3_form(d, fused, backward_sums, workspace_bytes, cus, f);
+}
+constexpr int ANY_CUS = 256;       // for the answers that do not depend on the device: kernel kind, workspace
 
 }  // namespace dua
 
@@ -1092,30 +966,27 @@ int dua_set_option(int key, int value) {
 }
 #endif
 
-int dua_conv3d_k3_kernel_kind(const dua_conv3_desc* d, int fused, int has_workspace) {
-  if (!d || !dua::conv_policy_ok(d)) return DUA_ERR_ARG;
-  (void)has_workspace;              // split-K applies below 1024 tiles only, where the answer is 0 anyway
-  return dua::conv3_kernel_kind(d, fused != 0);
+int dua_conv3d_k3_form(const dua_conv3_desc* d, int fused, long workspace_bytes, int cus, dua_conv3_form* out) {
+  dua::Conv3Form f;
+  if (!out) return DUA_ERR_ARG;
+  if (int e = dua::form_for(d, fused != 0, false, workspace_bytes, cus, &f)) return e;
+  *out = f;
+  return 0;
 }
 
-long dua_conv3d_k3_workspace(const dua_conv3_desc* d) {
-  using namespace dua::c3;
-  if (!d || (d->dtype != DUA_F16 && d->dtype != DUA_F32)) return DUA_ERR_ARG;
-  const int ck = 4 * (d->dtype == DUA_F16 ? 8 : 4);
-  const int nch = (d->Cin + ck - 1) / ck, nct = (d->Cout + BN - 1) / BN;
-  const int tiles = ((d->D + TD - 1) / TD) * ((d->H + TH - 1) / TH) * ((d->W + TW - 1) / TW);
-  int ks, ups;
-  dua::choose_split(tiles * nct * d->N, nch * 3, &ks, &ups);
-  return ks > 1 ? (long)ks * d->N * d->D * d->H * d->W * nct * BN * 4 : 0;
+int dua_conv3d_k3_kernel_kind(const dua_conv3_desc* d, int fused, int has_workspace) {
+  (void)has_workspace;              // ignored, see include/dua_hip.h: a workspace never moves a launch between the three kinds
+  dua::Conv3Form f;
+  if (int e = dua::conv3_form(d, fused != 0, false, 0, dua::ANY_CUS, &f)) return e;
+  return dua::conv3_kind_of(f);
 }
+
+long dua_conv3d_k3_workspace(const dua_conv3_desc* d) { return d ? dua::conv3_workspace_bytes(d) : DUA_ERR_ARG; }
 
 int dua_conv3d_k3_fwd(const dua_conv3_desc* d, const void* x, const void* w_packed, const float* bias_padded,
                       const dua_in_norm* in, void* y, dua_stat_word* out_stats, void* workspace, long workspace_bytes,
                       void* stream) {
-  if (!d || !x || !w_packed || !bias_padded || !y || !out_stats) return DUA_ERR_ARG;
-  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8)
-    return DUA_ERR_ARG;
-  if (in && in->stats && (!in->gamma || !in->beta || in->c_pad < d->Cin || in->count <= 0 || !(in->slope >= 0.f && in->slope <= 1.f))) return DUA_ERR_ARG;
+  if (!dua::conv_call_ok(d, {x, w_packed, bias_padded, y, out_stats}, in)) return DUA_ERR_ARG;
   if (d->dtype == DUA_F16)
     return dua::launch_conv3<dua::f16>(d, x, w_packed, bias_padded, in, y, out_stats, (float*)workspace, workspace_bytes, (hipStream_t)stream);
   if (d->dtype == DUA_F32)
@@ -1124,16 +995,15 @@ int dua_conv3d_k3_fwd(const dua_conv3_desc* d, const void* x, const void* w_pack
 }
 
 int dua_conv3d_k3_dgrad_reduce_supported(const dua_conv3_desc* d) {
-  if (!d || d->dtype != DUA_F16 || d->layout || d->tap_channel_plus1 || d->background || dua::conv_variant_of(d) != 0) return 0;
-  return dua::conv3_kernel_kind(d, false) == 2 ? 1 : 0;
+  dua::Conv3Form f;                 // the one form with the backward-sums epilogue
+  return dua::conv3_form(d, false, true, 0, dua::ANY_CUS, &f) == 0 ? 1 : 0;
 }
 
 int dua_conv3d_k3_dgrad_reduce(const dua_conv3_desc* d, const void* dy, const void* w_packed, const float* bias_padded, void* dx,
                                const void* raw, int raw_stride, int raw_off, const dua_in_norm* raw_in, double* sums, void* stream) {
-  if (!dua_conv3d_k3_dgrad_reduce_supported(d) || !dy || !w_packed || !bias_padded || !dx || !raw || !raw_in || !sums) return DUA_ERR_ARG;
-  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8) return DUA_ERR_ARG;
-  if (!raw_in->stats || !raw_in->gamma || !raw_in->beta || raw_in->c_pad < d->Cout || raw_in->count <= 0 ||
-      !(raw_in->slope >= 0.f && raw_in->slope <= 1.f) || raw_stride % 8 || raw_off % 8 || raw_off + d->Cout > raw_stride)
+  if (!dua::conv_call_ok(d, {dy, w_packed, bias_padded, dx, raw, raw_in, sums}, nullptr) || !dua_conv3d_k3_dgrad_reduce_supported(d))
+    return DUA_ERR_ARG;
+  if (!raw_in->stats || !dua::producer_ok(raw_in, d->Cout) || raw_stride % 8 || raw_off % 8 || raw_off + d->Cout > raw_stride)
     return DUA_ERR_ARG;
   const dua::BwdSums bw{raw, raw_stride, raw_off, raw_in, sums};
   return dua::launch_conv3<dua::f16>(d, dy, w_packed, bias_padded, nullptr, dx, nullptr, nullptr, 0, (hipStream_t)stream, &bw);

@@ -32,15 +32,7 @@
 
 namespace dua {
 
-namespace c3w {
-constexpr int TH = 8, TW = 8, HH = TH + 2, HW = TW + 2;
-constexpr int VSF = 32, RSF = 12 * VSF, PSF = HH * RSF;      // 384-byte rows, 3840-byte planes
-constexpr int BN = 64;
-constexpr int WPLANE = 18 * 1024;                              // [9 taps][2 k-groups][64 couts][16 B]
-constexpr int HALO_MAX = 10 * PSF;                             // 38400: the 8-deep tile
-constexpr int LDS_FIXED = HALO_MAX + 2 * WPLANE;               // 75264
-constexpr int SLAB = 3 * 4 * BN * 16;                          // 12288: one (kd, kh) slab of the packed weights (32-channel chunk)
-}  // namespace c3w
+// tile and LDS constants: namespace c3w, conv3_form.hpp
 
 // one 1 KB piece global -> LDS (64 lanes x 16 B, LDS address = M0 base + lane * 16); M0 saved / restored in the statement
 __device__ __forceinline__ void dma_piece(const char* src_lane, unsigned lds_dst) {
@@ -740,44 +732,35 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
   (void)ex;
 }
 
-static const LdsAttr kWideLdsAttrs[] = {{(const void*)conv3d_k3_wide_kernel, 80 * 1024}, {(const void*)conv3d_k3_wide_pt_kernel, 80 * 1024},
-                                        {(const void*)conv3d_k3_wide_bwd_kernel, 80 * 1024}};
+static const LdsAttr kWideLdsAttrs[] = {{(const void*)conv3d_k3_wide_kernel, conv3_lds_limit(DUA_CONV3_WIDE)},
+                                        {(const void*)conv3d_k3_wide_pt_kernel, conv3_lds_limit(DUA_CONV3_WIDE_PT)},
+                                        {(const void*)conv3d_k3_wide_bwd_kernel, conv3_lds_limit(DUA_CONV3_WIDE_BWD)}};
 static const LdsAttrs kWideLdsReg(kWideLdsAttrs);
 
 #ifdef DUA_STAMP
 extern "C" long dua_debug_stamps_wide(void* host, long bytes) { return stamps_out(host, bytes); }
 #endif
 
-bool conv3_wide_takes_bwd_sums(const Conv3Args& a) {
+// the owner's buffers of a backward-sums launch, as the epilogue addresses them
+static bool takes_bwd_sums(const Conv3Args& a) {
   return a.bw_raw && a.bw_xf.stats && a.bw_xf.gamma && a.bw_xf.beta && a.bw_xf.c_pad >= a.Cout && a.bw_stride % 8 == 0 && a.bw_off % 8 == 0 &&
          (long)a.D * a.H * a.W * a.bw_stride < 0x7fffffffL;
 }
 
-int launch_conv3_wide(Conv3Args a, int D, hipStream_t s, bool persistent, int stagger) {
-  using namespace c3w;
-  if (int e = ensure_prepared()) return e;
-  if (D % 8 || a.H % 8 || a.W % 8 || a.Cin % 16 || (a.xf.stats && a.Cin > 256)) return DUA_ERR_ARG;
-  if (a.in_blk && (a.Cin_off % 16 || a.Cin_stride % 16)) return DUA_ERR_ARG;
-  if (a.out_blk && (a.Cout_off % 16 || a.Cout_stride % 16)) return DUA_ERR_ARG;
-  a.tiles_h = a.H / 8; a.tiles_w = a.W / 8;
-  a.ntiles = (D / 8) * a.tiles_h * a.tiles_w;
-  const int lds = LDS_FIXED + (a.xf.stats ? 3 * 4 * a.Cin : 0) + (a.bw_sums ? 1024 : 0);
-  if (lds > 80 * 1024) return DUA_ERR_ARG;
-  if (a.bw_sums && (persistent || !conv3_wide_takes_bwd_sums(a))) return DUA_ERR_ARG;
-  if (persistent) {
-    // two workgroups per CU over the whole launch, shared by the (cout tile, sample) pairs; each walks its tiles with stride grid.x
-    const int cus = device_cus();
-    if (cus <= 0) return DUA_ERR_ARG;
-    const int pairs = (a.cout_pad / BN) * a.N;
-    int gx = (2 * cus + pairs - 1) / pairs;
-    gx = (gx + 7) & ~7;                                          // whole XCD rounds: tile t and t + grid.x stay on one XCD
-    if (gx > a.ntiles) gx = a.ntiles;
-    a.ksplit = stagger;
-    hipLaunchKernelGGL(conv3d_k3_wide_pt_kernel, dim3(gx, a.cout_pad / BN, a.N), dim3(256), lds, s, a);
-    return (int)hipGetLastError();
+int launch_conv3_wide(Conv3Args a, const Conv3Form& f, hipStream_t s) {
+  const dim3 grid(f.grid_x, f.grid_y, f.grid_z), block(256);
+  switch (f.kernel) {
+    case DUA_CONV3_WIDE: hipLaunchKernelGGL(conv3d_k3_wide_kernel, grid, block, f.lds_bytes, s, a); break;
+    case DUA_CONV3_WIDE_BWD:
+      if (!a.bw_sums || !takes_bwd_sums(a)) return DUA_ERR_ARG;
+      hipLaunchKernelGGL(conv3d_k3_wide_bwd_kernel, grid, block, f.lds_bytes, s, a);
+      break;
+    case DUA_CONV3_WIDE_PT:
+      a.ksplit = f.stagger;           // the persistent kernel reads its stagger there (it never splits K)
+      hipLaunchKernelGGL(conv3d_k3_wide_pt_kernel, grid, block, f.lds_bytes, s, a);
+      break;
+    default: return DUA_ERR_ARG;
   }
-  if (a.bw_sums) hipLaunchKernelGGL(conv3d_k3_wide_bwd_kernel, dim3(a.ntiles, a.cout_pad / BN, a.N), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(conv3d_k3_wide_kernel, dim3(a.ntiles, a.cout_pad / BN, a.N), dim3(256), lds, s, a);
   return (int)hipGetLastError();
 }
 

@@ -13,16 +13,12 @@
 // accumulators.  The producer's InstanceNorm+LeakyReLU is applied while staging (InXform).
 #include "common.hpp"
 #include "../../include/dua_hip.h"
+#include "conv3_form.hpp"
 
 namespace dua {
 
 
-namespace dc {
-constexpr int TM = 256, BN = 64, KG = 4;
-constexpr int VS = KG * 16 + 16;          // 80 B per voxel: conflict-free for 32 consecutive rows
-constexpr int A_BYTES = TM * VS;          // 20480
-constexpr int W_BYTES = KG * BN * 16;     // 4096
-}  // namespace dc
+// tile and LDS constants: namespaces dc / dcs, conv3_form.hpp
 
 struct DeconvArgs {
   const void* x; const void* w; const float* bias; void* y;
@@ -166,13 +162,6 @@ __global__ __launch_bounds__(256) void deconv_k2s2_kernel(DeconvArgs a) {
 // Cin <= 512), stages each in rows of its own (no workgroup barrier in the K loop; ds operations of one wave execute in
 // order), and the four partial tiles are added in a fixed order through LDS (deterministic) before the pixel-shuffle store.
 // Four times the workgroups, a quarter of the per-thread staging work, one memory round trip.
-namespace dcs {
-constexpr int TMS = 64, MC = 4;
-constexpr int STAGE = TMS * dc::VS + dc::W_BYTES;            // 5120 + 4096 per wave
-constexpr int RS = dc::BN * 4 + 16;                          // fp32 partial row: 272 B
-constexpr int RED = 4 * TMS * RS;                            // 69632: the staging rows live inside it
-}  // namespace dcs
-
 template <typename T>
 __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a) {
   using namespace dc;
@@ -679,101 +668,76 @@ static inline int deconv_res_lds(int nchunks, int nsk) {
   return 128 * (nchunks * 64 + 16) + 4 * nchunks * dc::W_BYTES + 2 * 128 * 80 + nsk * dc::W_BYTES;
 }
 
-// dynamic-LDS limits (raised once per device by ensure_prepared(), common.hpp)
-template <typename T> constexpr int deconv_plain_lds() {
-  constexpr int OS = dc::BN * (int)sizeof(T) + 16;
-  return ((dc::TM * OS > dc::A_BYTES + dc::W_BYTES) ? dc::TM * OS : dc::A_BYTES + dc::W_BYTES) + 3 * 4 * 1024;
-}
+// dynamic-LDS limits (raised once per device by ensure_prepared(), common.hpp): deconv_lds_limit(), which the forms report
 static const LdsAttr kDeconvLdsAttrs[] = {
-    {(const void*)deconv_k2s2_alltaps_kernel<f16, 2>, 160 * 1024},   {(const void*)deconv_k2s2_alltaps_kernel<f16, 1>, 160 * 1024},
-    {(const void*)deconv_k2s2_alltaps_kernel<float, 2>, 160 * 1024}, {(const void*)deconv_k2s2_alltaps_kernel<float, 1>, 160 * 1024},
-    {(const void*)deconv_k2s2_ksplit_kernel<f16>, dcs::RED + 3 * 4 * 1024},
-    {(const void*)deconv_k2s2_ksplit_kernel<float>, dcs::RED + 3 * 4 * 1024},
-    {(const void*)deconv_k2s2_kernel<f16>, deconv_plain_lds<f16>()},
-    {(const void*)deconv_k2s2_kernel<float>, deconv_plain_lds<float>()},
-    {(const void*)deconv_k2s2_res_kernel<1>, 160 * 1024}, {(const void*)deconv_k2s2_res_kernel<2>, 160 * 1024},
-    {(const void*)deconv_k2s2_res_kernel<3>, 160 * 1024}, {(const void*)deconv_k2s2_res_kernel<4>, 160 * 1024},
+    {(const void*)deconv_k2s2_alltaps_kernel<f16, 2>, deconv_lds_limit(DUA_DECONV_ALLTAPS_256, 2)},
+    {(const void*)deconv_k2s2_alltaps_kernel<f16, 1>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 2)},
+    {(const void*)deconv_k2s2_alltaps_kernel<float, 2>, deconv_lds_limit(DUA_DECONV_ALLTAPS_256, 4)},
+    {(const void*)deconv_k2s2_alltaps_kernel<float, 1>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 4)},
+    {(const void*)deconv_k2s2_ksplit_kernel<f16>, deconv_lds_limit(DUA_DECONV_KSPLIT, 2)},
+    {(const void*)deconv_k2s2_ksplit_kernel<float>, deconv_lds_limit(DUA_DECONV_KSPLIT, 4)},
+    {(const void*)deconv_k2s2_kernel<f16>, deconv_lds_limit(DUA_DECONV_ONE_TAP, 2)},
+    {(const void*)deconv_k2s2_kernel<float>, deconv_lds_limit(DUA_DECONV_ONE_TAP, 4)},
+    {(const void*)deconv_k2s2_res_kernel<1>, LDS_CU}, {(const void*)deconv_k2s2_res_kernel<2>, LDS_CU},
+    {(const void*)deconv_k2s2_res_kernel<3>, LDS_CU}, {(const void*)deconv_k2s2_res_kernel<4>, LDS_CU},
 };
 static const LdsAttrs kDeconvLdsReg(kDeconvLdsAttrs);
 
-// 2 = the all-taps kernel (large inputs: it may write 16-channel blocks), 1 = Cin chunks split over the waves, 0 = one tap per workgroup
-static int deconv_kernel_kind(const dua_conv3_desc* d) {
-  const int ck = dc::KG * (d->dtype == DUA_F16 ? 8 : 4);
-  const int nchunks = (d->Cin + ck - 1) / ck;
-  const long vox = (long)d->D * d->H * d->W;
-  if (vox >= 256L * 128 && nchunks <= 4) return 2;
-  if (nchunks >= 8 && nchunks <= 4 * dcs::MC && d->policy != 6) return 1;
-  return 0;
-}
-
+// One launch as deconv_form (conv3_form.hpp) decides it.  Do, Ho, Wo: the output extents, 0 = twice the input.
 template <typename T>
 static int launch_deconv(const dua_conv3_desc* d, const void* x, const void* w, const float* bias,
                          const dua_in_norm* in, void* y, hipStream_t s, int Do = 0, int Ho = 0, int Wo = 0) {
-  constexpr int CK = dc::KG * Elem<T>::EPG;
+  const int prepared = ensure_prepared();
+  DeconvForm f;
+  if (int e = deconv_form(d, in && in->stats, Do, Ho, Wo, &f)) return e;            // argument errors first
+  if (prepared) return prepared;
   DeconvArgs a;
   a.x = x; a.w = w; a.bias = bias; a.y = y;
   a.xf = make_xform(in, d->Cin);
   a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cin_stride = d->Cin_stride; a.Cin_off = d->Cin_off;
   a.Cout = d->Cout; a.Cout_stride = d->Cout_stride; a.Cout_off = d->Cout_off;
-  a.nchunks = (d->Cin + CK - 1) / CK;
-  a.nct = (d->Cout + dc::BN - 1) / dc::BN;
-  a.Do = Do ? Do : 2 * d->D; a.Ho = Ho ? Ho : 2 * d->H; a.Wo = Wo ? Wo : 2 * d->W;
-  a.pad = (a.Do | a.Ho | a.Wo) & 1;
-  const long vox = (long)d->D * d->H * d->W;
-  if (int e = ensure_prepared()) return e;
-  if (d->policy != 0 && d->policy != 6) return DUA_ERR_ARG;
-  const int g_conv_variant = d->policy;
+  a.nchunks = f.nchunks; a.nct = f.nct; a.lds_base = f.lds_base;
   a.out_blk = d->layout & DUA_OUT_BLOCKED ? 1 : 0;
-  if (d->layout & DUA_IN_BLOCKED) return DUA_ERR_ARG;
-  if (a.out_blk && (deconv_kernel_kind(d) != 2 || d->Cout_off % 16 || d->Cout_stride % 16 || (long)a.Do * a.Ho * a.Wo * 16 >= 0x7fffffffL)) return DUA_ERR_ARG;
-  if (vox >= 256L * 128 && a.nchunks <= 4) {          // enough tiles to fill the chip with one workgroup per 8 taps
-    // 128-voxel tiles: two workgroups per CU up to 64 input channels (70 KB each), one's pixel-shuffle stores under the
-    // other's loads; policy 6 keeps the 256-voxel form (one workgroup per CU) for A/B where it fits
-    auto lds_of = [&](int tm) {
-      return tm * (a.nchunks * 64 + 16) + 4 * a.nchunks * dc::W_BYTES + 2 * tm * (32 * (int)sizeof(T) + 16) +
-             (a.xf.stats ? 3 * 4 * a.nchunks * CK : 0);
-    };
-    const int mblk = g_conv_variant == 6 && lds_of(256) <= 160 * 1024 ? 2 : 1;
-    const int tm = 128 * mblk;
-    const int lds = lds_of(tm);
-    if (lds > 160 * 1024) return DUA_ERR_ARG;
-    dim3 grid2((unsigned)((vox + tm - 1) / tm), a.nct, d->N);
-    if (mblk == 2) hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 2>), grid2, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 1>), grid2, dim3(256), lds, s, a);
-    return (int)hipGetLastError();
+  a.Do = f.Do; a.Ho = f.Ho; a.Wo = f.Wo; a.pad = f.pad;
+  const dim3 grid(f.grid_x, f.grid_y, f.grid_z), block(256);
+  switch (f.kernel) {
+    case DUA_DECONV_ONE_TAP: hipLaunchKernelGGL(deconv_k2s2_kernel<T>, grid, block, f.lds_bytes, s, a); break;
+    case DUA_DECONV_KSPLIT: hipLaunchKernelGGL(deconv_k2s2_ksplit_kernel<T>, grid, block, f.lds_bytes, s, a); break;
+    case DUA_DECONV_ALLTAPS_128: hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 1>), grid, block, f.lds_bytes, s, a); break;
+    case DUA_DECONV_ALLTAPS_256: hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 2>), grid, block, f.lds_bytes, s, a); break;
+    default: return DUA_ERR_ARG;
   }
-  if (a.nchunks >= 8 && a.nchunks <= 4 * dcs::MC && g_conv_variant != 6) {   // Cin >= 256: waves split the Cin chunks (variant 6: the one-chunk-at-a-time kernel, A/B)
-    const int lds = dcs::RED + (a.xf.stats ? 3 * 4 * a.nchunks * CK : 0);
-    dim3 grid3((unsigned)((vox + dcs::TMS - 1) / dcs::TMS), 8 * a.nct, d->N);
-    hipLaunchKernelGGL(deconv_k2s2_ksplit_kernel<T>, grid3, dim3(256), lds, s, a);
-    return (int)hipGetLastError();
-  }
-  dim3 grid((unsigned)((vox + dc::TM - 1) / dc::TM), 8 * a.nct, d->N);
-  constexpr int OS = dc::BN * (int)sizeof(T) + 16;
-  constexpr int LDS = (dc::TM * OS > dc::A_BYTES + dc::W_BYTES) ? dc::TM * OS : dc::A_BYTES + dc::W_BYTES;
-  a.lds_base = LDS;
-  if (a.nchunks * CK > 1024) return DUA_ERR_ARG;
-  hipLaunchKernelGGL(deconv_k2s2_kernel<T>, grid, dim3(256), LDS + (a.xf.stats ? 3 * 4 * a.nchunks * CK : 0), s, a);
   return (int)hipGetLastError();
+}
+
+static int deconv_fwd(const dua_conv3_desc* d, int Do, int Ho, int Wo, const void* x, const void* w_packed, const float* bias_padded,
+                      const dua_in_norm* in, void* y, void* stream) {
+  if (!conv_call_ok(d, {x, w_packed, bias_padded, y}, in)) return DUA_ERR_ARG;
+  if (d->dtype == DUA_F16) return launch_deconv<f16>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
+  if (d->dtype == DUA_F32) return launch_deconv<float>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
+  return DUA_ERR_ARG;
 }
 
 }  // namespace dua
 
+extern "C" int dua_deconv_k2s2_form(const dua_conv3_desc* d, int fused, int Do, int Ho, int Wo, dua_deconv_form* out) {
+  dua::DeconvForm f;
+  if (!out) return DUA_ERR_ARG;
+  if (int e = dua::deconv_form(d, fused != 0, Do, Ho, Wo, &f)) return e;
+  *out = f;
+  return 0;
+}
+
 extern "C" int dua_deconv_k2s2_kernel_kind(const dua_conv3_desc* d) {
-  if (!d || (d->dtype != DUA_F16 && d->dtype != DUA_F32)) return DUA_ERR_ARG;
-  return dua::deconv_kernel_kind(d);
+  dua::DeconvForm f;
+  if (int e = dua::deconv_form(d, false, 0, 0, 0, &f)) return e;
+  return dua::deconv_kind_of(f);
 }
 
 extern "C" int dua_deconv_k2s2_fwd(const dua_conv3_desc* d, const void* x, const void* w_packed,
                                    const float* bias_padded, const dua_in_norm* in, void* y, void* stream) {
-  if (!d || !x || !w_packed || !bias_padded || !y) return DUA_ERR_ARG;
-  if (in && in->stats && (!in->gamma || !in->beta || in->c_pad < d->Cin || in->count <= 0 || !(in->slope >= 0.f && in->slope <= 1.f))) return DUA_ERR_ARG;
-  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8)
-    return DUA_ERR_ARG;
-  if (d->dtype == DUA_F16) return dua::launch_deconv<dua::f16>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream);
-  if (d->dtype == DUA_F32) return dua::launch_deconv<float>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream);
-  return DUA_ERR_ARG;
+  return dua::deconv_fwd(d, 0, 0, 0, x, w_packed, bias_padded, in, y, stream);
 }
 
 /* see include/dua_hip.h */
@@ -782,13 +746,7 @@ extern "C" int dua_deconv_k2s2_pad_fwd(const dua_conv3_desc* d, int Do, int Ho, 
   if (!d || d->D <= 0 || d->H <= 0 || d->W <= 0) return DUA_ERR_ARG;
   if ((Do != 2 * d->D && Do != 2 * d->D + 1) || (Ho != 2 * d->H && Ho != 2 * d->H + 1) || (Wo != 2 * d->W && Wo != 2 * d->W + 1))
     return DUA_ERR_ARG;
-  if (!x || !w_packed || !bias_padded || !y) return DUA_ERR_ARG;
-  if (in && in->stats && (!in->gamma || !in->beta || in->c_pad < d->Cin || in->count <= 0 || !(in->slope >= 0.f && in->slope <= 1.f))) return DUA_ERR_ARG;
-  if (d->Cin % 8 || d->Cout % 8 || d->Cin_stride % 8 || d->Cout_stride % 8 || d->Cin_off % 8 || d->Cout_off % 8)
-    return DUA_ERR_ARG;
-  if (d->dtype == DUA_F16) return dua::launch_deconv<dua::f16>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
-  if (d->dtype == DUA_F32) return dua::launch_deconv<float>(d, x, w_packed, bias_padded, in, y, (hipStream_t)stream, Do, Ho, Wo);
-  return DUA_ERR_ARG;
+  return dua::deconv_fwd(d, Do, Ho, Wo, x, w_packed, bias_padded, in, y, stream);
 }
 
 /* see include/dua_hip.h */

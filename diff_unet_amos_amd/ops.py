@@ -403,11 +403,21 @@ def conv3_workspace_bytes(dtype, N, D, H, W, cin, cout):
 # Launch form handed to the kernels with every call (dua_conv3_desc.policy; 0 = the launchers' automatic choice).  The kernel
 # tests and the A/B tools set these to reach forms the automatic choice would not take for their shapes; the library itself keeps
 # no option state.
-CONV_POLICY = 0          # conv3d_k3 / deconv_k2s2: 0, 2, 3, 6, 7 (| _native.POLICY_NO_FINISH)
+# conv3d_k3: 2 = 4x8x8 tiles, split-K with the wider target (up to 256 base workgroups) when a workspace is given; 3 = 2x8x8 tiles
+# (slab form); 6 / 7 = automatic without the kd-plane / the wide-tile form; 8 / 9 = persistent wide form.  deconv_k2s2: 6.
+CONV_POLICY = 0          # conv3d_k3 / deconv_k2s2: 0, 2, 3, 6, 7, 8, 9 (| _native.POLICY_NO_FINISH)
 WGRAD_POLICY = 0         # conv3d_k3_wgrad: bit field, see include/dua_hip.h
 
 KIND_V2, KIND_FIRST, KIND_WIDE = 0, 1, 2          # dua_conv3d_k3_kernel_kind
 DECONV_ALLTAPS = 2                                # dua_deconv_k2s2_kernel_kind
+
+
+def conv3_form(d, fused=False, workspace_bytes=0, cus=0):
+    """dua_conv3d_k3_form of a descriptor: the launch form the launcher itself decides (kernel, tile depth, split, grid, LDS).
+    ``workspace_bytes``: what the call will pass; ``cus`` > 0 answers without a device."""
+    f = nv.Conv3Form()
+    nv.check(nv.lib().dua_conv3d_k3_form(C.byref(d), 1 if fused else 0, int(workspace_bytes), int(cus), C.byref(f)), "dua_conv3d_k3_form")
+    return f
 
 
 def conv3_kernel_kind(dtype, N, D, H, W, cin, cin_stride, cout, fused=False, tap_channel=None, background=False):

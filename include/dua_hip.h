@@ -76,7 +76,8 @@ typedef struct {
   int policy;                      /* 0 = the launcher's automatic choice of kernel form.  Non-zero values select a form by hand --
                                       for the kernel tests (every form is exercised on shapes the automatic choice would not
                                       give it) and same-process A/B timing; results are the same.  dua_conv3d_k3_fwd: low byte
-                                      2 = 4x8x8 tiles without split-K, 3 = 2x8x8 tiles (slab form), 6 = automatic without the
+                                      2 = 4x8x8 tiles, split-K with the wider target (up to 256 base workgroups) when a workspace
+                                      is given, 3 = 2x8x8 tiles (slab form), 6 = automatic without the
                                       kd-plane / LDS-DMA form of the small layers, 7 = automatic without the wide-tile form, 8 / 9 = the wide-tile
                                       form with persistent workgroups (9: staggered start; both measured slower, kept for A/B);
                                       bit 8 (DUA_POLICY_NO_FINISH) = skip the split-K finish kernel (timing the main kernel alone:
@@ -95,9 +96,59 @@ typedef struct {
  * 16-channel blocks decides with the rule the launcher uses).  fused = the call will pass a producer descriptor.
  * dua_conv3d_k3_kernel_kind: 0 = conv3d_k3_v2_kernel (channels-last only), 1 = conv3d_k3_first_kernel (output may be
  * blocked), 2 = conv3d_k3_wide_kernel (input and output may be blocked).  dua_deconv_k2s2_kernel_kind: 0 = a kernel that
- * writes channels-last only, 2 = deconv_k2s2_alltaps_kernel (output may be blocked). */
+ * writes channels-last only, 2 = deconv_k2s2_alltaps_kernel (output may be blocked).  A descriptor the launcher would reject
+ * gives DUA_ERR_ARG.  has_workspace is ignored: split-K is taken only by layers of at most 256 4x8x8 workgroups and the
+ * wide-tile form only from 1024 on, so a workspace never moves a launch between these three kinds (dua_conv3d_k3_form tells
+ * whether it splits). */
 int dua_conv3d_k3_kernel_kind(const dua_conv3_desc* d, int fused, int has_workspace);
 int dua_deconv_k2s2_kernel_kind(const dua_conv3_desc* d);
+
+/* The whole launch form of a call, decided by the one host function the launchers themselves run (csrc/conv3_form.hpp): which
+ * kernel instantiation, its grid and dynamic LDS, and the split.  Both kernel_kind queries above are projections of it.
+ * fused = the call will pass a producer descriptor with statistics; workspace_bytes = what the call will pass (0 = none);
+ * cus = compute units to decide for, 0 = the current device (cus > 0 answers without touching the GPU; only the persistent
+ * forms' grids depend on it).  Returns 0 or DUA_ERR_ARG for a call the launcher rejects. */
+enum {
+  DUA_CONV3_FIRST = 0,       /* conv3d_k3_first_kernel: resident weights, persistent workgroups */
+  DUA_CONV3_TAP0 = 1,        /* conv3d_k3_v2_kernel<f16, 4, 0>: the lone tap channel */
+  DUA_CONV3_TAP1 = 2,        /* conv3d_k3_v2_kernel<f16, 4, 1>: 16 channels + the tap channel */
+  DUA_CONV3_WIDE = 3,        /* conv3d_k3_wide_kernel */
+  DUA_CONV3_WIDE_BWD = 4,    /* conv3d_k3_wide_bwd_kernel (dua_conv3d_k3_dgrad_reduce) */
+  DUA_CONV3_WIDE_PT = 5,     /* conv3d_k3_wide_pt_kernel: persistent workgroups */
+  DUA_CONV3_V2_4 = 6,        /* conv3d_k3_v2_kernel<T, 4>: 4x8x8 tiles, slab form */
+  DUA_CONV3_V2_4_HALF = 7,   /* ... <f16, 4, 2, true>: half-empty last Cin chunk */
+  DUA_CONV3_V2_4_KD = 8,     /* ... <T, 4, 2, false, true>: kd-plane form (split-K launches) */
+  DUA_CONV3_V2_2 = 9,        /* ... <T, 2>: 2x8x8 tiles, slab form */
+  DUA_CONV3_V2_2_KD = 10     /* ... <T, 2, 2, false, true>: 2x8x8 tiles, kd-plane form */
+};
+typedef struct {
+  int kernel;                /* DUA_CONV3_* */
+  int tile_depth;            /* output planes per tile: 2, 4 or 8 (wide) */
+  int ksplit, units_per_split; /* split-K over (Cin chunk, kd) units; ksplit == 1: no split */
+  int finish;                /* 1 = splitk_finish_kernel follows the main launch */
+  int grid_x, grid_y, grid_z; /* of the main launch (256 threads per workgroup) */
+  int lds_bytes;             /* dynamic LDS of the main launch */
+  int lds_limit;             /* the dynamic-LDS limit dua_prepare() registers for that kernel */
+  long workspace_needed;     /* bytes the split this policy wants for d needs (0: it wants none); the launch splits when
+                                workspace_bytes covers it.  Never more than dua_conv3d_k3_workspace(d) under the policies plans
+                                run with (0, 6, 7, 8, 9). */
+} dua_conv3_form;
+int dua_conv3d_k3_form(const dua_conv3_desc* d, int fused, long workspace_bytes, int cus, dua_conv3_form* out);
+
+enum {
+  DUA_DECONV_ONE_TAP = 0,    /* deconv_k2s2_kernel: 256 voxels x one tap per workgroup */
+  DUA_DECONV_KSPLIT = 1,     /* deconv_k2s2_ksplit_kernel: Cin chunks split over the waves */
+  DUA_DECONV_ALLTAPS_128 = 2, /* deconv_k2s2_alltaps_kernel<T, 1>: 128-voxel tiles */
+  DUA_DECONV_ALLTAPS_256 = 3 /* deconv_k2s2_alltaps_kernel<T, 2>: 256-voxel tiles (policy 6) */
+};
+typedef struct {
+  int kernel;                /* DUA_DECONV_* */
+  int tile_voxels;           /* input voxels per workgroup */
+  int grid_x, grid_y, grid_z;
+  int lds_bytes, lds_limit;  /* as in dua_conv3_form */
+} dua_deconv_form;
+/* Do, Ho, Wo: output extents as for dua_deconv_k2s2_pad_fwd, or 0, 0, 0 for dua_deconv_k2s2_fwd (twice the input). */
+int dua_deconv_k2s2_form(const dua_conv3_desc* d, int fused, int Do, int Ho, int Wo, dua_deconv_form* out);
 
 /* w_packed: from dua_pack_conv3_weights.  bias_padded: fp32, at least Cout entries (a buffer padded to
  * ceil(Cout/64)*64 works, entries behind Cout are never read).  in: NULL or the

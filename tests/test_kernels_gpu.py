@@ -111,7 +111,8 @@ def _fp64_bound_check(got, act, w, b, dtype, emulated=False, split_parts=0, seed
 @pytest.fixture
 def conv_variant(request):
     """Force one of the conv3d_k3 launch shapes (0: automatic policy with split-K / 2x8x8 tiles where they pay,
-    2: 4x8x8 tiles without split-K, 3: 2x8x8 tiles, 6: the policy with the kd-plane / LDS-DMA form of the small layers
+    2: 4x8x8 tiles, split-K with the wider target (up to 256 base workgroups) when a workspace is given -- these tests pass
+    none --, 3: 2x8x8 tiles, 6: the policy with the kd-plane / LDS-DMA form of the small layers
     switched off)."""
     ops = _ops()
     ops.CONV_POLICY = request.param          # handed to the kernels with every call (dua_conv3_desc.policy)

@@ -158,8 +158,8 @@ class _Checker:
         d = nv.Conv3Desc(nv.dt_code(x.dtype), N, D, H, W, cin, cs, cin_off, cout, y.shape[-1], cout_off,
                          0 if tap_channel is None else tap_channel + 1, 0,
                          (nv.IN_BLOCKED if in_blocked else 0) | (nv.OUT_BLOCKED if out_blocked else 0), ops.CONV_POLICY)
-        need = int(nv.lib().dua_conv3d_k3_workspace(ctypes.byref(d)))
-        split = need > 0 and workspace is not None and workspace.numel() * workspace.element_size() >= need
+        ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        split = ops.conv3_form(d, norm is not None, ws_bytes).ksplit > 1           # the launcher's own answer for this call
         kind = KIND_NAMES[int(nv.lib().dua_conv3d_k3_kernel_kind(ctypes.byref(d), 1 if norm is not None else 0, 1 if split else 0))]
         xs = x.clone()
         self.orig["conv3d_k3"](x, cin, cin_off, w_packed, bias_pad, cout, y, cout_off, out_stats, norm=norm, workspace=workspace,
