@@ -21,6 +21,7 @@ if os.environ.get("DUA_DEBUG") == "1" and os.environ.get("DUA_HIP_LIB"):
 
 F32, F16 = 0, 1
 U8 = 2                    # DUA_U8: uint8 / bool masks of the surface-distance entry points
+I16 = 3                   # DUA_I16: int16 Hounsfield units of the case-preparation entry points
 ERR_ARG = -22
 SURFACE_FIELDS = ("hd", "hd95", "asd", "assd", "tp", "fp", "fn", "tn", "hd95_lo", "hd95_hi", "asd_ba", "n_surface")
 
@@ -168,6 +169,12 @@ class AugSmoothing(C.Structure):
     _fields_ = [("alpha", C.c_float), ("order", C.c_float), ("epsilon", C.c_float), ("max_value", C.c_float)]
 
 
+class PrepGeom(C.Structure):
+    """dua_prep_geom."""
+    _fields_ = [("n_in", C.c_int * 3), ("n_out", C.c_int * 3), ("stride", C.c_long * 3), ("base", C.c_long),
+                ("src_voxels", C.c_long)]
+
+
 AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
 BLEND_MAX_CLASSES = 64   # DUA_BLEND_MAX_CLASSES
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
@@ -273,6 +280,9 @@ _SIGS = {
                                          _P, C.c_int, _P, _P, _P, _P]),
     "dua_blend_accumulate": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 + [_P, _P]),
     "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "dua_prep_foreground_box": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "dua_prep_resample": (C.c_int, [C.c_int, _P, _P, C.POINTER(PrepGeom), _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    "dua_prep_restore": (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -138,6 +138,22 @@ class DeviceVolume:
         x = ((x - a_min) / (a_max - a_min)).clamp_(0.0, 1.0)
         return cls(x, label, image_threshold=image_threshold, device=device, num_classes=num_classes)
 
+    @classmethod
+    def from_raw(cls, image, label, affine, pixdim=(1.5, 1.5, 2.0), axcodes="RAS", a_min=-175.0, a_max=250.0, image_threshold=0.0,
+                 device="cuda", num_classes=None):
+        """The whole deterministic front of the reference's transforms (utils.py:125-136: window, foreground crop, orientation,
+        spacing) on the device -- ``prepare.prepare_case`` on a scan as a reader hands it over (int16 or fp32 ``image``, uint8
+        ``label``, 4x4 ``affine``) -- then ``DeviceVolume``.  The ``PreparedCase`` (prepared affine, ``restore``) is kept as
+        ``volume.prepared``."""
+        from . import prepare
+        if label is None:
+            raise ValueError("DeviceVolume.from_raw: label is required (prepare.prepare_case prepares an image on its own)")
+        case = prepare.prepare_case(image, label, affine=affine, pixdim=pixdim, axcodes=axcodes, a_min=a_min, a_max=a_max,
+                                    device=device)
+        volume = cls(case.image, case.label, image_threshold=image_threshold, device=device, num_classes=num_classes)
+        volume.prepared = case
+        return volume
+
     @property
     def shape(self):
         return tuple(self.image.shape)

@@ -1776,3 +1776,76 @@ def dice_from_tallies(tallies):
     fp64 [C] on the tallies' device, no host read."""
     inter, denom = tallies[:, 0].double(), tallies[:, 1].double() + tallies[:, 2].double()
     return torch.where(denom > 0, 2.0 * inter / denom.clamp(min=1), torch.zeros_like(denom))
+
+
+# ---- case preparation: crop, reorient and resample a raw scan (csrc/volume_prep.hip; utils.py:125-136, :168-177) ----
+
+def _prep_dtype(src):
+    if src.dtype == torch.int16:
+        return nv.I16
+    if src.dtype == torch.float32:
+        return nv.F32
+    raise TypeError(f"a raw volume is int16 or float32, not {src.dtype}")
+
+
+def prep_foreground_box(src, a_min):
+    """dua_prep_foreground_box: int32 [8] on the device = min index per axis, max index per axis, the number of voxels above
+    ``a_min`` and 0, over ``src`` (int16 or fp32 [X0, X1, X2])."""
+    assert src.is_cuda and src.is_contiguous() and src.dim() == 3 and 0 < src.numel() < 2 ** 31, \
+        "src: contiguous [X0, X1, X2] device tensor of fewer than 2^31 voxels"
+    result = torch.empty(8, dtype=torch.int32, device=src.device)
+    with torch.cuda.device(src.device):
+        nv.check(nv.lib().dua_prep_foreground_box(_prep_dtype(src), nv.ptr(src), *src.shape, float(a_min), nv.ptr(result),
+                                                  nv.stream_ptr()), "dua_prep_foreground_box")
+    return result
+
+
+def prep_upload_tables(geom, device):
+    """The per-axis tables of a ``prepare.PreparedGeometry`` on ``device`` in one upload: (lo int32, weight fp32, nearest int32),
+    each [N0 + N1 + N2], axis 0 first."""
+    import numpy as np
+    n = sum(geom.shape)
+    words = np.concatenate([np.concatenate(geom.lo), np.concatenate(geom.nearest), np.concatenate(geom.weight).view(np.int32)])
+    tables = torch.from_numpy(words.astype(np.int32, copy=False)).to(device)
+    return tables[:n], tables[2 * n:].view(torch.float32), tables[n:2 * n]
+
+
+def prep_resample(src, src_label, geom, a_min, a_range, tables=None):
+    """dua_prep_resample: (image fp32 [*geom.shape], label uint8 [*geom.shape] or None) from ``src`` (int16 or fp32) and
+    ``src_label`` (uint8 or None), both [X0, X1, X2]; ``geom``: a ``prepare.PreparedGeometry``; ``tables``: what
+    ``prep_upload_tables`` returned for it (uploaded here when None)."""
+    assert src.is_cuda and src.is_contiguous() and src.dim() == 3, "src: contiguous [X0, X1, X2] device tensor"
+    if src_label is not None:
+        _u8c(src_label, "src_label")
+        assert src_label.shape == src.shape and src_label.device == src.device, "src_label: the shape and device of src"
+    assert tuple(src.shape) == tuple(geom.source_shape), f"src has shape {tuple(src.shape)}, the geometry {geom.source_shape}"
+    dev = src.device
+    lo, weight, nearest = tables if tables is not None else prep_upload_tables(geom, dev)
+    n = sum(geom.shape)
+    _i32c(lo, "lo"); _i32c(nearest, "nearest"); _f32c(weight, "weight")
+    assert lo.numel() == weight.numel() == nearest.numel() == n and lo.device == weight.device == nearest.device == dev, \
+        f"tables: {n} entries each on the source's device"
+    g = nv.PrepGeom((C.c_int * 3)(*geom.n_in), (C.c_int * 3)(*geom.shape), (C.c_long * 3)(*geom.stride), geom.base, src.numel())
+    image = torch.empty(geom.shape, dtype=torch.float32, device=dev)
+    label = torch.empty(geom.shape, dtype=torch.uint8, device=dev) if src_label is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_prep_resample(_prep_dtype(src), nv.ptr(src), nv.ptr(src_label), C.byref(g), nv.ptr(lo), nv.ptr(weight),
+                                            nv.ptr(nearest), float(a_min), float(a_range), nv.ptr(image), nv.ptr(label),
+                                            nv.stream_ptr()), "dua_prep_resample")
+    return image, label
+
+
+def prep_restore(mask, source_shape, tables):
+    """dua_prep_restore: uint8 [C, *source_shape] from ``mask`` (uint8 [C, *prepared]); ``tables``: the three int32 device
+    vectors of ``prepare.PreparedGeometry.restore``."""
+    _u8c(mask, "mask")
+    assert mask.dim() == 4 and 0 < mask[0].numel() < 2 ** 31, "mask: [C, N0, N1, N2]"
+    X = tuple(int(x) for x in source_shape)
+    for t, x, name in zip(tables, X, ("tab0", "tab1", "tab2")):
+        _i32c(t, name)
+        assert tuple(t.shape) == (x,) and t.device == mask.device, f"{name}: int32 [{x}] on the mask's device"
+    out = torch.empty((mask.shape[0],) + X, dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        nv.check(nv.lib().dua_prep_restore(nv.ptr(mask), mask[0].numel(), mask.shape[0], *X, *(nv.ptr(t) for t in tables),
+                                           nv.ptr(out), nv.stream_ptr()), "dua_prep_restore")
+    return out

@@ -988,6 +988,68 @@ int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, con
                      int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
                      int labels_dtype, int label_map, unsigned long long* tallies, void* stream);
 
+/* ---- case preparation: crop, reorient and resample a raw scan on the device -----------------------------------------
+ * The deterministic front of the reference's transform chain (utils.py:125-136 for training, :168-177 for validation:
+ * ScaleIntensityRanged(a_min, a_max -> 0, 1, clip), CropForegroundd(source_key="image"), Orientationd, Spacingd(bilinear |
+ * nearest)), from a scan as a NIfTI reader hands it over -- source [X0][X1][X2], DUA_I16 (Hounsfield units) or DUA_F32,
+ * C-contiguous, an optional uint8 label map of the same shape, and a 4x4 affine on the host -- to the fp32 image and uint8
+ * label map the training and evaluation paths take.  The semantics are fixed HERE (MONAI is not a dependency):
+ *
+ * 1. Window.  f(v) = min(max((v - a_min) / (a_max - a_min), 0), 1), applied to every SOURCE voxel before interpolation
+ *    (clipping does not commute with interpolation; the reference clips first).  fp32: t = v - a_min, q = t / range with
+ *    range = fp32(a_max - a_min) given by the caller, IEEE division, then the clamp (NaN -> 0).
+ * 2. Foreground box.  Per source axis [min, max + 1) over the voxels with f(v) > 0, i.e. v > a_min; margin 0.
+ * 3. Orientation.  Axis permutation and flips from the affine by nibabel's io_orientation rule: the 3x3 block divided by its
+ *    column norms, replaced by the nearest orthogonal matrix (P Q^T of its SVD); for source axes 0, 1, 2 in turn the world axis
+ *    with the largest absolute entry of that column, its sign the flip, that world axis's row zeroed before the next column.
+ *    Reordered and flipped to the requested axis codes (any of the 48; default "RAS").  Host arithmetic on 16 numbers: the
+ *    kernels see it as three signed element strides and a base offset, so every orientation is the same code.
+ * 4. Spacing.  Per oriented axis, with n_in the cropped extent, s_in the column norm and s_out the target spacing:
+ *    n_out = rint((n_in - 1) s_in / s_out) + 1 (half to even); output index i reads the coordinate
+ *    x = min(i s_out / s_in, n_in - 1), evaluated in fp64 ON THE HOST.  Image: linear between lo = min(floor(x), n_in - 2) and
+ *    lo + 1 with weight x - lo (n_in == 1: lo = 0, weight 0); label: index rint(x), half to even.  Rotation in the affine is
+ *    kept, only the column norms change, so the voxel-space map is per axis.  The host uploads three tables per axis -- lo
+ *    (int32), weight (fp32, rounded once from fp64), nearest (int32) -- and the kernel computes no coordinate: label indices
+ *    are exact.  Lerp order, fixed: the four pairs along W (the fastest prepared axis), then the two along H, then D; one
+ *    lerp is fmaf(weight, b - a, a), the difference rounded first.
+ * 5. Prepared affine: the source affine composed with the crop offset, the permutation and flips and the column rescale
+ *    (host; diff_unet_amos_amd/prepare.py).
+ * 6. Restore.  A uint8 mask on the prepared grid back on the source grid: a source voxel inside the foreground box reads the
+ *    prepared voxel at rint (half to even) of its inverse coordinate k s_in / s_out, clamped to the extent; a voxel outside the
+ *    box is 0.  Again per-axis tables from the host.
+ *
+ * dua_prep_foreground_box: one streaming pass.  result (int32 [8], WRITTEN): min index per source axis (words 0..2), max
+ * index per source axis (3..5), the number of foreground voxels (6), 0 (7); INT_MAX / -1 / 0 when there is none.  Workgroups
+ * combine with integer atomicMin / atomicMax / atomicAdd: the words do not depend on the order of arrival.
+ *
+ * dua_prep_resample: ONE launch writes image (fp32 [n_out0][n_out1][n_out2]) and, when src_label and label are given, label
+ * (uint8, same extents).  Oriented voxel (k0, k1, k2) of the cropped source is element base + k0 stride[0] + k1 stride[1] +
+ * k2 stride[2] of src and of src_label.  lo / weight / nearest: DEVICE tables [n_out0 + n_out1 + n_out2], axis 0 first; the
+ * kernel clamps their entries into [0, n_in - 1], and the call is rejected unless every corner of the oriented box lies inside
+ * [0, src_voxels): no table can make it read outside the source.  Per output voxel: 8 source elements and one label byte
+ * read, 4 + 1 bytes written.
+ *
+ * dua_prep_restore: out (uint8 [C][X0][X1][X2], WRITTEN) from mask (uint8 [C][prepared_voxels]).  tab0 / tab1 / tab2: DEVICE
+ * int32 [X0], [X1], [X2]; entry x of tab_a is the prepared index of source index x along its oriented axis TIMES that axis's
+ * element stride in the prepared volume, or -1 outside the box:
+ *   out[c][x0][x1][x2] = any table entry negative ? 0 : mask[c][tab0[x0] + tab1[x1] + tab2[x2]]
+ * (an offset outside [0, prepared_voxels) reads nothing and gives 0).
+ * Volumes hold fewer than 2^31 voxels.  Invalid arguments: DUA_ERR_ARG, before the device is touched. */
+#define DUA_I16 3
+typedef struct {
+  int n_in[3];                   /* extents of the cropped source along the oriented axes */
+  int n_out[3];                  /* extents of the prepared volume */
+  long stride[3];                /* signed element stride of each oriented axis in the source */
+  long base;                     /* element offset of oriented voxel (0, 0, 0) */
+  long src_voxels;               /* X0 X1 X2 */
+} dua_prep_geom;
+int dua_prep_foreground_box(int dtype, const void* src, int X0, int X1, int X2, float a_min, int* result, void* stream);
+int dua_prep_resample(int dtype, const void* src, const unsigned char* src_label, const dua_prep_geom* geom, const int* lo,
+                      const float* weight, const int* nearest, float a_min, float range, float* image, unsigned char* label,
+                      void* stream);
+int dua_prep_restore(const unsigned char* mask, long prepared_voxels, int C, int X0, int X1, int X2, const int* tab0,
+                     const int* tab1, const int* tab2, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
