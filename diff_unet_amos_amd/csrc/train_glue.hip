@@ -547,7 +547,7 @@ int dua_temb_train_bwd(int N, int half_dim, int hidden, const float* w1, const d
                        const float* saved, float* scratch, float* dw0, float* db0, float* dw1, float* db1, void* stream) {
   int P = 0;
   if (N <= 0 || N > 64 || half_dim <= 0 || 2 * half_dim > 1024 || hidden <= 0 || hidden % 256 || hidden > 512 || !w1 ||
-      (((size_t)w1) & 15) || !dadd || !saved || !scratch || !dw0 || !db0 || !dw1 || !db1 || !temb_blocks_ok(blocks, hidden, true, &P))
+      (((size_t)w1) & 15) || !dadd || !saved || !scratch || (((size_t)scratch) & 15) || !dw0 || !db0 || !dw1 || !db1 || !temb_blocks_ok(blocks, hidden, true, &P))
     return DUA_ERR_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const int nch1 = (P + dua::TB_ROWS - 1) / dua::TB_ROWS, nch2 = hidden / dua::TB_ROWS;

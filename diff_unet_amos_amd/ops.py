@@ -1047,7 +1047,8 @@ def temb_train_bwd(dadd, saved, half, w1, proj_w):
     P = sum(w.shape[0] for w in proj_w)
     assert dadd.numel() == N * P and saved.shape[1] == ed + 4 * hid
     nscratch = N * hid * (1 + -(-P // 64) + hid // 64)
-    flat = torch.empty(hid * ed + hid + hid * hid + hid + P * hid + P + nscratch, dtype=torch.float32, device=saved.device)
+    pad = -P % 4                            # the scratch is stored as 16-byte pieces: it starts on a multiple of four floats
+    flat = torch.empty(hid * ed + hid + hid * hid + hid + P * hid + P + pad + nscratch, dtype=torch.float32, device=saved.device)
     pos = [0]
 
     def take(*shape):
@@ -1061,6 +1062,7 @@ def temb_train_bwd(dadd, saved, half, w1, proj_w):
     dw0, db0, dw1, db1 = take(hid, ed), take(hid), take(hid, hid), take(hid)
     dws = [take(w.shape[0], hid) for w in proj_w]
     dbs = [take(w.shape[0]) for w in proj_w]
+    pos[0] += pad
     scratch = take(nscratch)
     blk = _temb_blocks(proj_w, dws=dws, dbs=dbs)
     nv.check(nv.lib().dua_temb_train_bwd(N, half, hid, nv.ptr(w1), C.byref(blk), nv.ptr(dadd), nv.ptr(saved), nv.ptr(scratch),

@@ -362,7 +362,8 @@ int dua_seg_loss_finish_mn(int N, int C, long voxels, int use_mse, int use_bce, 
  * fwd: writes add and saved = fp32 [N][2*half + 4*hidden] (e, z1, h1, z2, s).
  * bwd: from dadd and saved, every parameter gradient in three launches: dw0 [hidden][2*half], db0, dw1 [hidden][hidden], db1 and
  *      blocks->dw[b] [cout_b][hidden], blocks->db[b] [cout_b] (all WRITTEN, summed over the samples in a fixed order);
- *      scratch = fp32 [N * hidden * (1 + ceil(P / 64) + hidden / 64)], P = sum of cout.  hidden: 256 or 512; 2*half <= 1024; N <= 64; sum of cout <= 4096; weights 16-byte aligned. */
+ *      scratch = fp32 [N * hidden * (1 + ceil(P / 64) + hidden / 64)], P = sum of cout.  hidden: 256 or 512; 2*half <= 1024; N <= 64; sum of cout <= 4096; weights and
+ *      scratch 16-byte aligned (the chunk partials are stored as 16-byte pieces). */
 #define DUA_TEMB_MAX_BLOCKS 16
 typedef struct {
   int nblocks;
