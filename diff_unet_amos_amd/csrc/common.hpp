@@ -97,6 +97,30 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
 
+// Origin voxel of the 8x8x8 output tile that workgroup `bid` of `ntiles` (tiles_h x tiles_w per depth slab) computes.
+__device__ __forceinline__ void wide_tile_origin(int bid, int ntiles, int tiles_h, int tiles_w, int& d0, int& h0, int& w0) {
+  const int per_slab = tiles_h * tiles_w;
+  const int tile = xcd_remap(bid, ntiles);
+  const int td = tile / per_slab, rem = tile - td * per_slab, th = rem / tiles_w, tw = rem - th * tiles_w;
+  d0 = td * 8; h0 = th * 8; w0 = tw * 8;
+}
+
+// One 1 KB piece global -> LDS: 16 bytes per lane, lane i lands at lds_dst + 16 i (lds_dst wave-uniform).  Inline assembly on
+// purpose: hipcc neither counts these transfers nor waits for them (behind the builtin it puts an s_waitcnt vmcnt(0) in front
+// of the next LDS read), so the caller waits itself -- counted vmcnt, then a barrier, then the reads.  M0 (the LDS base of the
+// transfer) is compiler-reserved and not preserved around an asm statement: it is written in the SAME statement that reads
+// it and restored there; s_nop 0 is the one wait state the ReadM0 -> LDS-DMA hazard asks for.
+__device__ __forceinline__ void lds_dma_16(const void* src_lane, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(src_lane), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
+}
+// The same piece with M0 left at lds_dst: only for kernels in which nothing else uses M0 (no movrel, no LDS-DMA builtin, no
+// sendmsg) -- saving it costs the weight-gradient kernel 1-4 %.
+__device__ __forceinline__ void lds_dma_16_m0_unsaved(const void* src_lane, unsigned lds_dst) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src_lane), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
+}
+
 // Input transform applied while a consumer stages its operand: the producer stored the raw
 // convolution output and accumulated per-(n, c) sums of it; the consumer turns the sums into
 // InstanceNorm3d(affine) scale/shift in its preamble and applies
@@ -131,6 +155,13 @@ struct InXform {
   float eps, slope;
 };
 
+// The four summed words of a channel -> (sum x, sum x^2): THE conversion, also called directly by the kernels whose prologue
+// requests the words early and adds them later (wide_tile, upconv_k3_kernel: only the lanes that finish a group convert).
+__device__ __forceinline__ void stats_words_value(const stat_t (&w)[STAT_WORDS], double& S, double& Q) {
+  S = (double)w[0] + (double)w[1] * (1.0 / STAT_FRAC);
+  Q = (double)w[2] + (double)w[3] * (1.0 / STAT_FRAC);
+}
+
 // (sum x, sum x^2) of channel c of sample n: the replica rows are summed as integers (exact), then converted.
 __device__ __forceinline__ void stats_read(const stat_t* stats, int n, int c_pad, int c, double& S, double& Q) {
   stat_t w[STAT_WORDS] = {0, 0, 0, 0};
@@ -140,8 +171,21 @@ __device__ __forceinline__ void stats_read(const stat_t* stats, int n, int c_pad
 #pragma unroll
     for (int k = 0; k < STAT_WORDS; ++k) w[k] += p[(long)k * c_pad];
   }
-  S = (double)w[0] + (double)w[1] * (1.0 / STAT_FRAC);
-  Q = (double)w[2] + (double)w[3] * (1.0 / STAT_FRAC);
+  stats_words_value(w, S, Q);
+}
+
+// A lane's 2 x 4 loaded words (two replica rows of one channel, lane = (part, channel): stats_read_wave16) -> the channel's
+// (sum x, sum x^2): the two rows and the four parts are added as integers (exact; cross-lane, all 64 lanes active), then
+// converted.
+__device__ __forceinline__ void stats_words_to_sums(const stat_t (&v)[2 * STAT_WORDS], double& S, double& Q) {
+  stat_t w[STAT_WORDS];
+#pragma unroll
+  for (int k = 0; k < STAT_WORDS; ++k) {
+    w[k] = v[k] + v[STAT_WORDS + k];
+    w[k] += __shfl_xor(w[k], 16);
+    w[k] += __shfl_xor(w[k], 32);
+  }
+  stats_words_value(w, S, Q);
 }
 
 // The same sums read by a WHOLE WAVE for 16 channels at once: lane = (part = lane >> 4, channel c0 + (lane & 15)); every lane
@@ -161,16 +205,25 @@ __device__ __forceinline__ void stats_read_wave16(const stat_t* stats, int n, in
   S += __shfl_xor(S, 16); S += __shfl_xor(S, 32);
   Q += __shfl_xor(Q, 16); Q += __shfl_xor(Q, 32);
 #else
-  stat_t w[STAT_WORDS];
-#pragma unroll
-  for (int k = 0; k < STAT_WORDS; ++k) {
-    w[k] = v[k] + v[STAT_WORDS + k];
-    w[k] += __shfl_xor(w[k], 16);
-    w[k] += __shfl_xor(w[k], 32);
-  }
-  S = (double)w[0] + (double)w[1] * (1.0 / STAT_FRAC);
-  Q = (double)w[2] + (double)w[3] * (1.0 / STAT_FRAC);
+  stats_words_to_sums(v, S, Q);
 #endif
+}
+
+// InstanceNorm sums -> mean and reciprocal standard deviation, and -> the scale / shift of the affine transform.  THE definition:
+// every kernel that normalises (or differentiates through the normalisation) derives them here, so all of them round alike.
+__device__ __forceinline__ void norm_mean_rstd(double S, double Q, double inv_count, float eps, double& mean, float& rstd) {
+  mean = S * inv_count;
+  double var = Q * inv_count - mean * mean;
+  var = var > 0 ? var : 0;
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+__device__ __forceinline__ void norm_scale_shift(double S, double Q, double inv_count, float eps, float gamma, float beta,
+                                                 float& scale, float& shift) {
+  double mean;
+  float rstd;
+  norm_mean_rstd(S, Q, inv_count, eps, mean, rstd);
+  scale = gamma * rstd;
+  shift = beta - (float)mean * scale;
 }
 
 // Preamble: the workgroup's waves compute scale/shift/add for channels [c_begin, C) into LDS arrays, 16 channels per wave
@@ -214,13 +267,11 @@ __device__ __forceinline__ void xform_preamble(const InXform& xf, int n, int C, 
     for (int u = 1; u < UN; ++u)
       if (part == u) { Sm = S[u]; Qm = Q[u]; gm = gam[u]; bm = bet[u]; am = add[u]; }
     const int c = c0 + part * nw * 16 + (lane & 15);
-    const double mean = Sm * xf.inv_count;
-    double var = Qm * xf.inv_count - mean * mean;
-    var = var > 0 ? var : 0;
-    const float g = gm * (float)(1.0 / sqrt(var + (double)xf.eps));
+    float g, b;
+    norm_scale_shift(Sm, Qm, xf.inv_count, xf.eps, gm, bm, g, b);
     if (c0 + part * nw * 16 < C && c < C) {
       sc[c] = g;
-      sh[c] = bm - (float)mean * g;
+      sh[c] = b;
       ad[c] = am;
     }
   }

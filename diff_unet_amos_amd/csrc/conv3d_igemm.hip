@@ -182,18 +182,13 @@ __global__ __launch_bounds__(256, BIG ? 1 : 2) void conv3d_k3_v2_kernel(Conv3Arg
   };
 #endif
 
-  // BIG: one kd plane (36 pieces of 1 KB: 9 per wave) straight into ring slot `slot`.  Inline assembly (M0 saved and restored
-  // inside the statement): hipcc neither counts these transfers nor waits for them; the loop below does (counted vmcnt,
-  // then the barrier, then the reads).
+  // BIG: one kd plane (36 pieces of 1 KB: 9 per wave) straight into ring slot `slot` (lds_dma_16, common.hpp): hipcc neither
+  // counts these transfers nor waits for them; the loop below does (counted vmcnt, then the barrier, then the reads).
   auto dma_unit = [&](int u, int slot) {
     const char* src = wsrc + (long)u * BSLAB + (wave * 9) * 1024 + lane * 16;
     const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(wbuf + slot * BSLAB + (wave * 9) * 1024);
 #pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(src + j * 1024), "s"(__builtin_amdgcn_readfirstlane(dst + j * 1024)) : "memory");
-    }
+    for (int j = 0; j < 9; ++j) lds_dma_16(src + j * 1024, dst + j * 1024);
   };
 
   // accumulators start at the bias of the lane's output channel (split-K adds it in the finish kernel instead)
@@ -516,7 +511,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_first_kernel(Conv3Args a, in
   DUA_STAMP_AT(0, true);
   DUA_STAMP_AT(2, false);
   // ---- once per workgroup: resident weights (k-groups 0 and 1 of every tap of the packed slabs) by LDS-DMA, 54 pieces of
-  // 1 KB = [64 couts][16 B], all in flight together (inline assembly as in the kd-plane form above: the explicit
+  // 1 KB = [64 couts][16 B], all in flight together (lds_dma_16 as in the kd-plane form above: the explicit
   // s_waitcnt before the first barrier covers them), and the image-tap block ----
   {
     const char* wsrc = (const char*)a.w + (long)ct * a.nchunks * 9 * c3v2::SLAB + lane * 16;
@@ -524,11 +519,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_first_kernel(Conv3Args a, in
 #pragma unroll
     for (int j = 0; j < 14; ++j) {
       const int s2 = wave + NW * j;                           // piece = (tap, k-half)
-      if (s2 < 54) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(wsrc + ((s2 >> 1) * KG + (s2 & 1)) * 1024), "s"(__builtin_amdgcn_readfirstlane(dst + s2 * 1024)) : "memory");
-      }
+      if (s2 < 54) lds_dma_16(wsrc + ((s2 >> 1) * KG + (s2 & 1)) * 1024, dst + s2 * 1024);
     }
   }
   f16x8 tb[2][2];                                             // image-tap weights: [k-step][cout half], this lane's B fragments

@@ -42,24 +42,17 @@ struct Args {
 
 }  // namespace wg
 
-// 16 bytes per lane from global memory straight into LDS: lane i of the wave lands at lds_wave_base + 16 i
-// Written as inline assembly on purpose: behind the builtin hipcc (ROCm 7.2) cannot tell which LDS bytes a pending transfer
-// will write and puts an s_waitcnt vmcnt(0) in front of the next LDS read -- the k loop would wait for the transfer it is
-// meant to run under.  The loop below waits for its transfers itself (s_waitcnt vmcnt(0) + barrier before a buffer is read).
+// 16 bytes per lane from global memory straight into LDS: lane i of the wave lands at lds_wave_base + 16 i (common.hpp
+// lds_dma_16: inline assembly, the loop below waits for its transfers itself -- s_waitcnt vmcnt(0) + barrier before a buffer
+// is read).  Nothing else in this kernel uses M0, so it is not saved and restored: that form (kept under -DDUA_GLDS_SAVE_M0,
+// and used by the conv kernel's weight ring) costs this kernel 1-4 % (646 vs 622 us on 96^3 64->64, same box).  M0 holds a
+// full LDS byte address; the second buffer of this kernel starts above 64 KB.
 __device__ __forceinline__ void wg_glds16(const void* g, void* lds_wave_base) {
   const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds_wave_base;
-  // M0 (the LDS base of the transfer) is compiler-reserved and not preserved around an asm statement, so it is written in
-  // the SAME statement that reads it (cdna_hip_programming.md 5.7).  Nothing else in this kernel uses M0 (no movrel, no
-  // LDS-DMA builtin, no sendmsg), so it is not saved and restored: that form (kept under -DDUA_GLDS_SAVE_M0, and used by the
-  // conv kernel's weight ring) costs this kernel 1-4 % (646 vs 622 us on 96^3 64->64, same box).  M0 holds a full LDS
-  // byte address; the second buffer of this kernel starts above 64 KB.
 #ifdef DUA_GLDS_SAVE_M0
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(base)) : "memory");
+  lds_dma_16(g, base);
 #else
-  // (s_nop 0: the one wait state the ReadM0 -> LDS-DMA hazard asks for; hipcc does not look inside an asm statement)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(__builtin_amdgcn_readfirstlane(base)) : "memory");
+  lds_dma_16_m0_unsaved(g, base);
 #endif
 }
 

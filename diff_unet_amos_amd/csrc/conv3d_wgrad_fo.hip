@@ -39,11 +39,6 @@ struct Args {
 };
 }  // namespace wf
 
-__device__ __forceinline__ void wf_glds16(const void* g, unsigned lds_wave_base) {
-  // M0 written in the statement that reads it (nothing else in this kernel uses M0); s_nop 0: the ReadM0 -> LDS-DMA wait state
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_wave_base)) : "memory");
-}
-
 __global__ __launch_bounds__(wf::NT) void conv3d_k3_wgrad_fo_kernel(wf::Args a) {
   using namespace wf;
   using T = f16;
@@ -106,6 +101,7 @@ __global__ __launch_bounds__(wf::NT) void conv3d_k3_wgrad_fo_kernel(wf::Args a) 
     advance();
     const T* xb = (const T*)a.x + n * vox * a.Cin_stride + a.Cin_off + cs * 32 + 8 * g4;
     const T* yb = (const T*)a.dy + n * vox * a.Cout_stride + a.Cout_off + ct * 64 + 8 * g4;
+    // (nothing else in this kernel uses M0: the pieces leave it unsaved)
 #pragma unroll
     for (int k = 0; k < NPD; ++k) {
       const int q = wave + NW * k;                               // wave-uniform
@@ -117,14 +113,14 @@ __global__ __launch_bounds__(wf::NT) void conv3d_k3_wgrad_fo_kernel(wf::Args a) 
         const bool ok = xchan && v < XV && (unsigned)gd < (unsigned)a.D && (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
         okbits |= ok ? 1u << k : 0u;
         const int off = ok ? ((gd * a.H + gh) * a.W + gw) * a.Cin_stride : 0;        // (a sample's voxels x stride < 2^31: launcher)
-        if (v < XV) wf_glds16(xb + off, lds0 + buf * BUFB + 16 * q * RSB);          // (the lanes behind the last x voxel move nothing)
+        if (v < XV) lds_dma_16_m0_unsaved(xb + off, lds0 + buf * BUFB + 16 * q * RSB);          // (the lanes behind the last x voxel move nothing)
       } else {
         const int qq = q - XP, h = qq / (TV / 16), b = qq % (TV / 16);
         const int v = 16 * b + vloc, gd = d0 + (v >> 6), gh = h0 + ((v >> 3) & 7), gw = w0 + (v & 7);
         const bool ok = ct * 64 + 32 * h + 8 * g4 < a.Cout && gd < a.D && gh < a.H && gw < a.W;
         okbits |= ok ? 1u << k : 0u;
         const int off = ok ? ((gd * a.H + gh) * a.W + gw) * a.Cout_stride + 32 * h : 0;
-        wf_glds16(yb + off, lds0 + buf * BUFB + XIMG + h * YIMG + 16 * b * RSB);
+        lds_dma_16_m0_unsaved(yb + off, lds0 + buf * BUFB + XIMG + h * YIMG + 16 * b * RSB);
       }
     }
     return okbits;

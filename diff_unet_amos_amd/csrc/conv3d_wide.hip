@@ -34,16 +34,93 @@ namespace dua {
 
 // tile and LDS constants: namespace c3w, conv3_form.hpp
 
-// one 1 KB piece global -> LDS (64 lanes x 16 B, LDS address = M0 base + lane * 16); M0 saved / restored in the statement
-__device__ __forceinline__ void dma_piece(const char* src_lane, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src_lane), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
 #ifndef WIDE_LA
 #define WIDE_LA 1         // half-steps of A fragments in flight ahead of the MFMAs of the K loop
 #endif
+// ---- the pieces of the wide tile: one definition each, used by wide_tile (the shipped kernels) and by the persistent kernel ----
+// weights: kd plane `kd` of half chunk `hc` -> ring slot (18 pieces of 1 KB; wave w takes pieces w, w + 4, ...); wsrc = this
+// lane's 16 bytes of the cout tile's slabs, wlds = the ring's LDS address
+__device__ __forceinline__ void wide_dma_plane(const char* wsrc, const unsigned wlds, const int wave, const int hc, const int kd, const int slot) {
+  using namespace c3w;
+  const char* src = wsrc + (long)((hc >> 1) * 3 + kd) * 3 * SLAB + (hc & 1) * 2048;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int p = wave + 4 * j;                              // piece = (tap p >> 1, k-group p & 1)
+    if (p < 18) lds_dma_16(src + ((p >> 1) * 4 + (p & 1)) * 1024, wlds + slot * WPLANE + p * 1024);
+  }
+}
+// One phase = the 9 taps of a kd plane of the current half chunk (hp = its first halo plane) against a ring slot (wb = this
+// lane's B fragments in it): half-step h = (tap t = h / NH, block pair sub = h % NH) is 4 MFMAs on A pair (t, sub) and B pair t;
+// the fragments of half-step h + LA are requested before the MFMAs of half-step h issue.  mma(m, q, a, b): the MFMA into the
+// accumulator of block m, cout half q -- a plain array element or a tuple held by name.
+template <int NH, int LA, class MMA>
+__device__ __forceinline__ void wide_phase(const char* hp, const char* wb, const int a_even, const int a_odd, MMA mma) {
+  using namespace c3w;
+  f16x8 fa[LA + 1][2], fb[2][2];                                 // [buffer][block of the pair] / [buffer][cout half]
+  auto ldA = [&](int t, int sub, int b) {
+    const int kh = t / 3, kw = t - kh * 3;
+    const char* ap = hp + ((kh & 1) ? a_odd : a_even) + sub * PSF + kh * RSF + kw * VSF;
+    fa[b][0] = *(const f16x8*)ap;
+    fa[b][1] = *(const f16x8*)(ap + 4 * RSF);
+  };
+  auto ldB = [&](int t, int b) {
+    fb[b][0] = *(const f16x8*)(wb + t * 2048);
+    fb[b][1] = *(const f16x8*)(wb + t * 2048 + 512);
+  };
+  ldB(0, 0);
+#pragma unroll
+  for (int h = 0; h < LA; ++h) ldA(h / NH, h % NH, h);
+#pragma unroll
+  for (int h = 0; h < 9 * NH; ++h) {
+    const int t = h / NH, sub = h % NH;
+    if (h + LA < 9 * NH) {
+      const int t1 = (h + LA) / NH, sub1 = (h + LA) % NH;
+      if (LA == 1 && sub1 == 0) ldB(t1, t1 & 1);
+      ldA(t1, sub1, (h + LA) % (LA + 1));
+    }
+    if (LA > 1 && sub == 0 && t + 1 < 9) ldB(t + 1, (t + 1) & 1);
+    __builtin_amdgcn_sched_barrier(0);                           // keep the requests ahead of the MFMAs (hipcc sinks them otherwise)
+    mma(2 * sub, 0, fa[h % (LA + 1)][0], fb[t & 1][0]);
+    mma(2 * sub, 1, fa[h % (LA + 1)][0], fb[t & 1][1]);
+    mma(2 * sub + 1, 0, fa[h % (LA + 1)][1], fb[t & 1][0]);
+    mma(2 * sub + 1, 1, fa[h % (LA + 1)][1], fb[t & 1][1]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// epilogue staging: the 16 accumulator values v[i] of (block mm of the pair, cout half q) into the wave's rows `ot`, with the
+// InstanceNorm sums of the fp32 values
+template <class V>
+__device__ __forceinline__ void wide_stage16(char* ot, const int mm, const int q, const int r, const int hh, const V& acc16, float& s, float& ss) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float v = acc16[i];
+    s += v;
+    ss = fmaf(v, v, ss);
+    *(f16*)(ot + mm * 4096 + acc_row(i, hh) * 128 + (q * 32 + r) * 2) = (f16)v;
+  }
+}
+__device__ __forceinline__ void wide_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// ... and the two staged 32-voxel blocks = depth slice gd of the tile at (h0, w0) leave as whole voxel rows: a lane stores 8
+// channels of voxel v = 0..63 of the 8 x 8 slice
+__device__ __forceinline__ void wide_store_rows(const Conv3Args& a, f16* yout, const char* ot, const int gd, const int h0, const int w0,
+                                                const int ct, const int lane, const long nvox) {
+  using namespace c3w;
+  wide_wave_sync();
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int v = it * 8 + (lane >> 3), cg = lane & 7;
+    const int gh = h0 + (v >> 3), gw = w0 + (v & 7);
+    if (ct * BN + cg * 8 < a.Cout)
+      *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
+          *(const f16x8*)(ot + v * 128 + cg * 16);
+  }
+  wide_wave_sync();
+}
+
 // MB = 32-voxel blocks per wave: 4 (8x8x8 tile, wave = depth slices 2w and 2w+1) or 2 (4x8x8 tile, wave = depth slice w)
 template <int MB, bool BWD = false>
 __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const int d0, const int h0, const int w0,
@@ -112,17 +189,11 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
     }
   };
 
-  // ---- weights: kd plane `kd` of half chunk `hc` -> ring slot (18 pieces of 1 KB; wave w takes pieces w, w + 4, ...) ----
   const char* wsrc = (const char*)a.w + (long)ct * a.nchunks * 9 * SLAB + lane * 16;
   const unsigned wlds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)wbuf;
   auto dma_plane = [&](int u, int slot) {
     const int hc = u / 3, kd = u - hc * 3;
-    const char* src = wsrc + (long)((hc >> 1) * 3 + kd) * 3 * SLAB + (hc & 1) * 2048;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int p = wave + 4 * j;                              // piece = (tap p >> 1, k-group p & 1)
-      if (p < 18) dma_piece(src + ((p >> 1) * 4 + (p & 1)) * 1024, wlds + slot * WPLANE + p * 1024);
-    }
+    wide_dma_plane(wsrc, wlds, wave, hc, kd, slot);
   };
 
   // ---- prologue.  Everything that must come from memory is requested before anything waits, oldest first in the order it
@@ -135,7 +206,7 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
     const int bc = ct * BN + q * 32 + r;
     bias_q[q] = bc >= a.Cout ? 0.f : a.bias[bc];
   }
-  // scale / shift / add tables of the fused input transform: the arithmetic of xform_preamble (common.hpp) with its loads
+  // scale / shift / add tables of the fused input transform: xform_preamble (common.hpp: the same helpers) with its loads
   // split off, 16 channels per (wave, group u), up to UN groups per wave = 256 channels
   constexpr int UN = 4;
   stat_t sv[UN][2 * STAT_WORDS];
@@ -188,30 +259,27 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
         w[k] += __shfl_xor(w[k], 32);
       }
       if (part == u) {                     // the 16-lane part u finishes group u: one reciprocal square root per lane
-        Sm = (double)w[0] + (double)w[1] * (1.0 / STAT_FRAC);
-        Qm = (double)w[2] + (double)w[3] * (1.0 / STAT_FRAC);
+        stats_words_value(w, Sm, Qm);
         gm = gam[u]; bm = bet[u]; am = addv[u];
       }
     }
     const int c = (wave + 4 * part) * 16 + (lane & 15);
-    const double mean = Sm * a.xf.inv_count;
-    double var = Qm * a.xf.inv_count - mean * mean;
-    var = var > 0 ? var : 0;
-    const float g = gm * (float)(1.0 / sqrt(var + (double)a.xf.eps));
+    float g, b;
+    norm_scale_shift(Sm, Qm, a.xf.inv_count, a.xf.eps, gm, bm, g, b);
     if (c < a.Cin) {
       xsc[c] = g;
-      xsh[c] = bm - (float)mean * g;
+      xsh[c] = b;
       xad[c] = am;
     }
     __syncthreads();
   }
   if (bwd && lane < 16) {
-    const double mean = bwS * a.bw_xf.inv_count;
-    double var = bwQ * a.bw_xf.inv_count - mean * mean;
-    var = var > 0 ? var : 0;
+    double mean;
+    float rstd;
+    norm_mean_rstd(bwS, bwQ, a.bw_xf.inv_count, a.bw_xf.eps, mean, rstd);
     const int cl = wave * 16 + lane;
     bwc[cl] = (float)mean;
-    bwc[64 + cl] = (float)(1.0 / sqrt(var + (double)a.bw_xf.eps));
+    bwc[64 + cl] = rstd;
     bwc[128 + cl] = bwg;
     bwc[192 + cl] = bwb;
   }
@@ -237,42 +305,9 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
   const int a_even = a_base + ((hh ^ sw) << 4), a_odd = a_base + ((hh ^ sw ^ 1) << 4);      // parity of halo row h + kh
   const int b_base = (hh * BN + r) * 16;
 
-  // One phase = the 9 taps of kd plane `kd` of the current half chunk against ring slot `slot`: half-step h = (tap t = h / NH,
-  // block pair sub = h % NH) is 4 MFMAs on A pair (t, sub) and B pair t; the fragments of half-step h + 1 are requested
-  // before the MFMAs of half-step h issue.
   auto phase = [&](int kd, int slot) __attribute__((always_inline)) {
-    const char* hp = halo + kd * PSF;
-    const char* wb = wbuf + slot * WPLANE + b_base;
-    f16x8 fa[WIDE_LA + 1][2], fb[2][2];                          // [buffer][block of the pair] / [buffer][cout half]
-    auto ldA = [&](int t, int sub, int b) {
-      const int kh = t / 3, kw = t - kh * 3;
-      const char* ap = hp + ((kh & 1) ? a_odd : a_even) + sub * PSF + kh * RSF + kw * VSF;
-      fa[b][0] = *(const f16x8*)ap;
-      fa[b][1] = *(const f16x8*)(ap + 4 * RSF);
-    };
-    auto ldB = [&](int t, int b) {
-      fb[b][0] = *(const f16x8*)(wb + t * 2048);
-      fb[b][1] = *(const f16x8*)(wb + t * 2048 + 512);
-    };
-    ldB(0, 0);
-#pragma unroll
-    for (int h = 0; h < WIDE_LA; ++h) ldA(h / NH, h % NH, h);
-#pragma unroll
-    for (int h = 0; h < 9 * NH; ++h) {
-      const int t = h / NH, sub = h % NH;
-      if (h + WIDE_LA < 9 * NH) {
-        const int t1 = (h + WIDE_LA) / NH, sub1 = (h + WIDE_LA) % NH;
-        if (WIDE_LA == 1 && sub1 == 0) ldB(t1, t1 & 1);
-        ldA(t1, sub1, (h + WIDE_LA) % (WIDE_LA + 1));
-      }
-      if (WIDE_LA > 1 && sub == 0 && t + 1 < 9) ldB(t + 1, (t + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);                         // keep the requests ahead of the MFMAs (hipcc sinks them otherwise)
-      mma32(acc[2 * sub][0], fa[h % (WIDE_LA + 1)][0], fb[t & 1][0]);
-      mma32(acc[2 * sub][1], fa[h % (WIDE_LA + 1)][0], fb[t & 1][1]);
-      mma32(acc[2 * sub + 1][0], fa[h % (WIDE_LA + 1)][1], fb[t & 1][0]);
-      mma32(acc[2 * sub + 1][1], fa[h % (WIDE_LA + 1)][1], fb[t & 1][1]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    wide_phase<NH, WIDE_LA>(halo + kd * PSF, wbuf + slot * WPLANE + b_base, a_even, a_odd,
+                            [&](int m, int q, const f16x8& fa, const f16x8& fb) __attribute__((always_inline)) { mma32(acc[m][q], fa, fb); });
   };
 
   // The next half chunk's halo pieces (each touches 32 cache lines: ten back-to-back requests hold the wave for ~3 000 cycles)
@@ -343,9 +378,7 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             *(T*)(ot + mm * 4096 + acc_row(i, hh) * 128 + (q * 32 + r) * 2) = (T)acc[2 * pr + mm][q][i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wide_wave_sync();
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
         const int v = it * 8 + (lane >> 3);
@@ -363,9 +396,7 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
           }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wide_wave_sync();
     }
     // lanes with the same channel group (8 apart), then the four waves in a fixed order, then one double atomic per (sum, channel)
 #pragma unroll
@@ -402,29 +433,9 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float v = acc[2 * pr + mm][q][i];
-          s[q] += v;
-          ss[q] = fmaf(v, v, ss[q]);
-          *(T*)(ot + mm * 4096 + acc_row(i, hh) * 128 + (q * 32 + r) * 2) = (T)v;
-        }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int gd = d0 + dsl + pr;                                // blocks 2 pr and 2 pr + 1: depth slice dsl + pr, h rows 0..3 and 4..7
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int v = it * 8 + (lane >> 3), cg = lane & 7;         // v = 0..63: the 8 x 8 voxels of the depth slice
-      const int gh = h0 + (v >> 3), gw = w0 + (v & 7);
-      if (ct * BN + cg * 8 < a.Cout)
-        *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
-            *(const f16x8*)(ot + v * 128 + cg * 16);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int q = 0; q < 2; ++q) wide_stage16(ot, mm, q, r, hh, acc[2 * pr + mm][q], s[q], ss[q]);
+    // blocks 2 pr and 2 pr + 1: depth slice dsl + pr, h rows 0..3 and 4..7
+    wide_store_rows(a, yout, ot, d0 + dsl + pr, h0, w0, ct, lane, nvox);
   }
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -446,20 +457,18 @@ __device__ __forceinline__ void wide_tile(const Conv3Args& a, char* smem, const 
 // grid = (8x8x8 tiles in XCD-contiguous order, cout tiles, N)
 __global__ __launch_bounds__(256, 2) void conv3d_k3_wide_kernel(Conv3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int per_slab = a.tiles_h * a.tiles_w;
-  const int tile = xcd_remap(blockIdx.x, a.ntiles);
-  const int td = tile / per_slab, rem = tile - td * per_slab, th = rem / a.tiles_w, tw = rem - th * a.tiles_w;
-  wide_tile<4>(a, smem, td * 8, th * 8, tw * 8, blockIdx.y, blockIdx.z, blockIdx.x & (STAT_REPLICAS - 1));
+  int d0, h0, w0;
+  wide_tile_origin(blockIdx.x, a.ntiles, a.tiles_h, a.tiles_w, d0, h0, w0);
+  wide_tile<4>(a, smem, d0, h0, w0, blockIdx.y, blockIdx.z, blockIdx.x & (STAT_REPLICAS - 1));
 }
 
 
 // the data-gradient launches of training whose output is another layer's dA (Conv3Args::bw_sums): backward-sums epilogue
 __global__ __launch_bounds__(256, 2) void conv3d_k3_wide_bwd_kernel(Conv3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int per_slab = a.tiles_h * a.tiles_w;
-  const int tile = xcd_remap(blockIdx.x, a.ntiles);
-  const int td = tile / per_slab, rem = tile - td * per_slab, th = rem / a.tiles_w, tw = rem - th * a.tiles_w;
-  wide_tile<4, true>(a, smem, td * 8, th * 8, tw * 8, blockIdx.y, blockIdx.z, blockIdx.x & (STAT_REPLICAS - 1));
+  int d0, h0, w0;
+  wide_tile_origin(blockIdx.x, a.ntiles, a.tiles_h, a.tiles_w, d0, h0, w0);
+  wide_tile<4, true>(a, smem, d0, h0, w0, blockIdx.y, blockIdx.z, blockIdx.x & (STAT_REPLICAS - 1));
 }
 
 // ---- round 5: the same tile with PERSISTENT workgroups and the accumulators in v[128:255] by name (named_acc.hpp) ----
@@ -488,7 +497,6 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
   const int ct = blockIdx.y, n = blockIdx.z, replica = blockIdx.x & (STAT_REPLICAS - 1);
   const bool fused = a.xf.stats != nullptr;
   const int nhc = (a.Cin + 15) >> 4;
-  const int per_slab = a.tiles_h * a.tiles_w;
 
   // ---- halo pieces of this thread (see wide_tile): position (hy, hx) x half p, piece j = halo plane j ----
   const int p_t = tid & 1, pos = tid >> 1;
@@ -504,9 +512,7 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
   struct Geo { int d0, h0, w0, voff; bool ok_hw; };
   auto geo_of = [&](int t) {
     Geo g;
-    const int tile = xcd_remap(t, a.ntiles);
-    const int td = tile / per_slab, rem = tile - td * per_slab, th = rem / a.tiles_w, tw = rem - th * a.tiles_w;
-    g.d0 = td * 8; g.h0 = th * 8; g.w0 = tw * 8;
+    wide_tile_origin(t, a.ntiles, a.tiles_h, a.tiles_w, g.d0, g.h0, g.w0);
     const int gh = g.h0 + hy - 1, gw = g.w0 + hx - 1;
     g.ok_hw = pos < HH * HW && (unsigned)gh < (unsigned)a.H && (unsigned)gw < (unsigned)a.W;
     g.voff = g.ok_hw ? (((g.d0 - 1) * a.H + gh) * a.W + gw) * vstride : 0;
@@ -544,14 +550,7 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
 
   const char* wsrc = (const char*)a.w + (long)ct * a.nchunks * 9 * SLAB + lane * 16;
   const unsigned wlds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)wbuf;
-  auto dma_plane = [&](int hc, int kd, int slot) {
-    const char* src = wsrc + (long)((hc >> 1) * 3 + kd) * 3 * SLAB + (hc & 1) * 2048;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int p = wave + 4 * j;
-      if (p < 18) dma_piece(src + ((p >> 1) * 4 + (p & 1)) * 1024, wlds + slot * WPLANE + p * 1024);
-    }
-  };
+  auto dma_plane = [&](int hc, int kd, int slot) { wide_dma_plane(wsrc, wlds, wave, hc, kd, slot); };
 
   // ---- once per workgroup: bias, statistics -> tables, first tile's halo and first weight plane ----
   float bias_q[2];
@@ -574,36 +573,8 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
   const int b_base = (hh * BN + r) * 16;
 
   auto phase = [&](int kd, int sl) __attribute__((always_inline)) {
-    const char* hp = halo + kd * PSF;
-    const char* wb = wbuf + sl * WPLANE + b_base;
-    f16x8 fa[2][2], fb[2][2];
-    auto ldA = [&](int tp, int sub, int b) {
-      const int kh = tp / 3, kw = tp - kh * 3;
-      const char* ap = hp + ((kh & 1) ? a_odd : a_even) + sub * PSF + kh * RSF + kw * VSF;
-      fa[b][0] = *(const f16x8*)ap;
-      fa[b][1] = *(const f16x8*)(ap + 4 * RSF);
-    };
-    auto ldB = [&](int tp, int b) {
-      fb[b][0] = *(const f16x8*)(wb + tp * 2048);
-      fb[b][1] = *(const f16x8*)(wb + tp * 2048 + 512);
-    };
-    ldB(0, 0);
-    ldA(0, 0, 0);
-#pragma unroll
-    for (int h = 0; h < 18; ++h) {
-      const int tp = h >> 1, sub = h & 1;
-      if (h + 1 < 18) {
-        const int t1 = (h + 1) >> 1, sub1 = (h + 1) & 1;
-        if (sub1 == 0) ldB(t1, t1 & 1);
-        ldA(t1, sub1, (h + 1) & 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      named_mfma_sel(4 * sub + 0, fa[h & 1][0], fb[tp & 1][0]);          // tuple (2 sub + mm) * 2 + q
-      named_mfma_sel(4 * sub + 1, fa[h & 1][0], fb[tp & 1][1]);
-      named_mfma_sel(4 * sub + 2, fa[h & 1][1], fb[tp & 1][0]);
-      named_mfma_sel(4 * sub + 3, fa[h & 1][1], fb[tp & 1][1]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    wide_phase<2, 1>(halo + kd * PSF, wbuf + sl * WPLANE + b_base, a_even, a_odd,
+                     [&](int m, int q, const f16x8& fa, const f16x8& fb) __attribute__((always_inline)) { named_mfma_sel(m * 2 + q, fa, fb); });
   };
 
   const long nvox = (long)a.D * a.H * a.W;
@@ -679,31 +650,11 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void conv3d_k3_wide_pt
           for (int q = 0; q < 2; ++q) {
             float av[16];
             named_read16_sel((2 * pr + mm) * 2 + q, av);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              const float v = av[i];
-              s[q] += v;
-              ss[q] = fmaf(v, v, ss[q]);
-              *(T*)(ot + mm * 4096 + acc_row(i, hh) * 128 + (q * 32 + r) * 2) = (T)v;
-            }
+            wide_stage16(ot, mm, q, r, hh, av, s[q], ss[q]);
             asm volatile("" : "+v"(s[q]), "+v"(ss[q]));          // keeps the sum chain here (hipcc sinks it behind the stores)
             __builtin_amdgcn_sched_barrier(0);
           }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int gd = cur.d0 + 2 * wave + pr;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int v = it * 8 + (lane >> 3), cg = lane & 7;
-          const int gh = cur.h0 + (v >> 3), gw = cur.w0 + (v & 7);
-          if (ct * BN + cg * 8 < a.Cout)
-            *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
-                *(const f16x8*)(ot + v * 128 + cg * 16);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wide_store_rows(a, yout, ot, cur.d0 + 2 * wave + pr, cur.h0, cur.w0, ct, lane, nvox);
       }
 #pragma unroll
       for (int q = 0; q < 2; ++q) { Sacc[q] += (double)s[q]; Qacc[q] += (double)ss[q]; }

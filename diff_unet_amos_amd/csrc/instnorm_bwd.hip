@@ -23,12 +23,12 @@ __device__ __forceinline__ void norm_preamble(const InXform& xf, int n, int C, f
     const float gam = xf.gamma[cc], bet = xf.beta[cc];
     double S, Q;
     stats_read_wave16(xf.stats, n, xf.c_pad, cc, S, Q);
-    const double mean = S * xf.inv_count;
-    double var = Q * xf.inv_count - mean * mean;
-    var = var > 0 ? var : 0;
     if (ok && lane < 16) {
+      double mean;
+      float rstd;
+      norm_mean_rstd(S, Q, xf.inv_count, xf.eps, mean, rstd);
       mu[c] = (float)mean;
-      rs[c] = (float)(1.0 / sqrt(var + (double)xf.eps));
+      rs[c] = rstd;
       ga[c] = gam;
       be[c] = bet;
     }

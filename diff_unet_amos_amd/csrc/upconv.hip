@@ -51,12 +51,6 @@ struct UpConvArgs {
   int nchunks, ntiles, tiles_h, tiles_w;
 };
 
-__device__ __forceinline__ void upc_dma_piece(const char* src_lane, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src_lane), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
-}
-
 // GG = groups of 64 coarse channels (1 or 2): compile-time, so that the registers of a second group's prefetch and of the
 // statistics words of channels that do not exist are not allocated
 #ifndef UPC_LA
@@ -74,10 +68,9 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void upconv_k3_kernel(
   float* xad = xsh + a.Cu;
   float* ex = xad + a.Cu;                                      // [4 waves][64 couts][2]
 
-  const int per_slab = a.tiles_h * a.tiles_w;
-  const int tile = xcd_remap(blockIdx.x, a.ntiles);
-  const int td = tile / per_slab, rem = tile - td * per_slab, th = rem / a.tiles_w, tw = rem - th * a.tiles_w;
-  const int d0 = td * 8, h0 = th * 8, w0 = tw * 8, ct = blockIdx.y, n = blockIdx.z, replica = blockIdx.x & (STAT_REPLICAS - 1);
+  int d0, h0, w0;
+  wide_tile_origin(blockIdx.x, a.ntiles, a.tiles_h, a.tiles_w, d0, h0, w0);
+  const int ct = blockIdx.y, n = blockIdx.z, replica = blockIdx.x & (STAT_REPLICAS - 1);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, hh = lane >> 5;
   const int pd = wave >> 1, ph = wave & 1;
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void upconv_k3_kernel(
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
       const int p = wave + 4 * j;                              // piece = (tap p >> 1, k-group p & 1)
-      if (p < 18) upc_dma_piece(src + ((p >> 1) * 4 + (p & 1)) * 1024 + wlane, wlds + slot * WPLANE + p * 1024);
+      if (p < 18) lds_dma_16(src + ((p >> 1) * 4 + (p & 1)) * 1024 + wlane, wlds + slot * WPLANE + p * 1024);
     }
   };
 
@@ -239,16 +232,15 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void upconv_k3_kernel(
         w[k] += __shfl_xor(w[k], 32);
       }
       if (pr == u) {
-        Sm = (double)w[0] + (double)w[1] * (1.0 / STAT_FRAC);
-        Qm = (double)w[2] + (double)w[3] * (1.0 / STAT_FRAC);
+        stats_words_value(w, Sm, Qm);
         gm = gam[u]; bm = bet[u]; am = addv[u];
       }
     }
     const int c = (wave + 4 * pr) * 16 + (lane & 15);
-    const double mean = Sm * a.xf.inv_count;
-    double var = Qm * a.xf.inv_count - mean * mean;
-    var = var > 0 ? var : 0;
-    const float g = gm * (float)(1.0 / sqrt(var + (double)a.xf.eps));
+    double mean;
+    float rstd;
+    norm_mean_rstd(Sm, Qm, a.xf.inv_count, a.xf.eps, mean, rstd);
+    const float g = gm * rstd;
     if (c < a.Cu) {
       xsc[c] = g;
       xsh[c] = bm - (float)mean * g;
