@@ -20,6 +20,7 @@ import torch
 
 from . import _native as nv
 from . import ops
+from .sampler_driver import LazyEmbeddings, SamplerDriver
 
 SLOPE = 0.1          # LeakyReLU(0.1): models/diff_unet.py:34-35, pretrained/basic_unet.py:429
 EPS = 1e-5           # nn.InstanceNorm3d default
@@ -29,25 +30,11 @@ class _Conv:
     """One Convolution block (Conv3d + InstanceNorm affine) bound to its buffers."""
 
 
-class EmbeddingList(list):
-    """What embed_model(image) returns: indexable like the reference's list of 5 NCDHW tensors
-    (converted on first access), while the denoiser uses the channels-last device buffers."""
+class EmbeddingList(LazyEmbeddings):
+    """The reference's list of 5 NCDHW tensors."""
 
-    def __init__(self, plan, token):
-        super().__init__([None] * 5)
-        self.plan, self.token = plan, token
-
-    def __getitem__(self, i):
-        v = super().__getitem__(i)
-        if v is None:
-            p = self.plan
-            assert p.emb_token == self.token, "embeddings were overwritten by a later encoder pass"
-            v = ops.from_channels_last(p.emb[i], p.f[i])
-            super().__setitem__(i, v)
-        return v
-
-    def __iter__(self):
-        return (self[i] for i in range(5))
+    def _convert(self, i):
+        return ops.from_channels_last(self.plan.emb[i], self.plan.f[i])
 
 
 def level_geometry(D, H, W):
@@ -64,7 +51,7 @@ def level_geometry(D, H, W):
     return S, pad
 
 
-class Plan:
+class Plan(SamplerDriver):
     """Buffers + launch sequences for one (N, D, H, W, dtype).  Any extent >= 32 (odd ones included: level_geometry)."""
 
     def __init__(self, net, N, D, H, W, dtype, device):
@@ -111,21 +98,11 @@ class Plan:
         self.dec_out = dec_out
         # InstanceNorm sums of every conv layer live in ONE arena of fixed-point words, zeroed by a single memset per pass
         self._stat_slices = []
-        # sampler state
-        self.x_state = torch.zeros((N, *S[0], self.cx), dtype=torch.float32, device=device)
-        self.x_sum = torch.zeros((N, *S[0], self.cx), dtype=torch.float32, device=device)
-        self.cur_coef = torch.zeros((N, 8), dtype=torch.float32, device=device)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=device)
-        self.step_word = torch.zeros(1, dtype=torch.int32, device=device)
-        self.err_word = torch.zeros(1, dtype=torch.int32, device=device)     # set by step_begin on an out-of-range index
-        self.seed_word = torch.zeros(1, dtype=torch.int64, device=device)    # Philox key of the current sampling call
-        self.calls = 0
+        self._alloc_sampler_state(N, S[0], self.cx, device)
         self.logits = torch.zeros((N, self.C, *S[0]), dtype=torch.float32, device=device)
         self._bind()
         self._alloc_stats()
         self.weights_version = None
-        self.graphs = {}
-        self.tables = {}
 
     # ---- parameter binding -------------------------------------------------------------------
     def _mk(self, name, block, cin_packed=None, perm=None, tap=None):
@@ -418,30 +395,13 @@ class Plan:
         return self.dec[0][1]
 
     def tail(self, mode, noise=None, logits=None, xstart=None, use_sum=False):
-        """The Philox key of in-kernel noise is read from self.seed_word at run time (see new_seed)."""
+        """The Philox key of in-kernel noise is read from self.seed_word at run time (see SamplerDriver.new_seed)."""
         last = self.dec[0][1]
         ops.final_conv_sampler(self.uB[0], last.cout, self._norm(last, 0), self.wf, self.bf, self.C, mode,
                                coef=self.cur_coef, x_state=self.x_state, noise=noise, step_word=self.step_word,
                                xin=self.xin if mode != nv.MODE_LOGITS else None,
                                xstart_sum=self.x_sum if use_sum else None, logits=logits, xstart=xstart,
                                seed_dev=self.seed_word)
-
-    def new_seed(self, seed=None):
-        """Key of this call's in-kernel noise.  The reference draws a fresh th.randn_like every step of every call
-        (gaussian_diffusion.py:430,576); the counter-based generator needs a fresh KEY per call for the same effect:
-        one draw from torch's CPU generator (so torch.manual_seed governs it), mixed with the rank so that replicas
-        do not share a noise field.  The key lives in a device word, not in the captured graph."""
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            try:
-                import torch.distributed as dist
-                if dist.is_available() and dist.is_initialized():
-                    seed ^= (dist.get_rank() + 1) * 0x9E3779B97F4A7C15 & (2 ** 62 - 1)
-            except Exception:       # pragma: no cover - torch.distributed not built
-                pass
-        self.calls += 1
-        self.seed_word.fill_(int(seed) & (2 ** 63 - 1))
-        return seed
 
     # ---- the evaluation as one C-ABI call -------------------------------------------------------------------
     def native_step(self, mode, rows_per_sample=None, row_of_step=None, coef_table=None, noise=None, logits=None,
@@ -488,114 +448,26 @@ class Plan:
         self._step_keep = (p, noise, logits, xstart, rows_per_sample, row_of_step, coef_table)
         ops.denoiser_step(p)
 
-    # ---- public operations ------------------------------------------------------------------------
-    def denoise(self, x, t):
-        """logits = model(x, t, image, embeddings) for already-encoded image (denoiser.py:284-312)."""
-        self.refresh_weights()
-        N = self.N
-        assert tuple(x.shape) == (N, self.C, *self.dims) and t.numel() == N
-        ops.to_channels_last(x.detach().float().contiguous(), self.xin, 0, self.C)
-        T = self.temb_table.shape[0]
-        on_host = not t.is_cuda
-        if on_host and not bool(((t >= 0) & (t < T)).all()):
-            raise ValueError(f"timestep out of range: the model was built for 0 <= t < {T}, got {t.tolist()}")
-        rows = t.detach().to(device=self.dev, dtype=torch.int32).contiguous()
-        if not on_host:
-            self.err_word.zero_()
-        out = torch.empty((N, self.C, *self.dims), dtype=torch.float32, device=self.dev)
+    # ---- hooks of the shared sampler (sampler_driver.SamplerDriver) -----------------------------------------
+    def _evaluate(self, rows, out):
         self.native_step(nv.MODE_LOGITS, rows_per_sample=rows, logits=out)
-        if not on_host and int(self.err_word.item()):     # device-resident t: the kernel clamped it, say so
-            raise ValueError(f"timestep out of range: the model was built for 0 <= t < {T}")
-        return out
 
-    def sample_loop(self, diffusion, kind, noise=None, step_noise=None, eta=0.0, use_graph=True, seed=None,
-                    want_final_xstart=False, snapshots=None, want_sum=None):
-        """T reverse steps (T = diffusion.num_timesteps) starting from ``noise`` (x_T, NCDHW) or a fresh
-        draw.  ``step_noise``: optional list of per-step NCDHW draws (parity runs); otherwise the
-        tail kernel generates eps in-kernel (Philox, keyed per call: ``seed`` or a draw from torch's generator).
-        ``snapshots``: optional dict {step count k: None}; after k steps the state x is stored there (NCDHW copy;
-        eager mode) -- drift-versus-step measurements.  ``want_sum``: accumulate the sum of the per-step x0 predictions (what
-        models/diffusion/diffusion.py:94-98 sums from ``all_samples``); default: DDIM loops only -- the reference's p_sample_loop
-        (gaussian_diffusion.py:441-485) returns the final sample alone, and the sum is 113 MB of HBM traffic per step at 96^3 x 16.
-        Returns dict(sample, sum_pred_xstart (None without the sum))."""
-        want_sum = (kind == "ddim") if want_sum is None else bool(want_sum)
-        self.refresh_weights()
-        N, T = self.N, diffusion.num_timesteps
-        shape = (N, self.C, *self.dims)
-        if noise is None:
-            noise = torch.randn(*shape, device=self.dev)
-        assert tuple(noise.shape) == shape
-        x_T = noise.detach().float().contiguous()
-        ops.to_channels_last(x_T, self.x_state, 0, self.cx)
-        ops.to_channels_last(x_T, self.xin, 0, self.C)
-        self.x_sum.zero_()
-        mode = nv.MODE_DDPM if kind == "ddpm" else nv.MODE_DDIM
-        tkey = (diffusion, kind, float(eta))          # the object itself: the table keeps it alive, no id() reuse after GC
-        gkey = tkey + (want_sum,)
-        if tkey not in self.tables:
-            order = list(range(T))[::-1]
-            tt = torch.tensor(order)
-            coef = diffusion.ddpm_coef(tt) if kind == "ddpm" else diffusion.ddim_coef(tt, eta)
-            tmap = diffusion.model_timesteps()
-            self.tables[tkey] = (coef.to(self.dev).contiguous(),
-                                 torch.tensor([tmap[i] for i in order], dtype=torch.int32, device=self.dev))
-        coef_table, row_of_step = self.tables[tkey]
-        self.counter.zero_()
-        self.new_seed(seed)
-        if step_noise is not None:
-            assert len(step_noise) == T
-            use_graph = False
-        if snapshots:
-            use_graph = False
+    def _one_step(self, mode, row_of_step, coef_table, eps, want_sum):
+        self.native_step(mode, row_of_step=row_of_step, coef_table=coef_table, noise=eps, use_sum=want_sum)
 
-        def one_step(eps):
-            self.native_step(mode, row_of_step=row_of_step, coef_table=coef_table, noise=eps, use_sum=want_sum)
+    def _finish_count(self, kind, T):
+        """DDPM in an fp16 plan: the LAST steps run on the exact-fp32 path (see finish_fp32_steps in __init__)"""
+        return min(T, self.finish_fp32_steps) if (kind == "ddpm" and self.dtype == torch.float16) else 0
 
-        # DDPM in an fp16 plan: the LAST steps run on the exact-fp32 path (see finish_fp32_steps in __init__)
-        finish = min(T, self.finish_fp32_steps) if (kind == "ddpm" and self.dtype == torch.float16) else 0
-        lo_steps = T - finish
-
-        def finish_hi(first_step):
-            """steps [first_step, T) on the companion fp32 plan: hand the sampler state over, run, hand it back"""
-            hi = self._hi_plan()
-            hi.x_state.copy_(self.x_state)
-            hi.xin[..., :self.C].copy_(self.x_state.view(N, *self.dims, self.cx)[..., :self.C])
-            hi.x_sum.copy_(self.x_sum)
-            hi.counter.copy_(self.counter)
-            hi.seed_word.copy_(self.seed_word)
-            for k in range(first_step, T):
-                eps = None if step_noise is None else step_noise[k].detach().to(self.dev).float().contiguous()
-                hi.native_step(mode, row_of_step=row_of_step, coef_table=coef_table, noise=eps, use_sum=want_sum)
-                if snapshots and (k + 1) in snapshots:
-                    snapshots[k + 1] = ops.from_channels_last(hi.x_state, self.C)
-            self.x_state.copy_(hi.x_state)
-            self.x_sum.copy_(hi.x_sum)
-            self.counter.copy_(hi.counter)
-
-        if not use_graph:
-            for k in range(lo_steps):
-                one_step(None if step_noise is None else step_noise[k].detach().to(self.dev).float().contiguous())
-                if snapshots and (k + 1) in snapshots:
-                    snapshots[k + 1] = ops.from_channels_last(self.x_state, self.C)
-        else:
-            key = gkey
-            g = self.graphs.get(key)
-            if g is None:
-                # warm-up outside capture (sets kernel attributes, fills caches); state is reset below
-                one_step(None)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    one_step(None)
-                self.graphs[key] = g
-                ops.to_channels_last(x_T, self.x_state, 0, self.cx)
-                ops.to_channels_last(x_T, self.xin, 0, self.C)
-                self.x_sum.zero_()
-                self.counter.zero_()
-            for _ in range(lo_steps):
-                g.replay()
-        if finish:
-            finish_hi(lo_steps)
-        out = {"sample": ops.from_channels_last(self.x_state, self.C),
-               "sum_pred_xstart": ops.from_channels_last(self.x_sum, self.C) if want_sum else None}
-        return out
+    def _finish(self, first_step, T, run):
+        """steps [first_step, T) on the companion fp32 plan: hand the sampler state over, run, hand it back"""
+        hi = self._hi_plan()
+        hi.x_state.copy_(self.x_state)
+        hi.xin[..., :self.C].copy_(self.x_state.view(self.N, *self.dims, self.cx)[..., :self.C])
+        hi.x_sum.copy_(self.x_sum)
+        hi.counter.copy_(self.counter)
+        hi.seed_word.copy_(self.seed_word)
+        run(hi, first_step, T)
+        self.x_state.copy_(hi.x_state)
+        self.x_sum.copy_(hi.x_sum)
+        self.counter.copy_(hi.counter)

@@ -31,6 +31,7 @@ import torch
 
 from . import _native as nv
 from . import ops
+from .sampler_driver import LazyEmbeddings, SamplerDriver
 from .swin_unetr import HEADS, WINDOW
 
 SLOPE = 0.01         # get_act_layer(("leakyrelu", {"negative_slope": 0.01})), blocks.py:247
@@ -66,28 +67,14 @@ class _Res:
     """One UnetResBlock bound to its packed weights and statistics."""
 
 
-class SwinEmbeddings(list):
-    """What embed_model(image) returns: [hidden_states_out (5 tensors), enc0, enc1, enc2, enc3] like the reference
-    (NCDHW fp32, converted on first access) while the denoiser reads the channels-last device buffers."""
+class SwinEmbeddings(LazyEmbeddings):
+    """[hidden_states_out (5 tensors), enc0, enc1, enc2, enc3] like the reference (NCDHW fp32)."""
 
-    def __init__(self, plan, token):
-        super().__init__([None] * 5)
-        self.plan, self.token = plan, token
-
-    def __getitem__(self, i):
-        v = super().__getitem__(i)
-        if v is None:
-            p = self.plan
-            assert p.emb_token == self.token, "embeddings were overwritten by a later encoder pass"
-            if i == 0:
-                v = [ops.from_channels_last(p.e_hs[k], p.e_hs[k].shape[-1]) for k in range(5)]
-            else:
-                v = ops.from_channels_last(p.e_enc[i - 1], p.e_enc[i - 1].shape[-1])
-            super().__setitem__(i, v)
-        return v
-
-    def __iter__(self):
-        return (self[i] for i in range(5))
+    def _convert(self, i):
+        p = self.plan
+        if i == 0:
+            return [ops.from_channels_last(p.e_hs[k], p.e_hs[k].shape[-1]) for k in range(5)]
+        return ops.from_channels_last(p.e_enc[i - 1], p.e_enc[i - 1].shape[-1])
 
 
 class _OneGraph:
@@ -104,7 +91,7 @@ class _OneGraph:
             self.g.replay()
 
 
-class SwinPlan:
+class SwinPlan(SamplerDriver):
     """Buffers + launch sequences for one (N, D, H, W, dtype)."""
 
     def __init__(self, net, N, D, H, W, dtype, device):
@@ -214,18 +201,9 @@ class SwinPlan:
             self.hid_buf = torch.zeros(4 * tok_max, dtype=dtype, device=device)
             self.red_buf = torch.zeros(tok_max // 4 + 8, dtype=dtype, device=device)
             self.po_buf = torch.zeros(tok_max, dtype=dtype, device=device)
-        # ---- sampler state
-        self.x_state = torch.zeros((N, *S[0], self.cx), dtype=torch.float32, device=device)
-        self.x_sum = torch.zeros((N, *S[0], self.cx), dtype=torch.float32, device=device)
-        self.cur_coef = torch.zeros((N, 8), dtype=torch.float32, device=device)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=device)
-        self.step_word = torch.zeros(1, dtype=torch.int32, device=device)
-        self.err_word = torch.zeros(1, dtype=torch.int32, device=device)
-        self.seed_word = torch.zeros(1, dtype=torch.int64, device=device)
+        self._alloc_sampler_state(N, S[0], self.cx, device)
         self._bind()
         self.weights_version = None
-        self.graphs = {}
-        self.tables = {}
 
     # ---- parameter binding -------------------------------------------------------------------
     def _res(self, name, block, level, cin_packed=None, perm=None, tap=None):
@@ -611,14 +589,11 @@ class SwinPlan:
         return self._gemm_scratch(nbytes, 1)
 
     def capture_step(self, step_fn):
-        """Record ``step_fn`` (one sampler step: step_begin + denoiser_body + tail on the current stream) into a HIP graph;
-        the result has ``replay(times=1)``."""
-        step_fn()                                   # warm-up outside capture (kernel attributes, GEMM workspaces)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            step_fn()
-        return _OneGraph(g)
+        """Record ``step_fn`` (one sampler step: step_begin + denoiser_body + tail on the current stream) into a HIP graph
+        after a warm-up pass that sizes the GEMM workspaces; the result has ``replay(times=1)``."""
+        return _OneGraph(super()._capture(step_fn))
+
+    _capture = capture_step
 
     def tail(self, mode, noise=None, logits=None, use_sum=False):
         """UnetOutBlock (1x1x1, denoiser.py:399-400) fused with the sampler update (engine.Plan.tail's kernel, fed the
@@ -633,92 +608,15 @@ class SwinPlan:
                                xstart_sum=self.x_sum if use_sum else None, logits=logits, seed_dev=self.seed_word,
                                residual=residual)
 
-    def new_seed(self, seed=None):
-        """Philox key of this call's in-kernel noise (engine.Plan.new_seed)."""
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            try:
-                import torch.distributed as dist
-                if dist.is_available() and dist.is_initialized():
-                    seed ^= (dist.get_rank() + 1) * 0x9E3779B97F4A7C15 & (2 ** 62 - 1)
-            except Exception:       # pragma: no cover - torch.distributed not built
-                pass
-        self.seed_word.fill_(int(seed) & (2 ** 63 - 1))
-        return seed
-
-    def denoise(self, x, t):
-        """logits = model(x, t, image, embeddings) for an already-staged image (denoiser.py:353-403)."""
-        self.refresh_weights()
-        N = self.N
-        assert tuple(x.shape) == (N, self.C, *self.dims) and t.numel() == N
-        T = self.temb_table.shape[0]
-        on_host = not t.is_cuda
-        if on_host and not bool(((t >= 0) & (t < T)).all()):
-            raise ValueError(f"timestep out of range: the model was built for 0 <= t < {T}, got {t.tolist()}")
-        rows = t.detach().to(device=self.dev, dtype=torch.int32).contiguous()
-        if not on_host:
-            self.err_word.zero_()
-        ops.to_channels_last(x.detach().float().contiguous(), self.xin, 0, self.C)
-        ops.step_begin(N, self.temb_table, self.cur_add, rows_per_sample=rows, err_word=self.err_word, clear=self.den_stats)
+    # ---- hooks of the shared sampler (sampler_driver.SamplerDriver) -----------------------------------------
+    def _evaluate(self, rows, out):
+        ops.step_begin(self.N, self.temb_table, self.cur_add, rows_per_sample=rows, err_word=self.err_word, clear=self.den_stats)
         self.denoiser_body(zero_stats=False)
-        out = torch.empty((N, self.C, *self.dims), dtype=torch.float32, device=self.dev)
         self.tail(nv.MODE_LOGITS, logits=out)
-        if not on_host and int(self.err_word.item()):
-            raise ValueError(f"timestep out of range: the model was built for 0 <= t < {T}")
-        return out
 
-    def sample_loop(self, diffusion, kind, noise=None, step_noise=None, eta=0.0, use_graph=True, seed=None, want_sum=None):
-        """T reverse steps from ``noise`` (x_T, NCDHW) or a fresh draw: the loop bodies of p_sample_loop_progressive /
-        ddim_sample_loop_progressive (gaussian_diffusion.py:487-535, 667-716) around SwinUNETRDenoiser.forward, one
-        captured HIP graph replayed per step.  ``want_sum`` (default: DDIM loops only, see engine.Plan.sample_loop): keep the sum of
-        the x0 predictions.  Returns dict(sample, sum_pred_xstart (None without the sum))."""
-        want_sum = (kind == "ddim") if want_sum is None else bool(want_sum)
-        self.refresh_weights()
-        N, T = self.N, diffusion.num_timesteps
-        shape = (N, self.C, *self.dims)
-        if noise is None:
-            noise = torch.randn(*shape, device=self.dev)
-        assert tuple(noise.shape) == shape
-        x_T = noise.detach().float().contiguous()
-
-        def reset():
-            ops.to_channels_last(x_T, self.x_state, 0, self.cx)
-            ops.to_channels_last(x_T, self.xin, 0, self.C)
-            self.x_sum.zero_()
-            self.counter.zero_()
-
-        reset()
-        mode = nv.MODE_DDPM if kind == "ddpm" else nv.MODE_DDIM
-        tkey = (diffusion, kind, float(eta))          # the object itself: the table keeps it alive, no id() reuse after GC
-        if tkey not in self.tables:
-            order = list(range(T))[::-1]
-            tt = torch.tensor(order)
-            coef = diffusion.ddpm_coef(tt) if kind == "ddpm" else diffusion.ddim_coef(tt, eta)
-            tmap = diffusion.model_timesteps()
-            self.tables[tkey] = (coef.to(self.dev).contiguous(),
-                                 torch.tensor([tmap[i] for i in order], dtype=torch.int32, device=self.dev))
-        coef_table, row_of_step = self.tables[tkey]
-        self.new_seed(seed)
-        if step_noise is not None:
-            assert len(step_noise) == T
-            use_graph = False
-
-        def one_step(eps):
-            ops.step_begin(N, self.temb_table, self.cur_add, row_of_step=row_of_step, counter=self.counter,
-                           coef_table=coef_table, cur_coef=self.cur_coef, step_word=self.step_word, err_word=self.err_word,
-                           clear=self.den_stats)
-            self.denoiser_body(zero_stats=False)
-            self.tail(mode, noise=eps, use_sum=want_sum)
-
-        if not use_graph:
-            for k in range(T):
-                one_step(None if step_noise is None else step_noise[k].detach().to(self.dev).float().contiguous())
-        else:
-            g = self.graphs.get(tkey + (want_sum,))
-            if g is None:
-                g = self.capture_step(lambda: one_step(None))
-                self.graphs[tkey + (want_sum,)] = g
-                reset()
-            g.replay(T)
-        return {"sample": ops.from_channels_last(self.x_state, self.C),
-                "sum_pred_xstart": ops.from_channels_last(self.x_sum, self.C) if want_sum else None}
+    def _one_step(self, mode, row_of_step, coef_table, eps, want_sum):
+        ops.step_begin(self.N, self.temb_table, self.cur_add, row_of_step=row_of_step, counter=self.counter,
+                       coef_table=coef_table, cur_coef=self.cur_coef, step_word=self.step_word, err_word=self.err_word,
+                       clear=self.den_stats)
+        self.denoiser_body(zero_stats=False)
+        self.tail(mode, noise=eps, use_sum=want_sum)
