@@ -280,6 +280,11 @@ _SIGS = {
                                          _P, C.c_int, _P, _P, _P, _P]),
     "dua_blend_accumulate": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 + [_P, _P]),
     "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "dua_blend_accumulate_weighted": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P] +
+                                      [C.c_int] * 4 + [_P, _P]),
+    "dua_blend_weight_sum": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P,
+                                       C.c_int, C.c_int, C.c_int, _P]),
+    "dua_blend_finish_weighted": (C.c_int, [_P] + [C.c_int] * 5 + [_P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "dua_prep_foreground_box": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "dua_prep_resample": (C.c_int, [C.c_int, _P, _P, C.POINTER(PrepGeom), _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     "dua_prep_restore": (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

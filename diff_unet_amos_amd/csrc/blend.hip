@@ -19,6 +19,13 @@
 //            nothing is cropped and a plane is a multiple of 4 voxels, a lane takes 4 consecutive voxels (16-byte load of the
 //            sums, 16-byte store of q, 4-byte store of the mask, 16- or 4-byte load of the labels); otherwise one voxel.
 //            Counters: per lane -> wave shuffle -> LDS -> one 64-bit integer atomic per counter and workgroup.
+//   weighted forms (mode="gaussian"): the importance map is never stored.  It is an outer product of three per-axis vectors,
+//            clamped from below, so accumulate rebuilds w = max((g0[z] g1[y]) g2[x], floor) per voxel from the vectors (a few
+//            hundred bytes, cache resident) with the lane layout above -- g2 is indexed by the window x of each element, i.e.
+//            the group's x0 + j in the shifted wide form; weight_sum rebuilds the summed weights of the whole volume from the
+//            plan's per-axis starts (a voxel loops over the starts that cover it, D-major = window-index order); and finish
+//            divides by that volume instead of the product of three counts, same kernel body.  Every product and sum is a
+//            single rounded fp32 operation (__fmul_rn / __fadd_rn): the bits of `out[slice] += w * o; cnt[slice] += w`.
 #include "common.hpp"
 #include "../../include/dua_hip.h"
 
@@ -86,12 +93,89 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T
   }
 }
 
+// w of one voxel from the row's g0[z] g1[y] product: the outer-product order of the map, every product rounded, then the floor
+__device__ __forceinline__ float window_weight(float gzy, float gx, float floor_w) { return fmaxf(__fmul_rn(gzy, gx), floor_w); }
+
+// blend_accumulate_kernel with sum += w * window: same grid, lane layout, edges, fallback and row clamp
+template <typename T, bool WIDE>
+__global__ void __launch_bounds__(BLEND_THREADS)
+blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restrict__ row, float* __restrict__ sum,
+                                 const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2,
+                                 float floor_w, int B, int C, int rd, int rh, int rw, int Dp, int Hp, int Wp, int G, int* err) {
+  bool bad = false;
+  const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
+            w = clamp_flag(row[3], Wp - rw, bad);
+  if (bad && err && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *err = 1;
+  const int c = blockIdx.z, z = blockIdx.y;
+  const int it = blockIdx.x * BLEND_THREADS + threadIdx.x;
+  if (it >= rh * G) return;
+  const int y = it / G, g = it - y * G;
+  const long vrow = ((((long)b * C + c) * Dp + (d + z)) * Hp + (h + y)) * Wp + w;      // volume element of the row's x = 0
+  const T* wrow = win + (((long)c * rd + z) * rh + y) * rw;
+  const float gzy = __fmul_rn(g0[z], g1[y]);
+  if (WIDE) {
+    const int shift = (int)(vrow & 3);
+    const int x0 = 4 * g - shift;                   // window x of the group's first element: the index into g2 as well
+    if (x0 >= rw) return;
+    float* vp = sum + (vrow + x0);                  // 16-byte aligned
+    if (x0 >= 0 && x0 + 4 <= rw) {
+      f32x4 v = *reinterpret_cast<f32x4*>(vp);
+      const f32x4 o = load4(wrow + x0), gx = load4(g2 + x0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], __fmul_rn(window_weight(gzy, gx[j], floor_w), o[j]));
+      *reinterpret_cast<f32x4*>(vp) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        if (x >= 0 && x < rw) vp[j] = __fadd_rn(vp[j], __fmul_rn(window_weight(gzy, g2[x], floor_w), (float)wrow[x]));
+      }
+    }
+  } else {
+    if (g < rw) sum[vrow + g] = __fadd_rn(sum[vrow + g], __fmul_rn(window_weight(gzy, g2[g], floor_w), (float)wrow[g]));
+  }
+}
+
+// wsum [Dp][Hp][Wp]: one voxel per lane, the weights of the windows over it added in window-index order (the window grid is
+// the product of the three ascending start lists, D slowest).  A start is only compared with the voxel's coordinate, and the
+// vectors are indexed by coordinate - start inside [0, roi): no start value can lead outside them.
+__global__ void __launch_bounds__(BLEND_THREADS)
+blend_weight_sum_kernel(const int* __restrict__ sd, int nsd, const int* __restrict__ sh, int nsh, const int* __restrict__ sw,
+                        int nsw, int rd, int rh, int rw, const float* __restrict__ g0, const float* __restrict__ g1,
+                        const float* __restrict__ g2, float floor_w, float* __restrict__ wsum, int Hp, int Wp, unsigned V) {
+  const unsigned i = blockIdx.x * BLEND_THREADS + threadIdx.x;             // V < 2^31: no wrap
+  if (i >= V) return;
+  const int x = (int)(i % (unsigned)Wp);
+  const unsigned r = i / (unsigned)Wp;
+  const int y = (int)(r % (unsigned)Hp), z = (int)(r / (unsigned)Hp);
+  float acc = 0.f;
+  for (int a = 0; a < nsd; ++a) {
+    const int dz = z - sd[a];
+    if (dz < 0 || dz >= rd) continue;
+    const float gz = g0[dz];
+    for (int k = 0; k < nsh; ++k) {
+      const int dy = y - sh[k];
+      if (dy < 0 || dy >= rh) continue;
+      const float gzy = __fmul_rn(gz, g1[dy]);
+      for (int m = 0; m < nsw; ++m) {
+        const int dx = x - sw[m];
+        if (dx < 0 || dx >= rw) continue;
+        acc = __fadd_rn(acc, window_weight(gzy, g2[dx], floor_w));
+      }
+    }
+  }
+  wsum[i] = acc;
+}
+
 __device__ __forceinline__ bool sigmoid_above_half(float q) { return 1.f / (1.f + expf(-q)) > 0.5f; }
 
-template <int VEC>
+// WEIGHTED: the divisor is wsum [Dp][Hp][Wp] (blend_weight_sum_kernel) and nd, nh, nw are not read; otherwise the count
+// nd[z] nh[y] nw[x] and wsum is not read
+template <int VEC, bool WEIGHTED>
 __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float* __restrict__ sum, int C, int Dp, int Hp, int Wp,
                                                                      const int* __restrict__ nd, const int* __restrict__ nh,
-                                                                     const int* __restrict__ nw, int od, int oh, int ow, int D,
+                                                                     const int* __restrict__ nw, const float* __restrict__ wsum,
+                                                                     int od, int oh, int ow, int D,
                                                                      int H, int W, float* __restrict__ q_out,
                                                                      unsigned char* __restrict__ mask_out,
                                                                      const void* __restrict__ labels, int label_kind,
@@ -108,11 +192,15 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
     int x = (int)(i % W);
     const long r = i / W;
     int y = (int)(r % H), z = (int)(r / H);
-    float s[VEC];
+    float s[VEC], den[VEC] = {};
     bool lab[VEC] = {};
     if constexpr (VEC == 4) {                                 // nothing cropped: the sum plane has the output's layout
       const f32x4 v = *reinterpret_cast<const f32x4*>(sum + obase + i);
       s[0] = v[0]; s[1] = v[1]; s[2] = v[2]; s[3] = v[3];
+      if constexpr (WEIGHTED) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(wsum + i);
+        den[0] = t[0]; den[1] = t[1]; den[2] = t[2]; den[3] = t[3];
+      }
       if (label_kind == LABELS_ONEHOT_F32) {
         const f32x4 l = *reinterpret_cast<const f32x4*>(lf + lbase + i);
 #pragma unroll
@@ -127,16 +215,19 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
       }
     } else {
       s[0] = sum[(((long)plane * Dp + (od + z)) * Hp + (oh + y)) * Wp + (ow + x)];
+      if constexpr (WEIGHTED) den[0] = wsum[((long)(od + z) * Hp + (oh + y)) * Wp + (ow + x)];
       if (label_kind == LABELS_ONEHOT_F32) lab[0] = lf[lbase + i] != 0.f;
       else if (label_kind == LABELS_ONEHOT_U8) lab[0] = lu[lbase + i] != 0;
       else if (label_kind == LABELS_MAP_U8) lab[0] = lu[lbase + i] == (unsigned)c;
     }
     float q[VEC];
     unsigned m = 0;
-    int ndh = nd[od + z] * nh[oh + y];
+    int ndh = 0;
+    if constexpr (!WEIGHTED) ndh = nd[od + z] * nh[oh + y];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      q[j] = s[j] / (float)(ndh * nw[ow + x]);
+      if constexpr (WEIGHTED) q[j] = s[j] / den[j];
+      else q[j] = s[j] / (float)(ndh * nw[ow + x]);
       const bool a = sigmoid_above_half(q[j]);
       m |= (unsigned)a << (8 * j);
       if (label_kind != LABELS_NONE) {
@@ -147,7 +238,7 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
       if (j + 1 < VEC && ++x == W) {                          // the next voxel starts a row
         x = 0;
         if (++y == H) { y = 0; ++z; }
-        ndh = nd[od + z] * nh[oh + y];
+        if constexpr (!WEIGHTED) ndh = nd[od + z] * nh[oh + y];
       }
     }
     if constexpr (VEC == 4) {
@@ -178,16 +269,25 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
 
 }  // namespace dua
 
+// what dua_blend_accumulate and its weighted form ask of their common arguments
+static bool blend_accumulate_args_ok(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                     int table_rows, int table_off, int table_stride, const float* sum, int B, int Dp, int Hp,
+                                     int Wp) {
+  if ((dtype != DUA_F32 && dtype != DUA_F16) || nb < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || !windows || !table || !sum)
+    return false;
+  if (rd < 1 || rh < 1 || rw < 1 || B < 1 || Dp < rd || Hp < rh || Wp < rw || rd > 65535) return false;
+  if (table_rows < 1 || table_off < 0 || table_stride < 1 || (long)table_off + (long)(nb - 1) * table_stride >= table_rows)
+    return false;
+  if ((long)Dp * Hp * Wp >= (1L << 31) || (long)rd * rh * rw >= (1L << 31)) return false;
+  if (((size_t)windows & (dtype == DUA_F16 ? 1 : 3)) || ((size_t)sum & 3) || ((size_t)table & 3)) return false;
+  return true;
+}
+
 int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
                          int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
                          void* stream) {
-  if ((dtype != DUA_F32 && dtype != DUA_F16) || nb < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || !windows || !table || !sum)
+  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
     return DUA_ERR_ARG;
-  if (rd < 1 || rh < 1 || rw < 1 || B < 1 || Dp < rd || Hp < rh || Wp < rw || rd > 65535) return DUA_ERR_ARG;
-  if (table_rows < 1 || table_off < 0 || table_stride < 1 || (long)table_off + (long)(nb - 1) * table_stride >= table_rows)
-    return DUA_ERR_ARG;
-  if ((long)Dp * Hp * Wp >= (1L << 31) || (long)rd * rh * rw >= (1L << 31)) return DUA_ERR_ARG;
-  if (((size_t)windows & (dtype == DUA_F16 ? 1 : 3)) || ((size_t)sum & 3) || ((size_t)table & 3)) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool wide = ((size_t)sum & 15) == 0;
   const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
@@ -205,10 +305,52 @@ int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const
   return (int)hipGetLastError();
 }
 
-int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw, int od,
-                     int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
-                     int labels_dtype, int label_map, unsigned long long* tallies, void* stream) {
-  if (!sum || !nd || !nh || !nw || B < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || (long)B * C > 65535) return DUA_ERR_ARG;
+int dua_blend_accumulate_weighted(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                  int table_rows, int table_off, int table_stride, const float* g0, const float* g1,
+                                  const float* g2, float floor_w, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
+                                  void* stream) {
+  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
+    return DUA_ERR_ARG;
+  if (!g0 || !g1 || !g2 || (((size_t)g0 | (size_t)g1 | (size_t)g2) & 3) || !(floor_w > 0.f)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = ((size_t)sum & 15) == 0;
+  const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
+  const dim3 grid((unsigned)(((long)rh * G + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS), rd, C);
+  const long wvox = (long)C * rd * rh * rw;
+  for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
+    const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
+#define DUA_BLEND_ACC_W(T, WIDE)                                                                                            \
+  hipLaunchKernelGGL((dua::blend_accumulate_weighted_kernel<T, WIDE>), grid, dim3(dua::BLEND_THREADS), 0, s,                \
+                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, g0, g1, g2, floor_w, B, C, rd, rh, rw, Dp, Hp, Wp, \
+                     G, err_word)
+    if (dtype == DUA_F32) { if (wide) DUA_BLEND_ACC_W(float, true); else DUA_BLEND_ACC_W(float, false); }
+    else { if (wide) DUA_BLEND_ACC_W(dua::f16, true); else DUA_BLEND_ACC_W(dua::f16, false); }
+#undef DUA_BLEND_ACC_W
+  }
+  return (int)hipGetLastError();
+}
+
+int dua_blend_weight_sum(const int* starts_d, int nd, const int* starts_h, int nh, const int* starts_w, int nw, int rd, int rh,
+                         int rw, const float* g0, const float* g1, const float* g2, float floor_w, float* wsum, int Dp, int Hp,
+                         int Wp, void* stream) {
+  if (!starts_d || !starts_h || !starts_w || !g0 || !g1 || !g2 || !wsum || nd < 1 || nh < 1 || nw < 1) return DUA_ERR_ARG;
+  if (rd < 1 || rh < 1 || rw < 1 || Dp < rd || Hp < rh || Wp < rw || (long)Dp * Hp * Wp >= (1L << 31)) return DUA_ERR_ARG;
+  if ((((size_t)starts_d | (size_t)starts_h | (size_t)starts_w | (size_t)g0 | (size_t)g1 | (size_t)g2 | (size_t)wsum) & 3) ||
+      !(floor_w > 0.f))
+    return DUA_ERR_ARG;
+  const long V = (long)Dp * Hp * Wp;
+  hipLaunchKernelGGL(dua::blend_weight_sum_kernel, dim3((unsigned)((V + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS)),
+                     dim3(dua::BLEND_THREADS), 0, (hipStream_t)stream, starts_d, nd, starts_h, nh, starts_w, nw, rd, rh, rw, g0, g1,
+                     g2, floor_w, wsum, Hp, Wp, (unsigned)V);
+  return (int)hipGetLastError();
+}
+
+// dua_blend_finish (wsum == nullptr: the count vectors) and dua_blend_finish_weighted (wsum, no count vectors)
+static int blend_finish_launch(const float* sum, int B, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw,
+                               const float* wsum, int od, int oh, int ow, int D, int H, int W, float* q_out,
+                               unsigned char* mask_out, const void* labels, int labels_dtype, int label_map,
+                               unsigned long long* tallies, void* stream) {
+  if (!sum || ((size_t)wsum & 3) || B < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || (long)B * C > 65535) return DUA_ERR_ARG;
   if (D < 1 || H < 1 || W < 1 || od < 0 || oh < 0 || ow < 0 || od > Dp - D || oh > Hp - H || ow > Wp - W) return DUA_ERR_ARG;
   if ((long)Dp * Hp * Wp >= (1L << 31)) return DUA_ERR_ARG;
   if (!q_out && !mask_out && !tallies) return DUA_ERR_ARG;
@@ -231,16 +373,33 @@ int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, con
   }
   const long V = (long)D * H * W;
   const bool wide = D == Dp && H == Hp && W == Wp && V % 4 == 0 && ((size_t)sum & 15) == 0 && ((size_t)q_out & 15) == 0 &&
-                    ((size_t)mask_out & 3) == 0 && ((size_t)labels & (kind == dua::LABELS_ONEHOT_F32 ? 15 : 3)) == 0;
+                    ((size_t)mask_out & 3) == 0 && ((size_t)labels & (kind == dua::LABELS_ONEHOT_F32 ? 15 : 3)) == 0 &&
+                    ((size_t)wsum & 15) == 0;
   const long items = wide ? V / 4 : V;
   long blocks = (items + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS;
   if (blocks > dua::BLEND_FINISH_BLOCKS) blocks = dua::BLEND_FINISH_BLOCKS;
   const dim3 grid((unsigned)blocks, (unsigned)(B * C));
-  if (wide)
-    hipLaunchKernelGGL(dua::blend_finish_kernel<4>, grid, dim3(dua::BLEND_THREADS), 0, s, sum, C, Dp, Hp, Wp, nd, nh, nw, od, oh, ow,
-                       D, H, W, q_out, mask_out, labels, kind, tallies);
-  else
-    hipLaunchKernelGGL(dua::blend_finish_kernel<1>, grid, dim3(dua::BLEND_THREADS), 0, s, sum, C, Dp, Hp, Wp, nd, nh, nw, od, oh, ow,
-                       D, H, W, q_out, mask_out, labels, kind, tallies);
+#define DUA_BLEND_FINISH(VEC, WEIGHTED)                                                                                     \
+  hipLaunchKernelGGL((dua::blend_finish_kernel<VEC, WEIGHTED>), grid, dim3(dua::BLEND_THREADS), 0, s, sum, C, Dp, Hp, Wp, nd, nh, \
+                     nw, wsum, od, oh, ow, D, H, W, q_out, mask_out, labels, kind, tallies)
+  if (wsum) { if (wide) DUA_BLEND_FINISH(4, true); else DUA_BLEND_FINISH(1, true); }
+  else { if (wide) DUA_BLEND_FINISH(4, false); else DUA_BLEND_FINISH(1, false); }
+#undef DUA_BLEND_FINISH
   return (int)hipGetLastError();
+}
+
+int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw, int od,
+                     int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
+                     int labels_dtype, int label_map, unsigned long long* tallies, void* stream) {
+  if (!nd || !nh || !nw) return DUA_ERR_ARG;
+  return blend_finish_launch(sum, B, C, Dp, Hp, Wp, nd, nh, nw, nullptr, od, oh, ow, D, H, W, q_out, mask_out, labels,
+                             labels_dtype, label_map, tallies, stream);
+}
+
+int dua_blend_finish_weighted(const float* sum, int B, int C, int Dp, int Hp, int Wp, const float* wsum, int od, int oh, int ow,
+                              int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels, int labels_dtype,
+                              int label_map, unsigned long long* tallies, void* stream) {
+  if (!wsum) return DUA_ERR_ARG;
+  return blend_finish_launch(sum, B, C, Dp, Hp, Wp, nullptr, nullptr, nullptr, wsum, od, oh, ow, D, H, W, q_out, mask_out, labels,
+                             labels_dtype, label_map, tallies, stream);
 }

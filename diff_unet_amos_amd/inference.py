@@ -20,6 +20,11 @@ The streamed form (streamed_sliding_window_inference, evaluate_volume; csrc/blen
 predictor call's outputs are added into a device-resident fp32 sum volume at once, the window count is derived from the plan
 (the window grid is a dense product, so the count is a product of three per-axis vectors), one pass divides, crops,
 binarises and tallies Dice, and the multi-GPU form all-reduces the per-rank sum volumes instead of gathering windows.
+
+``mode="gaussian"`` (with ``sigma_scale``) on every function here is MONAI's second blending mode, restated from
+``compute_importance_map`` (MONAI >= 1.1; PARITY UNPINNED like the rest): a window's outputs are multiplied by a Gaussian
+importance map before they are added and the sum is divided by the summed maps.  ``importance_vectors`` is the single source of
+the weights; the default ``mode="constant"`` takes the code above unchanged.
 """
 from __future__ import annotations
 
@@ -88,6 +93,56 @@ def coverage_counts(padded, roi, starts):
     return out
 
 
+BLEND_MODES = ("constant", "gaussian")
+
+
+def _sigma_scales(sigma_scale):
+    scales = tuple(float(v) for v in sigma_scale) if isinstance(sigma_scale, (tuple, list)) else (float(sigma_scale),) * 3
+    if len(scales) != 3 or not all(0.0 < v < math.inf for v in scales):
+        raise ValueError(f"sigma_scale must be a positive number, or three of them, not {sigma_scale!r}")
+    return scales
+
+
+def importance_vectors(roi, mode="constant", sigma_scale=0.125):
+    """The importance map of ``mode`` as (g0, g1, g2, floor): fp32 CPU vectors [r0], [r1], [r2] and a float, the map being
+    ``w[z, y, x] = max((g0[z] * g1[y]) * g2[x], floor)`` with every product rounded to fp32 in this order (the outer-product
+    order of MONAI's compute_importance_map).  "gaussian": ``g_k = exp(x**2 / (-2 * sigma_k**2))`` in fp32 with
+    ``x = arange(-(r_k-1)/2, (r_k-1)/2 + 1)`` and ``sigma_k = r_k * sigma_scale_k``; ``floor = max(min(map), 1e-3)`` as an fp32
+    value (MONAI's ``clamp_(min=...)``).  "constant": ones and floor 1.  Every path takes its weights from here."""
+    if mode not in BLEND_MODES:
+        raise ValueError(f"mode must be one of {BLEND_MODES}, not {mode!r}")
+    scales = _sigma_scales(sigma_scale)
+    roi = tuple(int(r) for r in roi)
+    assert len(roi) == 3 and all(r >= 1 for r in roi)
+    if mode == "constant":
+        return (*(torch.ones(r, dtype=torch.float32) for r in roi), 1.0)
+    vectors = []
+    for r, scale in zip(roi, scales):
+        sigma = r * scale
+        x = torch.arange(start=-(r - 1) / 2.0, end=(r - 1) / 2.0 + 1, dtype=torch.float32)
+        vectors.append(torch.exp(x ** 2 / (-2 * sigma ** 2)))
+    g0, g1, g2 = vectors
+    # a rounded product of positive numbers is monotonic in each factor, so the smallest element of the map is the product
+    # of the three smallest elements taken in the map's own order
+    lowest = float((g0.min() * g1.min()) * g2.min())
+    floor = float(torch.tensor(max(lowest, 1e-3), dtype=torch.float32))
+    return g0, g1, g2, floor
+
+
+def importance_map(vectors, device=None, dtype=torch.float32):
+    """[r0, r1, r2] map of ``importance_vectors``' result, built in fp32 on the CPU, then moved."""
+    g0, g1, g2, floor = vectors
+    m = ((g0[:, None, None] * g1[None, :, None]) * g2[None, None, :]).clamp_(min=floor)
+    return m.to(device=device, dtype=dtype)
+
+
+def axis_starts(starts):
+    """The three ascending per-axis start lists whose product, first axis slowest, is the plan's ``starts``."""
+    per_axis = [sorted({s[k] for s in starts}) for k in range(3)]
+    assert list(itertools.product(*per_axis)) == list(starts), "window starts are not a dense product in D-major order"
+    return per_axis
+
+
 def window_table(starts, batch, device=None):
     """The plan as the int32 table dua_blend_accumulate reads: row ``idx`` = (b, d, h, w) of window ``idx`` = b * len(starts) + k,
     i.e. ``len(starts) * batch`` rows in window-index order.  Built once per plan (on ``device`` when given)."""
@@ -106,12 +161,19 @@ def blend_traffic_bytes(windows_total, channels, roi, batch, padded, world, wind
     return {"gathered": int(world) * per_rank * window, "reduced": volume}
 
 
-def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial, device, dtype):
+def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial, device, dtype, weights=None):
+    """``weights``: None = the constant map (sum / count); else the importance map [*roi] on ``device``: every window is
+    multiplied by it (one rounded product), added, and the sum is divided by the map summed once per window position."""
     out = torch.zeros((batch, channels, *padded), dtype=dtype, device=device)
     cnt = torch.zeros((1, 1, *padded), dtype=dtype, device=device)
     nwin = len(starts)
     for idx, o in outputs_by_index:
         b, (d, h, w) = idx // nwin, starts[idx % nwin]
+        if weights is not None:
+            out[b:b + 1, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += weights * o
+            if b == 0:
+                cnt[:, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += weights
+            continue
         out[b:b + 1, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += o
         if b == 0:
             cnt[:, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += 1
@@ -123,15 +185,23 @@ def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial,
     return out[tuple(sl)]
 
 
+def _blend_weights(roi, mode, sigma_scale, device, dtype):
+    """The ``weights`` argument of ``_blend`` for ``mode``; validates ``mode`` and ``sigma_scale`` either way."""
+    vectors = importance_vectors(roi, mode, sigma_scale)
+    return None if mode == "constant" else importance_map(vectors, device, dtype)
+
+
 def _window(inputs, idx, nwin, starts, roi):
     b, (d, h, w) = idx // nwin, starts[idx % nwin]
     return inputs[b:b + 1, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]]
 
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable, overlap: float = 0.25,
-                             **kwargs) -> torch.Tensor:
-    """Single-process form (engine.py:173-177 semantics).  ``predictor(window_batch, **kwargs)`` -> [b,C,*roi]."""
+                             mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
+    """Single-process form (engine.py:173-177 semantics).  ``predictor(window_batch, **kwargs)`` -> [b,C,*roi].
+    ``mode``: "constant" (the reference's) or "gaussian" with ``sigma_scale`` (``importance_vectors``)."""
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
+    importance_vectors(roi, mode, sigma_scale)              # refuse a bad mode or sigma_scale before any predictor call
     x = F.pad(inputs, pad=pad, mode="constant", value=0.0)
     nwin, total = len(starts), len(starts) * inputs.shape[0]
     results = []
@@ -140,7 +210,8 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int,
         seg = predictor(torch.cat([_window(x, i, nwin, starts, roi) for i in idxs]), **kwargs)
         results += [(i, seg[k:k + 1]) for k, i in enumerate(idxs)]
     first = results[0][1]
-    return _blend(results, inputs.shape[0], first.shape[1], padded, roi, starts, pad, spatial, first.device, first.dtype)
+    return _blend(results, inputs.shape[0], first.shape[1], padded, roi, starts, pad, spatial, first.device, first.dtype,
+                  _blend_weights(roi, mode, sigma_scale, first.device, first.dtype))
 
 
 def balanced_batches(n: int, max_batch: int):
@@ -157,14 +228,16 @@ def balanced_batches(n: int, max_batch: int):
 
 def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
                                      overlap: float = 0.25, group=None, gather_dtype: torch.dtype = None,
-                                     timings: dict = None, **kwargs) -> torch.Tensor:
+                                     timings: dict = None, mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
     """One process per GPU: windows dealt round-robin over the ranks of ``group``, one all-gather of the
     per-window outputs (fp32, or ``gather_dtype`` to halve the xGMI bytes), identical blend on every rank.
     ``inputs`` must be the same on all ranks.  ``timings`` (optional dict): accumulates the wall time of the
-    collective under "all_gather_s" (device synchronised around it) and records "gathered_bytes"."""
+    collective under "all_gather_s" (device synchronised around it) and records "gathered_bytes".  ``mode``,
+    ``sigma_scale``: as ``sliding_window_inference``."""
     import torch.distributed as dist
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
+    importance_vectors(roi, mode, sigma_scale)
     x = F.pad(inputs, pad=pad, mode="constant", value=0.0)
     nwin, total = len(starts), len(starts) * inputs.shape[0]
     mine = list(range(rank, total, world))
@@ -200,7 +273,8 @@ def sharded_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_si
         for k, i in enumerate(range(r, total, world)):
             results.append((i, gathered[r, k:k + 1].float()))
     results.sort(key=lambda t: t[0])
-    return _blend(results, inputs.shape[0], local.shape[1], padded, roi, starts, pad, spatial, local.device, torch.float32)
+    return _blend(results, inputs.shape[0], local.shape[1], padded, roi, starts, pad, spatial, local.device, torch.float32,
+                  _blend_weights(roi, mode, sigma_scale, local.device, torch.float32))
 
 
 def _need_device(t, what):
@@ -208,11 +282,17 @@ def _need_device(t, what):
         raise RuntimeError(f"{what} runs on an MI355X (device 'cuda'); there is no CPU path in this package")
 
 
-def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype, timings, kwargs):
+def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype, timings, kwargs, mode="constant",
+                  sigma_scale=0.125):
     """The sum volume fp32 [B, C, *padded] of this plan (all-reduced over ``group`` when given) and what the finish pass needs:
-    (sum volume, coverage vectors on the device, crop offsets, spatial)."""
+    (sum volume, divisor, crop offsets, spatial).  The divisor is the three coverage vectors on the device, or with
+    ``mode="gaussian"`` the weight-sum volume fp32 [*padded], which every rank derives from the plan for itself."""
     from . import ops
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
+    weights = None
+    vectors = importance_vectors(roi, mode, sigma_scale)
+    if mode != "constant":
+        weights = (*(g.to(inputs.device) for g in vectors[:3]), vectors[3])
     world, rank = 1, 0
     if group is not None:
         import torch.distributed as dist
@@ -236,7 +316,10 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
             acc = ops.zeros((batch, seg.shape[1], *padded), torch.float32, dev)
         if gather_dtype is not None:
             seg = seg.to(gather_dtype)
-        ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
+        if weights is None:
+            ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
+        else:
+            ops.blend_accumulate_weighted(acc, seg.contiguous(), table, idxs[0], weights, world, err)
         g += nb
         del seg
     if acc is None:          # more ranks than windows: still take part in the collective
@@ -255,44 +338,55 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
             timings["reduced_bytes"] = acc.numel() * acc.element_size()
     if int(err.item()):
         raise RuntimeError("streamed blend: a window position of the plan lies outside the padded volume")
-    coverage = [torch.tensor(n, dtype=torch.int32).to(dev) for n in coverage_counts(padded, roi, starts)]
     crop_lo = tuple(pad[2 * (2 - k)] for k in range(3))
+    if weights is not None:
+        per_axis = [torch.tensor(s, dtype=torch.int32).to(dev) for s in axis_starts(starts)]
+        return acc, ops.blend_weight_sum(per_axis, roi, padded, weights), crop_lo, spatial
+    coverage = [torch.tensor(n, dtype=torch.int32).to(dev) for n in coverage_counts(padded, roi, starts)]
     return acc, coverage, crop_lo, spatial
+
+
+def _streamed_finish(acc, divisor, crop_lo, spatial, **want):
+    """ops.blend_finish, or its weighted form when ``_streamed_sum`` returned a weight-sum volume."""
+    from . import ops
+    fn = ops.blend_finish_weighted if isinstance(divisor, torch.Tensor) else ops.blend_finish
+    return fn(acc, divisor, crop_lo, spatial, **want)
 
 
 def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
                                       overlap: float = 0.25, group=None, gather_dtype: torch.dtype = None,
-                                      timings: dict = None, **kwargs) -> torch.Tensor:
+                                      timings: dict = None, mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
     """The volume ``sliding_window_inference`` returns -- same plan, padding, window order and predictor calls -- without the list
     of window outputs: every call's outputs are added into a device-resident fp32 sum volume at once (dua_blend_accumulate:
     the fp32 additions of ``_blend`` in the same order), and one pass divides by the window count derived from the plan and
     crops (dua_blend_finish).  ``group=None``: one process.  With a group, each rank adds its round-robin windows (dealt in
     ``balanced_batches`` calls, as ``sharded_sliding_window_inference`` does) into its own sum volume and ONE all_reduce of the
     fp32 volumes follows; ``timings`` accumulates its wall time under "all_reduce_s" and records "reduced_bytes";
-    ``gather_dtype`` only narrows the window tensor handed to the accumulate call.  Device tensors only."""
-    from . import ops
+    ``gather_dtype`` only narrows the window tensor handed to the accumulate call.  ``mode="gaussian"``: the weighted entry
+    points (dua_blend_accumulate_weighted, dua_blend_weight_sum, dua_blend_finish_weighted), bit-equal to
+    ``sliding_window_inference(mode="gaussian")`` on the same device; the all-reduce is the same.  Device tensors only."""
     _need_device(inputs, "streamed_sliding_window_inference")
-    acc, coverage, crop_lo, spatial = _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype,
-                                                    timings, kwargs)
-    return ops.blend_finish(acc, coverage, crop_lo, spatial, want_q=True)[0]
+    acc, divisor, crop_lo, spatial = _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype,
+                                                   timings, kwargs, mode, sigma_scale)
+    return _streamed_finish(acc, divisor, crop_lo, spatial, want_q=True)[0]
 
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
-                    overlap: float = 0.25, distributed: bool = False, group=None):
+                    overlap: float = 0.25, distributed: bool = False, group=None, mode: str = "constant", sigma_scale=0.125):
     """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
     [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
     written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
     set) or a uint8 label map [B, D, H, W] (class c = channel c).  ``distributed``: shard the windows over the ranks of
-    ``group`` (default: the world) and all-reduce the sum volumes."""
+    ``group`` (default: the world) and all-reduce the sum volumes.  ``mode``, ``sigma_scale``: as ``sliding_window_inference``."""
     from . import ops
     _need_device(image, "evaluate_volume")
     if distributed and group is None:
         import torch.distributed as dist
         group = dist.group.WORLD
     with torch.no_grad():
-        acc, coverage, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
-                                                        None, None, dict(pred_type="ddim_sample"))
-        _, mask, tallies = ops.blend_finish(acc, coverage, crop_lo, spatial, want_mask=True, labels=labels)
+        acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
+                                                       None, None, dict(pred_type="ddim_sample"), mode, sigma_scale)
+        _, mask, tallies = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
     return mask, (ops.dice_from_tallies(tallies) if tallies is not None else None)
 
 
@@ -312,13 +406,14 @@ def dice_per_class(outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 
 def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
-          distributed: bool = False, group=None, streaming: bool = False) -> torch.Tensor:
+          distributed: bool = False, group=None, streaming: bool = False, mode: str = "constant", sigma_scale=0.125) -> torch.Tensor:
     """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
-    ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume)."""
+    ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume).  ``mode``, ``sigma_scale``: the blend's
+    importance map, as ``sliding_window_inference``."""
     if streaming:
-        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group)[0].float()
+        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, mode, sigma_scale)[0].float()
     fn = sharded_sliding_window_inference if distributed else sliding_window_inference
     kw = dict(group=group) if distributed else {}
     with torch.no_grad():
-        out = fn(image, roi_size, sw_batch_size, model, overlap, pred_type="ddim_sample", **kw)
+        out = fn(image, roi_size, sw_batch_size, model, overlap, mode=mode, sigma_scale=sigma_scale, pred_type="ddim_sample", **kw)
     return binarise(out)

@@ -1732,19 +1732,83 @@ def blend_accumulate(sum_volume, windows, table, table_off, table_stride=1, err=
     return sum_volume
 
 
+def _blend_weights(weights, roi, dev):
+    """(g0, g1, g2, floor): the fp32 device vectors [rd], [rh], [rw] and the floor of inference.importance_vectors."""
+    g0, g1, g2, floor = weights
+    for t, n, name in ((g0, roi[0], "g0"), (g1, roi[1], "g1"), (g2, roi[2], "g2")):
+        _f32c(t, name)
+        assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: fp32 [{n}] on the volume's device"
+    return g0, g1, g2, float(floor)
+
+
+def blend_accumulate_weighted(sum_volume, windows, table, table_off, weights, table_stride=1, err=None):
+    """dua_blend_accumulate_weighted: ``blend_accumulate`` with every window multiplied by the importance map first.
+    ``weights`` = (g0, g1, g2, floor): the map is max((g0[z] * g1[y]) * g2[x], floor), rebuilt per voxel."""
+    _f32c(sum_volume, "sum_volume"); _i32c(table, "table")
+    assert windows.is_cuda and windows.is_contiguous() and windows.dim() == 5, "windows: contiguous [nb, C, rd, rh, rw] device tensor"
+    assert sum_volume.dim() == 5 and table.dim() == 2 and table.shape[1] == 4, "sum_volume: [B, C, Dp, Hp, Wp]; table: int32 [rows, 4]"
+    assert windows.device == sum_volume.device == table.device, "every tensor on one device"
+    if err is not None:
+        _i32c(err, "err")
+        assert err.numel() == 1 and err.device == sum_volume.device
+    nb, Cn, rd, rh, rw = windows.shape
+    B, Cs, Dp, Hp, Wp = sum_volume.shape
+    assert Cn == Cs, f"windows have {Cn} channels, the sum volume {Cs}"
+    g0, g1, g2, floor = _blend_weights(weights, (rd, rh, rw), sum_volume.device)
+    with torch.cuda.device(sum_volume.device):
+        nv.check(nv.lib().dua_blend_accumulate_weighted(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows),
+                                                        nv.ptr(table), table.shape[0], int(table_off), int(table_stride),
+                                                        nv.ptr(g0), nv.ptr(g1), nv.ptr(g2), floor, nv.ptr(sum_volume), B, Dp, Hp,
+                                                        Wp, nv.ptr(err), nv.stream_ptr()), "dua_blend_accumulate_weighted")
+    return sum_volume
+
+
+def blend_weight_sum(axis_starts, roi, padded, weights):
+    """dua_blend_weight_sum: fp32 [Dp, Hp, Wp] = the importance map summed over the windows of the plan, in window-index
+    order.  ``axis_starts``: the three ascending int32 device vectors of per-axis window starts; ``weights`` as above."""
+    rd, rh, rw = (int(r) for r in roi)
+    Dp, Hp, Wp = (int(p) for p in padded)
+    sd, sh, sw = axis_starts
+    for t, name in ((sd, "starts_d"), (sh, "starts_h"), (sw, "starts_w")):
+        _i32c(t, name)
+        assert t.dim() == 1 and t.numel() >= 1 and t.device == sd.device, f"{name}: int32 vector on one device"
+    g0, g1, g2, floor = _blend_weights(weights, (rd, rh, rw), sd.device)
+    wsum = torch.empty((Dp, Hp, Wp), dtype=torch.float32, device=sd.device)
+    with torch.cuda.device(sd.device):
+        nv.check(nv.lib().dua_blend_weight_sum(nv.ptr(sd), sd.numel(), nv.ptr(sh), sh.numel(), nv.ptr(sw), sw.numel(), rd, rh, rw,
+                                               nv.ptr(g0), nv.ptr(g1), nv.ptr(g2), floor, nv.ptr(wsum), Dp, Hp, Wp,
+                                               nv.stream_ptr()), "dua_blend_weight_sum")
+    return wsum
+
+
+def blend_finish_weighted(sum_volume, wsum, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
+    """dua_blend_finish_weighted: ``blend_finish`` dividing by ``wsum`` (fp32 [Dp, Hp, Wp], ``blend_weight_sum``) instead of a
+    window count."""
+    return _blend_finish(sum_volume, None, wsum, crop_lo, spatial, want_q, want_mask, labels)
+
+
 def blend_finish(sum_volume, coverage, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
     """dua_blend_finish on the crop ``crop_lo`` .. ``crop_lo + spatial`` of ``sum_volume``: (q fp32 [B, C, *spatial] or None, mask
     uint8 [B, C, *spatial] or None, tallies int64 [C, 3] = (|A & B|, |A|, |B|) or None).  ``coverage``: the three int32 device
     vectors [Dp], [Hp], [Wp] whose product is the window count.  ``labels``: one-hot [B, C, *spatial] (fp32, uint8 or bool) or
     a uint8 label map [B, *spatial] (class c = channel c)."""
+    return _blend_finish(sum_volume, coverage, None, crop_lo, spatial, want_q, want_mask, labels)
+
+
+def _blend_finish(sum_volume, coverage, wsum, crop_lo, spatial, want_q, want_mask, labels):
+    """The two finish entry points: the divisor is the product of the ``coverage`` vectors, or ``wsum`` when given."""
     _f32c(sum_volume, "sum_volume")
     assert sum_volume.dim() == 5, "sum_volume: [B, C, Dp, Hp, Wp]"
     B, Cn, Dp, Hp, Wp = sum_volume.shape
     dev = sum_volume.device
-    nd, nh, nw = coverage
-    for t, n, name in ((nd, Dp, "nd"), (nh, Hp, "nh"), (nw, Wp, "nw")):
-        _i32c(t, name)
-        assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: int32 [{n}] on the volume's device"
+    if wsum is not None:
+        _f32c(wsum, "wsum")
+        assert tuple(wsum.shape) == (Dp, Hp, Wp) and wsum.device == dev, f"wsum: fp32 [{Dp}, {Hp}, {Wp}] on the volume's device"
+    else:
+        nd, nh, nw = coverage
+        for t, n, name in ((nd, Dp, "nd"), (nh, Hp, "nh"), (nw, Wp, "nw")):
+            _i32c(t, name)
+            assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: int32 [{n}] on the volume's device"
     od, oh, ow = (int(v) for v in crop_lo)
     D, H, W = (int(v) for v in spatial)
     code, is_map = nv.F32, 0
@@ -1767,9 +1831,13 @@ def blend_finish(sum_volume, coverage, crop_lo, spatial, want_q=False, want_mask
     mask = torch.empty((B, Cn, D, H, W), dtype=torch.uint8, device=dev) if want_mask else None
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if labels is not None else None
     with torch.cuda.device(dev):
-        nv.check(nv.lib().dua_blend_finish(nv.ptr(sum_volume), B, Cn, Dp, Hp, Wp, nv.ptr(nd), nv.ptr(nh), nv.ptr(nw), od, oh, ow, D, H, W,
-                                           nv.ptr(q), nv.ptr(mask), nv.ptr(labels), code, is_map, nv.ptr(tallies), nv.stream_ptr()),
-                 "dua_blend_finish")
+        tail = (od, oh, ow, D, H, W, nv.ptr(q), nv.ptr(mask), nv.ptr(labels), code, is_map, nv.ptr(tallies), nv.stream_ptr())
+        if wsum is not None:
+            nv.check(nv.lib().dua_blend_finish_weighted(nv.ptr(sum_volume), B, Cn, Dp, Hp, Wp, nv.ptr(wsum), *tail),
+                     "dua_blend_finish_weighted")
+        else:
+            nv.check(nv.lib().dua_blend_finish(nv.ptr(sum_volume), B, Cn, Dp, Hp, Wp, nv.ptr(nd), nv.ptr(nh), nv.ptr(nw), *tail),
+                     "dua_blend_finish")
     return q, mask, tallies
 
 

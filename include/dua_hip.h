@@ -989,6 +989,39 @@ int dua_blend_finish(const float* sum, int B, int C, int Dp, int Hp, int Wp, con
                      int oh, int ow, int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels,
                      int labels_dtype, int label_map, unsigned long long* tallies, void* stream);
 
+/* ---- evaluation: Gaussian window weighting of the streamed blend ---------------------------------------------------
+ * monai.inferers.sliding_window_inference(mode="gaussian", sigma_scale) restated (MONAI >= 1.1, compute_importance_map; the
+ * reference passes the default mode="constant", above).  For a roi (rd, rh, rw) the caller makes, in fp32 on the host,
+ *   g_k[i] = exp(x_i^2 / (-2 sigma_k^2)),  x = arange(-(r_k - 1) / 2, (r_k - 1) / 2 + 1),  sigma_k = r_k sigma_scale_k
+ * and the floor floor_w = max(min over the map of (g0[z] g1[y]) g2[x], 1e-3) (> 0).  The weight of window voxel (z, y, x) is
+ *   w = max((g0[z] * g1[y]) * g2[x], floor_w)          each product rounded to fp32, in this order
+ * -- the map is an outer product clamped from below, so it is rebuilt per voxel and never stored.  No operation below is
+ * contracted into a fused multiply-add.  g0, g1, g2: DEVICE fp32 [rd], [rh], [rw].
+ *
+ * dua_blend_accumulate_weighted: dua_blend_accumulate with
+ *   sum[b, :, d : d + rd, h : h + rh, w : w + rw] += w * (fp32) windows[k]      one rounded product, one rounded sum
+ * per window in the order of k; every other argument, the row clamp and *err_word as there.
+ *
+ * dua_blend_weight_sum: wsum fp32 [Dp][Hp][Wp] (WRITTEN) = per voxel the sum of w over the windows that cover it, added in
+ * window-index order starting from 0 -- what `wsum[slice] += w` per window of ONE volume of the batch accumulates.  The window
+ * grid is the product of three ascending per-axis start lists with the first axis slowest: starts_d, starts_h, starts_w
+ * (DEVICE int32 [nd], [nh], [nw]).  It depends on the plan alone, so every rank of a sharded blend computes all of it and only
+ * the sum volumes are reduced.  A voxel no window covers gets 0.
+ *
+ * dua_blend_finish_weighted: dua_blend_finish with q = sum / wsum[od + z][oh + y][ow + x] (IEEE fp32 division; wsum as
+ * written by dua_blend_weight_sum for the same plan) in place of the three count vectors; outputs, labels, tallies and limits
+ * as there.  Invalid arguments (a NULL pointer, C > DUA_BLEND_MAX_CLASSES, a non-positive extent or floor): DUA_ERR_ARG. */
+int dua_blend_accumulate_weighted(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                  int table_rows, int table_off, int table_stride, const float* g0, const float* g1,
+                                  const float* g2, float floor_w, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
+                                  void* stream);
+int dua_blend_weight_sum(const int* starts_d, int nd, const int* starts_h, int nh, const int* starts_w, int nw, int rd, int rh,
+                         int rw, const float* g0, const float* g1, const float* g2, float floor_w, float* wsum, int Dp, int Hp,
+                         int Wp, void* stream);
+int dua_blend_finish_weighted(const float* sum, int B, int C, int Dp, int Hp, int Wp, const float* wsum, int od, int oh, int ow,
+                              int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels, int labels_dtype,
+                              int label_map, unsigned long long* tallies, void* stream);
+
 /* ---- case preparation: crop, reorient and resample a raw scan on the device -----------------------------------------
  * The deterministic front of the reference's transform chain (utils.py:125-136 for training, :168-177 for validation:
  * ScaleIntensityRanged(a_min, a_max -> 0, 1, clip), CropForegroundd(source_key="image"), Orientationd, Spacingd(bilinear |

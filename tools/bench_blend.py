@@ -1,7 +1,7 @@
 """Time the whole-volume blend of sliding-window inference, streamed (csrc/blend.hip) against list-and-blend, predictor excluded.
 
     python tools/bench_blend.py [--volume 240 240 180] [--channels 16] [--roi 96] [--overlap 0.8] [--sw-batch 4]
-                                [--repeats 5] [--warmup 2]
+                                [--repeats 5] [--warmup 2] [--mode constant|gaussian] [--sigma-scale 0.125]
 
 A stub predictor hands out preallocated window outputs (a pool of --sw-batch random fp32 windows, reused by every call), so
 only the blend is timed.  Per repeat, alternating the two forms, between device synchronisations:
@@ -12,7 +12,11 @@ The two masks are compared outside |q| <= 2^-20 and the Dice vectors printed.  P
 what is resident before the call: pool, labels, table) is reported for both; the listed form's figure does NOT contain the
 list of window outputs a real predictor would leave (the pool is shared) -- that list is printed as derived bytes.  Bytes
 moved by the streamed form are computed from the shapes.  The last lines are the derived (not measured) bytes a rank receives
-in the gather and in the all-reduce form for 2, 4 and 8 ranks."""
+in the gather and in the all-reduce form for 2, 4 and 8 ranks.
+
+--mode gaussian: the streamed and the listed form blend with the Gaussian importance map (dua_blend_accumulate_weighted per
+call, one dua_blend_weight_sum, dua_blend_finish_weighted; ``_blend`` with the map), and the constant-mode streamed form is
+timed in the same alternation and printed next to them as "streamed_constant_seconds"."""
 import argparse
 import json
 import os
@@ -25,8 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from diff_unet_amos_amd import ops  # noqa: E402
-from diff_unet_amos_amd.inference import (_blend, _plan, binarise, blend_traffic_bytes, coverage_counts, dice_per_class,  # noqa: E402
-                                          window_table)
+from diff_unet_amos_amd.inference import (_blend, _plan, axis_starts, binarise, blend_traffic_bytes, coverage_counts,  # noqa: E402
+                                          dice_per_class, importance_map, importance_vectors, window_table)
 
 
 def clocks():
@@ -46,6 +50,8 @@ def main():
     ap.add_argument("--sw-batch", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--mode", choices=["constant", "gaussian"], default="constant")
+    ap.add_argument("--sigma-scale", type=float, default=0.125)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_blend.py measures on an MI355X; no GPU here")
@@ -63,6 +69,20 @@ def main():
     calls = [(g0, min(args.sw_batch, nwin - g0)) for g0 in range(0, nwin, args.sw_batch)]
     listed_windows = [(g0 + k, pool[k:k + 1]) for g0, nb in calls for k in range(nb)]
 
+    gaussian = args.mode == "gaussian"
+    vectors = importance_vectors(roi, args.mode, args.sigma_scale)
+    weights = (*(v.to(dev) for v in vectors[:3]), vectors[3])
+    wmap = importance_map(vectors, dev) if gaussian else None
+    per_axis = [torch.tensor(s, dtype=torch.int32, device=dev) for s in axis_starts(starts)]
+
+    def streamed_gaussian():
+        acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
+        for g0, nb in calls:
+            ops.blend_accumulate_weighted(acc, pool[:nb], table, g0, weights)
+        wsum = ops.blend_weight_sum(per_axis, roi, padded, weights)
+        _, mask, tallies = ops.blend_finish_weighted(acc, wsum, crop_lo, spatial, want_mask=True, labels=labels)
+        return mask, ops.dice_from_tallies(tallies)
+
     def streamed():
         acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
         for g0, nb in calls:
@@ -71,7 +91,7 @@ def main():
         return mask, ops.dice_from_tallies(tallies)
 
     def listed():
-        q = _blend(listed_windows, 1, Cn, padded, roi, starts, pad, spatial, dev, torch.float32)
+        q = _blend(listed_windows, 1, Cn, padded, roi, starts, pad, spatial, dev, torch.float32, wmap)
         mask = binarise(q)
         return mask, dice_per_class(mask, labels), q
 
@@ -86,9 +106,13 @@ def main():
 
     for _ in range(args.warmup):
         run(streamed); run(listed)
-    ts, tl, ps, pl = [], [], [], []
-    for _ in range(args.repeats):                                  # alternate the two forms
-        t, p, (mask_s, dice_s) = run(streamed)
+        if gaussian:
+            run(streamed_gaussian)
+    ts, tl, ps, pl, tc = [], [], [], [], []
+    for _ in range(args.repeats):                                  # alternate the forms
+        if gaussian:
+            tc.append(run(streamed)[0])
+        t, p, (mask_s, dice_s) = run(streamed_gaussian if gaussian else streamed)
         ts.append(t); ps.append(p)
         t, p, (mask_l, dice_l, q) = run(listed)
         tl.append(t); pl.append(p)
@@ -98,10 +122,14 @@ def main():
     volume_bytes = Cn * padded[0] * padded[1] * padded[2] * 4
     out_vox = Cn * spatial[0] * spatial[1] * spatial[2]
     moved = nwin * 3 * window_bytes + volume_bytes + volume_bytes + out_vox * (1 + 4)       # accumulate; zero fill; finish
+    if gaussian:                                                   # wsum written once, read once by the finish pass
+        moved += 2 * (volume_bytes // Cn)
     med_s, med_l = statistics.median(ts), statistics.median(tl)
     print(json.dumps({
         "plan": {"volume": list(spatial), "padded": list(padded), "channels": Cn, "roi": list(roi), "overlap": args.overlap,
                  "windows": nwin, "sw_batch": args.sw_batch, "calls": len(calls)},
+        "mode": args.mode, "sigma_scale": args.sigma_scale,
+        **({"streamed_constant_seconds": {"median": statistics.median(tc), "min": min(tc), "max": max(tc)}} if gaussian else {}),
         "clocks": clocks(), "device": torch.cuda.get_device_name(dev), "warmup": args.warmup, "repeats": args.repeats,
         "streamed_seconds": {"median": med_s, "min": min(ts), "max": max(ts)},
         "listed_seconds": {"median": med_l, "min": min(tl), "max": max(tl)},
