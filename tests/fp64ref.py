@@ -589,3 +589,90 @@ def deconv_bwd_ref(x, dyf, w, dtype):
     aw = (X.abs().t() @ A.abs()).reshape(Cin, 2, 2, 2, Cout).permute(0, 4, 1, 2, 3)
     shp = (N, D, H, W, Cin)
     return dx.reshape(shp), ax.reshape(shp), sq.reshape(shp), dw.contiguous(), aw.contiguous()
+
+
+# ---- forward transposed convolution, materialize and the training head, standalone ---------------------------------------------
+# Chains read off csrc/deconv.hip and csrc/head.hip.  fp16: a 32-channel chunk is two MFMA 32x32x16 steps (16 products each, + log2(16)
+# adds inside the instruction).  fp32: a 16-channel chunk is eight MFMA 32x32x2 steps; whether a step rounds once or once per product
+# is not specified, so every product counts as one fmaf of the chain (the module docstring's rule for fp32 kernels).
+def deconv_fwd_chain(form, cin, dtype):
+    """Longest fp32 chain of one output element of dua_deconv_k2s2_fwd in the given form.
+    "one_tap" (deconv_k2s2_kernel): the chunks one after the other into one accumulator, then + bias.
+    "ksplit" (deconv_k2s2_ksplit_kernel): wave w sums chunks w, w + 4, ... (ceil(nchunks / 4) of them); the four partial tiles are
+    added to zero in the order 0..3 (4 additions, the first of them exact), then + bias.
+    "alltaps" (deconv_k2s2_alltaps_kernel, both tile sizes): the accumulator STARTS at the bias (a term of the sum, no rounding of
+    its own), then the chunks one after the other."""
+    ck, per_chunk, inside = (32, 2, 4) if dtype == torch.float16 else (16, 16, 0)
+    nch = _cdiv(cin, ck)
+    if form == "one_tap":
+        return per_chunk * nch + inside + 1
+    if form == "ksplit":
+        return per_chunk * _cdiv(nch, 4) + inside + 4 + 1
+    if form == "alltaps":
+        return per_chunk * nch + inside
+    raise ValueError(form)
+
+
+def deconv_ref_by_child(A, w, bias, dtype, child):
+    """``deconv_ref`` evaluated child by child: the same three sums, without gathering a [P, Cin, Cout] weight tensor per voxel
+    (P = every voxel of an output with 512 input channels would be gigabytes)."""
+    P, cout = A.shape[0], w.shape[1]
+    ref = torch.zeros((P, cout), dtype=torch.float64)
+    ab, sq = torch.zeros_like(ref), torch.zeros_like(ref)
+    for k in range(8):
+        rows = (child == k).nonzero().view(-1)
+        if rows.numel():
+            r, a, s = deconv_ref(A[rows], w, bias, dtype, torch.full((1,), k, dtype=torch.int64).expand(rows.numel()))
+            ref[rows], ab[rows], sq[rows] = r, a, s
+    return ref, ab, sq
+
+
+def all_voxels(N, dims):
+    """int64 [N D H W, 4] (n, d, h, w): every voxel, in sample_voxels' sorted order."""
+    D, H, W = dims
+    g = torch.meshgrid(torch.arange(N), torch.arange(D), torch.arange(H), torch.arange(W), indexing="ij")
+    return torch.stack([t.reshape(-1) for t in g], 1)
+
+
+def deconv_sources(pts, coarse_dims):
+    """Output voxels of a (possibly replicate-padded) transposed convolution -> (parent voxel [P, 4] in the coarse grid, child
+    [P] = (d & 1) * 4 + (h & 1) * 2 + (w & 1)) of the voxel each value is computed at (replicate_source)."""
+    q = replicate_source(pts, coarse_dims)
+    parent = q.clone()
+    parent[:, 1:] >>= 1
+    return parent, (q[:, 1] & 1) * 4 + (q[:, 2] & 1) * 2 + (q[:, 3] & 1)
+
+
+def channel_sums(x):
+    """float64 [N, C, 2] = (sum x, sum x^2) over the voxels of channels-last x [N, ..., C]: the statistics a producer leaves."""
+    v = x.double().reshape(x.shape[0], -1, x.shape[-1])
+    return torch.stack([v.sum(1), (v * v).sum(1)], -1)
+
+
+def pool_ref(ref, bnd):
+    """Floor MaxPool3d(2) of a channels-last fp64 reference [N, D, H, W, C] and, per window, the largest of its eight bounds: the
+    maximum of the rounded outputs is the rounding of the maximum, so it lies within that of the fp64 maximum."""
+    p = lambda t: torch.nn.functional.max_pool3d(t.permute(0, 4, 1, 2, 3), 2).permute(0, 2, 3, 4, 1)      # noqa: E731
+    return p(ref), p(bnd)
+
+
+def head_fwd_route(C, dtype):
+    """dua_head_fwd: "mfma" (head_fwd_mfma_kernel: fp16, C = 32 or 64, the weights rounded to fp16 MFMA operands) or "plain"
+    (head_fwd_kernel: fp32 weights in registers, one fmaf per channel)."""
+    return "mfma" if dtype == torch.float16 and C in (32, 64) else "plain"
+
+
+def head_fwd_chain(C, dtype):
+    """mfma: the accumulator starts at the bias, C / 32 MFMA 16x16x32 steps (+ log2(32) adds inside); plain: bias, then C fmaf."""
+    return C // 32 + 5 if head_fwd_route(C, dtype) == "mfma" else C + 1
+
+
+def head_fwd_ref(u, w, b, dtype):
+    """logits = u W^T + b on the operands as the kernel rounds them: u [P, C] float64 (stored values), w fp32 [K, C] (through
+    fp16 on the mfma route), b fp32 [K].  Returns (ref, sum |terms|, sum terms^2), [P, K]."""
+    wq = w.detach().float().cpu()
+    if head_fwd_route(w.shape[1], dtype) == "mfma":
+        wq = wq.half()
+    ref, ab, sq = contract(u, wq.double().t())
+    bb = b.detach().double().cpu()[None]
+    return ref + bb, ab + bb.abs(), sq
