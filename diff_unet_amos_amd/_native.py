@@ -177,6 +177,7 @@ class PrepGeom(C.Structure):
 
 AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
 BLEND_MAX_CLASSES = 64   # DUA_BLEND_MAX_CLASSES
+CC_MAX_CAP = 65536       # DUA_CC_MAX_CAP
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
 
 _P = C.c_void_p
@@ -271,6 +272,11 @@ _SIGS = {
     "dua_surface_edt_sq": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P]),
     "dua_surface_distance_table": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
                                    [C.c_double] * 3 + [C.c_int, _P, _P, _P, C.c_long, _P]),
+    "dua_cc_scratch_bytes": (C.c_long, [C.c_int] * 5),
+    "dua_cc_label": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P, C.c_long, _P]),
+    "dua_cc_sizes": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, _P, _P]),
+    "dua_cc_filter": (C.c_int, [C.c_int] * 4 + [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_long, _P, _P, C.c_int,
+                                C.c_int, C.c_int, _P, _P, C.c_long, _P]),
     "dua_aug_count_candidates": (C.c_int, [_P, _P, C.c_long, C.c_float, _P, _P]),
     "dua_aug_draw": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P,
                                _P]),

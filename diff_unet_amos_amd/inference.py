@@ -372,22 +372,42 @@ def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_s
 
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
-                    overlap: float = 0.25, distributed: bool = False, group=None, mode: str = "constant", sigma_scale=0.125):
+                    overlap: float = 0.25, distributed: bool = False, group=None, postprocess: dict = None,
+                    mode: str = "constant", sigma_scale=0.125):
     """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
     [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
     written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
     set) or a uint8 label map [B, D, H, W] (class c = channel c).  ``distributed``: shard the windows over the ranks of
-    ``group`` (default: the world) and all-reduce the sum volumes.  ``mode``, ``sigma_scale``: as ``sliding_window_inference``."""
+    ``group`` (default: the world) and all-reduce the sum volumes.  ``mode``, ``sigma_scale``: as ``sliding_window_inference``.
+    ``postprocess``: None, or a dict of ``postprocess.keep_largest_components`` keyword arguments (connectivity,
+    num_components, min_size, channels, cap): the finish pass then writes the mask only, the component filter runs on it and
+    tallies Dice in its own pass, and the result is (filtered mask, Dice of the filtered mask)."""
     from . import ops
     _need_device(image, "evaluate_volume")
+    if postprocess is not None:
+        _postprocess_kwargs(postprocess)
     if distributed and group is None:
         import torch.distributed as dist
         group = dist.group.WORLD
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale)
-        _, mask, tallies = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
+        if postprocess is not None:
+            from .postprocess import filter_components
+            _, mask, _ = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True)
+            mask, tallies = filter_components(mask, labels=labels, **postprocess)
+        else:
+            _, mask, tallies = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
     return mask, (ops.dice_from_tallies(tallies) if tallies is not None else None)
+
+
+POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "channels", "cap")
+
+
+def _postprocess_kwargs(postprocess):
+    """Refuse a ``postprocess`` argument that is not a dict of ``keep_largest_components`` keywords, before any predictor call."""
+    if not isinstance(postprocess, dict) or any(k not in POSTPROCESS_KEYS for k in postprocess):
+        raise ValueError(f"postprocess: None or a dict with keys among {POSTPROCESS_KEYS}, got {postprocess!r}")
 
 
 def binarise(outputs: torch.Tensor) -> torch.Tensor:
@@ -406,14 +426,22 @@ def dice_per_class(outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 
 def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
-          distributed: bool = False, group=None, streaming: bool = False, mode: str = "constant", sigma_scale=0.125) -> torch.Tensor:
+          distributed: bool = False, group=None, streaming: bool = False, postprocess: dict = None, mode: str = "constant",
+          sigma_scale=0.125) -> torch.Tensor:
     """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
     ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume).  ``mode``, ``sigma_scale``: the blend's
-    importance map, as ``sliding_window_inference``."""
+    importance map, as ``sliding_window_inference``.  ``postprocess``: None, or a dict of
+    ``postprocess.keep_largest_components`` keyword arguments applied to the binarised volume (fp32 is returned either way)."""
+    if postprocess is not None:
+        _postprocess_kwargs(postprocess)
     if streaming:
-        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, mode, sigma_scale)[0].float()
+        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess, mode,
+                               sigma_scale)[0].float()
     fn = sharded_sliding_window_inference if distributed else sliding_window_inference
     kw = dict(group=group) if distributed else {}
     with torch.no_grad():
         out = fn(image, roi_size, sw_batch_size, model, overlap, mode=mode, sigma_scale=sigma_scale, pred_type="ddim_sample", **kw)
+    if postprocess is not None:
+        from .postprocess import keep_largest_components
+        return keep_largest_components(binarise(out), **postprocess).float()
     return binarise(out)

@@ -1604,6 +1604,100 @@ def surface_distance_table(test, reference, voxel_spacing=None, connectivity=1, 
     return counts, out
 
 
+# ---- evaluation: connected components (csrc/components.hip) -------------------------------------------------------------------
+
+def _cc_workspace(V, D, H, W, cap, device):
+    need = int(nv.lib().dua_cc_scratch_bytes(V, D, H, W, int(cap)))
+    if need < 0:
+        raise ValueError(f"connected components: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1) "
+                         f"or cap={cap} (1..{nv.CC_MAX_CAP})")
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
+def _cc_flags(flags, V, name, device):
+    if flags is None:
+        return None
+    assert flags.is_cuda and flags.device == device and flags.dtype == torch.uint8 and flags.is_contiguous() and \
+        tuple(flags.shape) == (V,), f"{name}: contiguous uint8 [{V}] on the mask's device"
+    return flags
+
+
+def cc_label(mask, connectivity=1, select=None):
+    """dua_cc_label for every volume of mask ([..., D, H, W]; fp32, uint8 or bool): (labels int32 [V, D, H, W], counts int32 [V]),
+    the labels of scipy.ndimage.label per volume.  ``select``: uint8 [V] device flags, a volume with 0 is not labelled (labels 0,
+    count 0).  No host synchronisation."""
+    m, code, V, D, H, W = _surface_mask(mask, "mask")
+    select = _cc_flags(select, V, "select", m.device)
+    ws, need = _cc_workspace(V, D, H, W, 1, m.device)
+    labels = torch.empty((V, D, H, W), dtype=torch.int32, device=m.device)
+    counts = torch.empty((V,), dtype=torch.int32, device=m.device)
+    with torch.cuda.device(m.device):
+        nv.check(nv.lib().dua_cc_label(V, D, H, W, nv.ptr(m), code, D * H * W, int(connectivity), nv.ptr(select), nv.ptr(labels),
+                                       nv.ptr(counts), nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_label")
+    return labels, counts
+
+
+def cc_sizes(labels, cap):
+    """dua_cc_sizes: int32 [V, cap], entry l - 1 = the voxels of label l of labels (int32 [V, D, H, W]); labels above ``cap`` are
+    not tallied."""
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 4, \
+        "labels: contiguous int32 [V, D, H, W] device tensor"
+    V, D, H, W = labels.shape
+    sizes = torch.empty((V, int(cap)), dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        nv.check(nv.lib().dua_cc_sizes(V, D, H, W, nv.ptr(labels), int(cap), nv.ptr(sizes), nv.stream_ptr()), "dua_cc_sizes")
+    return sizes
+
+
+def cc_filter(labels, counts, sizes, k=1, min_size=0, apply=None, mask=None, reference=None, classes=1, label_map=False):
+    """dua_cc_filter: (out uint8 [V, D, H, W], tallies int64 [classes, 3] or None).  ``labels`` / ``counts`` / ``sizes`` as
+    ``cc_label`` and ``cc_sizes`` return them; the ``k`` largest components of a volume are kept (0: no limit), none below
+    ``min_size`` voxels.  ``apply``: uint8 [V] device flags, a volume with 0 is passed through from ``mask`` ([..., D, H, W] with
+    V volumes).  ``reference``: one-hot [V, D, H, W] (fp32, uint8 or bool) or, with ``label_map``, a uint8 label map
+    [V / classes, D, H, W]; with it, the tallies of ``blend_finish`` for the filtered mask (class = volume index mod
+    ``classes``)."""
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 4, \
+        "labels: contiguous int32 [V, D, H, W] device tensor"
+    V, D, H, W = labels.shape
+    dev = labels.device
+    _i32c(counts, "counts")
+    _i32c(sizes, "sizes")
+    assert tuple(counts.shape) == (V,) and sizes.dim() == 2 and sizes.shape[0] == V and counts.device == dev and \
+        sizes.device == dev, f"counts int32 [{V}] and sizes int32 [{V}, cap] on the labels' device"
+    cap = int(sizes.shape[1])
+    apply = _cc_flags(apply, V, "apply", dev)
+    m, mcode = None, 0
+    if mask is not None:
+        m, mcode, Vm, *ext = _surface_mask(mask, "mask")
+        assert (Vm, *ext) == (V, D, H, W) and m.device == dev, "mask: the volumes the labels were made from"
+    assert apply is None or m is not None, "apply: volumes passed through are copied from mask"
+    ref, rcode, is_map, Cn = None, 0, 0, 1
+    if reference is not None:
+        Cn = int(classes)
+        assert reference.is_cuda and reference.device == dev, "reference: on the labels' device"
+        assert Cn >= 1 and V % Cn == 0, f"classes must divide the {V} volumes"
+        ref = reference.view(torch.uint8) if reference.dtype == torch.bool else reference
+        ref = ref.contiguous()
+        if label_map:
+            if ref.dtype != torch.uint8:
+                raise TypeError(f"reference: a label map is uint8, not {ref.dtype}")
+            assert ref.numel() == (V // Cn) * D * H * W, f"label map: {V // Cn} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
+            rcode, is_map = nv.U8, 1
+        else:
+            if ref.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(f"reference: one-hot labels are float32, uint8 or bool, not {ref.dtype}")
+            assert ref.numel() == V * D * H * W, f"one-hot reference: {V} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
+            rcode = nv.F32 if ref.dtype == torch.float32 else nv.U8
+    ws, need = _cc_workspace(V, D, H, W, cap, dev)
+    out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_cc_filter(V, D, H, W, nv.ptr(labels), nv.ptr(counts), nv.ptr(sizes), cap, int(k), int(min_size),
+                                        nv.ptr(apply), nv.ptr(m), mcode, D * H * W if m is not None else 0, nv.ptr(out), nv.ptr(ref),
+                                        rcode, is_map, Cn, nv.ptr(tallies), nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_filter")
+    return out, tallies
+
+
 # ---- training input: augmented batches from device-resident volumes (csrc/augment.hip; utils.py:143-160, engine.py:157-165) ----
 
 def _i32c(t, name):

@@ -1,0 +1,164 @@
+"""Connected-component post-processing of a segmentation mask, on the device: label the components of every (sample, class)
+volume, count their voxels, keep the largest ones and drop those below a size -- the step between ``evaluate_volume``'s mask
+and the surface metrics of ``metrics.py`` (one stray island far from an organ sets that organ's Hausdorff distance).
+
+One labelling in HIP (csrc/components.hip, include/dua_hip.h "evaluation: connected components") serves every function here,
+with these semantics, per 3-D volume [D, H, W] of a [..., D, H, W] mask (non-zero = foreground):
+
+- labels = scipy.ndimage.label(volume, generate_binary_structure(3, connectivity))[0]: 6, 18 or 26 neighbours for connectivity
+  1, 2, 3; background 0; components numbered 1, 2, ... by their first voxel in raster order (W fastest); count = their number;
+- sizes[l - 1] = the voxels of label l, in a table of ``cap`` entries;
+- keep-largest: the ``num_components`` components first in np.argsort(-sizes, kind="stable") -- the largest, a tie going to
+  the component whose first voxel comes first; ``num_components=0`` puts no limit on the number;
+- ``min_size``: a component with fewer voxels is dropped (exactly ``min_size`` voxels: kept);
+- ``channels``: the class channels (axis -4) that are filtered; every other channel is copied through as (mask != 0);
+- overflow: a volume with more than ``cap`` components has only its first ``cap`` (by number) tallied and considered; the
+  components numbered above ``cap`` are dropped by the filter.  ``count`` tells: compare it with ``cap``.
+
+Everything is integer work: results are exact, and equal between runs.  Nothing synchronises with the host, so every function
+can be captured into a graph.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _native as nv
+from . import ops
+
+DEFAULT_CAP = 16384          # entries of the size table per volume when ``cap`` is not given (the overflow rule above)
+
+
+def _device_mask(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a torch tensor on the MI355X")
+    if t.dim() < 3 or 0 in t.shape:
+        raise ValueError(f"{name}: a non-empty [..., D, H, W] mask, got {tuple(t.shape)}")
+    if t.is_complex():
+        raise ValueError(f"{name}: a real or boolean mask, not {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+    if t.dtype not in (torch.float32, torch.uint8, torch.bool):
+        t = t != 0
+    return t
+
+
+def _connectivity(connectivity):
+    if isinstance(connectivity, bool) or connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1, 2 or 3, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _count(value, name):
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise ValueError(f"{name} must be an integer >= 0, got {value!r}")
+    return value
+
+
+def _cap(cap):
+    cap = DEFAULT_CAP if cap is None else cap
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= nv.CC_MAX_CAP:
+        raise ValueError(f"cap must be an integer in 1..{nv.CC_MAX_CAP}, got {cap!r}")
+    return cap
+
+
+def _channels(mask, channels):
+    """The sorted channel list of ``channels`` (None: all), checked against the channel axis (-4) of ``mask``."""
+    if channels is None:
+        return None
+    if not isinstance(mask, torch.Tensor):
+        raise TypeError("mask: a torch tensor on the MI355X")
+    if mask.dim() < 4:
+        raise ValueError(f"channels needs a mask with a channel axis, [..., C, D, H, W]; got {tuple(mask.shape)}")
+    Cn = mask.shape[-4]
+    chosen = sorted({int(c) for c in channels})
+    if any(c < 0 or c >= Cn for c in chosen):
+        raise ValueError(f"channels must lie in 0..{Cn - 1}, got {list(channels)!r}")
+    return chosen
+
+
+def _channel_flags(mask, chosen):
+    """uint8 [V] device flags of the volumes whose channel is in ``chosen``, or None for all; filled on the device, so a graph
+    capture holds no copy from the host."""
+    if chosen is None:
+        return None
+    Cn = mask.shape[-4]
+    flags = torch.zeros((mask.numel() // (Cn * mask.shape[-3] * mask.shape[-2] * mask.shape[-1]), Cn), dtype=torch.uint8,
+                        device=mask.device)
+    for c in chosen:
+        flags[:, c] = 1
+    return flags.view(-1)
+
+
+def label_components(mask, connectivity=1):
+    """(labels int32 shaped like ``mask``, count int32 shaped like ``mask.shape[:-3]``) of a [..., D, H, W] device mask (fp32,
+    uint8 or bool; other dtypes are compared with 0 first).  Per volume, labels equals
+    scipy.ndimage.label(volume, generate_binary_structure(3, connectivity))[0] and count its number of components."""
+    conn = _connectivity(connectivity)
+    mask = _device_mask(mask, "mask")
+    labels, counts = ops.cc_label(mask, conn)
+    return labels.view(mask.shape), counts.view(mask.shape[:-3])
+
+
+def component_sizes(labels, count, cap=None):
+    """int32 [..., cap]: entry l - 1 is the number of voxels with label l of ``labels`` (int32 [..., D, H, W], as
+    ``label_components`` returns it with ``count``).  A volume with count > cap has its labels above ``cap`` left out."""
+    cap = _cap(cap)
+    for t, name in ((labels, "labels"), (count, "count")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on the MI355X")
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name}: int32 as label_components returns it, not {t.dtype}")
+    if labels.dim() < 3 or 0 in labels.shape or tuple(count.shape) != tuple(labels.shape[:-3]):
+        raise ValueError(f"labels [..., D, H, W] and count [...] of one label_components call, got {tuple(labels.shape)} and "
+                         f"{tuple(count.shape)}")
+    for t, name in ((labels, "labels"), (count, "count")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+    sizes = ops.cc_sizes(labels.contiguous().view(-1, *labels.shape[-3:]), cap)
+    return sizes.view(*labels.shape[:-3], cap)
+
+
+def filter_components(mask, connectivity=1, num_components=1, min_size=0, channels=None, cap=None, labels=None):
+    """``keep_largest_components`` and, when ``labels`` is given, the Dice tallies of its result in the same pass: (filtered
+    uint8 mask, tallies int64 [C, 3] = (|A & B|, |A|, |B|) per class or None).  ``mask``: [B, C, D, H, W] when ``labels`` is
+    given; ``labels``: one-hot like ``mask`` (fp32, uint8 or bool) or a uint8 label map [B, D, H, W] (class c = channel c), as
+    ``evaluate_volume`` takes them.  ``ops.dice_from_tallies`` turns the tallies into Dice."""
+    conn, k, min_size, cap = _connectivity(connectivity), _count(num_components, "num_components"), _count(min_size, "min_size"), \
+        _cap(cap)
+    chosen = _channels(mask, channels)
+    mask = _device_mask(mask, "mask")
+    flags = _channel_flags(mask, chosen)
+    ref, Cn, is_map = None, 1, False
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+            raise RuntimeError("labels: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+        if mask.dim() != 5:
+            raise ValueError(f"with labels, mask is [B, C, D, H, W]; got {tuple(mask.shape)}")
+        Cn = mask.shape[1]
+        if tuple(labels.shape) == tuple(mask.shape):
+            ref = labels if labels.dtype in (torch.float32, torch.uint8, torch.bool) else labels != 0
+        elif tuple(labels.shape) == (mask.shape[0], *mask.shape[2:]) and labels.dtype == torch.uint8:
+            ref, is_map = labels, True
+        else:
+            raise ValueError(f"labels: one-hot {tuple(mask.shape)} or a uint8 label map {(mask.shape[0], *mask.shape[2:])}, got "
+                             f"{labels.dtype} {tuple(labels.shape)}")
+        if Cn > nv.BLEND_MAX_CLASSES:
+            raise ValueError(f"at most {nv.BLEND_MAX_CLASSES} classes, got {Cn}")
+    lab, counts = ops.cc_label(mask, conn, select=flags)
+    sizes = ops.cc_sizes(lab, cap)
+    out, tallies = ops.cc_filter(lab, counts, sizes, k, min_size, apply=flags, mask=mask if flags is not None else None,
+                                 reference=ref, classes=Cn, label_map=is_map)
+    return out.view(mask.shape), tallies
+
+
+def keep_largest_components(mask, connectivity=1, num_components=1, min_size=0, channels=None, cap=None):
+    """uint8 like ``mask`` ([..., D, H, W] or, with ``channels``, [..., C, D, H, W]): 1 where the voxel belongs to one of the
+    ``num_components`` largest components of its volume (ties to the component whose first voxel comes first; 0 = no limit)
+    that has at least ``min_size`` voxels.  ``channels``: the class channels that are filtered, the others are copied through
+    (for AMOS, ``range(1, 16)`` leaves the background channel alone); None filters all."""
+    return filter_components(mask, connectivity, num_components, min_size, channels, cap)[0]
+
+
+def remove_small_components(mask, min_size, connectivity=1, channels=None, cap=None):
+    """``keep_largest_components`` without a limit on the number: every component of at least ``min_size`` voxels stays."""
+    return filter_components(mask, connectivity, 0, min_size, channels, cap)[0]

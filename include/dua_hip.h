@@ -834,6 +834,53 @@ int dua_surface_distance_table(int V, int D, int H, int W, const void* test, int
                                double sh, double sw, int nan_for_nonexisting, unsigned long long* counts, double* out,
                                void* workspace, long workspace_bytes, void* stream);
 
+/* ---- evaluation: connected components -----------------------------------------------------------------------------------
+ * Connected-component labelling of V = N * C binary volumes [D][H][W] and the post-processing filter built on it (keep the
+ * k largest components of each class, drop components below a size), between the mask of dua_blend_finish and the surface
+ * metrics above.  Conventions as there: masks DUA_F32 or DUA_U8 (uint8 / bool), non-zero = foreground; volume v (= n C + c)
+ * starts vstride elements after volume v - 1 and is dense [D][H][W]; connectivity k in 1..3 is
+ * generate_binary_structure(3, k) (6, 18 or 26 neighbours).  V <= 65535 and D H W < 2^31 - 1 (a voxel's linear index inside its
+ * volume is an int32).  Every entry point only enqueues on `stream`: nothing is read back, nothing synchronises.  The work is
+ * integer-only (union-find with integer atomicMin, a fixed-order prefix sum, integer atomic adds), so every output is exact
+ * and identical between runs.  Invalid arguments (a NULL pointer, extents out of range, connectivity outside 1..3, a stride
+ * below D H W, k < 0, cap outside 1..DUA_CC_MAX_CAP, a workspace that is too small or not 256-byte aligned, an int32 / fp32 /
+ * 64-bit array that is not aligned to its element): DUA_ERR_ARG, before the device is touched.
+ *
+ * Labels.  Per volume, labels[v] equals scipy.ndimage.label(mask[v], generate_binary_structure(3, k))[0]: background 0, the
+ * components numbered 1, 2, ... by their first voxel in raster order ([D][H][W], W fastest); counts[v] is their number.
+ * Sizes.  sizes[v][l - 1] = the number of voxels with label l, for 1 <= l <= cap; entries above counts[v] are 0.
+ * Overflow rule.  A volume with counts[v] > cap has overflowed the table: its labels above cap are NOT tallied and are NEVER
+ * kept by the filter (the filter sees the first cap components only).  Nothing is written out of bounds; the caller compares
+ * counts with cap to learn of it.
+ * Filter.  With n = min(counts[v], cap), label l in 1..n is kept when
+ *   (k == 0 or its position in np.argsort(-sizes[v][:n], kind="stable") is below k)  and  sizes[v][l - 1] >= min_size
+ * -- the k largest components, a tie going to the smaller label, i.e. the component whose first voxel comes first; k == 0
+ * puts no limit on the number; min_size <= 1 drops nothing. */
+#define DUA_CC_MAX_CAP 65536
+/* Bytes of workspace dua_cc_label and dua_cc_filter take for this batch (DUA_ERR_ARG for bad extents or cap): one int32 per
+ * voxel (the union-find parents), one int32 per 1024 voxels (the numbering scan) and V cap bytes (the filter's keep table). */
+long dua_cc_scratch_bytes(int V, int D, int H, int W, int cap);
+/* labels (int32 [V][D H W], WRITTEN) and counts (int32 [V], WRITTEN) of mask.  select (uint8 [V], may be NULL = all): a
+ * volume with select[v] == 0 is not labelled -- labels all 0, counts[v] = 0 -- and costs one streaming pass.  workspace: at
+ * least dua_cc_scratch_bytes(V, D, H, W, cap) bytes for any cap (cap = 1 gives the least), 256-byte aligned. */
+int dua_cc_label(int V, int D, int H, int W, const void* mask, int mask_dtype, long mask_vstride, int connectivity,
+                 const unsigned char* select, int* labels, int* counts, void* workspace, long workspace_bytes, void* stream);
+/* sizes (int32 [V][cap], WRITTEN: the call zeroes it first) from labels (int32 [V][D H W]); one integer atomic add per
+ * distinct label per wave of 64 voxels. */
+int dua_cc_sizes(int V, int D, int H, int W, const int* labels, int cap, int* sizes, void* stream);
+/* out (uint8 [V][D H W], WRITTEN) = 1 where the voxel's component is kept by the rule above, else 0, from labels, counts and
+ * sizes as the two calls above left them (same cap).  apply (uint8 [V], may be NULL = all): a volume with apply[v] == 0 is
+ * passed through, out = (mask != 0); mask / mask_dtype / mask_vstride are read for those volumes only and may be NULL / 0 / 0
+ * when apply is NULL.  reference and tallies are given together or not at all: tallies (64-bit unsigned [C][3], WRITTEN, the
+ * call zeroes it first) = |A & B|, |A|, |B| per class c = v mod C over batch and space, A = out, B = reference, in the layout
+ * of dua_blend_finish -- label_map == 0: one-hot [V][D H W], DUA_F32 or DUA_U8, non-zero = set; label_map != 0: DUA_U8
+ * [V / C][D H W] of class ids.  C divides V, C <= DUA_BLEND_MAX_CLASSES (C is ignored without a reference).  workspace: at
+ * least dua_cc_scratch_bytes(V, D, H, W, cap) bytes, 256-byte aligned. */
+int dua_cc_filter(int V, int D, int H, int W, const int* labels, const int* counts, const int* sizes, int cap, int k,
+                  int min_size, const unsigned char* apply, const void* mask, int mask_dtype, long mask_vstride,
+                  unsigned char* out, const void* reference, int reference_dtype, int label_map, int C,
+                  unsigned long long* tallies, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- training input: augmented batches from device-resident volumes ------------------------------------------------
  * The random tail of the reference's training transforms (utils.py:143-160: RandCropByPosNegLabeld, three RandFlipd,
  * RandRotate90d, RandScaleIntensityd, RandShiftIntensityd) and the one-hot expansion of Engine.convert_labels
