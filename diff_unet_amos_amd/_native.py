@@ -178,6 +178,7 @@ class PrepGeom(C.Structure):
 AUG_CHUNK, AUG_MAX_CLASSES, AUG_PARAM_WORDS = 1024, 64, 8
 BLEND_MAX_CLASSES = 64   # DUA_BLEND_MAX_CLASSES
 CC_MAX_CAP = 65536       # DUA_CC_MAX_CAP
+SUF_MAX_RUNS = 16        # DUA_SUF_MAX_RUNS
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
 
 _P = C.c_void_p
@@ -294,6 +295,7 @@ _SIGS = {
     "dua_prep_foreground_box": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "dua_prep_resample": (C.c_int, [C.c_int, _P, _P, C.POINTER(PrepGeom), _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     "dua_prep_restore": (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "dua_suf_accumulate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -18,10 +18,10 @@ class DiffSwinUNETR(Diffusion):
     def __init__(self, spatial_dims: int = 3, in_channels: int = 1, out_channels: int = 1, image_size: int = 96,
                  spatial_size: int = 96, features: Sequence[int] = (64, 64, 128, 256, 512, 64), feature_size: int = 48,
                  noise_ratio: float = 0.5, dropout: float = 0.2, timesteps: int = 1000, mode: str = "train",
-                 sample_steps: int = 10, compute_dtype: torch.dtype = torch.float16):
+                 sample_steps: int = 10, compute_dtype: torch.dtype = torch.float16, uncer_step: int = None):
         super().__init__(spatial_dims=spatial_dims, in_channels=in_channels, out_channels=out_channels,
                          image_size=image_size, spatial_size=spatial_size, features=features, dropout=dropout,
-                         timesteps=timesteps, mode=mode, sample_steps=sample_steps)
+                         timesteps=timesteps, mode=mode, sample_steps=sample_steps, uncer_step=uncer_step)
         self.feature_size = feature_size
         self.compute_dtype = compute_dtype
         self.embed_model = SwinUNETREncoder(image_size, in_channels, spatial_dims=spatial_dims, feature_size=feature_size,

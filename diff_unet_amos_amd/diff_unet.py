@@ -16,8 +16,10 @@ class _FusedAdapter:
     def __init__(self, plan):
         self.plan = plan
 
-    def sample_loop(self, diffusion, kind, shape, noise=None, model_kwargs=None, eta=0.0, step_noise=None):
+    def sample_loop(self, diffusion, kind, shape, noise=None, model_kwargs=None, eta=0.0, step_noise=None, fuse_runs=None):
         assert tuple(shape) == (self.plan.N, self.plan.C, *self.plan.dims)
+        if fuse_runs is not None:        # Step-Uncertainty Fusion of the batch's runs: the result carries fused_pred_xstart
+            return self.plan.sample_loop(diffusion, kind, noise=noise, eta=eta, step_noise=step_noise, fuse_runs=fuse_runs)
         out = self.plan.sample_loop(diffusion, kind, noise=noise, eta=eta, step_noise=step_noise)
         # One tensor that already is the sum over steps: summing ``all_samples`` as
         # models/diffusion/diffusion.py:94-98 does gives the reference's result without keeping T tensors.
@@ -57,10 +59,10 @@ class DiffUNet(Diffusion):
     def __init__(self, spatial_dims: int = 3, in_channels: int = 3, out_channels: int = 1, image_size: int = 96,
                  spatial_size: int = 96, features: Sequence[int] = (64, 64, 128, 256, 512, 64), dropout: float = 0.2,
                  timesteps: int = 1000, mode: str = "train", sample_steps: int = 10,
-                 compute_dtype: torch.dtype = torch.float16):
+                 compute_dtype: torch.dtype = torch.float16, uncer_step: int = None):
         super().__init__(spatial_dims=spatial_dims, in_channels=in_channels, out_channels=out_channels,
                          image_size=image_size, spatial_size=spatial_size, features=features, dropout=dropout,
-                         timesteps=timesteps, mode=mode, sample_steps=sample_steps)
+                         timesteps=timesteps, mode=mode, sample_steps=sample_steps, uncer_step=uncer_step)
         self.features = tuple(features)
         self.compute_dtype = compute_dtype
         self.embed_model = BasicUNetEncoder(3, in_channels, 2, features)

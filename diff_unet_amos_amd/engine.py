@@ -455,6 +455,9 @@ class Plan(SamplerDriver):
     def _one_step(self, mode, row_of_step, coef_table, eps, want_sum):
         self.native_step(mode, row_of_step=row_of_step, coef_table=coef_table, noise=eps, use_sum=want_sum)
 
+    def _one_step_logits(self, mode, row_of_step, coef_table, eps, logits):
+        self.native_step(mode, row_of_step=row_of_step, coef_table=coef_table, noise=eps, logits=logits)
+
     def _finish_count(self, kind, T):
         """DDPM in an fp16 plan: the LAST steps run on the exact-fp32 path (see finish_fp32_steps in __init__)"""
         return min(T, self.finish_fp32_steps) if (kind == "ddpm" and self.dtype == torch.float16) else 0

@@ -352,6 +352,45 @@ def make_spaced(timesteps, sections):
                            loss_type=LossType.RESCALED_KL)
 
 
+SUF_P_MIN = 0.001       # compute_uncer's floor under the mean prediction's probability
+
+
+def suf_step_coef(num_steps, device=None):
+    """a_k = sigmoid((k + 1) / T) for the T steps of a sampling loop in loop order (k = 0: the noisiest step): evaluated in
+    float64 and rounded once to fp32 -- the table dua_suf_accumulate reads and ``step_uncertainty_fusion`` uses."""
+    a = 1.0 / (1.0 + np.exp(-np.arange(1, num_steps + 1, dtype=np.float64) / num_steps))
+    return torch.from_numpy(a.astype(np.float32)).to(device)
+
+
+def step_uncertainty_fusion(all_model_outputs, all_samples):
+    """Step-Uncertainty Fusion (SUF) of R runs of a T-step DDIM loop, Diff-UNet's published inference rule, in torch operators
+    on whatever device the tensors live on.  ``all_model_outputs[r][k]`` / ``all_samples[r][k]``: run r's raw model output and
+    clamped x0 prediction at step k (loop order), as ``ddim_sample_loop`` returns them, each [G, C, ...].  Per element
+
+        m = (l_0 + ... + l_{R-1}) / R;  p = max(sigmoid(m), 0.001);  u = -p log(p);  a_k = sigmoid((k + 1) / T)
+        acc += exp(a_k (1 - u)) (x0_0 + ... + x0_{R-1})            for k = 0 .. T-1, acc = 0 before the loop
+
+    (compute_uncer and the fusion loop of the original code, its hard-coded 10 read as T; sums in run order).  With R = 1 the
+    steps are still weighted: this is not the plain sum of the predictions.  The HIP form of one step is
+    ops.suf_accumulate (include/dua_hip.h has the same formula)."""
+    R = len(all_model_outputs)
+    assert R >= 1 and len(all_samples) == R
+    T = len(all_model_outputs[0])
+    assert T >= 1 and all(len(run) == T for run in list(all_model_outputs) + list(all_samples))
+    first = all_samples[0][0]
+    coef = suf_step_coef(T).to(first.dtype)
+    acc = torch.zeros_like(first)
+    for k in range(T):
+        m, x = all_model_outputs[0][k].to(first), all_samples[0][k].to(first)
+        for r in range(1, R):
+            m = m + all_model_outputs[r][k].to(first)
+            x = x + all_samples[r][k].to(first)
+        p = torch.sigmoid(m / R).clamp_(min=SUF_P_MIN)
+        u = -p * torch.log(p)
+        acc = acc + torch.exp(coef[k].item() * (1 - u)) * x
+    return acc
+
+
 class UniformSampler:
     """resample.py:42-66: uniform timestep draw from numpy's GLOBAL RNG, unit weights."""
 

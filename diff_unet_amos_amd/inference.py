@@ -199,7 +199,9 @@ def _window(inputs, idx, nwin, starts, roi):
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable, overlap: float = 0.25,
                              mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
     """Single-process form (engine.py:173-177 semantics).  ``predictor(window_batch, **kwargs)`` -> [b,C,*roi].
-    ``mode``: "constant" (the reference's) or "gaussian" with ``sigma_scale`` (``importance_vectors``)."""
+    ``mode``: "constant" (the reference's) or "gaussian" with ``sigma_scale`` (``importance_vectors``).
+    A model built with ``uncer_step=R`` is a predictor like any other here and in the sharded and streamed forms: the switch
+    lives on the model, every window batch of b comes back as [b, C, *roi] (the Step-Uncertainty Fusion of its R runs)."""
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
     importance_vectors(roi, mode, sigma_scale)              # refuse a bad mode or sigma_scale before any predictor call
     x = F.pad(inputs, pad=pad, mode="constant", value=0.0)
@@ -381,7 +383,9 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     ``group`` (default: the world) and all-reduce the sum volumes.  ``mode``, ``sigma_scale``: as ``sliding_window_inference``.
     ``postprocess``: None, or a dict of ``postprocess.keep_largest_components`` keyword arguments (connectivity,
     num_components, min_size, channels, cap): the finish pass then writes the mask only, the component filter runs on it and
-    tallies Dice in its own pass, and the result is (filtered mask, Dice of the filtered mask)."""
+    tallies Dice in its own pass, and the result is (filtered mask, Dice of the filtered mask).
+    A ``model`` built with ``uncer_step=R`` needs no argument here: each predictor call then runs R DDIM loops per window and
+    returns their Step-Uncertainty Fusion (a plan of sw_batch_size R rows)."""
     from . import ops
     _need_device(image, "evaluate_volume")
     if postprocess is not None:
@@ -431,7 +435,8 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
     ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume).  ``mode``, ``sigma_scale``: the blend's
     importance map, as ``sliding_window_inference``.  ``postprocess``: None, or a dict of
-    ``postprocess.keep_largest_components`` keyword arguments applied to the binarised volume (fp32 is returned either way)."""
+    ``postprocess.keep_largest_components`` keyword arguments applied to the binarised volume (fp32 is returned either way).
+    Step-Uncertainty Fusion is the model's switch (``DiffUNet(..., uncer_step=R)``), not an argument of this function."""
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
     if streaming:

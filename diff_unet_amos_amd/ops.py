@@ -1246,6 +1246,23 @@ def denoiser_step(plan_struct):
     nv.check(nv.lib().dua_denoiser_step(C.byref(plan_struct), nv.stream_ptr()), "dua_denoiser_step")
 
 
+def suf_accumulate(logits, acc, step_coef, step_word=None, step=0, err_word=None):
+    """dua_suf_accumulate: one step of the Step-Uncertainty Fusion.  ``logits`` fp32 [G R, C, ...] (the step's raw model outputs,
+    the R runs of a group in adjacent rows), ``acc`` fp32 [G, C, ...] (in/out), ``step_coef`` fp32 [T] on the device
+    (gaussian_diffusion.suf_step_coef).  The step index is read from ``step_word`` (int32[1], device) or, without it, is ``step``."""
+    _f32c(logits, "logits"); _f32c(acc, "acc"); _f32c(step_coef, "step_coef")
+    G, Cc = acc.shape[:2]
+    vox = acc[0, 0].numel()
+    assert logits.shape[0] % G == 0 and tuple(logits.shape[1:]) == tuple(acc.shape[1:])
+    R = logits.shape[0] // G
+    for t in (step_word, err_word):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.int32 and t.numel() >= 1
+    nv.check(nv.lib().dua_suf_accumulate(G, R, Cc, vox, nv.ptr(logits), nv.ptr(step_coef), step_coef.numel(), nv.ptr(step_word),
+                                         int(step), nv.ptr(err_word), nv.ptr(acc), nv.stream_ptr()), "dua_suf_accumulate")
+    return acc
+
+
 def window_attention(qkv, heads, bias_t, mask_t=None, windows_per_image=1, region_ids=None, out=None, bias_table=None,
                      table_grid=(7, 7, 7)):
     """Softmax attention inside windows (models/swin_unetr/attention.py:97-120 between the qkv and proj Linear layers).

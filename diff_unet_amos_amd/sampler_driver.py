@@ -3,13 +3,15 @@ sampler state, the per-call Philox key, the step tables, the reverse loop with i
 single denoiser evaluation with its timestep check, and the lazily converted list an encoder pass returns.
 
 A plan supplies ``N, C, cx, dims, dev, xin, temb_table, emb_token, refresh_weights`` and the hooks ``_one_step``, ``_evaluate``
-and, where it differs from the default here, ``_capture`` / ``_finish_count`` / ``_finish``."""
+and, where it differs from the default here, ``_capture`` / ``_finish_count`` / ``_finish``; ``_one_step_logits`` is the step of a
+loop that fuses repeated runs (``sample_loop(fuse_runs=R)``: Step-Uncertainty Fusion, include/dua_hip.h)."""
 from __future__ import annotations
 
 import torch
 
 from . import _native as nv
 from . import ops
+from .gaussian_diffusion import suf_step_coef
 
 
 class LazyEmbeddings(list):
@@ -88,6 +90,15 @@ class SamplerDriver:
         in-kernel noise)."""
         raise NotImplementedError
 
+    def _one_step_logits(self, mode, row_of_step, coef_table, eps, logits):
+        """``_one_step`` without the running sum that also writes the step's raw model output into ``logits`` (fp32 NCDHW): the
+        step of a loop with ``fuse_runs``.  Called only then, so a loop without fusion sees exactly the hooks it always did."""
+        raise NotImplementedError
+
+    def _accumulate_runs(self, logits, acc, step_coef):
+        """Fold the step that just ran into ``acc``: dua_suf_accumulate at the step index step begin left in ``step_word``."""
+        ops.suf_accumulate(logits, acc, step_coef, step_word=self.step_word, err_word=self.err_word)
+
     def _evaluate(self, rows, out):
         """One denoiser evaluation of the staged ``xin`` at table rows ``rows`` (int32, device) into ``out`` (NCDHW logits)."""
         raise NotImplementedError
@@ -129,8 +140,24 @@ class SamplerDriver:
             raise ValueError(f"timestep out of range: the model was built for 0 <= t < {T}")
         return out
 
+    def _fusion_state(self, diffusion, R):
+        """(logits, acc, step_coef) of a loop that fuses R runs: persistent, allocated before any capture.  logits [N, C, ...] is
+        what every step's tail writes, acc [N / R, C, ...] the fused result, step_coef the table a_k of this process."""
+        shape = (self.N, self.C, *self.dims)
+        if getattr(self, "suf_logits", None) is None:
+            own = getattr(self, "logits", None)          # a plan that already keeps an NCDHW logits buffer lends it
+            ok = own is not None and tuple(own.shape) == shape and own.dtype == torch.float32
+            self.suf_logits = own if ok else torch.zeros(shape, dtype=torch.float32, device=self.dev)
+            self.suf_acc = {}
+        if R not in self.suf_acc:
+            self.suf_acc[R] = torch.zeros((self.N // R, *shape[1:]), dtype=torch.float32, device=self.dev)
+        tkey = (diffusion, "suf")
+        if tkey not in self.tables:
+            self.tables[tkey] = suf_step_coef(diffusion.num_timesteps, self.dev)
+        return self.suf_logits, self.suf_acc[R], self.tables[tkey]
+
     def sample_loop(self, diffusion, kind, noise=None, step_noise=None, eta=0.0, use_graph=True, seed=None, want_sum=None,
-                    snapshots=None):
+                    snapshots=None, fuse_runs=None, step_logits=None):
         """T reverse steps (T = diffusion.num_timesteps) starting from ``noise`` (x_T, NCDHW) or a fresh draw: the loop bodies
         of p_sample_loop_progressive / ddim_sample_loop_progressive (gaussian_diffusion.py:487-535, 667-716), one captured HIP
         graph replayed per step.  ``step_noise``: optional list of per-step NCDHW draws (parity runs; eager mode); otherwise the
@@ -139,9 +166,27 @@ class SamplerDriver:
         eager mode) -- drift-versus-step measurements.  ``want_sum``: accumulate the sum of the per-step x0 predictions (what
         models/diffusion/diffusion.py:94-98 sums from ``all_samples``); default: DDIM loops only -- the reference's p_sample_loop
         (gaussian_diffusion.py:441-485) returns the final sample alone, and the sum is 113 MB of HBM traffic per step at 96^3 x 16.
+        ``fuse_runs`` = R (DDIM only): the batch is N / R windows of R runs each, rows g R .. g R + R - 1 belonging to window g
+        (every row with its own x_T), and each step is followed by the Step-Uncertainty Fusion of its R model outputs
+        (dua_suf_accumulate, include/dua_hip.h has the formula) in the same captured graph; no plain sum is kept, and the
+        result carries ``fused_pred_xstart`` (NCDHW [N / R, C, ...]).  R = 1 is not the plain sum: the steps are still weighted.
+        ``step_logits``: optional list; with ``fuse_runs`` (eager mode) a copy of every step's logits is appended to it.
         Returns dict(sample, sum_pred_xstart (None without the sum))."""
+        fuse = None
+        if fuse_runs is not None:
+            R = int(fuse_runs)
+            if kind != "ddim":
+                raise NotImplementedError("fuse_runs: Step-Uncertainty Fusion is defined for the DDIM loop only")
+            if not 1 <= R <= nv.SUF_MAX_RUNS or self.N % R:
+                raise ValueError(f"fuse_runs={fuse_runs}: the plan's batch of {self.N} is not a whole number of windows of "
+                                 f"1 <= R <= {nv.SUF_MAX_RUNS} runs")
+            if self._finish_count(kind, diffusion.num_timesteps):
+                raise NotImplementedError("fuse_runs: finishing steps on a companion plan are not fused")
+            want_sum = False
         want_sum = (kind == "ddim") if want_sum is None else bool(want_sum)
         self.refresh_weights()
+        if fuse_runs is not None:
+            fuse = self._fusion_state(diffusion, R)
         T = diffusion.num_timesteps
         shape = (self.N, self.C, *self.dims)
         if noise is None:
@@ -154,8 +199,11 @@ class SamplerDriver:
         self.new_seed(seed)
         if step_noise is not None:
             assert len(step_noise) == T
-        if step_noise is not None or snapshots:
+        if step_noise is not None or snapshots or step_logits is not None:
             use_graph = False
+        if fuse is not None:
+            return self._fused_loop(fuse, R, diffusion, mode, coef_table, row_of_step, x_T, step_noise, eta, use_graph, snapshots,
+                                    step_logits)
 
         def run(plan, first, last):
             for k in range(first, last):
@@ -178,3 +226,33 @@ class SamplerDriver:
         if finish:
             self._finish(T - finish, T, run)
         return self._result(want_sum)
+
+    def _fused_loop(self, fuse, R, diffusion, mode, coef_table, row_of_step, x_T, step_noise, eta, use_graph, snapshots, step_logits):
+        """The loop of ``sample_loop(fuse_runs=R)``: T times (step with logits, accumulate), eagerly or from one captured graph."""
+        logits, acc, step_coef = fuse
+        T = diffusion.num_timesteps
+
+        def step(eps=None):
+            self._one_step_logits(mode, row_of_step, coef_table, eps, logits)
+            self._accumulate_runs(logits, acc, step_coef)
+
+        acc.zero_()
+        if not use_graph:
+            for k in range(T):
+                step(None if step_noise is None else step_noise[k].detach().to(self.dev).float().contiguous())
+                if step_logits is not None:
+                    step_logits.append(logits.clone())
+                if snapshots and (k + 1) in snapshots:
+                    snapshots[k + 1] = ops.from_channels_last(self.x_state, self.C)
+        else:
+            gkey = (diffusion, "ddim", float(eta), False, "fuse_runs", R)
+            g = self.graphs.get(gkey)
+            if g is None:
+                g = self.graphs[gkey] = self._capture(step)
+                self._reset(x_T)                    # the warm-up step advanced the state and the fused sum
+                acc.zero_()
+            for _ in range(T):
+                g.replay()
+        out = self._result(False)
+        out["fused_pred_xstart"] = acc.clone()
+        return out

@@ -620,3 +620,10 @@ class SwinPlan(SamplerDriver):
                        clear=self.den_stats)
         self.denoiser_body(zero_stats=False)
         self.tail(mode, noise=eps, use_sum=want_sum)
+
+    def _one_step_logits(self, mode, row_of_step, coef_table, eps, logits):
+        ops.step_begin(self.N, self.temb_table, self.cur_add, row_of_step=row_of_step, counter=self.counter,
+                       coef_table=coef_table, cur_coef=self.cur_coef, step_word=self.step_word, err_word=self.err_word,
+                       clear=self.den_stats)
+        self.denoiser_body(zero_stats=False)
+        self.tail(mode, noise=eps, logits=logits)

@@ -1131,6 +1131,39 @@ int dua_prep_resample(int dtype, const void* src, const unsigned char* src_label
 int dua_prep_restore(const unsigned char* mask, long prepared_voxels, int C, int X0, int X1, int X2, const int* tab0,
                      const int* tab1, const int* tab2, unsigned char* out, void* stream);
 
+/* ---- Step-Uncertainty Fusion of repeated DDIM runs (csrc/suf.hip) ---------------------------------------------------------
+ * Diff-UNet's published inference rule: the DDIM loop runs R times per window, and after every step the runs' predictions
+ * are added into the result with a weight that grows with the step index and shrinks with the entropy of the runs' mean
+ * prediction.  The R runs of window (group) g are the adjacent batch rows n = g R + r of one launch plan with N = G R, so all
+ * of them are in memory at the same step and the fusion is one launch behind the step's tail -- no per-step history.
+ *
+ * Step k = 0 .. nsteps-1 counts in loop order (k = 0 is the noisiest step); l_r is run r's raw model output at this step
+ * (the tail's `logits`, the reference's model_output).  Per (g, class c, voxel v), all in fp32:
+ *   m   = (l_0 + l_1 + ... + l_{R-1}) / R              sum in run order, IEEE division
+ *   p   = sigmoid(m);  p = max(p, 0.001)
+ *   u   = -p log(p)
+ *   a_k = step_coef[k] = sigmoid((k + 1) / nsteps)     fp32 table made by the host
+ *   w   = exp(a_k (1 - u))
+ *   acc += w (x0_0 + ... + x0_{R-1}),   x0_r = clamp(l_r, -1, 1)     sum in run order
+ * acc is zero when the loop starts and is the loop's result.  This is compute_uncer and the fusion loop of the original
+ * Diff-UNet code with its hard-coded 10 read as the number of sampling steps.
+ *
+ * x0_r is derived from the logits INSIDE the kernel: on this path p_mean_variance clamps the model output and does nothing
+ * else, so the clamp of the same fp32 value is the tail's `xstart` bit for bit, and the kernel reads R tensors per step, not
+ * 2 R.  R = 1 is NOT the plain sum of the predictions: one run is still weighted per step.
+ *
+ * dua_suf_accumulate: logits fp32 [G R][C][voxels] (read only), acc fp32 [G][C][voxels] (in/out), step_coef DEVICE fp32
+ * [nsteps].  The step index is *step_word (DEVICE int32, what dua_step_begin left there: one captured graph serves every
+ * step) or, with step_word == NULL, `step`.  A device-side index outside [0, nsteps) is clamped into the table (no wild
+ * read) and *err_word (DEVICE int, may be NULL; the caller zeroes it) is set to 1, as dua_step_begin does; a host-side `step`
+ * outside the table is rejected.  One thread owns an element of acc and there are no atomics: two calls on the same inputs
+ * give the same bits.  16-byte loads and stores when voxels % 4 == 0 and both pointers are 16-byte aligned, a scalar path
+ * otherwise.  1 <= R <= DUA_SUF_MAX_RUNS, G <= 65535.  Traffic: (R + 2) C voxels 4 bytes per group.
+ * Invalid arguments: DUA_ERR_ARG, before the device is touched. */
+#define DUA_SUF_MAX_RUNS 16
+int dua_suf_accumulate(int G, int R, int C, long voxels, const float* logits, const float* step_coef, int nsteps,
+                       const int* step_word, int step, int* err_word, float* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
