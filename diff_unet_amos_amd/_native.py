@@ -23,6 +23,8 @@ F32, F16 = 0, 1
 U8 = 2                    # DUA_U8: uint8 / bool masks of the surface-distance entry points
 I16 = 3                   # DUA_I16: int16 Hounsfield units of the case-preparation entry points
 ERR_ARG = -22
+SURFACE_MAX_TOLERANCES = 8              # DUA_SURFACE_MAX_TOLERANCES
+SURFACE_MAX_TOLERANCE_ENTRIES = 128     # DUA_SURFACE_MAX_TOLERANCE_ENTRIES
 SURFACE_FIELDS = ("hd", "hd95", "asd", "assd", "tp", "fp", "fn", "tn", "hd95_lo", "hd95_hi", "asd_ba", "n_surface")
 
 
@@ -273,6 +275,14 @@ _SIGS = {
     "dua_surface_edt_sq": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P]),
     "dua_surface_distance_table": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
                                    [C.c_double] * 3 + [C.c_int, _P, _P, _P, C.c_long, _P]),
+    "dua_surface_edt_sq_bounded": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int] + [C.c_double] * 4 + [_P, _P]),
+    "dua_surface_dice_scratch_bytes": (C.c_long, [C.c_int] * 4),
+    "dua_surface_dice_table": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
+                               [C.c_double] * 3 + [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P, _P, _P,
+                                                   C.c_long, _P]),
+    "dua_surface_report": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int] +
+                           [C.c_double] * 3 + [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P, C.c_long,
+                                               _P]),
     "dua_cc_scratch_bytes": (C.c_long, [C.c_int] * 5),
     "dua_cc_label": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P, C.c_long, _P]),
     "dua_cc_sizes": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, _P, _P]),

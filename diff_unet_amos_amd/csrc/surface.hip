@@ -18,6 +18,10 @@
 //            per-volume 256-bin integer histograms, then one step that fixes the digit), and one pass for the smallest
 //            value above the selected one.  sqrt is monotone, so selecting on squared distances selects the distances.
 //   finish : per volume, the block sums in a fixed order, the wrapper rule (A or B empty or full -> NaN / 0) and the table.
+//   dice   : normalized surface Dice in the voxel-count form: one pass over the surface bytes counts, per direction and
+//            tolerance, the surface voxels with d^2 <= tau^2 (integer atomics), one thread per (volume, tolerance) divides.  It
+//            needs distances up to the largest tolerance only, so its transform is band-limited (BOUNDED): values above
+//            cap2 = tau_max^2 become +inf in every pass and no search goes past them; every value <= cap2 keeps its bits.
 // Every sum is taken in a fixed order and every atomic is an integer one, so two runs on the same masks agree bit for bit.
 #include "common.hpp"
 #include "../../include/dua_hip.h"
@@ -102,9 +106,11 @@ __global__ __launch_bounds__(SURF_THREADS) void surface_masks_kernel(const TA* _
 
 // W pass.  grid (ceil(D*H / R), V, dirs), 64 threads, R rows of S u16 in LDS (S even, S / 2 odd: lanes on different rows hit
 // different banks).  Direction z: seed where (seeds & mask_z) != 0; out + z * out_dir = sw2 * g^2, +inf on a row without seeds.
+// BOUNDED (the band-limited transform): a value above cap2 is written as +inf.
+template <bool BOUNDED>
 __global__ __launch_bounds__(ROWS_THREADS) void edt_rows_kernel(const unsigned char* __restrict__ seeds, long seeds_vs, int mask0,
                                                                 int mask1, int D, int H, int W, int R, int S, double sw2,
-                                                                double* __restrict__ out, long out_dir) {
+                                                                double* __restrict__ out, long out_dir, double cap2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned short* row = (unsigned short*)smem;
   const int v = blockIdx.y, z = blockIdx.z;
@@ -136,7 +142,11 @@ __global__ __launch_bounds__(ROWS_THREADS) void edt_rows_kernel(const unsigned c
   for (int i = threadIdx.x; i < nr * W; i += ROWS_THREADS) {
     const int r = i / W, x = i - r * W;
     const unsigned g = row[r * S + x];
-    dst[i] = g == ROW_NONE ? (double)INFINITY : sw2 * (double)(g * g);
+    double val = g == ROW_NONE ? (double)INFINITY : sw2 * (double)(g * g);
+    if constexpr (BOUNDED) {
+      if (val > cap2) val = (double)INFINITY;
+    }
+    dst[i] = val;
   }
 }
 
@@ -144,12 +154,19 @@ __global__ __launch_bounds__(ROWS_THREADS) void edt_rows_kernel(const unsigned c
 // grid (outer_n * nwc, V, dirs), 256 threads; a block owns columns [w0, w0 + WC) of one outer index over the whole line.
 // GATHER = false: every voxel of a column with a finite value is rewritten.  GATHER = true (the last pass of the metric table):
 // only voxels whose surface byte has qmask_z set are evaluated; their squared distance is written in place, the block's sum of
-// distances goes to partial[(z V + v) P + blockIdx.x] and its largest squared distance into maxbits[z V + v] (atomicMax).
-template <bool GATHER>
+// distances goes to partial[(z V + v) P + blockIdx.x] and its largest squared distance into maxbits[z V + v] (atomicMax);
+// STATS = false (surface Dice, which counts and never sums) leaves both out.
+// BOUNDED (the band-limited transform, inputs already +inf above cap2): the outward search also stops once s^2 k^2 > cap2 and
+// a result above cap2 is written as +inf.  A sum of two non-negative terms is at least each of them (rounding is monotone), so
+// a candidate dropped here exceeds cap2 in the unbounded search too; every result <= cap2 is the minimum of the same sums as
+// there, hence the same bits.  A column (GATHER = false) or a query (GATHER = true) whose whole neighbourhood is +inf costs at
+// most sqrt(cap2) / s steps, and a column whose inputs are all +inf is skipped through colflag as before.
+template <bool GATHER, bool BOUNDED, bool STATS>
 __global__ __launch_bounds__(256) void edt_cols_kernel(double* __restrict__ buf, long vox, int L, long lstride, long ostride,
                                                        int W, int WC, int nwc, double s2, const unsigned char* __restrict__ surf,
                                                        long svs, int qmask0, int qmask1, double* __restrict__ partial, int P,
-                                                       unsigned long long* __restrict__ maxbits) {
+                                                       unsigned long long* __restrict__ maxbits, double cap2) {
+  static_assert(GATHER || !STATS, "the sums and the maximum belong to the gather form");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* red = (double*)smem;                                         // [256]
   double* f = (double*)(smem + 256 * sizeof(double));                  // [L][WC]
@@ -190,17 +207,23 @@ __global__ __launch_bounds__(256) void edt_cols_kernel(double* __restrict__ buf,
       for (int k = 1; k < L; ++k) {
         const double ck = s2 * (double)((long)k * k);
         if (!(ck < best)) break;
+        if constexpr (BOUNDED) {
+          if (ck > cap2) break;
+        }
         if (l >= k) best = fmin(best, f[(l - k) * WC + w] + ck);
         if (l + k < L) best = fmin(best, f[(l + k) * WC + w] + ck);
       }
+      if constexpr (BOUNDED) {
+        if (best > cap2) best = (double)INFINITY;
+      }
       col[(size_t)l * lstride + w] = best;
-      if constexpr (GATHER) {
+      if constexpr (STATS) {
         sum += sqrt(best);
         mx = fmax(mx, best);
       }
     }
   }
-  if constexpr (GATHER) {
+  if constexpr (STATS) {
     red[threadIdx.x] = sum;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -366,6 +389,86 @@ __global__ __launch_bounds__(256) void surface_finish_kernel(int V, long vox, co
   o[DUA_SURFACE_HD95_HI] = hi;
 }
 
+// ---- surface Dice (normalized surface Dice, voxel-count form) -----------------------------------------------------------------
+// The squared tolerances of the call, [classes][T] row-major, by value in the kernel arguments (at most 1 KiB): nothing is
+// copied to the device and nothing waits for a copy.  Volume v reads row v % classes.
+struct SurfaceTolerances {
+  double t2[DUA_SURFACE_MAX_TOLERANCE_ENTRIES];
+};
+
+// The surface voxels of volume v as in select_pass_kernel (16-byte groups of surface bytes, dist read only where a bit is set):
+// within[v][t][side] += #{surface voxels of side with d^2 <= tau_t^2}, side 0 = border(A) against border(B).  Per-thread integer
+// counts, shuffles across the wave, LDS across the block, one 64-bit integer atomic per block and (side, t).  within pre-zeroed.
+__global__ __launch_bounds__(SURF_THREADS) void surface_count_kernel(const unsigned char* __restrict__ surf, long svs,
+                                                                     const double* __restrict__ dist, long vox, int classes, int T,
+                                                                     const SurfaceTolerances tol,
+                                                                     unsigned long long* __restrict__ within) {
+  constexpr int MT = DUA_SURFACE_MAX_TOLERANCES;
+  __shared__ int red[SURF_THREADS / 64][2 * MT];
+  const int v = blockIdx.y, V = gridDim.y;
+  const double* row = tol.t2 + (size_t)(v % classes) * T;
+  double t2[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) t2[t] = t < T ? row[t] : -1.0;          // d^2 >= 0 is never within an unused slot
+  int cnt[2][MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) cnt[0][t] = cnt[1][t] = 0;
+  const uint4* s16 = (const uint4*)(surf + (size_t)v * svs);
+  const long groups = svs / 16;
+  const double* d0 = dist + (size_t)v * vox;
+  const double* d1 = dist + ((size_t)V + v) * vox;
+  for (int j = 0; j < SEL_GROUPS; ++j) {
+    const long g = ((long)blockIdx.x * SEL_GROUPS + j) * SURF_THREADS + threadIdx.x;
+    if (g >= groups) break;
+    const uint4 q = s16[g];
+    if ((q.x | q.y | q.z | q.w) == 0) continue;
+    const unsigned words[4] = {q.x, q.y, q.z, q.w};
+    for (int e = 0; e < 16; ++e) {
+      const unsigned s = (words[e >> 2] >> ((e & 3) * 8)) & 3u;
+      if (!s) continue;
+      const size_t p = (size_t)g * 16 + e;
+      if (s & 1u) {
+        const double d2 = d0[p];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) cnt[0][t] += d2 <= t2[t];
+      }
+      if (s & 2u) {
+        const double d2 = d1[p];
+#pragma unroll
+        for (int t = 0; t < MT; ++t) cnt[1][t] += d2 <= t2[t];
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int side = 0; side < 2; ++side)
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int c = wave_sum(cnt[side][t]);
+      if (lane == 0) red[wv][side * MT + t] = c;
+    }
+  __syncthreads();
+  if (threadIdx.x < 2 * MT) {
+    const int side = threadIdx.x / MT, t = threadIdx.x % MT;
+    long long total = 0;
+    for (int k = 0; k < SURF_THREADS / 64; ++k) total += red[k][threadIdx.x];
+    if (t < T && total) atomicAdd(&within[((size_t)v * T + t) * 2 + side], (unsigned long long)total);
+  }
+}
+
+// one thread per (v, t): nsd = (within_AB + within_BA) / (|border A| + |border B|), one fp64 division of two integers; no
+// surface voxel at all -> NaN (0 with nan_for_nonexisting = 0).  One empty border gives 0 by itself (nothing lies within).
+__global__ void surface_dice_finish_kernel(int V, int T, const unsigned long long* __restrict__ counts,
+                                           const unsigned long long* __restrict__ within, int nan_for_nonexisting,
+                                           double* __restrict__ nsd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V * T) return;
+  const int v = i / T;
+  const unsigned long long den = counts[(size_t)v * 5 + 3] + counts[(size_t)v * 5 + 4];
+  const unsigned long long num = within[(size_t)i * 2] + within[(size_t)i * 2 + 1];
+  nsd[i] = den ? (double)num / (double)den : (nan_for_nonexisting ? (double)NAN : 0.0);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
 static long align256(long x) { return (x + 255) & ~255L; }
@@ -396,32 +499,45 @@ static int cols_wc(int L, int W, bool gather) {
   return wc;
 }
 
-// the three EDT passes over dirs (1 or 2) directions: seeds [V][seeds_vs] bytes; out: dirs x [V][vox] fp64
+// the three EDT passes over dirs (1 or 2) directions: seeds [V][seeds_vs] bytes; out: dirs x [V][vox] fp64.
+// surf: the D pass in gather form (queries = the surface bytes' bits 1 | 2); partial and maxbits: with its sums and maxima.
+// bounded: the band-limited transform (exact up to cap2, +inf above); its gather form has no sums (no caller asks for both).
 static int edt_launch(int V, int D, int H, int W, const unsigned char* seeds, long seeds_vs, int smask0, int smask1, int dirs,
                       double sd, double sh, double sw, double* out, const unsigned char* surf, long svs, double* partial,
-                      unsigned long long* maxbits, hipStream_t s) {
+                      unsigned long long* maxbits, bool bounded, double cap2, hipStream_t s) {
   const long vox = (long)D * H * W, dir_stride = (long)V * vox;
   const int S = rows_stride(W);
   int R = ROWS_LDS / (S * 2);
   if (R > ROWS_THREADS) R = ROWS_THREADS;
   const long rows = (long)D * H;
-  hipLaunchKernelGGL(edt_rows_kernel, dim3((unsigned)((rows + R - 1) / R), V, dirs), dim3(ROWS_THREADS), (size_t)R * S * 2, s,
-                     seeds, seeds_vs, smask0, smask1, D, H, W, R, S, sw * sw, out, dir_stride);
+  const dim3 rgrid((unsigned)((rows + R - 1) / R), V, dirs);
+  if (bounded)
+    hipLaunchKernelGGL(edt_rows_kernel<true>, rgrid, dim3(ROWS_THREADS), (size_t)R * S * 2, s, seeds, seeds_vs, smask0, smask1, D,
+                       H, W, R, S, sw * sw, out, dir_stride, cap2);
+  else
+    hipLaunchKernelGGL(edt_rows_kernel<false>, rgrid, dim3(ROWS_THREADS), (size_t)R * S * 2, s, seeds, seeds_vs, smask0, smask1,
+                       D, H, W, R, S, sw * sw, out, dir_stride, 0.0);
+#define COLS_LAUNCH(G, B, ST, grid, lds, L, ls, os, wc, nwc, s2, P)                                                          \
+  hipLaunchKernelGGL((edt_cols_kernel<G, B, ST>), grid, dim3(256), lds, s, out, vox, L, ls, os, W, wc, nwc, s2,               \
+                     G ? surf : nullptr, G ? svs : 0L, G ? 1 : 0, G ? 2 : 0, ST ? partial : nullptr, P, ST ? maxbits : nullptr, \
+                     B ? cap2 : 0.0)
   // H pass: line along H (stride W), outer index d (stride H W)
   int wc = cols_wc(H, W, false), nwc = (W + wc - 1) / wc;
-  hipLaunchKernelGGL(edt_cols_kernel<false>, dim3((unsigned)((long)D * nwc), V, dirs), dim3(256), cols_lds(H, wc, false), s, out,
-                     vox, H, (long)W, (long)H * W, W, wc, nwc, sh * sh, nullptr, 0L, 0, 0, nullptr, 0, nullptr);
+  const dim3 hgrid((unsigned)((long)D * nwc), V, dirs);
+  if (bounded) COLS_LAUNCH(false, true, false, hgrid, cols_lds(H, wc, false), H, (long)W, (long)H * W, wc, nwc, sh * sh, 0);
+  else COLS_LAUNCH(false, false, false, hgrid, cols_lds(H, wc, false), H, (long)W, (long)H * W, wc, nwc, sh * sh, 0);
   // D pass: line along D (stride H W), outer index h (stride W)
-  const bool gather = surf != nullptr;
+  const bool gather = surf != nullptr, stats = partial != nullptr;
   wc = cols_wc(D, W, gather);
   nwc = (W + wc - 1) / wc;
   const dim3 grid((unsigned)((long)H * nwc), V, dirs);
-  if (gather)
-    hipLaunchKernelGGL(edt_cols_kernel<true>, grid, dim3(256), cols_lds(D, wc, true), s, out, vox, D, (long)H * W, (long)W,
-                       W, wc, nwc, sd * sd, surf, svs, 1, 2, partial, H * nwc, maxbits);
-  else
-    hipLaunchKernelGGL(edt_cols_kernel<false>, grid, dim3(256), cols_lds(D, wc, false), s, out, vox, D, (long)H * W,
-                       (long)W, W, wc, nwc, sd * sd, nullptr, 0L, 0, 0, nullptr, 0, nullptr);
+  const size_t lds = cols_lds(D, wc, gather);
+  if (gather && stats && !bounded) COLS_LAUNCH(true, false, true, grid, lds, D, (long)H * W, (long)W, wc, nwc, sd * sd, H * nwc);
+  else if (gather && !bounded) COLS_LAUNCH(true, false, false, grid, lds, D, (long)H * W, (long)W, wc, nwc, sd * sd, 0);
+  else if (gather) COLS_LAUNCH(true, true, false, grid, lds, D, (long)H * W, (long)W, wc, nwc, sd * sd, 0);
+  else if (bounded) COLS_LAUNCH(false, true, false, grid, lds, D, (long)H * W, (long)W, wc, nwc, sd * sd, 0);
+  else COLS_LAUNCH(false, false, false, grid, lds, D, (long)H * W, (long)W, wc, nwc, sd * sd, 0);
+#undef COLS_LAUNCH
   return (int)hipGetLastError();
 }
 
@@ -462,7 +578,99 @@ static SurfaceScratch scratch_layout(int V, int D, int H, int W) {
 
 static bool mask_dtype_ok(int t) { return t == DUA_F32 || t == DUA_U8; }
 
+// surface Dice alone: the surface bytes and the two distance volumes
+struct DiceScratch {
+  long surf, dist, total;
+};
+
+static DiceScratch dice_layout(int V, int D, int H, int W) {
+  DiceScratch L;
+  const long vox = (long)D * H * W;
+  L.surf = 0;
+  L.dist = align256((long)V * align256(vox));
+  L.total = align256(L.dist + 2L * V * vox * 8);
+  return L;
+}
+
+// the [classes][T] table of a call: squared (tau * tau, rounded once) into tol, the largest square into cap2
+static bool tolerances_ok(int V, int classes, int T, const double* tolerances, SurfaceTolerances& tol, double& cap2) {
+  if (!tolerances || classes < 1 || V % classes != 0 || T < 1 || T > DUA_SURFACE_MAX_TOLERANCES ||
+      (long)classes * T > DUA_SURFACE_MAX_TOLERANCE_ENTRIES)
+    return false;
+  cap2 = 0.0;
+  for (int i = 0; i < DUA_SURFACE_MAX_TOLERANCE_ENTRIES; ++i) tol.t2[i] = -1.0;
+  for (int i = 0; i < classes * T; ++i) {
+    const double t = tolerances[i];
+    if (!isfinite(t) || t < 0.0) return false;
+    tol.t2[i] = t * t;
+    if (tol.t2[i] > cap2) cap2 = tol.t2[i];
+  }
+  return true;
+}
+
+// count and finish on a gathered dist buffer (both directions): within [V][T][2], nsd [V][T]
+static int dice_launch(int V, long vox, const unsigned char* surf, long svs, const double* dist, int classes, int T,
+                       const SurfaceTolerances& tol, const unsigned long long* counts, int nan_for_nonexisting,
+                       unsigned long long* within, double* nsd, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(within, 0, (size_t)V * T * 2 * sizeof(unsigned long long), s);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid((unsigned)((svs / 16 + SURF_THREADS * SEL_GROUPS - 1) / (SURF_THREADS * SEL_GROUPS)), V);
+  hipLaunchKernelGGL(surface_count_kernel, grid, dim3(SURF_THREADS), 0, s, surf, svs, dist, vox, classes, T, tol, within);
+  hipLaunchKernelGGL(surface_dice_finish_kernel, dim3((V * T + 255) / 256), dim3(256), 0, s, V, T, counts, within,
+                     nan_for_nonexisting, nsd);
+  return (int)hipGetLastError();
+}
+
 }  // namespace dua
+
+// the distance table; with tol, the surface Dice outputs too, counted on the same dist buffer (dua_surface_report)
+static int surface_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride, const void* reference,
+                         int reference_dtype, long reference_vstride, int connectivity, double sd, double sh, double sw,
+                         int nan_for_nonexisting, unsigned long long* counts, double* out, void* workspace, long workspace_bytes,
+                         int classes, int T, const dua::SurfaceTolerances* tol, unsigned long long* within, double* nsd,
+                         void* stream) {
+  const long vox = (long)D * H * W;
+  if (!dua::extents_ok(V, D, H, W) || !test || !reference || !counts || !out || !workspace || connectivity < 1 ||
+      connectivity > 3 || !dua::mask_dtype_ok(test_dtype) || !dua::mask_dtype_ok(reference_dtype) || test_vstride < vox ||
+      reference_vstride < vox || !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw))
+    return DUA_ERR_ARG;
+  const dua::SurfaceScratch L = dua::scratch_layout(V, D, H, W);
+  if (workspace_bytes < L.total || ((size_t)workspace & 255) != 0) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  unsigned char* surf = ws + L.surf;
+  double* dist = (double*)(ws + L.dist);
+  double* partial = (double*)(ws + L.partial);
+  unsigned long long* maxbits = (unsigned long long*)(ws + L.maxbits);
+  unsigned* hist = (unsigned*)(ws + L.hist);
+  unsigned long long* sel = (unsigned long long*)(ws + L.sel);
+  unsigned long long* nextmin = (unsigned long long*)(ws + L.nextmin);
+  const long svs = dua::align256(vox);
+  int rc = dua::masks_launch(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride,
+                             connectivity, surf, svs, counts, s);
+  if (rc) return rc;
+  hipError_t e = hipMemsetAsync(maxbits, 0, (size_t)2 * V * 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, (size_t)V * 256 * 4, s);
+  if (e == hipSuccess) e = hipMemsetAsync(nextmin, 0xFF, (size_t)V * 8, s);
+  if (e != hipSuccess) return (int)e;
+  // direction 0: seeds border(B) (bit 1), read at border(A) (bit 0); direction 1 the other way round
+  rc = dua::edt_launch(V, D, H, W, surf, svs, 2, 1, 2, sd, sh, sw, dist, surf, svs, partial, maxbits, false, 0.0, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(dua::select_init_kernel, dim3((V + 255) / 256), dim3(256), 0, s, V, counts, sel);
+  const dim3 sgrid((unsigned)((svs / 16 + dua::SURF_THREADS * dua::SEL_GROUPS - 1) / (dua::SURF_THREADS * dua::SEL_GROUPS)), V);
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    hipLaunchKernelGGL(dua::select_pass_kernel<0>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, shift, sel, hist,
+                       nextmin);
+    hipLaunchKernelGGL(dua::select_step_kernel, dim3(V), dim3(256), 0, s, shift, sel, hist);
+  }
+  hipLaunchKernelGGL(dua::select_pass_kernel<1>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, 0, sel, hist, nextmin);
+  const int wc = dua::cols_wc(D, W, true);
+  hipLaunchKernelGGL(dua::surface_finish_kernel, dim3(V), dim3(256), 0, s, V, vox, counts, partial, H * ((W + wc - 1) / wc),
+                     maxbits, sel, nextmin, nan_for_nonexisting, out);
+  if (tol) return dua::dice_launch(V, vox, surf, svs, dist, classes, T, *tol, counts, nan_for_nonexisting, within, nsd, s);
+  return (int)hipGetLastError();
+}
+
 
 extern "C" {
 
@@ -490,52 +698,73 @@ int dua_surface_edt_sq(int V, int D, int H, int W, const unsigned char* seeds, l
       !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw))
     return DUA_ERR_ARG;
   return dua::edt_launch(V, D, H, W, seeds, seeds_vstride, seed_mask, seed_mask, 1, sd, sh, sw, out, nullptr, 0, nullptr, nullptr,
-                         (hipStream_t)stream);
+                         false, 0.0, (hipStream_t)stream);
 }
+
+int dua_surface_edt_sq_bounded(int V, int D, int H, int W, const unsigned char* seeds, long seeds_vstride, int seed_mask,
+                               double sd, double sh, double sw, double max_distance, double* out, void* stream) {
+  const long vox = (long)D * H * W;
+  if (!dua::extents_ok(V, D, H, W) || !seeds || !out || seeds_vstride < vox || (seed_mask & 255) == 0 ||
+      !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw) || !(max_distance >= 0.0))
+    return DUA_ERR_ARG;
+  return dua::edt_launch(V, D, H, W, seeds, seeds_vstride, seed_mask, seed_mask, 1, sd, sh, sw, out, nullptr, 0, nullptr, nullptr,
+                         true, max_distance * max_distance, (hipStream_t)stream);
+}
+
 
 int dua_surface_distance_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride,
                                const void* reference, int reference_dtype, long reference_vstride, int connectivity, double sd,
                                double sh, double sw, int nan_for_nonexisting, unsigned long long* counts, double* out,
                                void* workspace, long workspace_bytes, void* stream) {
+  return surface_table(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride, connectivity,
+                       sd, sh, sw, nan_for_nonexisting, counts, out, workspace, workspace_bytes, 0, 0, nullptr, nullptr, nullptr,
+                       stream);
+}
+
+long dua_surface_dice_scratch_bytes(int V, int D, int H, int W) {
+  if (!dua::extents_ok(V, D, H, W)) return DUA_ERR_ARG;
+  return dua::dice_layout(V, D, H, W).total;
+}
+
+int dua_surface_dice_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride,
+                           const void* reference, int reference_dtype, long reference_vstride, int connectivity, double sd,
+                           double sh, double sw, int classes, int T, const double* tolerances, int nan_for_nonexisting,
+                           int bounded, unsigned long long* counts, unsigned long long* within, double* nsd, void* workspace,
+                           long workspace_bytes, void* stream) {
   const long vox = (long)D * H * W;
-  if (!dua::extents_ok(V, D, H, W) || !test || !reference || !counts || !out || !workspace || connectivity < 1 ||
+  dua::SurfaceTolerances tol;
+  double cap2 = 0.0;
+  if (!dua::extents_ok(V, D, H, W) || !test || !reference || !counts || !within || !nsd || !workspace || connectivity < 1 ||
       connectivity > 3 || !dua::mask_dtype_ok(test_dtype) || !dua::mask_dtype_ok(reference_dtype) || test_vstride < vox ||
-      reference_vstride < vox || !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw))
+      reference_vstride < vox || !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw) ||
+      !dua::tolerances_ok(V, classes, T, tolerances, tol, cap2))
     return DUA_ERR_ARG;
-  const dua::SurfaceScratch L = dua::scratch_layout(V, D, H, W);
+  const dua::DiceScratch L = dua::dice_layout(V, D, H, W);
   if (workspace_bytes < L.total || ((size_t)workspace & 255) != 0) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)workspace;
-  unsigned char* surf = ws + L.surf;
-  double* dist = (double*)(ws + L.dist);
-  double* partial = (double*)(ws + L.partial);
-  unsigned long long* maxbits = (unsigned long long*)(ws + L.maxbits);
-  unsigned* hist = (unsigned*)(ws + L.hist);
-  unsigned long long* sel = (unsigned long long*)(ws + L.sel);
-  unsigned long long* nextmin = (unsigned long long*)(ws + L.nextmin);
+  unsigned char* surf = (unsigned char*)workspace + L.surf;
+  double* dist = (double*)((unsigned char*)workspace + L.dist);
   const long svs = dua::align256(vox);
   int rc = dua::masks_launch(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride,
                              connectivity, surf, svs, counts, s);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(maxbits, 0, (size_t)2 * V * 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, (size_t)V * 256 * 4, s);
-  if (e == hipSuccess) e = hipMemsetAsync(nextmin, 0xFF, (size_t)V * 8, s);
-  if (e != hipSuccess) return (int)e;
   // direction 0: seeds border(B) (bit 1), read at border(A) (bit 0); direction 1 the other way round
-  rc = dua::edt_launch(V, D, H, W, surf, svs, 2, 1, 2, sd, sh, sw, dist, surf, svs, partial, maxbits, s);
+  rc = dua::edt_launch(V, D, H, W, surf, svs, 2, 1, 2, sd, sh, sw, dist, surf, svs, nullptr, nullptr, bounded != 0, cap2, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(dua::select_init_kernel, dim3((V + 255) / 256), dim3(256), 0, s, V, counts, sel);
-  const dim3 sgrid((unsigned)((svs / 16 + dua::SURF_THREADS * dua::SEL_GROUPS - 1) / (dua::SURF_THREADS * dua::SEL_GROUPS)), V);
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    hipLaunchKernelGGL(dua::select_pass_kernel<0>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, shift, sel, hist,
-                       nextmin);
-    hipLaunchKernelGGL(dua::select_step_kernel, dim3(V), dim3(256), 0, s, shift, sel, hist);
-  }
-  hipLaunchKernelGGL(dua::select_pass_kernel<1>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, 0, sel, hist, nextmin);
-  const int wc = dua::cols_wc(D, W, true);
-  hipLaunchKernelGGL(dua::surface_finish_kernel, dim3(V), dim3(256), 0, s, V, vox, counts, partial, H * ((W + wc - 1) / wc),
-                     maxbits, sel, nextmin, nan_for_nonexisting, out);
-  return (int)hipGetLastError();
+  return dua::dice_launch(V, vox, surf, svs, dist, classes, T, tol, counts, nan_for_nonexisting, within, nsd, s);
+}
+
+int dua_surface_report(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride, const void* reference,
+                       int reference_dtype, long reference_vstride, int connectivity, double sd, double sh, double sw, int classes,
+                       int T, const double* tolerances, int nan_for_nonexisting, unsigned long long* counts, double* out,
+                       unsigned long long* within, double* nsd, void* workspace, long workspace_bytes, void* stream) {
+  dua::SurfaceTolerances tol;
+  double cap2 = 0.0;
+  if (!within || !nsd || !dua::extents_ok(V, D, H, W) || !dua::tolerances_ok(V, classes, T, tolerances, tol, cap2))
+    return DUA_ERR_ARG;
+  return surface_table(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride, connectivity,
+                       sd, sh, sw, nan_for_nonexisting, counts, out, workspace, workspace_bytes, classes, T, &tol, within, nsd,
+                       stream);
 }
 
 }  // extern "C"

@@ -375,7 +375,7 @@ def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_s
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
                     overlap: float = 0.25, distributed: bool = False, group=None, postprocess: dict = None,
-                    mode: str = "constant", sigma_scale=0.125):
+                    surface: dict = None, mode: str = "constant", sigma_scale=0.125):
     """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
     [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
     written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
@@ -385,8 +385,14 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     num_components, min_size, channels, cap): the finish pass then writes the mask only, the component filter runs on it and
     tallies Dice in its own pass, and the result is (filtered mask, Dice of the filtered mask).
     A ``model`` built with ``uncer_step=R`` needs no argument here: each predictor call then runs R DDIM loops per window and
-    returns their Step-Uncertainty Fusion (a plan of sw_batch_size R rows)."""
+    returns their Step-Uncertainty Fusion (a plan of sw_batch_size R rows).
+    ``surface``: None, or a dict with keys among ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting",
+    "distances"); it needs ``labels``.  The result is then (mask, dice, report): ``metrics.surface_dice_table`` (Normalized
+    Surface Dice at ``tolerance``) of the returned mask -- the filtered one with ``postprocess`` -- against the labels, or
+    ``metrics.surface_report`` (the distance table too) with ``distances=True``."""
     from . import ops
+    if surface is not None:
+        _surface_kwargs(surface, labels)
     _need_device(image, "evaluate_volume")
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
@@ -402,7 +408,34 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
             mask, tallies = filter_components(mask, labels=labels, **postprocess)
         else:
             _, mask, tallies = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
-    return mask, (ops.dice_from_tallies(tallies) if tallies is not None else None)
+    dice = ops.dice_from_tallies(tallies) if tallies is not None else None
+    if surface is None:
+        return mask, dice
+    from . import metrics
+    kw = dict(surface)
+    fn = metrics.surface_report if kw.pop("distances", False) else metrics.surface_dice_table
+    return mask, dice, fn(mask, _one_hot_labels(labels, mask.shape[1]), kw.pop("tolerance"), **kw)
+
+
+SURFACE_KEYS = ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting", "distances")
+
+
+def _surface_kwargs(surface, labels):
+    """Refuse a ``surface`` argument that is not a dict of these keys with a tolerance, or that comes without labels, before any
+    predictor call."""
+    if not isinstance(surface, dict) or any(k not in SURFACE_KEYS for k in surface) or "tolerance" not in surface:
+        raise ValueError(f"surface: None or a dict with a 'tolerance' and keys among {SURFACE_KEYS}, got {surface!r}")
+    if labels is None:
+        raise ValueError("surface: the surface metrics compare the mask with labels; labels is None")
+
+
+def _one_hot_labels(labels, channels):
+    """``evaluate_volume``'s labels as a [B, C, D, H, W] mask: a one-hot tensor as it is, a uint8 label map [B, D, H, W]
+    expanded (class c = channel c)."""
+    if labels.dim() == 4:
+        classes = torch.arange(channels, device=labels.device, dtype=labels.dtype).view(1, channels, 1, 1, 1)
+        return labels[:, None] == classes
+    return labels
 
 
 POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "channels", "cap")
@@ -440,8 +473,8 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
     if streaming:
-        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess, mode,
-                               sigma_scale)[0].float()
+        return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess,
+                               mode=mode, sigma_scale=sigma_scale)[0].float()
     fn = sharded_sliding_window_inference if distributed else sliding_window_inference
     kw = dict(group=group) if distributed else {}
     with torch.no_grad():

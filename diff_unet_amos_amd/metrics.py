@@ -13,6 +13,17 @@ batch in HIP (csrc/surface.hip, include/dua_hip.h "evaluation: surface distances
 Metrics are taken per (n, c) on the 3-D volume [D, H, W].  (Handed a [1, D, H, W] array, medpy would treat the batch as a
 fourth axis, and its border-value-0 erosion along that axis would make every foreground voxel a surface voxel; that behaviour
 is not reproduced.)  There is no CPU path.
+
+``surface_dice_table`` adds Normalized Surface Dice (surface Dice at a tolerance), the second AMOS ranking metric, in the
+voxel-count form (the one MONAI's SurfaceDiceMetric uses), with the same border and distances:
+
+- within(A, B, tau) = the number of voxels of border(A) whose distance to border(B) is <= tau (compared squared, in fp64);
+- nsd(tau) = (within(A, B) + within(B, A)) / (|border A| + |border B|);
+- one border empty -> 0; both empty -> NaN, or 0 with nan_for_nonexisting=False.  The wrapper rule above does not apply (a full
+  mask has a border: the faces of the volume).
+
+The surfel-area-weighted form of the DeepMind ``surface-distance`` library is deliberately not provided; numbers of the two
+forms must not be compared.  ``surface_report`` gives the distance table and the surface Dice from one distance transform.
 """
 from __future__ import annotations
 
@@ -22,6 +33,7 @@ from . import _native as nv
 from . import ops
 
 TABLE_KEYS = ("hd", "hd95", "asd", "assd", "tp", "fp", "fn", "tn")
+DICE_KEYS = ("nsd", "within_test", "within_reference", "surface_test", "surface_reference")
 
 
 def _device_mask(t, name):
@@ -81,3 +93,85 @@ def avg_surface_distance_symmetric(test=None, reference=None, confusion_matrix=N
                                    voxel_spacing=None, connectivity=1, **kwargs):
     """metric.py:371-386 for one 3-D mask pair: a Python float."""
     return _one(test, reference, "assd", nan_for_nonexisting, voxel_spacing, connectivity)
+
+
+def _pair5(test, reference, connectivity):
+    test, reference = _device_mask(test, "test"), _device_mask(reference, "reference")
+    if test.dim() != 5 or tuple(test.shape) != tuple(reference.shape):
+        raise ValueError(f"test and reference: two [N, C, D, H, W] masks of one shape, got {tuple(test.shape)} and "
+                         f"{tuple(reference.shape)}")
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1, 2 or 3, got {connectivity!r}")
+    return test, reference
+
+
+def _tolerance_rows(tolerance, classes):
+    """``tolerance`` as a [classes][T] list of floats: a scalar (every class, T = 1), a length-``classes`` sequence (one per
+    class, T = 1) or a [classes, T] array."""
+    if isinstance(tolerance, torch.Tensor):
+        tolerance = tolerance.tolist()
+    elif hasattr(tolerance, "tolist"):
+        tolerance = tolerance.tolist()
+    if isinstance(tolerance, (int, float)):
+        rows = [[float(tolerance)]] * classes
+    else:
+        tolerance = list(tolerance)
+        if len(tolerance) != classes:
+            raise ValueError(f"tolerance: a scalar, {classes} values (one per class) or a [{classes}, T] table, got "
+                             f"{tolerance!r}")
+        rows = [[float(x) for x in r] if isinstance(r, (list, tuple)) else [float(r)] for r in tolerance]
+    T = len(rows[0])
+    limit = nv.SURFACE_MAX_TOLERANCE_ENTRIES
+    if any(len(r) != T for r in rows) or not 1 <= T <= nv.SURFACE_MAX_TOLERANCES or classes * T > limit:
+        raise ValueError(f"tolerance: 1 to {nv.SURFACE_MAX_TOLERANCES} values per class and at most {limit} in all, got "
+                         f"{tolerance!r}")
+    if not all(0.0 <= x < float("inf") for r in rows for x in r):
+        raise ValueError(f"tolerance: finite values >= 0, got {tolerance!r}")
+    return rows
+
+
+def _dice_dict(counts, within, nsd, N, Cc):
+    T = nsd.shape[1]
+    return {"nsd": nsd.reshape(N, Cc, T), "within_test": within[:, :, 0].reshape(N, Cc, T),
+            "within_reference": within[:, :, 1].reshape(N, Cc, T), "surface_test": counts[:, 3].reshape(N, Cc),
+            "surface_reference": counts[:, 4].reshape(N, Cc)}
+
+
+def surface_dice_table(test, reference, tolerance, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True):
+    """Normalized Surface Dice (voxel-count form; not the surfel-area form of the DeepMind surface-distance library) of every
+    (n, c) of two [N, C, D, H, W] device masks (dtypes as ``surface_distance_table``).  ``tolerance``, in the unit of
+    voxel_spacing: a scalar, a length-C sequence (one per class) or a [C, T] table (T tolerances per class, 1 <= T <= 8,
+    C T <= 128), finite and >= 0.  Returns a dict of device tensors: ``nsd`` fp64 [N, C, T]; ``within_test`` /
+    ``within_reference`` int64 [N, C, T] (surface voxels of test / reference within the tolerance of the other surface);
+    ``surface_test`` / ``surface_reference`` int64 [N, C] (|border|).  nsd = (within_test + within_reference) / (surface_test +
+    surface_reference); one surface empty -> 0; both empty -> NaN (0 with nan_for_nonexisting=False).  Nothing is synchronised
+    with the host."""
+    test, reference = _pair5(test, reference, connectivity)
+    N, Cc = test.shape[:2]
+    rows = _tolerance_rows(tolerance, Cc)
+    counts, within, nsd = ops.surface_dice_table(test, reference, rows, voxel_spacing, connectivity, nan_for_nonexisting)
+    return _dice_dict(counts, within, nsd, N, Cc)
+
+
+def surface_report(test, reference, tolerance, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True):
+    """The keys of ``surface_distance_table`` and of ``surface_dice_table`` in one dict, from one border pass and one distance
+    transform (dua_surface_report); every value is bit-identical to the separate calls'."""
+    test, reference = _pair5(test, reference, connectivity)
+    N, Cc = test.shape[:2]
+    rows = _tolerance_rows(tolerance, Cc)
+    counts, table, within, nsd = ops.surface_report(test, reference, rows, voxel_spacing, connectivity, nan_for_nonexisting)
+    col = {name: i for i, name in enumerate(nv.SURFACE_FIELDS)}
+    out = {k: table[:, col[k]].reshape(N, Cc) for k in TABLE_KEYS}
+    out.update(_dice_dict(counts, within, nsd, N, Cc))
+    return out
+
+
+def normalized_surface_dice(test, reference, tolerance, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True):
+    """Normalized Surface Dice of one 3-D mask pair at one tolerance (voxel-count form, see ``surface_dice_table``): a Python
+    float."""
+    test, reference = _device_mask(test, "test"), _device_mask(reference, "reference")
+    if test.dim() != 3 or tuple(test.shape) != tuple(reference.shape):
+        raise ValueError(f"test and reference: two 3-D masks of one shape, got {tuple(test.shape)} and {tuple(reference.shape)}")
+    t = surface_dice_table(test[None, None], reference[None, None], float(tolerance), voxel_spacing, connectivity,
+                           nan_for_nonexisting)
+    return float(t["nsd"][0, 0, 0])

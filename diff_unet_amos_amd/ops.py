@@ -1588,13 +1588,19 @@ def surface_masks(test, reference, connectivity=1):
     return surf, counts
 
 
-def surface_edt_sq(seeds, voxel_spacing=None, seed_mask=1):
+def surface_edt_sq(seeds, voxel_spacing=None, seed_mask=1, max_distance=None):
     """dua_surface_edt_sq: fp64 [V, D, H, W] squared distance (offsets scaled by voxel_spacing = (d, h, w)) to the nearest voxel
-    of seeds (uint8 [..., D, H, W]) with a bit of seed_mask set; +inf in a volume without seeds."""
+    of seeds (uint8 [..., D, H, W]) with a bit of seed_mask set; +inf in a volume without seeds.  max_distance (a float >= 0):
+    dua_surface_edt_sq_bounded, the same bits wherever the value is <= max_distance ** 2 and +inf everywhere else."""
     assert seeds.is_cuda and seeds.dtype in (torch.uint8, torch.bool)
     s, _, V, D, H, W = _surface_mask(seeds, "seeds")
     sd, sh, sw = _spacing3(voxel_spacing)
     out = torch.empty((V, D, H, W), dtype=torch.float64, device=s.device)
+    if max_distance is not None:
+        nv.check(nv.lib().dua_surface_edt_sq_bounded(V, D, H, W, nv.ptr(s), D * H * W, int(seed_mask), sd, sh, sw,
+                                                     float(max_distance), nv.ptr(out), nv.stream_ptr()),
+                 "dua_surface_edt_sq_bounded")
+        return out
     nv.check(nv.lib().dua_surface_edt_sq(V, D, H, W, nv.ptr(s), D * H * W, int(seed_mask), sd, sh, sw, nv.ptr(out),
                                          nv.stream_ptr()), "dua_surface_edt_sq")
     return out
@@ -1619,6 +1625,67 @@ def surface_distance_table(test, reference, voxel_spacing=None, connectivity=1, 
                                           int(bool(nan_for_nonexisting)), nv.ptr(counts), nv.ptr(out), nv.ptr(ws), need,
                                           nv.stream_ptr()), "dua_surface_distance_table")
     return counts, out
+
+
+def _tolerance_table(tolerances):
+    """A [classes][T] table of tolerances as (ctypes fp64 array, classes, T).  The limits and the values are checked by the entry
+    point (DUA_ERR_ARG); here only the shape."""
+    import ctypes as C
+    rows = [[float(x) for x in row] for row in tolerances]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError(f"tolerances: a [classes][T] table with classes >= 1 and T >= 1, got {tolerances!r}")
+    flat = [x for r in rows for x in r]
+    return (C.c_double * len(flat))(*flat), len(rows), len(rows[0])
+
+
+def surface_dice_table(test, reference, tolerances, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True, bounded=True):
+    """dua_surface_dice_table for every volume of test / reference ([..., D, H, W], same shape): normalized surface Dice in the
+    voxel-count form (not the surfel-area form of the DeepMind surface-distance library).  tolerances: a host [classes][T] table
+    (nested sequences), volume v reads row v % classes.  Returns (counts int64 [V, 5], within int64 [V, T, 2] with [..., 0] =
+    test -> reference, nsd fp64 [V, T]).  bounded: the band-limited distance transform (the same outputs; kept for the A/B).
+    No host synchronisation."""
+    a, ca, V, D, H, W = _surface_mask(test, "test")
+    b, cb, Vb, *ext = _surface_mask(reference, "reference")
+    assert (Vb, *ext) == (V, D, H, W), "test and reference must have the same shape"
+    sd, sh, sw = _spacing3(voxel_spacing)
+    tol, classes, T = _tolerance_table(tolerances)
+    L = nv.lib()
+    need = int(L.dua_surface_dice_scratch_bytes(V, D, H, W))
+    if need < 0:
+        raise ValueError(f"surface Dice: unsupported extents V={V}, D={D}, H={H}, W={W}")
+    ws = torch.empty(need, dtype=torch.uint8, device=a.device)
+    counts = torch.empty((V, 5), dtype=torch.int64, device=a.device)
+    within = torch.empty((V, T, 2), dtype=torch.int64, device=a.device)
+    nsd = torch.empty((V, T), dtype=torch.float64, device=a.device)
+    vox = D * H * W
+    nv.check(L.dua_surface_dice_table(V, D, H, W, nv.ptr(a), ca, vox, nv.ptr(b), cb, vox, int(connectivity), sd, sh, sw, classes,
+                                      T, tol, int(bool(nan_for_nonexisting)), int(bool(bounded)), nv.ptr(counts),
+                                      nv.ptr(within), nv.ptr(nsd), nv.ptr(ws), need, nv.stream_ptr()), "dua_surface_dice_table")
+    return counts, within, nsd
+
+
+def surface_report(test, reference, tolerances, voxel_spacing=None, connectivity=1, nan_for_nonexisting=True):
+    """dua_surface_report: what surface_distance_table and surface_dice_table return, from one border pass and one unbounded
+    transform: (counts int64 [V, 5], table fp64 [V, len(nv.SURFACE_FIELDS)], within int64 [V, T, 2], nsd fp64 [V, T])."""
+    a, ca, V, D, H, W = _surface_mask(test, "test")
+    b, cb, Vb, *ext = _surface_mask(reference, "reference")
+    assert (Vb, *ext) == (V, D, H, W), "test and reference must have the same shape"
+    sd, sh, sw = _spacing3(voxel_spacing)
+    tol, classes, T = _tolerance_table(tolerances)
+    L = nv.lib()
+    need = int(L.dua_surface_scratch_bytes(V, D, H, W))
+    if need < 0:
+        raise ValueError(f"surface distances: unsupported extents V={V}, D={D}, H={H}, W={W}")
+    ws = torch.empty(need, dtype=torch.uint8, device=a.device)
+    counts = torch.empty((V, 5), dtype=torch.int64, device=a.device)
+    out = torch.empty((V, len(nv.SURFACE_FIELDS)), dtype=torch.float64, device=a.device)
+    within = torch.empty((V, T, 2), dtype=torch.int64, device=a.device)
+    nsd = torch.empty((V, T), dtype=torch.float64, device=a.device)
+    vox = D * H * W
+    nv.check(L.dua_surface_report(V, D, H, W, nv.ptr(a), ca, vox, nv.ptr(b), cb, vox, int(connectivity), sd, sh, sw, classes, T,
+                                  tol, int(bool(nan_for_nonexisting)), nv.ptr(counts), nv.ptr(out), nv.ptr(within), nv.ptr(nsd),
+                                  nv.ptr(ws), need, nv.stream_ptr()), "dua_surface_report")
+    return counts, out, within, nsd
 
 
 # ---- evaluation: connected components (csrc/components.hip) -------------------------------------------------------------------

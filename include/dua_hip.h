@@ -834,6 +834,50 @@ int dua_surface_distance_table(int V, int D, int H, int W, const void* test, int
                                double sh, double sw, int nan_for_nonexisting, unsigned long long* counts, double* out,
                                void* workspace, long workspace_bytes, void* stream);
 
+/* ---- evaluation: normalized surface Dice ------------------------------------------------------------------------------------
+ * Normalized Surface Dice (surface Dice at a tolerance) in the voxel-count form, per pair A (test), B (reference), with the
+ * border, distances, masks, strides, spacings and connectivity of the section above:
+ *   d_AB(v)       = for v in border(A), the Euclidean distance to the nearest voxel of border(B); +inf when border(B) is empty;
+ *   within_AB(t)  = #{v in border(A) : d_AB(v)^2 <= t * t}, the comparison on squared distances in fp64 (t * t rounded once, the
+ *                   squared distance exactly the value the transform holds; no square root);  within_BA likewise;
+ *   nsd(t)        = (within_AB + within_BA) / (|border A| + |border B|), one fp64 division of two integers;
+ *   one border empty -> 0; both empty -> NaN (0 with nan_for_nonexisting = 0).  The wrapper rule of the distance table (a full
+ *   mask -> NaN) does NOT apply: a full mask has a border, the faces of the volume.
+ * This is NOT the surfel-area-weighted surface Dice of the DeepMind surface-distance library: numbers of the two forms are not
+ * comparable.
+ * Tolerances: a HOST array fp64 [classes][T], 1 <= T <= DUA_SURFACE_MAX_TOLERANCES, classes * T <=
+ * DUA_SURFACE_MAX_TOLERANCE_ENTRIES, classes >= 1 and V % classes == 0, every value finite and >= 0 (0 counts coincident border
+ * voxels).  Volume v uses row v % classes.  The table is read before the call returns and travels to the device inside the
+ * kernel arguments: no copy, no synchronisation, capturable.  Outputs: counts as dua_surface_masks; within (uint64 [V][T][2],
+ * WRITTEN; [..][0] = within_AB, [..][1] = within_BA); nsd (fp64 [V][T], WRITTEN).  Integer atomics only: two calls agree bit
+ * for bit.  Invalid arguments: DUA_ERR_ARG, before the device is touched. */
+#define DUA_SURFACE_MAX_TOLERANCES 8
+#define DUA_SURFACE_MAX_TOLERANCE_ENTRIES 128
+/* The band-limited squared distance transform: dua_surface_edt_sq, but out is exact (bit-identical to dua_surface_edt_sq) where
+ * the distance is <= max_distance (compared squared: value <= max_distance * max_distance) and +inf everywhere else; no search
+ * goes further than max_distance.  max_distance >= 0 (+inf allowed: the unbounded result), not NaN. */
+int dua_surface_edt_sq_bounded(int V, int D, int H, int W, const unsigned char* seeds, long seeds_vstride, int seed_mask,
+                               double sd, double sh, double sw, double max_distance, double* out, void* stream);
+/* Bytes of workspace dua_surface_dice_table needs (DUA_ERR_ARG for bad extents): the surface bytes and two fp64 distance
+ * volumes per pair. */
+long dua_surface_dice_scratch_bytes(int V, int D, int H, int W);
+/* Surface Dice alone: the border pass, the transform in both directions evaluated at the surface voxels only, one counting
+ * pass, the division.  bounded != 0: the band-limited transform with max_distance = the largest tolerance of the table;
+ * bounded = 0: the unbounded one; the outputs are identical.  workspace: at least dua_surface_dice_scratch_bytes(V, D, H, W)
+ * bytes, 256-byte aligned. */
+int dua_surface_dice_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride,
+                           const void* reference, int reference_dtype, long reference_vstride, int connectivity, double sd,
+                           double sh, double sw, int classes, int T, const double* tolerances, int nan_for_nonexisting,
+                           int bounded, unsigned long long* counts, unsigned long long* within, double* nsd, void* workspace,
+                           long workspace_bytes, void* stream);
+/* A case report: everything dua_surface_distance_table writes (counts, out; same values bit for bit) and the surface Dice
+ * outputs of dua_surface_dice_table, from one border pass and one unbounded transform; the counting pass reads the distance
+ * buffer the table leaves.  workspace: at least dua_surface_scratch_bytes(V, D, H, W) bytes, 256-byte aligned. */
+int dua_surface_report(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride, const void* reference,
+                       int reference_dtype, long reference_vstride, int connectivity, double sd, double sh, double sw, int classes,
+                       int T, const double* tolerances, int nan_for_nonexisting, unsigned long long* counts, double* out,
+                       unsigned long long* within, double* nsd, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- evaluation: connected components -----------------------------------------------------------------------------------
  * Connected-component labelling of V = N * C binary volumes [D][H][W] and the post-processing filter built on it (keep the
  * k largest components of each class, drop components below a size), between the mask of dua_blend_finish and the surface
