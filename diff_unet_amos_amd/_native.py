@@ -299,6 +299,10 @@ _SIGS = {
     "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "dua_blend_accumulate_weighted": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P] +
                                       [C.c_int] * 4 + [_P, _P]),
+    "dua_blend_accumulate_mirrored": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 +
+                                      [_P, _P]),
+    "dua_blend_accumulate_weighted_mirrored": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                                                       C.c_float, _P] + [C.c_int] * 4 + [_P, _P]),
     "dua_blend_weight_sum": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P,
                                        C.c_int, C.c_int, C.c_int, _P]),
     "dua_blend_finish_weighted": (C.c_int, [_P] + [C.c_int] * 5 + [_P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),

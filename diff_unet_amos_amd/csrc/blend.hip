@@ -26,6 +26,13 @@
 //            plan's per-axis starts (a voxel loops over the starts that cover it, D-major = window-index order); and finish
 //            divides by that volume instead of the product of three counts, same kernel body.  Every product and sum is a
 //            single rounded fp32 operation (__fmul_rn / __fadd_rn): the bits of `out[slice] += w * o; cnt[slice] += w`.
+//   mirrored forms (mirror test-time augmentation): the un-flip of a window predicted under axis flips is a different READ ORDER
+//            of the window side, template flag MIRROR on the two accumulate kernels.  The lanes still own the volume's 16-byte
+//            groups; a flip of D or H only changes which window row a lane reads, and a flip of W means the four volume
+//            elements at window x0 .. x0 + 3 come from window elements rw-1-x0-3 .. rw-1-x0: one vector load where that
+//            address is aligned (as often as in the unmirrored form when rw is a multiple of 4), reversed in registers.  The
+//            importance weight stays indexed by the volume-side (z, y, x): it multiplies the un-flipped output.  MIRROR = false
+//            is the kernel as it was; the flip word is its last argument and is not read there.
 #include "common.hpp"
 #include "../../include/dua_hip.h"
 
@@ -56,11 +63,16 @@ __device__ __forceinline__ f32x4 load4(const f16* p) {
   return f32x4{(float)p[0], (float)p[1], (float)p[2], (float)p[3]};
 }
 
-// one window [C][rd][rh][rw] at `win`, its position in `row` (b, d, h, w); grid = (ceil(rh G / threads), rd, C)
-template <typename T, bool WIDE>
+__device__ __forceinline__ f32x4 reversed(f32x4 v) { return f32x4{v[3], v[2], v[1], v[0]}; }
+
+// one window [C][rd][rh][rw] at `win`, its position in `row` (b, d, h, w); grid = (ceil(rh G / threads), rd, C).
+// MIRROR: the window is read un-flipped, sum[.., d + z, h + y, w + x] += win[c, m0(z), m1(y), m2(x)], m_a(i) = r_a - 1 - i when bit
+// a of `flip` is set, else i
+template <typename T, bool WIDE, bool MIRROR>
 __global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T* __restrict__ win, const int* __restrict__ row,
                                                                          float* __restrict__ sum, int B, int C, int rd, int rh,
-                                                                         int rw, int Dp, int Hp, int Wp, int G, int* err) {
+                                                                         int rw, int Dp, int Hp, int Wp, int G, int* err,
+                                                                         int flip) {
   bool bad = false;
   const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
             w = clamp_flag(row[3], Wp - rw, bad);
@@ -70,7 +82,9 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T
   if (it >= rh * G) return;
   const int y = it / G, g = it - y * G;
   const long vrow = ((((long)b * C + c) * Dp + (d + z)) * Hp + (h + y)) * Wp + w;      // volume element of the row's x = 0
-  const T* wrow = win + (((long)c * rd + z) * rh + y) * rw;
+  const int wz = MIRROR && (flip & 1) ? rd - 1 - z : z, wy = MIRROR && (flip & 2) ? rh - 1 - y : y;      // the window row read
+  const T* wrow = win + (((long)c * rd + wz) * rh + wy) * rw;
+  const bool fx = MIRROR && (flip & 4);             // W reversed: volume x reads window rw - 1 - x
   if (WIDE) {
     const int shift = (int)(vrow & 3);
     const int x0 = 4 * g - shift;                   // window x of the group's first element
@@ -78,18 +92,19 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T
     float* vp = sum + (vrow + x0);                  // 16-byte aligned
     if (x0 >= 0 && x0 + 4 <= rw) {
       f32x4 v = *reinterpret_cast<f32x4*>(vp);
-      const f32x4 o = load4(wrow + x0);
+      f32x4 o = load4(wrow + (fx ? rw - 4 - x0 : x0));          // one load either way: the address is selected, not the path
+      if (fx) o = reversed(o);
       v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3];
       *reinterpret_cast<f32x4*>(vp) = v;
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int x = x0 + j;
-        if (x >= 0 && x < rw) vp[j] += (float)wrow[x];
+        if (x >= 0 && x < rw) vp[j] += (float)wrow[fx ? rw - 1 - x : x];
       }
     }
   } else {
-    if (g < rw) sum[vrow + g] += (float)wrow[g];
+    if (g < rw) sum[vrow + g] += (float)wrow[fx ? rw - 1 - g : g];
   }
 }
 
@@ -97,11 +112,12 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T
 __device__ __forceinline__ float window_weight(float gzy, float gx, float floor_w) { return fmaxf(__fmul_rn(gzy, gx), floor_w); }
 
 // blend_accumulate_kernel with sum += w * window: same grid, lane layout, edges, fallback and row clamp
-template <typename T, bool WIDE>
+template <typename T, bool WIDE, bool MIRROR>
 __global__ void __launch_bounds__(BLEND_THREADS)
 blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restrict__ row, float* __restrict__ sum,
                                  const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2,
-                                 float floor_w, int B, int C, int rd, int rh, int rw, int Dp, int Hp, int Wp, int G, int* err) {
+                                 float floor_w, int B, int C, int rd, int rh, int rw, int Dp, int Hp, int Wp, int G, int* err,
+                                 int flip) {
   bool bad = false;
   const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
             w = clamp_flag(row[3], Wp - rw, bad);
@@ -111,7 +127,9 @@ blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restric
   if (it >= rh * G) return;
   const int y = it / G, g = it - y * G;
   const long vrow = ((((long)b * C + c) * Dp + (d + z)) * Hp + (h + y)) * Wp + w;      // volume element of the row's x = 0
-  const T* wrow = win + (((long)c * rd + z) * rh + y) * rw;
+  const int wz = MIRROR && (flip & 1) ? rd - 1 - z : z, wy = MIRROR && (flip & 2) ? rh - 1 - y : y;      // the window row read
+  const T* wrow = win + (((long)c * rd + wz) * rh + wy) * rw;
+  const bool fx = MIRROR && (flip & 4);             // W reversed: volume x reads window rw - 1 - x
   const float gzy = __fmul_rn(g0[z], g1[y]);
   if (WIDE) {
     const int shift = (int)(vrow & 3);
@@ -120,7 +138,9 @@ blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restric
     float* vp = sum + (vrow + x0);                  // 16-byte aligned
     if (x0 >= 0 && x0 + 4 <= rw) {
       f32x4 v = *reinterpret_cast<f32x4*>(vp);
-      const f32x4 o = load4(wrow + x0), gx = load4(g2 + x0);
+      f32x4 o = load4(wrow + (fx ? rw - 4 - x0 : x0));
+      const f32x4 gx = load4(g2 + x0);
+      if (fx) o = reversed(o);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], __fmul_rn(window_weight(gzy, gx[j], floor_w), o[j]));
       *reinterpret_cast<f32x4*>(vp) = v;
@@ -128,11 +148,13 @@ blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restric
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int x = x0 + j;
-        if (x >= 0 && x < rw) vp[j] = __fadd_rn(vp[j], __fmul_rn(window_weight(gzy, g2[x], floor_w), (float)wrow[x]));
+        if (x >= 0 && x < rw)
+          vp[j] = __fadd_rn(vp[j], __fmul_rn(window_weight(gzy, g2[x], floor_w), (float)wrow[fx ? rw - 1 - x : x]));
       }
     }
   } else {
-    if (g < rw) sum[vrow + g] = __fadd_rn(sum[vrow + g], __fmul_rn(window_weight(gzy, g2[g], floor_w), (float)wrow[g]));
+    if (g < rw)
+      sum[vrow + g] = __fadd_rn(sum[vrow + g], __fmul_rn(window_weight(gzy, g2[g], floor_w), (float)wrow[fx ? rw - 1 - g : g]));
   }
 }
 
@@ -269,7 +291,7 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
 
 }  // namespace dua
 
-// what dua_blend_accumulate and its weighted form ask of their common arguments
+// what dua_blend_accumulate, its weighted and its mirrored forms ask of their common arguments
 static bool blend_accumulate_args_ok(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
                                      int table_rows, int table_off, int table_stride, const float* sum, int B, int Dp, int Hp,
                                      int Wp) {
@@ -283,11 +305,13 @@ static bool blend_accumulate_args_ok(int dtype, int nb, int C, int rd, int rh, i
   return true;
 }
 
-int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
-                         int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
-                         void* stream) {
+// dua_blend_accumulate and dua_blend_accumulate_mirrored: flip == 0 launches the unmirrored instantiation
+static int blend_accumulate_launch(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                   int table_rows, int table_off, int table_stride, int flip, float* sum, int B, int Dp, int Hp,
+                                   int Wp, int* err_word, void* stream) {
   if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
     return DUA_ERR_ARG;
+  if (flip < 0 || flip > 7) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool wide = ((size_t)sum & 15) == 0;
   const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
@@ -295,12 +319,59 @@ int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const
   const long wvox = (long)C * rd * rh * rw;
   for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
     const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
-#define DUA_BLEND_ACC(T, WIDE)                                                                                              \
-  hipLaunchKernelGGL((dua::blend_accumulate_kernel<T, WIDE>), grid, dim3(dua::BLEND_THREADS), 0, s,                         \
-                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, B, C, rd, rh, rw, Dp, Hp, Wp, G, err_word)
-    if (dtype == DUA_F32) { if (wide) DUA_BLEND_ACC(float, true); else DUA_BLEND_ACC(float, false); }
-    else { if (wide) DUA_BLEND_ACC(dua::f16, true); else DUA_BLEND_ACC(dua::f16, false); }
+#define DUA_BLEND_ACC(T, WIDE, MIRROR)                                                                                      \
+  hipLaunchKernelGGL((dua::blend_accumulate_kernel<T, WIDE, MIRROR>), grid, dim3(dua::BLEND_THREADS), 0, s,                 \
+                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, B, C, rd, rh, rw, Dp, Hp, Wp, G, err_word, flip)
+#define DUA_BLEND_ACC_T(T)                                                                                                  \
+  if (flip) { if (wide) DUA_BLEND_ACC(T, true, true); else DUA_BLEND_ACC(T, false, true); }                                 \
+  else { if (wide) DUA_BLEND_ACC(T, true, false); else DUA_BLEND_ACC(T, false, false); }
+    if (dtype == DUA_F32) { DUA_BLEND_ACC_T(float) } else { DUA_BLEND_ACC_T(dua::f16) }
+#undef DUA_BLEND_ACC_T
 #undef DUA_BLEND_ACC
+  }
+  return (int)hipGetLastError();
+}
+
+int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
+                         int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
+                         void* stream) {
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, sum, B, Dp, Hp,
+                                 Wp, err_word, stream);
+}
+
+int dua_blend_accumulate_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                  int table_rows, int table_off, int table_stride, int flip, float* sum, int B, int Dp, int Hp,
+                                  int Wp, int* err_word, void* stream) {
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, sum, B, Dp,
+                                 Hp, Wp, err_word, stream);
+}
+
+// dua_blend_accumulate_weighted and dua_blend_accumulate_weighted_mirrored, as blend_accumulate_launch
+static int blend_accumulate_weighted_launch(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                            int table_rows, int table_off, int table_stride, int flip, const float* g0,
+                                            const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp,
+                                            int Wp, int* err_word, void* stream) {
+  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
+    return DUA_ERR_ARG;
+  if (!g0 || !g1 || !g2 || (((size_t)g0 | (size_t)g1 | (size_t)g2) & 3) || !(floor_w > 0.f)) return DUA_ERR_ARG;
+  if (flip < 0 || flip > 7) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = ((size_t)sum & 15) == 0;
+  const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
+  const dim3 grid((unsigned)(((long)rh * G + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS), rd, C);
+  const long wvox = (long)C * rd * rh * rw;
+  for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
+    const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
+#define DUA_BLEND_ACC_W(T, WIDE, MIRROR)                                                                                    \
+  hipLaunchKernelGGL((dua::blend_accumulate_weighted_kernel<T, WIDE, MIRROR>), grid, dim3(dua::BLEND_THREADS), 0, s,        \
+                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, g0, g1, g2, floor_w, B, C, rd, rh, rw, Dp, Hp, Wp, \
+                     G, err_word, flip)
+#define DUA_BLEND_ACC_W_T(T)                                                                                                \
+  if (flip) { if (wide) DUA_BLEND_ACC_W(T, true, true); else DUA_BLEND_ACC_W(T, false, true); }                             \
+  else { if (wide) DUA_BLEND_ACC_W(T, true, false); else DUA_BLEND_ACC_W(T, false, false); }
+    if (dtype == DUA_F32) { DUA_BLEND_ACC_W_T(float) } else { DUA_BLEND_ACC_W_T(dua::f16) }
+#undef DUA_BLEND_ACC_W_T
+#undef DUA_BLEND_ACC_W
   }
   return (int)hipGetLastError();
 }
@@ -309,25 +380,16 @@ int dua_blend_accumulate_weighted(int dtype, int nb, int C, int rd, int rh, int 
                                   int table_rows, int table_off, int table_stride, const float* g0, const float* g1,
                                   const float* g2, float floor_w, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
                                   void* stream) {
-  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
-    return DUA_ERR_ARG;
-  if (!g0 || !g1 || !g2 || (((size_t)g0 | (size_t)g1 | (size_t)g2) & 3) || !(floor_w > 0.f)) return DUA_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = ((size_t)sum & 15) == 0;
-  const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
-  const dim3 grid((unsigned)(((long)rh * G + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS), rd, C);
-  const long wvox = (long)C * rd * rh * rw;
-  for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
-    const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
-#define DUA_BLEND_ACC_W(T, WIDE)                                                                                            \
-  hipLaunchKernelGGL((dua::blend_accumulate_weighted_kernel<T, WIDE>), grid, dim3(dua::BLEND_THREADS), 0, s,                \
-                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, g0, g1, g2, floor_w, B, C, rd, rh, rw, Dp, Hp, Wp, \
-                     G, err_word)
-    if (dtype == DUA_F32) { if (wide) DUA_BLEND_ACC_W(float, true); else DUA_BLEND_ACC_W(float, false); }
-    else { if (wide) DUA_BLEND_ACC_W(dua::f16, true); else DUA_BLEND_ACC_W(dua::f16, false); }
-#undef DUA_BLEND_ACC_W
-  }
-  return (int)hipGetLastError();
+  return blend_accumulate_weighted_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, g0, g1,
+                                          g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
+}
+
+int dua_blend_accumulate_weighted_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                           int table_rows, int table_off, int table_stride, int flip, const float* g0,
+                                           const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp,
+                                           int Wp, int* err_word, void* stream) {
+  return blend_accumulate_weighted_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, g0,
+                                          g1, g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
 }
 
 int dua_blend_weight_sum(const int* starts_d, int nd, const int* starts_h, int nh, const int* starts_w, int nw, int rd, int rh,

@@ -25,11 +25,18 @@ binarises and tallies Dice, and the multi-GPU form all-reduces the per-rank sum 
 ``compute_importance_map`` (MONAI >= 1.1; PARITY UNPINNED like the rest): a window's outputs are multiplied by a Gaussian
 importance map before they are added and the sum is divided by the summed maps.  ``importance_vectors`` is the single source of
 the weights; the default ``mode="constant"`` takes the code above unchanged.
+
+``mirror_axes`` on the single-process and the streamed functions is mirror test-time augmentation (nnU-Net's default inference;
+the reference trains with independent flips of the three spatial axes, utils.py:154-156, and predicts each window once): every
+window batch is predicted under every flip of the given axes, the outputs are un-flipped and all of them are averaged.  The
+contract is written once in include/dua_hip.h; ``mirror_flips`` is its flip set.  The default ``mirror_axes=None`` takes the
+code above unchanged.
 """
 from __future__ import annotations
 
 import itertools
 import math
+import numbers
 from typing import Callable, Sequence
 
 import torch
@@ -161,23 +168,46 @@ def blend_traffic_bytes(windows_total, channels, roi, batch, padded, world, wind
     return {"gathered": int(world) * per_rank * window, "reduced": volume}
 
 
-def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial, device, dtype, weights=None):
+def mirror_flips(mirror_axes):
+    """The flip set of mirror test-time augmentation: every subset of ``mirror_axes`` (distinct spatial axes from {0, 1, 2} =
+    D, H, W of [B, C, D, H, W], in any order; None or () = no augmentation) as a 3-bit mask, bit a set = axis a reversed, in
+    ascending order -- so the identity, mask 0, comes first: ``(2, 0)`` -> ``(0, 1, 4, 5)``, ``None`` -> ``(0,)``.
+    ValueError on an axis outside {0, 1, 2}, a duplicate or a non-integer."""
+    bits = 0
+    for a in () if mirror_axes is None else tuple(mirror_axes):
+        if isinstance(a, bool) or not isinstance(a, numbers.Integral) or a not in (0, 1, 2) or bits >> int(a) & 1:
+            raise ValueError(f"mirror_axes: distinct spatial axes from (0, 1, 2), not {mirror_axes!r}")
+        bits |= 1 << int(a)
+    return tuple(f for f in range(8) if f & ~bits == 0)
+
+
+def _flip_dims(flip):
+    """The dims of ``torch.flip`` on a [b, C, D, H, W] tensor for a flip mask."""
+    return [2 + a for a in range(3) if flip >> a & 1]
+
+
+def _blend(outputs_by_index, batch, channels, padded, roi, starts, pad, spatial, device, dtype, weights=None, flips=1):
     """``weights``: None = the constant map (sum / count); else the importance map [*roi] on ``device``: every window is
-    multiplied by it (one rounded product), added, and the sum is divided by the map summed once per window position."""
+    multiplied by it (one rounded product), added, and the sum is divided by the map summed once per window position.
+    ``flips`` = F: every window index comes F times (its un-flipped outputs under the F flips of ``mirror_flips``); the count,
+    or the map, is added for the first of them only and the divisor is F times it (a power of two: exact)."""
     out = torch.zeros((batch, channels, *padded), dtype=dtype, device=device)
     cnt = torch.zeros((1, 1, *padded), dtype=dtype, device=device)
     nwin = len(starts)
+    counted = set()
     for idx, o in outputs_by_index:
         b, (d, h, w) = idx // nwin, starts[idx % nwin]
+        first = idx not in counted
+        counted.add(idx)
         if weights is not None:
             out[b:b + 1, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += weights * o
-            if b == 0:
+            if b == 0 and first:
                 cnt[:, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += weights
             continue
         out[b:b + 1, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += o
-        if b == 0:
+        if b == 0 and first:
             cnt[:, :, d:d + roi[0], h:h + roi[1], w:w + roi[2]] += 1
-    out = out / cnt
+    out = out / cnt if flips == 1 else out / (cnt * flips)
     sl = [slice(None), slice(None)]
     for k in range(3):                                   # crop the padding away again
         lo = pad[2 * (2 - k)]
@@ -197,23 +227,31 @@ def _window(inputs, idx, nwin, starts, roi):
 
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable, overlap: float = 0.25,
-                             mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
+                             mirror_axes=None, mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
     """Single-process form (engine.py:173-177 semantics).  ``predictor(window_batch, **kwargs)`` -> [b,C,*roi].
     ``mode``: "constant" (the reference's) or "gaussian" with ``sigma_scale`` (``importance_vectors``).
     A model built with ``uncer_step=R`` is a predictor like any other here and in the sharded and streamed forms: the switch
-    lives on the model, every window batch of b comes back as [b, C, *roi] (the Step-Uncertainty Fusion of its R runs)."""
+    lives on the model, every window batch of b comes back as [b, C, *roi] (the Step-Uncertainty Fusion of its R runs).
+    ``mirror_axes``: None, or the spatial axes (0 = D, 1 = H, 2 = W) of mirror test-time augmentation: each window batch is
+    gathered once and predicted under every flip of ``mirror_flips(mirror_axes)`` in order, ``flip(predictor(flip(windows, f)),
+    f)``, every un-flipped output is blended as a window output of its own and the divisor is F = 2^k times the unmirrored one.
+    Step-Uncertainty Fusion composes without change (it lives in the predictor: F R DDIM loops per window)."""
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
     importance_vectors(roi, mode, sigma_scale)              # refuse a bad mode or sigma_scale before any predictor call
+    flips = mirror_flips(mirror_axes)
     x = F.pad(inputs, pad=pad, mode="constant", value=0.0)
     nwin, total = len(starts), len(starts) * inputs.shape[0]
     results = []
     for g in range(0, total, sw_batch_size):
         idxs = list(range(g, min(g + sw_batch_size, total)))
-        seg = predictor(torch.cat([_window(x, i, nwin, starts, roi) for i in idxs]), **kwargs)
-        results += [(i, seg[k:k + 1]) for k, i in enumerate(idxs)]
+        windows = torch.cat([_window(x, i, nwin, starts, roi) for i in idxs])
+        for f in flips:
+            seg = predictor(windows, **kwargs) if f == 0 else \
+                torch.flip(predictor(torch.flip(windows, _flip_dims(f)), **kwargs), _flip_dims(f))
+            results += [(i, seg[k:k + 1]) for k, i in enumerate(idxs)]
     first = results[0][1]
     return _blend(results, inputs.shape[0], first.shape[1], padded, roi, starts, pad, spatial, first.device, first.dtype,
-                  _blend_weights(roi, mode, sigma_scale, first.device, first.dtype))
+                  _blend_weights(roi, mode, sigma_scale, first.device, first.dtype), len(flips))
 
 
 def balanced_batches(n: int, max_batch: int):
@@ -285,12 +323,15 @@ def _need_device(t, what):
 
 
 def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype, timings, kwargs, mode="constant",
-                  sigma_scale=0.125):
+                  sigma_scale=0.125, mirror_axes=None):
     """The sum volume fp32 [B, C, *padded] of this plan (all-reduced over ``group`` when given) and what the finish pass needs:
     (sum volume, divisor, crop offsets, spatial).  The divisor is the three coverage vectors on the device, or with
-    ``mode="gaussian"`` the weight-sum volume fp32 [*padded], which every rank derives from the plan for itself."""
+    ``mode="gaussian"`` the weight-sum volume fp32 [*padded], which every rank derives from the plan for itself.  With
+    ``mirror_axes`` every call's window batch is predicted under the F flips of ``mirror_flips`` and each raw output goes to
+    the mirrored accumulate entry point, which un-flips it while reading; the divisor returned is F times the unmirrored one."""
     from . import ops
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
+    flips = mirror_flips(mirror_axes)
     weights = None
     vectors = importance_vectors(roi, mode, sigma_scale)
     if mode != "constant":
@@ -313,17 +354,25 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
     g = 0
     for nb in sizes:
         idxs = mine[g:g + nb]
-        seg = predictor(torch.cat([_window(x, i, nwin, starts, roi) for i in idxs]), **kwargs)
-        if acc is None:
-            acc = ops.zeros((batch, seg.shape[1], *padded), torch.float32, dev)
-        if gather_dtype is not None:
-            seg = seg.to(gather_dtype)
-        if weights is None:
-            ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
-        else:
-            ops.blend_accumulate_weighted(acc, seg.contiguous(), table, idxs[0], weights, world, err)
+        windows = torch.cat([_window(x, i, nwin, starts, roi) for i in idxs])
+        for f in flips:
+            seg = predictor(windows if f == 0 else torch.flip(windows, _flip_dims(f)), **kwargs)
+            if acc is None:
+                acc = ops.zeros((batch, seg.shape[1], *padded), torch.float32, dev)
+            if gather_dtype is not None:
+                seg = seg.to(gather_dtype)
+            if f == 0:
+                if weights is None:
+                    ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
+                else:
+                    ops.blend_accumulate_weighted(acc, seg.contiguous(), table, idxs[0], weights, world, err)
+            elif weights is None:
+                ops.blend_accumulate_mirrored(acc, seg.contiguous(), table, idxs[0], f, world, err)
+            else:
+                ops.blend_accumulate_weighted_mirrored(acc, seg.contiguous(), table, idxs[0], weights, f, world, err)
+            del seg
         g += nb
-        del seg
+        del windows
     if acc is None:          # more ranks than windows: still take part in the collective
         probe = predictor(_window(x, 0, nwin, starts, roi), **kwargs)
         acc = ops.zeros((batch, probe.shape[1], *padded), torch.float32, dev)
@@ -343,8 +392,11 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
     crop_lo = tuple(pad[2 * (2 - k)] for k in range(3))
     if weights is not None:
         per_axis = [torch.tensor(s, dtype=torch.int32).to(dev) for s in axis_starts(starts)]
-        return acc, ops.blend_weight_sum(per_axis, roi, padded, weights), crop_lo, spatial
-    coverage = [torch.tensor(n, dtype=torch.int32).to(dev) for n in coverage_counts(padded, roi, starts)]
+        wsum = ops.blend_weight_sum(per_axis, roi, padded, weights)
+        return acc, wsum if len(flips) == 1 else wsum.mul_(len(flips)), crop_lo, spatial
+    counts = coverage_counts(padded, roi, starts)
+    counts[0] = [n * len(flips) for n in counts[0]]            # F nd[z] nh[y] nw[x]: the finish pass needs no change
+    coverage = [torch.tensor(n, dtype=torch.int32).to(dev) for n in counts]
     return acc, coverage, crop_lo, spatial
 
 
@@ -357,7 +409,8 @@ def _streamed_finish(acc, divisor, crop_lo, spatial, **want):
 
 def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
                                       overlap: float = 0.25, group=None, gather_dtype: torch.dtype = None,
-                                      timings: dict = None, mode: str = "constant", sigma_scale=0.125, **kwargs) -> torch.Tensor:
+                                      timings: dict = None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125,
+                                      **kwargs) -> torch.Tensor:
     """The volume ``sliding_window_inference`` returns -- same plan, padding, window order and predictor calls -- without the list
     of window outputs: every call's outputs are added into a device-resident fp32 sum volume at once (dua_blend_accumulate:
     the fp32 additions of ``_blend`` in the same order), and one pass divides by the window count derived from the plan and
@@ -366,16 +419,20 @@ def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_s
     fp32 volumes follows; ``timings`` accumulates its wall time under "all_reduce_s" and records "reduced_bytes";
     ``gather_dtype`` only narrows the window tensor handed to the accumulate call.  ``mode="gaussian"``: the weighted entry
     points (dua_blend_accumulate_weighted, dua_blend_weight_sum, dua_blend_finish_weighted), bit-equal to
-    ``sliding_window_inference(mode="gaussian")`` on the same device; the all-reduce is the same.  Device tensors only."""
+    ``sliding_window_inference(mode="gaussian")`` on the same device; the all-reduce is the same.  ``mirror_axes``: as
+    ``sliding_window_inference``, bit-equal to it on the same device in both modes; the raw output of each flipped call goes
+    to dua_blend_accumulate_mirrored (or its weighted form), which un-flips it while reading -- no flipped copy of a window
+    output -- and the divisor is scaled by F.  With a group each rank runs the F flips of its own windows into its own sum
+    volume: the all-reduced bytes are unchanged.  Device tensors only."""
     _need_device(inputs, "streamed_sliding_window_inference")
     acc, divisor, crop_lo, spatial = _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype,
-                                                   timings, kwargs, mode, sigma_scale)
+                                                   timings, kwargs, mode, sigma_scale, mirror_axes)
     return _streamed_finish(acc, divisor, crop_lo, spatial, want_q=True)[0]
 
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
                     overlap: float = 0.25, distributed: bool = False, group=None, postprocess: dict = None,
-                    surface: dict = None, mode: str = "constant", sigma_scale=0.125):
+                    surface: dict = None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125):
     """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
     [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
     written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
@@ -389,8 +446,12 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     ``surface``: None, or a dict with keys among ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting",
     "distances"); it needs ``labels``.  The result is then (mask, dice, report): ``metrics.surface_dice_table`` (Normalized
     Surface Dice at ``tolerance``) of the returned mask -- the filtered one with ``postprocess`` -- against the labels, or
-    ``metrics.surface_report`` (the distance table too) with ``distances=True``."""
+    ``metrics.surface_report`` (the distance table too) with ``distances=True``.
+    ``mirror_axes``: mirror test-time augmentation as in ``streamed_sliding_window_inference`` (F predictor calls per window
+    batch, the same all-reduce).  ``postprocess``, ``surface`` and Step-Uncertainty Fusion compose with it without change:
+    they run after the finish pass, or inside the predictor."""
     from . import ops
+    mirror_flips(mirror_axes)                              # refuse bad axes before any predictor call
     if surface is not None:
         _surface_kwargs(surface, labels)
     _need_device(image, "evaluate_volume")
@@ -401,7 +462,7 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
         group = dist.group.WORLD
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
-                                                       None, None, dict(pred_type="ddim_sample"), mode, sigma_scale)
+                                                       None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
         if postprocess is not None:
             from .postprocess import filter_components
             _, mask, _ = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True)
@@ -463,20 +524,27 @@ def dice_per_class(outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 
 def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
-          distributed: bool = False, group=None, streaming: bool = False, postprocess: dict = None, mode: str = "constant",
-          sigma_scale=0.125) -> torch.Tensor:
+          distributed: bool = False, group=None, streaming: bool = False, postprocess: dict = None, mirror_axes=None,
+          mode: str = "constant", sigma_scale=0.125) -> torch.Tensor:
     """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
     ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume).  ``mode``, ``sigma_scale``: the blend's
     importance map, as ``sliding_window_inference``.  ``postprocess``: None, or a dict of
     ``postprocess.keep_largest_components`` keyword arguments applied to the binarised volume (fp32 is returned either way).
-    Step-Uncertainty Fusion is the model's switch (``DiffUNet(..., uncer_step=R)``), not an argument of this function."""
+    Step-Uncertainty Fusion is the model's switch (``DiffUNet(..., uncer_step=R)``), not an argument of this function.
+    ``mirror_axes``: mirror test-time augmentation, as ``sliding_window_inference``; ``postprocess`` and Step-Uncertainty
+    Fusion compose with it without change.  The all-gather form (``distributed=True, streaming=False``) does not take it --
+    its gathered bytes would grow F-fold -- and raises ValueError: use ``streaming=True``, whose all-reduce does not grow."""
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
+    augmented = len(mirror_flips(mirror_axes)) > 1
     if streaming:
         return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess,
-                               mode=mode, sigma_scale=sigma_scale)[0].float()
+                               mirror_axes=mirror_axes, mode=mode, sigma_scale=sigma_scale)[0].float()
+    if distributed and augmented:
+        raise ValueError("mirror_axes: the all-gather form would gather F times the window outputs; pass streaming=True "
+                         "(one all-reduce of the same size) for mirror test-time augmentation across ranks")
     fn = sharded_sliding_window_inference if distributed else sliding_window_inference
-    kw = dict(group=group) if distributed else {}
+    kw = dict(group=group) if distributed else dict(mirror_axes=mirror_axes)
     with torch.no_grad():
         out = fn(image, roi_size, sw_batch_size, model, overlap, mode=mode, sigma_scale=sigma_scale, pred_type="ddim_sample", **kw)
     if postprocess is not None:

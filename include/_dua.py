@@ -34,6 +34,15 @@ _L.dua_conv3d_k3_fwd.restype = C.c_int
 _L.dua_conv3d_k3_fwd.argtypes = [C.POINTER(Conv3Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InNorm),
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
 DUA_F16 = 1
+# mirror test-time augmentation of the streamed blend: dua_blend_accumulate[_weighted] with the un-flip of a window predicted
+# under axis flips folded into the read of the window (flip: bit a set = spatial axis a reversed; the contract is in dua_hip.h)
+_L.dua_blend_accumulate_mirrored.restype = C.c_int
+_L.dua_blend_accumulate_mirrored.argtypes = ([C.c_int] * 6 + [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] +
+                                             [C.c_int] * 4 + [C.c_void_p, C.c_void_p])
+_L.dua_blend_accumulate_weighted_mirrored.restype = C.c_int
+_L.dua_blend_accumulate_weighted_mirrored.argtypes = ([C.c_int] * 6 + [C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                                                      [C.c_void_p] * 3 + [C.c_float, C.c_void_p] + [C.c_int] * 4 +
+                                                      [C.c_void_p, C.c_void_p])
 
 
 def _stream():

@@ -1113,6 +1113,42 @@ int dua_blend_finish_weighted(const float* sum, int B, int C, int Dp, int Hp, in
                               int D, int H, int W, float* q_out, unsigned char* mask_out, const void* labels, int labels_dtype,
                               int label_map, unsigned long long* tallies, void* stream);
 
+/* ---- evaluation: mirror test-time augmentation in the streamed blend ------------------------------------------------
+ * Every window is predicted again under axis flips, the predictions are un-flipped and averaged -- the inference that matches
+ * how the reference trains (utils.py:154-156 flips every training patch along each of the three spatial axes independently;
+ * Engine.infer, engine.py:167-182, predicts each window once).  The contract, written once here:
+ *   mirror_axes  a collection of distinct spatial axes from {0, 1, 2} (0 = D, 1 = H, 2 = W of [B][C][D][H][W]), in any order.
+ *   flip set     every subset of those axes, F = 2^k of them.  A flip is a 3-bit mask, bit a set = axis a reversed; flips are
+ *                visited in ascending mask order, so mask 0 (the identity) comes first.
+ *   plan         windows, padding, window order and batching are those of the unmirrored blend.
+ *   order        for each predictor call's window batch (gathered once), for each mask f in order:
+ *                o = predictor(flip(windows, f)); o = flip(o, f); then the slice-add of every window of the batch in
+ *                window-index order.
+ *   weight       with the Gaussian weighting, w multiplies the UN-FLIPPED output: it is indexed by the volume-side window
+ *                coordinate (z, y, x).
+ *   divisor      F times the unmirrored divisor: F (window count), or F (the weight sum built once per window position).  F is a
+ *                power of two, so the scaling is exact in fp32; the caller scales one coverage vector, or wsum, by F.
+ *
+ * dua_blend_accumulate_mirrored: dua_blend_accumulate with the un-flip folded into the read of the window side --
+ *   sum[b, c, d + z, h + y, w + x] += (fp32) windows[k][c, m0(z), m1(y), m2(x)],   m_a(i) = r_a - 1 - i when bit a of flip is
+ *   set, else i                                              (r_0, r_1, r_2 = rd, rh, rw)
+ * i.e. the bits of `sum[slice] += flip(windows[k], f)` per window in the order of k, with no flipped temporary.  windows:
+ * DUA_F32 or DUA_F16.  The volume side keeps its aligned 16-byte accesses; a reversed W reads the four window elements of a
+ * group with one vector load where their address is aligned (16 bytes fp32, 8 bytes fp16) and by element otherwise.
+ * flip == 0 gives the bits of dua_blend_accumulate; flip outside 0 .. 7: DUA_ERR_ARG.  Every other argument, the row clamp and
+ * *err_word as in dua_blend_accumulate.
+ *
+ * dua_blend_accumulate_weighted_mirrored: the same with
+ *   sum[...] += max((g0[z] * g1[y]) * g2[x], floor_w) * (fp32) windows[k][c, m0(z), m1(y), m2(x)]
+ * every product and sum a single rounded fp32 operation, as in dua_blend_accumulate_weighted; flip == 0 gives its bits. */
+int dua_blend_accumulate_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                  int table_rows, int table_off, int table_stride, int flip, float* sum, int B, int Dp, int Hp,
+                                  int Wp, int* err_word, void* stream);
+int dua_blend_accumulate_weighted_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
+                                           int table_rows, int table_off, int table_stride, int flip, const float* g0,
+                                           const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp,
+                                           int Wp, int* err_word, void* stream);
+
 /* ---- case preparation: crop, reorient and resample a raw scan on the device -----------------------------------------
  * The deterministic front of the reference's transform chain (utils.py:125-136 for training, :168-177 for validation:
  * ScaleIntensityRanged(a_min, a_max -> 0, 1, clip), CropForegroundd(source_key="image"), Orientationd, Spacingd(bilinear |

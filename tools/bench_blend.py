@@ -1,7 +1,7 @@
 """Time the whole-volume blend of sliding-window inference, streamed (csrc/blend.hip) against list-and-blend, predictor excluded.
 
     python tools/bench_blend.py [--volume 240 240 180] [--channels 16] [--roi 96] [--overlap 0.8] [--sw-batch 4]
-                                [--repeats 5] [--warmup 2] [--mode constant|gaussian] [--sigma-scale 0.125]
+                                [--repeats 5] [--warmup 2] [--mode constant|gaussian] [--sigma-scale 0.125] [--mirror 0,1,2]
 
 A stub predictor hands out preallocated window outputs (a pool of --sw-batch random fp32 windows, reused by every call), so
 only the blend is timed.  Per repeat, alternating the two forms, between device synchronisations:
@@ -16,7 +16,17 @@ in the gather and in the all-reduce form for 2, 4 and 8 ranks.
 
 --mode gaussian: the streamed and the listed form blend with the Gaussian importance map (dua_blend_accumulate_weighted per
 call, one dua_blend_weight_sum, dua_blend_finish_weighted; ``_blend`` with the map), and the constant-mode streamed form is
-timed in the same alternation and printed next to them as "streamed_constant_seconds"."""
+timed in the same alternation and printed next to them as "streamed_constant_seconds".
+
+--mirror AXES (e.g. 0,1,2): instead of the above, the accumulate step of mirror test-time augmentation alone, over every call of
+the plan into the same sum volume, alternating per repeat between device synchronisations:
+  (a) the unmirrored accumulate (dua_blend_accumulate, or its weighted form with --mode gaussian);
+  (b) the mirrored accumulate, once per flip mask of the axes (dua_blend_accumulate_mirrored: the un-flip is the read order);
+  (c) torch.flip of the call's window outputs followed by the unmirrored accumulate -- the only way without the mirrored entry
+      point -- once per mask.
+One JSON line: median seconds of each, derived bytes (window read, volume read, volume written per window; (c) adds a read and
+a write of the window) and rates, the ratios (b)/(a) and (b)/(c) per mask.  The three forms add different values, so only
+times are compared; tests/test_mirror_gpu.py has the bit-equality of (b) and (c)."""
 import argparse
 import json
 import os
@@ -41,6 +51,72 @@ def clocks():
         return "not available"
 
 
+def mirror_bench(args, dev, pool, table, calls, weights, Cn, roi, padded, nwin):
+    from diff_unet_amos_amd.inference import _flip_dims, mirror_flips
+    masks = mirror_flips(args.mirror)
+    acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
+
+    def plain(windows, g0):
+        if weights is None:
+            ops.blend_accumulate(acc, windows, table, g0)
+        else:
+            ops.blend_accumulate_weighted(acc, windows, table, g0, weights)
+
+    def unmirrored():
+        for g0, nb in calls:
+            plain(pool[:nb], g0)
+
+    def mirrored(f):
+        for g0, nb in calls:
+            if weights is None:
+                ops.blend_accumulate_mirrored(acc, pool[:nb], table, g0, f)
+            else:
+                ops.blend_accumulate_weighted_mirrored(acc, pool[:nb], table, g0, weights, f)
+
+    def flip_then_plain(f):
+        for g0, nb in calls:
+            plain(torch.flip(pool[:nb], _flip_dims(f)) if f else pool[:nb], g0)
+
+    def run(fn, *a):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(*a)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    forms = [("a", unmirrored, ())] + [(f"b{f}", mirrored, (f,)) for f in masks] + [(f"c{f}", flip_then_plain, (f,)) for f in masks]
+    for _ in range(args.warmup):
+        for _, fn, a in forms:
+            run(fn, *a)
+    times = {name: [] for name, _, _ in forms}
+    for _ in range(args.repeats):                                  # alternate the forms
+        for name, fn, a in forms:
+            times[name].append(run(fn, *a))
+    med = {name: statistics.median(t) for name, t in times.items()}
+
+    def spread(name):
+        return {"median": med[name], "min": min(times[name]), "max": max(times[name])}
+
+    window_bytes = Cn * roi[0] * roi[1] * roi[2] * 4
+    moved = nwin * 3 * window_bytes                                # window read, volume read, volume written
+    moved_c = nwin * 5 * window_bytes                              # + torch.flip: window read, flipped copy written
+    print(json.dumps({
+        "mirror_axes": list(args.mirror), "masks": list(masks), "mode": args.mode,
+        "plan": {"padded": list(padded), "channels": Cn, "roi": list(roi), "windows": nwin, "sw_batch": args.sw_batch,
+                 "calls": len(calls)},
+        "clocks": clocks(), "device": torch.cuda.get_device_name(dev), "warmup": args.warmup, "repeats": args.repeats,
+        "a_unmirrored_seconds": spread("a"),
+        "b_mirrored_seconds": {str(f): spread(f"b{f}") for f in masks},
+        "c_flip_then_unmirrored_seconds": {str(f): spread(f"c{f}") for f in masks},
+        "microseconds_per_window": {"a": 1e6 * med["a"] / nwin, **{f"b{f}": 1e6 * med[f"b{f}"] / nwin for f in masks},
+                                    **{f"c{f}": 1e6 * med[f"c{f}"] / nwin for f in masks}},
+        "bytes_moved_derived": {"a_and_b": moved, "c_flipped_masks": moved_c},
+        "bytes_per_second": {"a": moved / med["a"], **{f"b{f}": moved / med[f"b{f}"] for f in masks}},
+        "b_over_a": {str(f): med[f"b{f}"] / med["a"] for f in masks},
+        "b_over_c": {str(f): med[f"b{f}"] / med[f"c{f}"] for f in masks},
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--volume", type=int, nargs=3, default=[240, 240, 180])
@@ -52,6 +128,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--mode", choices=["constant", "gaussian"], default="constant")
     ap.add_argument("--sigma-scale", type=float, default=0.125)
+    ap.add_argument("--mirror", type=lambda t: tuple(int(v) for v in t.split(",")), default=None, metavar="AXES")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_blend.py measures on an MI355X; no GPU here")
@@ -74,6 +151,9 @@ def main():
     weights = (*(v.to(dev) for v in vectors[:3]), vectors[3])
     wmap = importance_map(vectors, dev) if gaussian else None
     per_axis = [torch.tensor(s, dtype=torch.int32, device=dev) for s in axis_starts(starts)]
+
+    if args.mirror is not None:
+        return mirror_bench(args, dev, pool, table, calls, weights if gaussian else None, Cn, roi, padded, nwin)
 
     def streamed_gaussian():
         acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
