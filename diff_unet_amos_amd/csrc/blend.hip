@@ -15,24 +15,26 @@
 //            aligned, four dword loads otherwise: reads of one cache line by neighbouring lanes).  A volume whose base is not
 //            16-byte aligned takes the one-element-per-lane form.
 //            Every lane reads the table row (a wave-uniform load) and clamps it into the volume before forming an address.
+//            There is ONE kernel, blend_accumulate_kernel<T, WIDE, WEIGHTED, MIRROR>; the four entry points differ only in its
+//            two last flags, and a flag that is off leaves its arguments unread.
+//            WEIGHTED (mode="gaussian"): the importance map is never stored.  It is an outer product of three per-axis
+//            vectors, clamped from below, so a lane rebuilds w = max((g0[z] g1[y]) g2[x], floor) per voxel from the vectors (a
+//            few hundred bytes, cache resident) -- g2 is indexed by the window x of each element, i.e. the group's x0 + j in
+//            the shifted wide form.  Every product and sum is a single rounded fp32 operation (__fmul_rn / __fadd_rn): the
+//            bits of `out[slice] += w * o`.
+//            MIRROR (mirror test-time augmentation): the un-flip of a window predicted under axis flips is a different READ
+//            ORDER of the window side.  The lanes still own the volume's 16-byte groups; a flip of D or H only changes which
+//            window row a lane reads, and a flip of W means the four volume elements at window x0 .. x0 + 3 come from window
+//            elements rw-1-x0-3 .. rw-1-x0: one vector load where that address is aligned (as often as in the unmirrored form
+//            when rw is a multiple of 4), reversed in registers.  The importance weight stays indexed by the volume-side
+//            (z, y, x): it multiplies the un-flipped output.
 //   finish : grid = (blocks, B C): a workgroup stays inside one channel plane, so its Dice tallies are three counters.  When
 //            nothing is cropped and a plane is a multiple of 4 voxels, a lane takes 4 consecutive voxels (16-byte load of the
 //            sums, 16-byte store of q, 4-byte store of the mask, 16- or 4-byte load of the labels); otherwise one voxel.
 //            Counters: per lane -> wave shuffle -> LDS -> one 64-bit integer atomic per counter and workgroup.
-//   weighted forms (mode="gaussian"): the importance map is never stored.  It is an outer product of three per-axis vectors,
-//            clamped from below, so accumulate rebuilds w = max((g0[z] g1[y]) g2[x], floor) per voxel from the vectors (a few
-//            hundred bytes, cache resident) with the lane layout above -- g2 is indexed by the window x of each element, i.e.
-//            the group's x0 + j in the shifted wide form; weight_sum rebuilds the summed weights of the whole volume from the
-//            plan's per-axis starts (a voxel loops over the starts that cover it, D-major = window-index order); and finish
-//            divides by that volume instead of the product of three counts, same kernel body.  Every product and sum is a
-//            single rounded fp32 operation (__fmul_rn / __fadd_rn): the bits of `out[slice] += w * o; cnt[slice] += w`.
-//   mirrored forms (mirror test-time augmentation): the un-flip of a window predicted under axis flips is a different READ ORDER
-//            of the window side, template flag MIRROR on the two accumulate kernels.  The lanes still own the volume's 16-byte
-//            groups; a flip of D or H only changes which window row a lane reads, and a flip of W means the four volume
-//            elements at window x0 .. x0 + 3 come from window elements rw-1-x0-3 .. rw-1-x0: one vector load where that
-//            address is aligned (as often as in the unmirrored form when rw is a multiple of 4), reversed in registers.  The
-//            importance weight stays indexed by the volume-side (z, y, x): it multiplies the un-flipped output.  MIRROR = false
-//            is the kernel as it was; the flip word is its last argument and is not read there.
+//   weight_sum, weighted finish : weight_sum rebuilds the summed weights of the whole volume from the plan's per-axis starts (a
+//            voxel loops over the starts that cover it, D-major = window-index order, `cnt[slice] += w` in single rounded
+//            additions), and finish divides by that volume instead of the product of three counts, same kernel body.
 #include "common.hpp"
 #include "../../include/dua_hip.h"
 
@@ -65,59 +67,25 @@ __device__ __forceinline__ f32x4 load4(const f16* p) {
 
 __device__ __forceinline__ f32x4 reversed(f32x4 v) { return f32x4{v[3], v[2], v[1], v[0]}; }
 
-// one window [C][rd][rh][rw] at `win`, its position in `row` (b, d, h, w); grid = (ceil(rh G / threads), rd, C).
-// MIRROR: the window is read un-flipped, sum[.., d + z, h + y, w + x] += win[c, m0(z), m1(y), m2(x)], m_a(i) = r_a - 1 - i when bit
-// a of `flip` is set, else i
-template <typename T, bool WIDE, bool MIRROR>
-__global__ void __launch_bounds__(BLEND_THREADS) blend_accumulate_kernel(const T* __restrict__ win, const int* __restrict__ row,
-                                                                         float* __restrict__ sum, int B, int C, int rd, int rh,
-                                                                         int rw, int Dp, int Hp, int Wp, int G, int* err,
-                                                                         int flip) {
-  bool bad = false;
-  const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
-            w = clamp_flag(row[3], Wp - rw, bad);
-  if (bad && err && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *err = 1;
-  const int c = blockIdx.z, z = blockIdx.y;
-  const int it = blockIdx.x * BLEND_THREADS + threadIdx.x;
-  if (it >= rh * G) return;
-  const int y = it / G, g = it - y * G;
-  const long vrow = ((((long)b * C + c) * Dp + (d + z)) * Hp + (h + y)) * Wp + w;      // volume element of the row's x = 0
-  const int wz = MIRROR && (flip & 1) ? rd - 1 - z : z, wy = MIRROR && (flip & 2) ? rh - 1 - y : y;      // the window row read
-  const T* wrow = win + (((long)c * rd + wz) * rh + wy) * rw;
-  const bool fx = MIRROR && (flip & 4);             // W reversed: volume x reads window rw - 1 - x
-  if (WIDE) {
-    const int shift = (int)(vrow & 3);
-    const int x0 = 4 * g - shift;                   // window x of the group's first element
-    if (x0 >= rw) return;
-    float* vp = sum + (vrow + x0);                  // 16-byte aligned
-    if (x0 >= 0 && x0 + 4 <= rw) {
-      f32x4 v = *reinterpret_cast<f32x4*>(vp);
-      f32x4 o = load4(wrow + (fx ? rw - 4 - x0 : x0));          // one load either way: the address is selected, not the path
-      if (fx) o = reversed(o);
-      v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3];
-      *reinterpret_cast<f32x4*>(vp) = v;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int x = x0 + j;
-        if (x >= 0 && x < rw) vp[j] += (float)wrow[fx ? rw - 1 - x : x];
-      }
-    }
-  } else {
-    if (g < rw) sum[vrow + g] += (float)wrow[fx ? rw - 1 - g : g];
-  }
-}
-
 // w of one voxel from the row's g0[z] g1[y] product: the outer-product order of the map, every product rounded, then the floor
 __device__ __forceinline__ float window_weight(float gzy, float gx, float floor_w) { return fmaxf(__fmul_rn(gzy, gx), floor_w); }
 
-// blend_accumulate_kernel with sum += w * window: same grid, lane layout, edges, fallback and row clamp
-template <typename T, bool WIDE, bool MIRROR>
+// the new sum value: v + o, or v + w o with every operation rounded once
+template <bool WEIGHTED>
+__device__ __forceinline__ float blend_add(float v, float o, float gzy, float gx, float floor_w) {
+  if constexpr (WEIGHTED) return __fadd_rn(v, __fmul_rn(window_weight(gzy, gx, floor_w), o));
+  else return v + o;
+}
+
+// one window [C][rd][rh][rw] at `win`, its position in `row` (b, d, h, w); grid = (ceil(rh G / threads), rd, C).
+// WEIGHTED: sum += w * window with w = max((g0[z] g1[y]) g2[x], floor_w); otherwise g0, g1, g2 and floor_w are not read.
+// MIRROR: the window is read un-flipped, sum[.., d + z, h + y, w + x] += win[c, m0(z), m1(y), m2(x)], m_a(i) = r_a - 1 - i when bit
+// a of `flip` is set, else i; otherwise `flip` is not read
+template <typename T, bool WIDE, bool WEIGHTED, bool MIRROR>
 __global__ void __launch_bounds__(BLEND_THREADS)
-blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restrict__ row, float* __restrict__ sum,
-                                 const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2,
-                                 float floor_w, int B, int C, int rd, int rh, int rw, int Dp, int Hp, int Wp, int G, int* err,
-                                 int flip) {
+blend_accumulate_kernel(const T* __restrict__ win, const int* __restrict__ row, float* __restrict__ sum,
+                        const float* __restrict__ g0, const float* __restrict__ g1, const float* __restrict__ g2, float floor_w,
+                        int B, int C, int rd, int rh, int rw, int Dp, int Hp, int Wp, int G, int* err, int flip) {
   bool bad = false;
   const int b = clamp_flag(row[0], B - 1, bad), d = clamp_flag(row[1], Dp - rd, bad), h = clamp_flag(row[2], Hp - rh, bad),
             w = clamp_flag(row[3], Wp - rw, bad);
@@ -130,7 +98,7 @@ blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restric
   const int wz = MIRROR && (flip & 1) ? rd - 1 - z : z, wy = MIRROR && (flip & 2) ? rh - 1 - y : y;      // the window row read
   const T* wrow = win + (((long)c * rd + wz) * rh + wy) * rw;
   const bool fx = MIRROR && (flip & 4);             // W reversed: volume x reads window rw - 1 - x
-  const float gzy = __fmul_rn(g0[z], g1[y]);
+  const float gzy = WEIGHTED ? __fmul_rn(g0[z], g1[y]) : 0.f;
   if (WIDE) {
     const int shift = (int)(vrow & 3);
     const int x0 = 4 * g - shift;                   // window x of the group's first element: the index into g2 as well
@@ -138,23 +106,23 @@ blend_accumulate_weighted_kernel(const T* __restrict__ win, const int* __restric
     float* vp = sum + (vrow + x0);                  // 16-byte aligned
     if (x0 >= 0 && x0 + 4 <= rw) {
       f32x4 v = *reinterpret_cast<f32x4*>(vp);
-      f32x4 o = load4(wrow + (fx ? rw - 4 - x0 : x0));
-      const f32x4 gx = load4(g2 + x0);
+      f32x4 o = load4(wrow + (fx ? rw - 4 - x0 : x0));          // one load either way: the address is selected, not the path
+      const f32x4 gx = WEIGHTED ? load4(g2 + x0) : f32x4{};
       if (fx) o = reversed(o);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = __fadd_rn(v[j], __fmul_rn(window_weight(gzy, gx[j], floor_w), o[j]));
+      for (int j = 0; j < 4; ++j) v[j] = blend_add<WEIGHTED>(v[j], o[j], gzy, gx[j], floor_w);
       *reinterpret_cast<f32x4*>(vp) = v;
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int x = x0 + j;
         if (x >= 0 && x < rw)
-          vp[j] = __fadd_rn(vp[j], __fmul_rn(window_weight(gzy, g2[x], floor_w), (float)wrow[fx ? rw - 1 - x : x]));
+          vp[j] = blend_add<WEIGHTED>(vp[j], (float)wrow[fx ? rw - 1 - x : x], gzy, WEIGHTED ? g2[x] : 0.f, floor_w);
       }
     }
   } else {
     if (g < rw)
-      sum[vrow + g] = __fadd_rn(sum[vrow + g], __fmul_rn(window_weight(gzy, g2[g], floor_w), (float)wrow[fx ? rw - 1 - g : g]));
+      sum[vrow + g] = blend_add<WEIGHTED>(sum[vrow + g], (float)wrow[fx ? rw - 1 - g : g], gzy, WEIGHTED ? g2[g] : 0.f, floor_w);
   }
 }
 
@@ -291,26 +259,20 @@ __global__ void __launch_bounds__(BLEND_THREADS) blend_finish_kernel(const float
 
 }  // namespace dua
 
-// what dua_blend_accumulate, its weighted and its mirrored forms ask of their common arguments
-static bool blend_accumulate_args_ok(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
-                                     int table_rows, int table_off, int table_stride, const float* sum, int B, int Dp, int Hp,
-                                     int Wp) {
-  if ((dtype != DUA_F32 && dtype != DUA_F16) || nb < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || !windows || !table || !sum)
-    return false;
-  if (rd < 1 || rh < 1 || rw < 1 || B < 1 || Dp < rd || Hp < rh || Wp < rw || rd > 65535) return false;
-  if (table_rows < 1 || table_off < 0 || table_stride < 1 || (long)table_off + (long)(nb - 1) * table_stride >= table_rows)
-    return false;
-  if ((long)Dp * Hp * Wp >= (1L << 31) || (long)rd * rh * rw >= (1L << 31)) return false;
-  if (((size_t)windows & (dtype == DUA_F16 ? 1 : 3)) || ((size_t)sum & 3) || ((size_t)table & 3)) return false;
-  return true;
-}
-
-// dua_blend_accumulate and dua_blend_accumulate_mirrored: flip == 0 launches the unmirrored instantiation
+// the four accumulate entry points: `weighted` says whether g0, g1, g2, floor_w are given, flip == 0 launches the unmirrored
+// instantiation
 static int blend_accumulate_launch(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
-                                   int table_rows, int table_off, int table_stride, int flip, float* sum, int B, int Dp, int Hp,
-                                   int Wp, int* err_word, void* stream) {
-  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
+                                   int table_rows, int table_off, int table_stride, int flip, bool weighted, const float* g0,
+                                   const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp, int Wp,
+                                   int* err_word, void* stream) {
+  if ((dtype != DUA_F32 && dtype != DUA_F16) || nb < 1 || C < 1 || C > DUA_BLEND_MAX_CLASSES || !windows || !table || !sum)
     return DUA_ERR_ARG;
+  if (rd < 1 || rh < 1 || rw < 1 || B < 1 || Dp < rd || Hp < rh || Wp < rw || rd > 65535) return DUA_ERR_ARG;
+  if (table_rows < 1 || table_off < 0 || table_stride < 1 || (long)table_off + (long)(nb - 1) * table_stride >= table_rows)
+    return DUA_ERR_ARG;
+  if ((long)Dp * Hp * Wp >= (1L << 31) || (long)rd * rh * rw >= (1L << 31)) return DUA_ERR_ARG;
+  if (((size_t)windows & (dtype == DUA_F16 ? 1 : 3)) || ((size_t)sum & 3) || ((size_t)table & 3)) return DUA_ERR_ARG;
+  if (weighted && (!g0 || !g1 || !g2 || (((size_t)g0 | (size_t)g1 | (size_t)g2) & 3) || !(floor_w > 0.f))) return DUA_ERR_ARG;
   if (flip < 0 || flip > 7) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool wide = ((size_t)sum & 15) == 0;
@@ -319,14 +281,18 @@ static int blend_accumulate_launch(int dtype, int nb, int C, int rd, int rh, int
   const long wvox = (long)C * rd * rh * rw;
   for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
     const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
-#define DUA_BLEND_ACC(T, WIDE, MIRROR)                                                                                      \
-  hipLaunchKernelGGL((dua::blend_accumulate_kernel<T, WIDE, MIRROR>), grid, dim3(dua::BLEND_THREADS), 0, s,                 \
-                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, B, C, rd, rh, rw, Dp, Hp, Wp, G, err_word, flip)
-#define DUA_BLEND_ACC_T(T)                                                                                                  \
-  if (flip) { if (wide) DUA_BLEND_ACC(T, true, true); else DUA_BLEND_ACC(T, false, true); }                                 \
-  else { if (wide) DUA_BLEND_ACC(T, true, false); else DUA_BLEND_ACC(T, false, false); }
+#define DUA_BLEND_ACC(T, WIDE, WEIGHTED, MIRROR)                                                                            \
+  hipLaunchKernelGGL((dua::blend_accumulate_kernel<T, WIDE, WEIGHTED, MIRROR>), grid, dim3(dua::BLEND_THREADS), 0, s,       \
+                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, g0, g1, g2, floor_w, B, C, rd, rh, rw, Dp, Hp, Wp, \
+                     G, err_word, flip)
+#define DUA_BLEND_ACC_M(T, WIDE, WEIGHTED)                                                                                  \
+  if (flip) DUA_BLEND_ACC(T, WIDE, WEIGHTED, true); else DUA_BLEND_ACC(T, WIDE, WEIGHTED, false)
+#define DUA_BLEND_ACC_W(T, WIDE) if (weighted) { DUA_BLEND_ACC_M(T, WIDE, true); } else { DUA_BLEND_ACC_M(T, WIDE, false); }
+#define DUA_BLEND_ACC_T(T) if (wide) { DUA_BLEND_ACC_W(T, true) } else { DUA_BLEND_ACC_W(T, false) }
     if (dtype == DUA_F32) { DUA_BLEND_ACC_T(float) } else { DUA_BLEND_ACC_T(dua::f16) }
 #undef DUA_BLEND_ACC_T
+#undef DUA_BLEND_ACC_W
+#undef DUA_BLEND_ACC_M
 #undef DUA_BLEND_ACC
   }
   return (int)hipGetLastError();
@@ -335,61 +301,31 @@ static int blend_accumulate_launch(int dtype, int nb, int C, int rd, int rh, int
 int dua_blend_accumulate(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table, int table_rows,
                          int table_off, int table_stride, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
                          void* stream) {
-  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, sum, B, Dp, Hp,
-                                 Wp, err_word, stream);
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, false, nullptr,
+                                 nullptr, nullptr, 0.f, sum, B, Dp, Hp, Wp, err_word, stream);
 }
 
 int dua_blend_accumulate_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
                                   int table_rows, int table_off, int table_stride, int flip, float* sum, int B, int Dp, int Hp,
                                   int Wp, int* err_word, void* stream) {
-  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, sum, B, Dp,
-                                 Hp, Wp, err_word, stream);
-}
-
-// dua_blend_accumulate_weighted and dua_blend_accumulate_weighted_mirrored, as blend_accumulate_launch
-static int blend_accumulate_weighted_launch(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
-                                            int table_rows, int table_off, int table_stride, int flip, const float* g0,
-                                            const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp,
-                                            int Wp, int* err_word, void* stream) {
-  if (!blend_accumulate_args_ok(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, sum, B, Dp, Hp, Wp))
-    return DUA_ERR_ARG;
-  if (!g0 || !g1 || !g2 || (((size_t)g0 | (size_t)g1 | (size_t)g2) & 3) || !(floor_w > 0.f)) return DUA_ERR_ARG;
-  if (flip < 0 || flip > 7) return DUA_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = ((size_t)sum & 15) == 0;
-  const int G = wide ? (rw + 3) / 4 + 1 : rw;                // groups a row can touch at any shift
-  const dim3 grid((unsigned)(((long)rh * G + dua::BLEND_THREADS - 1) / dua::BLEND_THREADS), rd, C);
-  const long wvox = (long)C * rd * rh * rw;
-  for (int k = 0; k < nb; ++k) {                              // stream order = window-index order
-    const int* row = table + 4 * ((long)table_off + (long)k * table_stride);
-#define DUA_BLEND_ACC_W(T, WIDE, MIRROR)                                                                                    \
-  hipLaunchKernelGGL((dua::blend_accumulate_weighted_kernel<T, WIDE, MIRROR>), grid, dim3(dua::BLEND_THREADS), 0, s,        \
-                     reinterpret_cast<const T*>(windows) + k * wvox, row, sum, g0, g1, g2, floor_w, B, C, rd, rh, rw, Dp, Hp, Wp, \
-                     G, err_word, flip)
-#define DUA_BLEND_ACC_W_T(T)                                                                                                \
-  if (flip) { if (wide) DUA_BLEND_ACC_W(T, true, true); else DUA_BLEND_ACC_W(T, false, true); }                             \
-  else { if (wide) DUA_BLEND_ACC_W(T, true, false); else DUA_BLEND_ACC_W(T, false, false); }
-    if (dtype == DUA_F32) { DUA_BLEND_ACC_W_T(float) } else { DUA_BLEND_ACC_W_T(dua::f16) }
-#undef DUA_BLEND_ACC_W_T
-#undef DUA_BLEND_ACC_W
-  }
-  return (int)hipGetLastError();
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, false,
+                                 nullptr, nullptr, nullptr, 0.f, sum, B, Dp, Hp, Wp, err_word, stream);
 }
 
 int dua_blend_accumulate_weighted(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
                                   int table_rows, int table_off, int table_stride, const float* g0, const float* g1,
                                   const float* g2, float floor_w, float* sum, int B, int Dp, int Hp, int Wp, int* err_word,
                                   void* stream) {
-  return blend_accumulate_weighted_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, g0, g1,
-                                          g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, 0, true, g0, g1,
+                                 g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
 }
 
 int dua_blend_accumulate_weighted_mirrored(int dtype, int nb, int C, int rd, int rh, int rw, const void* windows, const int* table,
                                            int table_rows, int table_off, int table_stride, int flip, const float* g0,
                                            const float* g1, const float* g2, float floor_w, float* sum, int B, int Dp, int Hp,
                                            int Wp, int* err_word, void* stream) {
-  return blend_accumulate_weighted_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, g0,
-                                          g1, g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
+  return blend_accumulate_launch(dtype, nb, C, rd, rh, rw, windows, table, table_rows, table_off, table_stride, flip, true, g0, g1,
+                                 g2, floor_w, sum, B, Dp, Hp, Wp, err_word, stream);
 }
 
 int dua_blend_weight_sum(const int* starts_d, int nd, const int* starts_h, int nh, const int* starts_w, int nw, int rd, int rh,

@@ -328,7 +328,7 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
     (sum volume, divisor, crop offsets, spatial).  The divisor is the three coverage vectors on the device, or with
     ``mode="gaussian"`` the weight-sum volume fp32 [*padded], which every rank derives from the plan for itself.  With
     ``mirror_axes`` every call's window batch is predicted under the F flips of ``mirror_flips`` and each raw output goes to
-    the mirrored accumulate entry point, which un-flips it while reading; the divisor returned is F times the unmirrored one."""
+    ``ops.blend_accumulate`` with its flip mask, which un-flips it while reading; the divisor returned is F times the unmirrored one."""
     from . import ops
     spatial, roi, padded, pad, starts = _plan(inputs, roi_size, overlap)
     flips = mirror_flips(mirror_axes)
@@ -361,15 +361,7 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
                 acc = ops.zeros((batch, seg.shape[1], *padded), torch.float32, dev)
             if gather_dtype is not None:
                 seg = seg.to(gather_dtype)
-            if f == 0:
-                if weights is None:
-                    ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err)
-                else:
-                    ops.blend_accumulate_weighted(acc, seg.contiguous(), table, idxs[0], weights, world, err)
-            elif weights is None:
-                ops.blend_accumulate_mirrored(acc, seg.contiguous(), table, idxs[0], f, world, err)
-            else:
-                ops.blend_accumulate_weighted_mirrored(acc, seg.contiguous(), table, idxs[0], weights, f, world, err)
+            ops.blend_accumulate(acc, seg.contiguous(), table, idxs[0], world, err, weights=weights, flip=f)
             del seg
         g += nb
         del windows
@@ -400,13 +392,6 @@ def _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, ga
     return acc, coverage, crop_lo, spatial
 
 
-def _streamed_finish(acc, divisor, crop_lo, spatial, **want):
-    """ops.blend_finish, or its weighted form when ``_streamed_sum`` returned a weight-sum volume."""
-    from . import ops
-    fn = ops.blend_finish_weighted if isinstance(divisor, torch.Tensor) else ops.blend_finish
-    return fn(acc, divisor, crop_lo, spatial, **want)
-
-
 def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable,
                                       overlap: float = 0.25, group=None, gather_dtype: torch.dtype = None,
                                       timings: dict = None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125,
@@ -424,10 +409,11 @@ def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_s
     to dua_blend_accumulate_mirrored (or its weighted form), which un-flips it while reading -- no flipped copy of a window
     output -- and the divisor is scaled by F.  With a group each rank runs the F flips of its own windows into its own sum
     volume: the all-reduced bytes are unchanged.  Device tensors only."""
+    from . import ops
     _need_device(inputs, "streamed_sliding_window_inference")
     acc, divisor, crop_lo, spatial = _streamed_sum(inputs, roi_size, sw_batch_size, predictor, overlap, group, gather_dtype,
                                                    timings, kwargs, mode, sigma_scale, mirror_axes)
-    return _streamed_finish(acc, divisor, crop_lo, spatial, want_q=True)[0]
+    return ops.blend_finish(acc, divisor, crop_lo, spatial, want_q=True)[0]
 
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
@@ -465,10 +451,10 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
         if postprocess is not None:
             from .postprocess import filter_components
-            _, mask, _ = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True)
+            _, mask, _ = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True)
             mask, tallies = filter_components(mask, labels=labels, **postprocess)
         else:
-            _, mask, tallies = _streamed_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
+            _, mask, tallies = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
     dice = ops.dice_from_tallies(tallies) if tallies is not None else None
     if surface is None:
         return mask, dice

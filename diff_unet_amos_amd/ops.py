@@ -1889,51 +1889,11 @@ def aug_apply_smoothed(table, centroids, smoothing, params, roi, class_ids, imag
 
 # ---- evaluation: streamed sliding-window blend (csrc/blend.hip; engine.py:173-180, metric.py:37-49) ----
 
-def _blend_accumulate_shapes(sum_volume, windows, table, err):
-    """What the four accumulate entry points ask of their common arguments: (nb, C, rd, rh, rw, B, Dp, Hp, Wp)."""
-    _f32c(sum_volume, "sum_volume"); _i32c(table, "table")
-    assert windows.is_cuda and windows.is_contiguous() and windows.dim() == 5, "windows: contiguous [nb, C, rd, rh, rw] device tensor"
-    assert sum_volume.dim() == 5 and table.dim() == 2 and table.shape[1] == 4, "sum_volume: [B, C, Dp, Hp, Wp]; table: int32 [rows, 4]"
-    assert windows.device == sum_volume.device == table.device, "every tensor on one device"
-    if err is not None:
-        _i32c(err, "err")
-        assert err.numel() == 1 and err.device == sum_volume.device
-    nb, Cn, rd, rh, rw = windows.shape
-    B, Cs, Dp, Hp, Wp = sum_volume.shape
-    assert Cn == Cs, f"windows have {Cn} channels, the sum volume {Cs}"
-    return nb, Cn, rd, rh, rw, B, Dp, Hp, Wp
-
-
 def _flip_mask(flip):
     flip = int(flip)
     if not 0 <= flip <= 7:
         raise ValueError(f"flip: a mask of the spatial axes 0 .. 7 (bit a = axis a reversed), not {flip}")
     return flip
-
-
-def blend_accumulate(sum_volume, windows, table, table_off, table_stride=1, err=None):
-    """dua_blend_accumulate: ``sum_volume`` (fp32 [B, C, Dp, Hp, Wp]) += the ``windows`` ([nb, C, rd, rh, rw], fp32 or fp16) at the
-    positions rows ``table_off + k * table_stride`` of ``table`` (int32 [rows, 4] of (b, d, h, w)) give, in the order of k.
-    ``err`` (int32 [1], zeroed by the caller) is set to 1 by a row that had to be clamped into the volume."""
-    nb, Cn, rd, rh, rw, B, Dp, Hp, Wp = _blend_accumulate_shapes(sum_volume, windows, table, err)
-    with torch.cuda.device(sum_volume.device):
-        nv.check(nv.lib().dua_blend_accumulate(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows), nv.ptr(table),
-                                               table.shape[0], int(table_off), int(table_stride), nv.ptr(sum_volume), B, Dp, Hp, Wp,
-                                               nv.ptr(err), nv.stream_ptr()), "dua_blend_accumulate")
-    return sum_volume
-
-
-def blend_accumulate_mirrored(sum_volume, windows, table, table_off, flip, table_stride=1, err=None):
-    """dua_blend_accumulate_mirrored: ``blend_accumulate`` of ``torch.flip(windows, dims)`` without the flipped temporary --
-    ``flip`` is the mask of reversed spatial axes (bit 0 = D, bit 1 = H, bit 2 = W; 0 = ``blend_accumulate``'s bits)."""
-    nb, Cn, rd, rh, rw, B, Dp, Hp, Wp = _blend_accumulate_shapes(sum_volume, windows, table, err)
-    flip = _flip_mask(flip)
-    with torch.cuda.device(sum_volume.device):
-        nv.check(nv.lib().dua_blend_accumulate_mirrored(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows),
-                                                        nv.ptr(table), table.shape[0], int(table_off), int(table_stride), flip,
-                                                        nv.ptr(sum_volume), B, Dp, Hp, Wp, nv.ptr(err), nv.stream_ptr()),
-                 "dua_blend_accumulate_mirrored")
-    return sum_volume
 
 
 def _blend_weights(weights, roi, dev):
@@ -1945,31 +1905,33 @@ def _blend_weights(weights, roi, dev):
     return g0, g1, g2, float(floor)
 
 
-def blend_accumulate_weighted(sum_volume, windows, table, table_off, weights, table_stride=1, err=None):
-    """dua_blend_accumulate_weighted: ``blend_accumulate`` with every window multiplied by the importance map first.
-    ``weights`` = (g0, g1, g2, floor): the map is max((g0[z] * g1[y]) * g2[x], floor), rebuilt per voxel."""
-    nb, Cn, rd, rh, rw, B, Dp, Hp, Wp = _blend_accumulate_shapes(sum_volume, windows, table, err)
-    g0, g1, g2, floor = _blend_weights(weights, (rd, rh, rw), sum_volume.device)
+def blend_accumulate(sum_volume, windows, table, table_off, table_stride=1, err=None, weights=None, flip=0):
+    """dua_blend_accumulate[_weighted][_mirrored]: ``sum_volume`` (fp32 [B, C, Dp, Hp, Wp]) += the ``windows`` ([nb, C, rd, rh, rw],
+    fp32 or fp16) at the positions rows ``table_off + k * table_stride`` of ``table`` (int32 [rows, 4] of (b, d, h, w)) give, in
+    the order of k.  ``err`` (int32 [1], zeroed by the caller) is set to 1 by a row that had to be clamped into the volume.
+    ``weights`` = (g0, g1, g2, floor): every window is multiplied by the importance map max((g0[z] * g1[y]) * g2[x], floor)
+    first, rebuilt per voxel.  ``flip``: the mask of reversed spatial axes (bit 0 = D, bit 1 = H, bit 2 = W) -- the bits of
+    accumulating ``torch.flip(windows, dims)``, the map multiplying the un-flipped window, without the flipped temporary."""
+    _f32c(sum_volume, "sum_volume"); _i32c(table, "table")
+    assert windows.is_cuda and windows.is_contiguous() and windows.dim() == 5, "windows: contiguous [nb, C, rd, rh, rw] device tensor"
+    assert sum_volume.dim() == 5 and table.dim() == 2 and table.shape[1] == 4, "sum_volume: [B, C, Dp, Hp, Wp]; table: int32 [rows, 4]"
+    assert windows.device == sum_volume.device == table.device, "every tensor on one device"
+    if err is not None:
+        _i32c(err, "err")
+        assert err.numel() == 1 and err.device == sum_volume.device
+    nb, Cn, rd, rh, rw = windows.shape
+    B, Cs, Dp, Hp, Wp = sum_volume.shape
+    assert Cn == Cs, f"windows have {Cn} channels, the sum volume {Cs}"
+    name, extra = "dua_blend_accumulate", ()
+    if weights is not None:
+        g0, g1, g2, floor = _blend_weights(weights, (rd, rh, rw), sum_volume.device)
+        name, extra = name + "_weighted", (nv.ptr(g0), nv.ptr(g1), nv.ptr(g2), floor)
+    if flip:
+        name, extra = name + "_mirrored", (_flip_mask(flip), *extra)
     with torch.cuda.device(sum_volume.device):
-        nv.check(nv.lib().dua_blend_accumulate_weighted(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows),
-                                                        nv.ptr(table), table.shape[0], int(table_off), int(table_stride),
-                                                        nv.ptr(g0), nv.ptr(g1), nv.ptr(g2), floor, nv.ptr(sum_volume), B, Dp, Hp,
-                                                        Wp, nv.ptr(err), nv.stream_ptr()), "dua_blend_accumulate_weighted")
-    return sum_volume
-
-
-def blend_accumulate_weighted_mirrored(sum_volume, windows, table, table_off, weights, flip, table_stride=1, err=None):
-    """dua_blend_accumulate_weighted_mirrored: ``blend_accumulate_weighted`` of ``torch.flip(windows, dims)`` -- the map
-    multiplies the un-flipped window -- without the flipped temporary; ``flip`` as in ``blend_accumulate_mirrored``."""
-    nb, Cn, rd, rh, rw, B, Dp, Hp, Wp = _blend_accumulate_shapes(sum_volume, windows, table, err)
-    g0, g1, g2, floor = _blend_weights(weights, (rd, rh, rw), sum_volume.device)
-    flip = _flip_mask(flip)
-    with torch.cuda.device(sum_volume.device):
-        nv.check(nv.lib().dua_blend_accumulate_weighted_mirrored(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows),
-                                                                 nv.ptr(table), table.shape[0], int(table_off), int(table_stride),
-                                                                 flip, nv.ptr(g0), nv.ptr(g1), nv.ptr(g2), floor,
-                                                                 nv.ptr(sum_volume), B, Dp, Hp, Wp, nv.ptr(err), nv.stream_ptr()),
-                 "dua_blend_accumulate_weighted_mirrored")
+        nv.check(getattr(nv.lib(), name)(nv.dt_code(windows.dtype), nb, Cn, rd, rh, rw, nv.ptr(windows), nv.ptr(table), table.shape[0],
+                                         int(table_off), int(table_stride), *extra, nv.ptr(sum_volume), B, Dp, Hp, Wp, nv.ptr(err),
+                                         nv.stream_ptr()), name)
     return sum_volume
 
 
@@ -1991,22 +1953,13 @@ def blend_weight_sum(axis_starts, roi, padded, weights):
     return wsum
 
 
-def blend_finish_weighted(sum_volume, wsum, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
-    """dua_blend_finish_weighted: ``blend_finish`` dividing by ``wsum`` (fp32 [Dp, Hp, Wp], ``blend_weight_sum``) instead of a
-    window count."""
-    return _blend_finish(sum_volume, None, wsum, crop_lo, spatial, want_q, want_mask, labels)
-
-
-def blend_finish(sum_volume, coverage, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
-    """dua_blend_finish on the crop ``crop_lo`` .. ``crop_lo + spatial`` of ``sum_volume``: (q fp32 [B, C, *spatial] or None, mask
-    uint8 [B, C, *spatial] or None, tallies int64 [C, 3] = (|A & B|, |A|, |B|) or None).  ``coverage``: the three int32 device
-    vectors [Dp], [Hp], [Wp] whose product is the window count.  ``labels``: one-hot [B, C, *spatial] (fp32, uint8 or bool) or
-    a uint8 label map [B, *spatial] (class c = channel c)."""
-    return _blend_finish(sum_volume, coverage, None, crop_lo, spatial, want_q, want_mask, labels)
-
-
-def _blend_finish(sum_volume, coverage, wsum, crop_lo, spatial, want_q, want_mask, labels):
-    """The two finish entry points: the divisor is the product of the ``coverage`` vectors, or ``wsum`` when given."""
+def blend_finish(sum_volume, divisor, crop_lo, spatial, want_q=False, want_mask=False, labels=None):
+    """dua_blend_finish[_weighted] on the crop ``crop_lo`` .. ``crop_lo + spatial`` of ``sum_volume``: (q fp32 [B, C, *spatial] or
+    None, mask uint8 [B, C, *spatial] or None, tallies int64 [C, 3] = (|A & B|, |A|, |B|) or None).  ``divisor``: the three
+    int32 device vectors [Dp], [Hp], [Wp] whose product is the window count, or the fp32 [Dp, Hp, Wp] tensor of
+    ``blend_weight_sum``.  ``labels``: one-hot [B, C, *spatial] (fp32, uint8 or bool) or a uint8 label map [B, *spatial]
+    (class c = channel c)."""
+    wsum = divisor if isinstance(divisor, torch.Tensor) else None
     _f32c(sum_volume, "sum_volume")
     assert sum_volume.dim() == 5, "sum_volume: [B, C, Dp, Hp, Wp]"
     B, Cn, Dp, Hp, Wp = sum_volume.shape
@@ -2015,7 +1968,7 @@ def _blend_finish(sum_volume, coverage, wsum, crop_lo, spatial, want_q, want_mas
         _f32c(wsum, "wsum")
         assert tuple(wsum.shape) == (Dp, Hp, Wp) and wsum.device == dev, f"wsum: fp32 [{Dp}, {Hp}, {Wp}] on the volume's device"
     else:
-        nd, nh, nw = coverage
+        nd, nh, nw = divisor
         for t, n, name in ((nd, Dp, "nd"), (nh, Hp, "nh"), (nw, Wp, "nw")):
             _i32c(t, name)
             assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: int32 [{n}] on the volume's device"

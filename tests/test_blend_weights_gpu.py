@@ -140,8 +140,8 @@ def test_sum_volume_at_a_misaligned_base(volume, roi, overlap, windows_dtype):
     for i in range(0, nwin * B, 3):
         idxs = list(range(i, min(i + 3, nwin * B)))
         seg = torch.cat([pred(_window(x, j, nwin, starts, roi)) for j in idxs]).to(windows_dtype)
-        ops.blend_accumulate_weighted(shifted, seg, table, i, weights, err=err)
-        ops.blend_accumulate_weighted(aligned, seg, table, i, weights, err=err)
+        ops.blend_accumulate(shifted, seg, table, i, weights=weights, err=err)
+        ops.blend_accumulate(aligned, seg, table, i, weights=weights, err=err)
     assert int(err.item()) == 0
     assert torch.equal(shifted, want_sum) and torch.equal(aligned, want_sum)
     assert float(backing[0]) == 0 and float(backing[n + 1:].abs().sum()) == 0                  # nothing beside the view
@@ -149,8 +149,8 @@ def test_sum_volume_at_a_misaligned_base(volume, roi, overlap, windows_dtype):
     wsum = ops.blend_weight_sum(per_axis, roi, padded, weights)
     assert torch.equal(wsum, want_cnt)
     lo = tuple(pad[2 * (2 - k)] for k in range(3))
-    assert torch.equal(ops.blend_finish_weighted(shifted, wsum, lo, spatial, want_q=True)[0], want_q)
-    assert torch.equal(ops.blend_finish_weighted(aligned, wsum, lo, spatial, want_q=True)[0], want_q)
+    assert torch.equal(ops.blend_finish(shifted, wsum, lo, spatial, want_q=True)[0], want_q)
+    assert torch.equal(ops.blend_finish(aligned, wsum, lo, spatial, want_q=True)[0], want_q)
 
 
 PLANTED = [(3, 4, 17), (10, 20, 16), (31, 0, 31), (16, 16, 24), (0, 31, 20)]
@@ -211,10 +211,10 @@ def test_mask_and_dice_of_the_weighted_finish_pass(case):
     x = torch.nn.functional.pad(vol, pad)
     weights = _device_weights(roi, sigma_scale, dev)[0]
     for i in range(len(starts) * B):
-        ops.blend_accumulate_weighted(acc, pred(_window(x, i, len(starts), starts, roi)), table, i, weights)
+        ops.blend_accumulate(acc, pred(_window(x, i, len(starts), starts, roi)), table, i, weights=weights)
     assert torch.equal(acc, want_sum)
     wsum = ops.blend_weight_sum([torch.tensor(s, dtype=torch.int32, device=dev) for s in axis_starts(starts)], roi, padded, weights)
-    q2, mask2, tallies = ops.blend_finish_weighted(acc, wsum, lo, spatial, want_q=True, want_mask=True, labels=label_map)
+    q2, mask2, tallies = ops.blend_finish(acc, wsum, lo, spatial, want_q=True, want_mask=True, labels=label_map)
     assert torch.equal(q2, want_q) and torch.equal(mask2, mask)
     a, b = want_mask, map_onehot
     want_t = torch.stack([(a & b).sum((0, 2, 3, 4)), a.sum((0, 2, 3, 4)), b.sum((0, 2, 3, 4))], dim=1)
@@ -271,10 +271,10 @@ def test_a_clamped_row_sets_err_and_stays_inside_the_volume():
     win = torch.ones(1, Cn, R, R, R, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     bad = torch.tensor([[0, 0, 0, 0], [3, -5, 2, 100], [-1, 5, 1000, 4]], dtype=torch.int32).to(dev)
-    ops.blend_accumulate_weighted(acc, win, bad, 0, weights, err=err)
+    ops.blend_accumulate(acc, win, bad, 0, weights=weights, err=err)
     torch.cuda.synchronize()
     assert int(err.item()) == 0
-    ops.blend_accumulate_weighted(acc, torch.ones(2, Cn, R, R, R, device=dev), bad, 1, weights, err=err)
+    ops.blend_accumulate(acc, torch.ones(2, Cn, R, R, R, device=dev), bad, 1, weights=weights, err=err)
     torch.cuda.synchronize()
     assert int(err.item()) == 1
     want = torch.zeros_like(acc)
@@ -346,7 +346,7 @@ def test_argument_errors_of_the_weighted_entry_points():
     assert finish(od=1) == nv.ERR_ARG and finish(D=P + 1) == nv.ERR_ARG and finish(D=0) == nv.ERR_ARG
     torch.cuda.synchronize()
     with pytest.raises(ValueError):
-        ops.blend_accumulate_weighted(acc, win.double(), table, 0, (g0, g1, g2, floor))
+        ops.blend_accumulate(acc, win.double(), table, 0, weights=(g0, g1, g2, floor))
     with pytest.raises(ValueError):
         streamed_sliding_window_inference(acc, (R, R, R), 1, lambda x, **kw: x, mode="linear")
     with pytest.raises(ValueError):

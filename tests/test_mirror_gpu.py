@@ -1,4 +1,4 @@
-"""Mirror test-time augmentation on the GPU (csrc/blend.hip, the MIRROR forms of the accumulate kernels): the two entry points
+"""Mirror test-time augmentation on the GPU (csrc/blend.hip, the MIRROR forms of the accumulate kernel): the two entry points
 bit for bit against ``sum[slice] += torch.flip(window)`` at every shift, edge and mask, the streamed path against the
 list-and-blend path, evaluate_volume, the two-rank all-reduce form against the fp64 restatement, argument errors."""
 import os
@@ -75,15 +75,15 @@ def test_op_equals_slice_add_of_the_flipped_window_bit_for_bit(dtype, weighted, 
                             want[b, :, d:d + rd, h:h + rh, w:w + rw] += o if wmap is None else wmap * o
                         got = _copy_at(start, narrow)
                         if weighted:
-                            ops.blend_accumulate_weighted_mirrored(got, win, table, 1, weights, flip)
+                            ops.blend_accumulate(got, win, table, 1, weights=weights, flip=flip)
                         else:
-                            ops.blend_accumulate_mirrored(got, win, table, 1, flip)
+                            ops.blend_accumulate(got, win, table, 1, flip=flip)
                         assert torch.equal(got, want), (rw, rd, rh, Cn, flip, int((got != want).sum()))
                         checked += 1
                         if flip == 0:
                             plain = _copy_at(start, narrow)
                             if weighted:
-                                ops.blend_accumulate_weighted(plain, win, table, 1, weights)
+                                ops.blend_accumulate(plain, win, table, 1, weights=weights)
                             else:
                                 ops.blend_accumulate(plain, win, table, 1)
                             assert torch.equal(got, plain)
@@ -231,18 +231,18 @@ def test_argument_errors_and_an_out_of_range_row():
     assert int(err.item()) == 0 and float(acc.abs().sum()) == 0.0          # no refused call touched the volume
     for bad in (8, -1):
         with pytest.raises(ValueError):
-            ops.blend_accumulate_mirrored(acc, win, table, 0, bad)
+            ops.blend_accumulate(acc, win, table, 0, flip=bad)
         with pytest.raises(ValueError):
-            ops.blend_accumulate_weighted_mirrored(acc, win, table, 0, weights, bad)
+            ops.blend_accumulate(acc, win, table, 0, weights=weights, flip=bad)
     with pytest.raises(ValueError):
-        ops.blend_accumulate_mirrored(acc, win.double(), table, 0, 1)
+        ops.blend_accumulate(acc, win.double(), table, 0, flip=1)
 
     # rows outside the volume, built on the host: clamped into it and flagged, no fault -- as the unmirrored form
     bad_rows = torch.tensor([[0, 0, 0, 0], [3, -5, 2, 100], [-1, 5, 1000, 4]], dtype=torch.int32).to(dev)
-    ops.blend_accumulate_mirrored(acc, win[:1], bad_rows, 0, 6, err=err)
+    ops.blend_accumulate(acc, win[:1], bad_rows, 0, flip=6, err=err)
     torch.cuda.synchronize()
     assert int(err.item()) == 0
-    ops.blend_accumulate_mirrored(acc, win, bad_rows, 1, 6, err=err)
+    ops.blend_accumulate(acc, win, bad_rows, 1, flip=6, err=err)
     torch.cuda.synchronize()
     assert int(err.item()) == 1
     want = torch.zeros_like(acc)

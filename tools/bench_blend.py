@@ -56,26 +56,13 @@ def mirror_bench(args, dev, pool, table, calls, weights, Cn, roi, padded, nwin):
     masks = mirror_flips(args.mirror)
     acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
 
-    def plain(windows, g0):
-        if weights is None:
-            ops.blend_accumulate(acc, windows, table, g0)
-        else:
-            ops.blend_accumulate_weighted(acc, windows, table, g0, weights)
-
-    def unmirrored():
+    def mirrored(f=0):
         for g0, nb in calls:
-            plain(pool[:nb], g0)
-
-    def mirrored(f):
-        for g0, nb in calls:
-            if weights is None:
-                ops.blend_accumulate_mirrored(acc, pool[:nb], table, g0, f)
-            else:
-                ops.blend_accumulate_weighted_mirrored(acc, pool[:nb], table, g0, weights, f)
+            ops.blend_accumulate(acc, pool[:nb], table, g0, weights=weights, flip=f)
 
     def flip_then_plain(f):
         for g0, nb in calls:
-            plain(torch.flip(pool[:nb], _flip_dims(f)) if f else pool[:nb], g0)
+            ops.blend_accumulate(acc, torch.flip(pool[:nb], _flip_dims(f)) if f else pool[:nb], table, g0, weights=weights)
 
     def run(fn, *a):
         torch.cuda.synchronize()
@@ -84,7 +71,7 @@ def mirror_bench(args, dev, pool, table, calls, weights, Cn, roi, padded, nwin):
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    forms = [("a", unmirrored, ())] + [(f"b{f}", mirrored, (f,)) for f in masks] + [(f"c{f}", flip_then_plain, (f,)) for f in masks]
+    forms = [("a", mirrored, ())] + [(f"b{f}", mirrored, (f,)) for f in masks] + [(f"c{f}", flip_then_plain, (f,)) for f in masks]
     for _ in range(args.warmup):
         for _, fn, a in forms:
             run(fn, *a)
@@ -155,20 +142,16 @@ def main():
     if args.mirror is not None:
         return mirror_bench(args, dev, pool, table, calls, weights if gaussian else None, Cn, roi, padded, nwin)
 
-    def streamed_gaussian():
+    def streamed(weights=None):
         acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
         for g0, nb in calls:
-            ops.blend_accumulate_weighted(acc, pool[:nb], table, g0, weights)
-        wsum = ops.blend_weight_sum(per_axis, roi, padded, weights)
-        _, mask, tallies = ops.blend_finish_weighted(acc, wsum, crop_lo, spatial, want_mask=True, labels=labels)
+            ops.blend_accumulate(acc, pool[:nb], table, g0, weights=weights)
+        divisor = cov if weights is None else ops.blend_weight_sum(per_axis, roi, padded, weights)
+        _, mask, tallies = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
         return mask, ops.dice_from_tallies(tallies)
 
-    def streamed():
-        acc = ops.zeros((1, Cn, *padded), torch.float32, dev)
-        for g0, nb in calls:
-            ops.blend_accumulate(acc, pool[:nb], table, g0)
-        _, mask, tallies = ops.blend_finish(acc, cov, crop_lo, spatial, want_mask=True, labels=labels)
-        return mask, ops.dice_from_tallies(tallies)
+    def streamed_gaussian():
+        return streamed(weights)
 
     def listed():
         q = _blend(listed_windows, 1, Cn, padded, roi, starts, pad, spatial, dev, torch.float32, wmap)
