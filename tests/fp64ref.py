@@ -229,6 +229,27 @@ def deconv_ref(A, w, bias, dtype, child):
     return ref + b, ab + b.abs(), sq
 
 
+def deconv_res_ref(lo, skip, w3, wd, child, up_first=True):
+    """dua_deconv_k2s2_res_fwd at sampled fine-grid voxels: conv1x1x1(cat((ConvTranspose3d_k2s2(lo), skip))) without the
+    upsampled tensor.  lo [P, Cu] = the coarse activation at each voxel's parent, skip [P, Cs] = the skip half at the voxel
+    (float64, exact fp16 values), ``child`` [P] = (d & 1) * 4 + (h & 1) * 2 + (w & 1); w3 [Cout, Cmid + Cs] (``up_first``: the
+    upsampled half's columns first), wd [Cu, Cmid, 2, 2, 2].  The composed weights W3_up . Wd[child] are formed in fp32 and
+    rounded once to fp16 as ops.pack_deconv_res_weights forms them (a one-ulp flip of a weight whose fp32 composition sums in
+    another order is what the caller's ``emulated_in`` term of ``bound`` covers), the skip weights are rounded to fp16.
+    Returns (ref, sum |terms|, sum terms^2), each [P, Cout]; the chain is ``chain_length(Cu + Cs, fp16)``."""
+    w3, wd = w3.detach().float().cpu(), wd.detach().float().cpu()
+    Cu, Cmid = wd.shape[:2]
+    Cs = w3.shape[1] - Cmid
+    w3_up, w3_sk = (w3[:, :Cmid], w3[:, Cmid:]) if up_first else (w3[:, Cs:], w3[:, :Cs])
+    comp = torch.einsum("umk,om->uok", wd.reshape(Cu, Cmid, 8), w3_up).half().double()          # [Cu, Cout, 8]
+    wsk = w3_sk.half().double().t()                                                              # [Cs, Cout]
+    Wc = comp[:, :, child].permute(2, 0, 1)                                                      # [P, Cu, Cout]
+    ref = torch.einsum("pc,pco->po", lo, Wc) + skip @ wsk
+    ab = torch.einsum("pc,pco->po", lo.abs(), Wc.abs()) + skip.abs() @ wsk.abs()
+    sq = torch.einsum("pc,pco->po", lo ** 2, Wc ** 2) + skip ** 2 @ wsk ** 2
+    return ref, ab, sq
+
+
 def replicate_source(pts, coarse_dims):
     """Output voxels of a transposed convolution whose buffer is one plane longer on an odd axis: the replicate-padded plane
     2 * S copies plane 2 * S - 1 (UpCat.forward's pad).  Returns the voxel the value is computed at."""

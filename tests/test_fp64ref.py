@@ -331,3 +331,63 @@ def test_instnorm_backward_bound_rejects_a_wrong_slope_outside_the_kink_margin()
     res = R.check(dY, r["dY"], R.in_bwd_dy_bound(r, b1, b2, torch.float16))
     assert res.ratio > 1.0, res
     assert tuple(res.where) == flip
+
+
+# ---- the residual branch over cat((ConvTranspose3d(lo), skip)) without the upsampled tensor (R.deconv_res_ref) ---------------------
+def _deconv_res_case():
+    """48 coarse channels -> 48 middle, 48 skip channels, 48 outputs on an 8 x 12 x 8 fine grid; the kernel's stand-in composes
+    the weights per child with matrix products in fp32 (another summation order than the reference's einsum), rounds them once
+    to fp16, contracts in fp32 and stores fp16."""
+    g = torch.Generator().manual_seed(11)
+    Cu, Cmid, Cs, Co, dims = 48, 48, 48, 48, (8, 12, 8)
+    lo = torch.randn(1, *(s // 2 for s in dims), Cu, generator=g).half()
+    skip = torch.randn(1, *dims, Cs, generator=g).half()
+    w3 = torch.randn(Co, Cmid + Cs, generator=g) / (Cmid + Cs) ** 0.5
+    wd = torch.randn(Cu, Cmid, 2, 2, 2, generator=g) / Cu ** 0.5
+    pts = R.sample_voxels(1, dims, n_random=200, seed=3)
+    child = (pts[:, 1] & 1) * 4 + (pts[:, 2] & 1) * 2 + (pts[:, 3] & 1)
+    par = pts.clone()
+    par[:, 1:] >>= 1
+    lo_q, sk_q = R.gather_points(lo, par, 0, Cu), R.gather_points(skip, pts, 0, Cs)
+    comp = torch.stack([(w3[:, :Cmid] @ wd.reshape(Cu, Cmid, 8)[:, :, k].t()).half().float() for k in range(8)])     # [8, Co, Cu]
+    wsk = w3[:, Cmid:].half().float()
+
+    def stand_in(ch, with_skip=True):
+        y = torch.einsum("pc,poc->po", lo_q.float(), comp[ch])
+        if with_skip:
+            y = y + sk_q.float() @ wsk.t()
+        return y.half()
+
+    ref, ab, sq = R.deconv_res_ref(lo_q, sk_q, w3, wd, child)
+    bnd = R.bound(ref, ab, sq, R.chain_length(Cu + Cs, torch.float16), torch.float16, emulated_in=torch.float16)
+    return dict(pts=pts, child=child, stand_in=stand_in, ref=ref, bnd=bnd)
+
+
+def test_deconv_res_emulation_passes():
+    c = _deconv_res_case()
+    r = R.check(c["stand_in"](c["child"]), c["ref"], c["bnd"], c["pts"])
+    assert r.ratio <= 1, r
+    assert r.ratio > 0.05, f"the bound is loose where it should be tight: {r}"
+
+
+@pytest.mark.parametrize("where", [BORDER, INTERIOR], ids=["border", "interior"])
+def test_deconv_res_wrong_child_is_rejected(where):
+    """One voxel takes the composed weights of the child with the other parity along w."""
+    c = _deconv_res_case()
+    where = (where[0], where[1], where[2], where[3] % 8)          # the case's grid is 8 wide
+    i = _row(c["pts"], where)
+    ch = c["child"].clone()
+    ch[i] ^= 1
+    got = c["stand_in"](c["child"])
+    got[i] = c["stand_in"](ch)[i]
+    r = R.check(got, c["ref"], c["bnd"], c["pts"])
+    assert r.ratio > 1 and r.where[0] == where, r
+
+
+def test_deconv_res_missing_skip_term_is_rejected():
+    c = _deconv_res_case()
+    i = _row(c["pts"], (0, 7, 8, 4))
+    got = c["stand_in"](c["child"])
+    got[i] = c["stand_in"](c["child"], with_skip=False)[i]
+    r = R.check(got, c["ref"], c["bnd"], c["pts"])
+    assert r.ratio > 1 and r.where[0] == (0, 7, 8, 4), r

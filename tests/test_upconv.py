@@ -284,16 +284,11 @@ def test_deconv_res_matches_deconv_cat_pointwise(shape):
     # pack_deconv_res_weights does; a one-ulp flip of a weight whose fp32 composition sums in another order is the RSS term),
     # the skip weights rounded to fp16, per element at the sampled fine-grid voxels
     import fp64ref as R
-    comp = torch.einsum("umk,om->uok", wd.float().reshape(Cu, Cmid, 8), w3[:, :Cmid].float()).half().double()   # [Cu, Cout, 8]
-    wsk = w3[:, Cmid:].half().double().t()                                                                       # [Cs, Cout]
     pts = R.sample_voxels(N, (2 * D, 2 * H, 2 * W), n_random=1000, seed=sum(shape))
     child = (pts[:, 1] & 1) * 4 + (pts[:, 2] & 1) * 2 + (pts[:, 3] & 1)
     lo_q = lo.to(dt).double()[pts[:, 0], :, pts[:, 1] >> 1, pts[:, 2] >> 1, pts[:, 3] >> 1]                    # [P, Cu]
     sk_q = skip.to(dt).double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]]                                  # [P, Cs]
-    Wc = comp[:, :, child].permute(2, 0, 1)                                                                       # [P, Cu, Cout]
-    ref64 = torch.einsum("pc,pco->po", lo_q, Wc) + sk_q @ wsk
-    ab = torch.einsum("pc,pco->po", lo_q.abs(), Wc.abs()) + sk_q.abs() @ wsk.abs()
-    sq = torch.einsum("pc,pco->po", lo_q ** 2, Wc ** 2) + sk_q ** 2 @ wsk ** 2
+    ref64, ab, sq = R.deconv_res_ref(lo_q, sk_q, w3, wd, child, up_first=True)
     bnd = R.bound(ref64, ab, sq, R.chain_length(Cu + Cs, dt), dt, emulated_in=dt)
     r = R.check(got.double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]], ref64, bnd, pts)
     assert r.ratio <= 1, r
