@@ -309,6 +309,8 @@ _SIGS = {
     "dua_prep_foreground_box": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "dua_prep_resample": (C.c_int, [C.c_int, _P, _P, C.POINTER(PrepGeom), _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
     "dua_prep_restore": (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "dua_blend_finish_labelmap": (C.c_int, [_P] + [C.c_int] * 4 + [_P] * 4 + [C.c_int] * 9 + [_P] * 6 + [C.c_int] * 3 + [C.c_float] +
+                                  [_P] * 4),
     "dua_suf_accumulate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
 }
 

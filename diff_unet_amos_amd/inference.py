@@ -464,6 +464,64 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     return mask, dice, fn(mask, _one_hot_labels(labels, mask.shape[1]), kw.pop("tolerance"), **kw)
 
 
+def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
+                 distributed: bool = False, group=None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125,
+                 min_prob: float = 0.0):
+    """The deliverable of one case: (label map uint8 on the grid of the SCAN, Dice fp64 [C] against ``label`` or None).  ``case``:
+    a ``prepare.PreparedCase`` -- the streamed blend runs on ``case.image[None, None]`` and one pass
+    (dua_blend_finish_labelmap) turns the sum volume into the label map: per voxel of the scan the class probabilities
+    sigmoid(blend) of the 8 surrounding prepared voxels, interpolated linearly, the lowest class with the largest one, 0 below
+    ``min_prob`` and outside the foreground box.  No [C, *scan] tensor is written.  ``case`` may be a plain device tensor
+    [1, 1, D, H, W] instead: it is its own grid (identity tables, every weight 0), and the result is the arg-max of
+    sigmoid(blend) on it.  ``label``: the raw uint8 label map of the scan, [*scan] on the case's device; class c = channel c, a
+    value >= C counts nowhere.  The other arguments as ``evaluate_volume``.  Argument errors are raised before any predictor
+    call."""
+    from . import ops
+    from .prepare import PreparedCase
+    mirror_flips(mirror_axes)
+    min_prob = float(min_prob)
+    if not 0.0 <= min_prob <= 1.0:                       # NaN fails both comparisons
+        raise ValueError(f"segment_case: min_prob lies in [0, 1], got {min_prob}")
+    if isinstance(case, PreparedCase):
+        image, source_shape = case.image, tuple(case.source_shape)
+        if not torch.is_tensor(image) or image.dim() != 3 or image.dtype != torch.float32:
+            raise ValueError("segment_case: case.image is an fp32 tensor [D, H, W]")
+        image = image[None, None]
+    elif torch.is_tensor(case):
+        if case.dim() != 5 or case.shape[0] != 1 or case.shape[1] != 1:
+            raise ValueError(f"segment_case: a plain volume is [1, 1, D, H, W] (one case per call), got {tuple(case.shape)}")
+        if case.dtype != torch.float32:
+            raise ValueError(f"segment_case: a plain volume is float32, got {case.dtype}")
+        image, source_shape = case, tuple(case.shape[2:])
+    else:
+        raise ValueError("segment_case: case is a PreparedCase or a device tensor [1, 1, D, H, W]")
+    if label is not None:
+        if not torch.is_tensor(label) or label.dtype != torch.uint8:
+            raise ValueError("segment_case: label is a uint8 tensor, the raw label map of the scan")
+        if tuple(label.shape) != source_shape:
+            raise ValueError(f"segment_case: label has the shape of the scan {source_shape}, got {tuple(label.shape)}")
+    _need_device(image, "segment_case")
+    if label is not None:
+        if label.device != image.device:
+            raise ValueError(f"segment_case: label is on {label.device}, the case on {image.device}")
+    if distributed and group is None:
+        import torch.distributed as dist
+        group = dist.group.WORLD
+    if isinstance(case, PreparedCase):
+        tables = case.linear_tables()
+    else:
+        D, H, W = source_shape
+        steps = (H * W, W, 1)
+        tables = (tuple(torch.arange(n, dtype=torch.int32, device=image.device) * s for n, s in zip(source_shape, steps)),
+                  tuple(torch.zeros(n, dtype=torch.float32, device=image.device) for n in source_shape), (0, 1, 2))
+    with torch.no_grad():
+        acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
+                                                       None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
+        out, tallies = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
+                                                 None if label is None else label.contiguous())
+    return out, ops.dice_from_tallies(tallies) if tallies is not None else None
+
+
 SURFACE_KEYS = ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting", "distances")
 
 

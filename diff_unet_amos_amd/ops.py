@@ -2004,6 +2004,54 @@ def blend_finish(sum_volume, divisor, crop_lo, spatial, want_q=False, want_mask=
     return q, mask, tallies
 
 
+def blend_finish_labelmap(sum_volume, divisor, crop_lo, spatial, tables, source_shape, min_prob=0.0, reference=None):
+    """dua_blend_finish_labelmap: (label map uint8 [*source_shape], tallies int64 [C, 3] or None) from the sum volume of one
+    case, fp32 [1, C, Dp, Hp, Wp] (or [C, Dp, Hp, Wp]).  ``divisor``, ``crop_lo``, ``spatial``: as ``blend_finish``.  ``tables``:
+    (three int32 device vectors lo [X_p], three fp32 device vectors weight [X_p], the prepared axis of each source axis) --
+    ``prepare.PreparedCase.linear_tables()``.  ``reference``: a uint8 label map [*source_shape] on the same device."""
+    wsum = divisor if isinstance(divisor, torch.Tensor) else None
+    _f32c(sum_volume, "sum_volume")
+    if sum_volume.dim() == 5:
+        assert sum_volume.shape[0] == 1, f"sum_volume: one volume per call, got a batch of {sum_volume.shape[0]}"
+        sum_volume = sum_volume[0]
+    assert sum_volume.dim() == 4, "sum_volume: [1, C, Dp, Hp, Wp] or [C, Dp, Hp, Wp]"
+    Cn, Dp, Hp, Wp = sum_volume.shape
+    if Cn > min(nv.BLEND_MAX_CLASSES, 255):
+        raise ValueError(f"at most {min(nv.BLEND_MAX_CLASSES, 255)} classes, got {Cn}")
+    dev = sum_volume.device
+    if wsum is not None:
+        _f32c(wsum, "wsum")
+        assert tuple(wsum.shape) == (Dp, Hp, Wp) and wsum.device == dev, f"wsum: fp32 [{Dp}, {Hp}, {Wp}] on the volume's device"
+        counts = (None, None, None)
+    else:
+        counts = tuple(divisor)
+        for t, n, name in zip(counts, (Dp, Hp, Wp), ("nd", "nh", "nw")):
+            _i32c(t, name)
+            assert tuple(t.shape) == (n,) and t.device == dev, f"{name}: int32 [{n}] on the volume's device"
+    od, oh, ow = (int(v) for v in crop_lo)
+    D, H, W = (int(v) for v in spatial)
+    X = tuple(int(x) for x in source_shape)
+    lo, weight, axis = tables
+    axis = tuple(int(a) for a in axis)
+    assert len(X) == 3 and sorted(axis) == [0, 1, 2], "source_shape: three extents; tables: a permutation of the axes"
+    for t, w, x, p in zip(lo, weight, X, range(3)):
+        _i32c(t, f"lo[{p}]"); _f32c(w, f"weight[{p}]")
+        assert tuple(t.shape) == tuple(w.shape) == (x,) and t.device == w.device == dev, \
+            f"tables of source axis {p}: [{x}] on the volume's device"
+    if reference is not None:
+        _u8c(reference, "reference")
+        assert tuple(reference.shape) == X and reference.device == dev, f"reference: uint8 {list(X)} on the volume's device"
+    out = torch.empty(X, dtype=torch.uint8, device=dev)
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if reference is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_blend_finish_labelmap(nv.ptr(sum_volume), Cn, Dp, Hp, Wp, *(nv.ptr(t) for t in counts), nv.ptr(wsum),
+                                                    od, oh, ow, D, H, W, *X, *(nv.ptr(t) for t in lo),
+                                                    *(nv.ptr(t) for t in weight), *axis, float(min_prob), nv.ptr(out),
+                                                    nv.ptr(reference), nv.ptr(tallies), nv.stream_ptr()),
+                 "dua_blend_finish_labelmap")
+    return out, tallies
+
+
 def dice_from_tallies(tallies):
     """The dice_per_class rule (metric.py:37-49) on dua_blend_finish's counts: 2 |A & B| / (|A| + |B|), 0 when both are empty;
     fp64 [C] on the tallies' device, no host read."""

@@ -9,6 +9,7 @@ one box pass and one fused gather (csrc/volume_prep.hip)::
     case = prepare_case(image_hu, label, affine=affine)              # one host read: the foreground box
     volume = DeviceVolume(case.image, case.label, num_classes=16)    # or DeviceVolume.from_raw(image_hu, label, affine)
     mask_on_scan_grid = case.restore(prediction_mask)                # uint8 [C, *prepared] -> uint8 [C, *source]
+    label_map, dice = inference.segment_case(model, case, raw_label) # uint8 [*source]: one class per voxel of the scan
 
 What each step computes is fixed in include/dua_hip.h ("case preparation"), not by MONAI's source; tests/prepare_ref.py
 restates it in fp64.  The geometry is host arithmetic on 16 numbers and a few KB of per-axis tables (numpy, fp64): the
@@ -82,6 +83,31 @@ def restore_table(n_in, s_in, s_out, n_out):
     clamped to [0, n_out - 1]."""
     y = np.arange(int(n_in), dtype=np.float64) * float(s_in) / float(s_out)
     return np.clip(np.rint(y), 0, int(n_out) - 1).astype(np.int64)
+
+
+def linear_restore_tables(geometry):
+    """The linear way back of a ``PreparedGeometry``, per SOURCE axis: dict(lo, weight, step, axis), each a 3-tuple.  ``axis[p]`` is
+    the prepared axis that shows source axis p, n its extent.  For the oriented index k of a source index inside the box,
+    y = min(k s_in / s_out, n - 1), lower = floor(y) and ``weight`` = y - lower (fp32 [X_p], rounded once; at y = n - 1 the lower
+    index is the last one and the weight 0, so equal spacings give zero weights throughout);
+    ``lo`` (int32 [X_p]) is lower times the prepared element stride of that axis, -1 outside the box; a flipped axis reads the
+    tables back to front.  ``step`` is that stride -- the distance to the upper neighbour -- or 0 when n == 1, where lower and
+    weight are 0 as well.  ``spacing_tables`` in the other direction, the linear twin of ``PreparedGeometry.restore``
+    (include/dua_hip.h, "label map on the grid of the scan")."""
+    g = geometry
+    out_stride = (g.shape[1] * g.shape[2], g.shape[2], 1)
+    lo, weight, step, axis = [None] * 3, [None] * 3, [0] * 3, [0] * 3
+    for j, (p, f) in enumerate(zip(g.perm, g.flip)):
+        n = g.shape[j]
+        y = np.minimum(np.arange(g.n_in[j], dtype=np.float64) * g.s_in[j] / g.pixdim[j], float(n - 1))
+        lower = np.floor(y)
+        w = (y - lower).astype(np.float32)
+        below = lower.astype(np.int64) * out_stride[j]
+        tab, wt = np.full(g.source_shape[p], -1, dtype=np.int64), np.zeros(g.source_shape[p], dtype=np.float32)
+        b0, b1 = g.box[p]
+        tab[b0:b1], wt[b0:b1] = (below[::-1], w[::-1]) if f else (below, w)
+        lo[p], weight[p], step[p], axis[p] = tab.astype(np.int32), wt, out_stride[j] if n > 1 else 0, j
+    return dict(lo=tuple(lo), weight=tuple(weight), step=tuple(step), axis=tuple(axis))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -164,11 +190,23 @@ class PreparedCase:
     orientation: tuple
     geometry: PreparedGeometry
     _restore_tables: object = None
+    _linear_tables: object = None
 
     @property
     def tables(self):
         g = self.geometry
         return {"lo": g.lo, "weight": g.weight, "nearest": g.nearest}
+
+    def linear_tables(self):
+        """``linear_restore_tables`` of this case on its device, as ``ops.blend_finish_labelmap`` takes them: (three int32 lo
+        vectors, three fp32 weight vectors, the prepared axis of each source axis); uploaded once."""
+        import torch
+        if self._linear_tables is None:
+            t = linear_restore_tables(self.geometry)
+            dev = self.image.device
+            self._linear_tables = (tuple(torch.from_numpy(v).to(dev) for v in t["lo"]),
+                                   tuple(torch.from_numpy(v).to(dev) for v in t["weight"]), t["axis"])
+        return self._linear_tables
 
     def restore(self, mask):
         """A uint8 (or bool) mask on the prepared grid, [*prepared] or [C, *prepared], on the grid of the scan: uint8 [*source]

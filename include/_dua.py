@@ -43,6 +43,11 @@ _L.dua_blend_accumulate_weighted_mirrored.restype = C.c_int
 _L.dua_blend_accumulate_weighted_mirrored.argtypes = ([C.c_int] * 6 + [C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                                                       [C.c_void_p] * 3 + [C.c_float, C.c_void_p] + [C.c_int] * 4 +
                                                       [C.c_void_p, C.c_void_p])
+# the uint8 label map on the grid of the scan straight from the sum volume of the streamed blend (corner logits, sigmoid,
+# trilinear interpolation by per-axis tables, arg-max, optional tallies against the scan's label; the contract is in dua_hip.h)
+_L.dua_blend_finish_labelmap.restype = C.c_int
+_L.dua_blend_finish_labelmap.argtypes = ([C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p] * 6 +
+                                         [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 4)
 
 
 def _stream():

@@ -1211,6 +1211,51 @@ int dua_prep_resample(int dtype, const void* src, const unsigned char* src_label
 int dua_prep_restore(const unsigned char* mask, long prepared_voxels, int C, int X0, int X1, int X2, const int* tab0,
                      const int* tab1, const int* tab2, unsigned char* out, void* stream);
 
+/* ---- label map on the grid of the scan, from the blended sum volume (csrc/labelmap.hip) -----------------------------
+ * The deliverable of a segmentation model: ONE uint8 label per voxel of the scan.  The usual export resamples the class
+ * probabilities to the scan's grid and takes the arg-max there; the reference has no such step (test.py scores on the prepared
+ * grid), so the contract is fixed HERE.  One volume per call.  The prepared grid is the crop [od, od + D) x [oh, oh + H) x
+ * [ow, ow + W) of the sum volume fp32 [C][Dp][Hp][Wp] of dua_blend_accumulate; the source grid is [X0][X1][X2].
+ *
+ * Tables (DEVICE, from the host: diff_unet_amos_amd/prepare.py linear_restore_tables).  Source axis p maps to prepared axis
+ * axis_p (axis0, axis1, axis2: a permutation of 0, 1, 2).  lo_p: int32 [X_p], the lower prepared index along axis_p TIMES that
+ * axis's element stride in the prepared volume (H W, W, 1), or negative outside the foreground box; w_p: fp32 [X_p], the weight
+ * of the upper neighbour.  Host arithmetic in fp64 per oriented index k: y = min(k s_in / s_out, n - 1), lower = floor(y),
+ * weight = y - lower rounded once to fp32 (n = the prepared extent; n == 1: 0 and 0; y == n - 1: the last index and 0, so a
+ * grid of the scan's own spacing is copied exactly); a flipped axis reads the table back to front.  The upper neighbour is
+ * min(lower + 1, n - 1): the lower index itself at the end of the extent, where the weight is 0.
+ * The kernel divides an entry by its stride and clamps the index into [0, n - 1]: no table makes it read outside the volume.
+ *
+ * Per source voxel (x0, x1, x2):
+ *   1. any lo_p[x_p] negative: label 0.
+ *   2. for each channel c and each of the 8 corners (z, y, x) of the prepared cell, the logit
+ *        q = sum[c][od + z][oh + y][ow + x] / divisor(z, y, x)                          IEEE fp32 division
+ *      with divisor = (float)(nd[od + z] nh[oh + y] nw[ow + x]) (the count vectors of dua_blend_finish) or
+ *      wsum[od + z][oh + y][ow + x] (dua_blend_finish_weighted): exactly one of (nd, nh, nw) and wsum is given, and q is the
+ *      q_out of that entry point, bit for bit.
+ *   3. p = 1 / (1 + __expf(-q)) in fp32 (the sigmoid of csrc/seg_loss.hip).
+ *   4. seven lerps fmaf(w, b - a, a), the difference rounded first, nothing contracted: the four pairs along prepared axis 2,
+ *      then the two along axis 1, then axis 0 -- the form and order of dua_prep_resample.
+ *   5. label = the lowest c whose interpolated probability is the largest: c ascends, a channel wins with a strict >, a NaN
+ *      never wins (all NaN: label 0).
+ *   6. winning probability < min_prob: label 0.  min_prob in [0, 1]; 0 switches the rule off.
+ * label_out: uint8 [X0][X1][X2] (WRITTEN).  reference (or NULL): uint8 [X0][X1][X2], a label map of the scan; tallies (given
+ * exactly when reference is): 64-bit unsigned [C][3] (WRITTEN, the call zeroes it first) = |label == c and reference == c|,
+ * |label == c|, |reference == c|, the layout of dua_blend_finish; a reference value >= C counts nowhere.  Integer counters,
+ * one integer atomic per non-zero word and workgroup: exact, independent of the order of arrival.
+ * The interpolated probabilities are never stored: the running best (p, c) lives in registers while c walks the channels.
+ * Per source voxel inside the box: 8 C fp32 reads of the sum volume (neighbouring voxels share corners: cache hits),
+ * 8 C exponentials, 16 C divisions; 1 byte written, 1 read with a reference.
+ * C <= DUA_BLEND_MAX_CLASSES and C <= 255; every volume holds fewer than 2^31 voxels; fp32 and int32 pointers 4-byte, tallies
+ * 8-byte aligned.  Invalid arguments (a NULL pointer, both or neither divisor form, C out of range, a non-positive or too
+ * large extent, a crop outside the volume, axes that are no permutation, min_prob outside [0, 1] or NaN, a misaligned
+ * pointer): DUA_ERR_ARG, before the device is touched. */
+int dua_blend_finish_labelmap(const float* sum, int C, int Dp, int Hp, int Wp, const int* nd, const int* nh, const int* nw,
+                              const float* wsum, int od, int oh, int ow, int D, int H, int W, int X0, int X1, int X2,
+                              const int* lo0, const int* lo1, const int* lo2, const float* w0, const float* w1, const float* w2,
+                              int axis0, int axis1, int axis2, float min_prob, unsigned char* label_out,
+                              const unsigned char* reference, unsigned long long* tallies, void* stream);
+
 /* ---- Step-Uncertainty Fusion of repeated DDIM runs (csrc/suf.hip) ---------------------------------------------------------
  * Diff-UNet's published inference rule: the DDIM loop runs R times per window, and after every step the runs' predictions
  * are added into the result with a weight that grows with the step index and shrinks with the entropy of the runs' mean
