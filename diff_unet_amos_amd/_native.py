@@ -171,6 +171,12 @@ class AugSmoothing(C.Structure):
     _fields_ = [("alpha", C.c_float), ("order", C.c_float), ("epsilon", C.c_float), ("max_value", C.c_float)]
 
 
+class AugAffineConfig(C.Structure):
+    """dua_aug_affine_config."""
+    _fields_ = [("rotate_prob", C.c_float), ("rotate_tan_half", C.c_float * 3), ("zoom_prob", C.c_float), ("zoom_min", C.c_float),
+                ("zoom_span", C.c_float), ("pad_value", C.c_float), ("reserved", C.c_int)]
+
+
 class PrepGeom(C.Structure):
     """dua_prep_geom."""
     _fields_ = [("n_in", C.c_int * 3), ("n_out", C.c_int * 3), ("stride", C.c_long * 3), ("base", C.c_long),
@@ -182,6 +188,7 @@ BLEND_MAX_CLASSES = 64   # DUA_BLEND_MAX_CLASSES
 CC_MAX_CAP = 65536       # DUA_CC_MAX_CAP
 SUF_MAX_RUNS = 16        # DUA_SUF_MAX_RUNS
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
+AUG_AFFINE_M, AUG_AFFINE_T, AUG_AFFINE_ZOOM, AUG_AFFINE_EVENTS, AUG_AFFINE_PAD, AUG_AFFINE_WORDS = 0, 9, 12, 13, 14, 16
 
 _P = C.c_void_p
 ABI_VERSION = 8          # DUA_ABI_VERSION of include/dua_hip.h this binding was written against
@@ -295,6 +302,10 @@ _SIGS = {
     "dua_aug_class_centroids": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dua_aug_apply_smoothed": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _P, C.c_int, _P, _P, _P, _P]),
+    "dua_aug_draw_affine": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.POINTER(AugAffineConfig), C.c_ulonglong, _P,
+                                      C.c_int, C.c_ulonglong, _P, _P, _P, _P]),
+    "dua_aug_apply_affine": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _P, C.c_int, _P, _P, _P, _P]),
     "dua_blend_accumulate": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 + [_P, _P]),
     "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "dua_blend_accumulate_weighted": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P] +

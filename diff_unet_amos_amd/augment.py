@@ -21,6 +21,15 @@ smoothed channels are evaluated where the patch is written::
 
 ``class_ids=range(1, K)`` is the reference's ``labels[:, 1:]`` for training (engine.py:159-160).  tests/label_smoothing_ref.py
 restates the definition; tests/golden/label_smoothing_golden.npz holds the reference's own outputs.
+
+Random rotation and zoom, the two spatial augmentations that resample (the reference has neither; nnU-Net and MONAI's
+RandAffined / RandZoomd apply them by default), come from the same two launches as well::
+
+    producer = DeviceBatchProducer(volumes, rotate_prob=0.2, rotate_range=(0.52, 0.52, 0.52), zoom_prob=0.2,
+                                   zoom_range=(0.7, 1.4))
+    images, labels = producer.next(ids)          # trilinear image, nearest label, pad_value outside the volume
+
+include/dua_hip.h ("random rotation and zoom") fixes them; tests/augment_affine_ref.py restates that text.
 """
 from __future__ import annotations
 
@@ -50,6 +59,19 @@ def pack_params(ints, floats, device=None):
         raise ValueError("pack_params: as many rows of floats as of integers")
     out = torch.cat([ints.cpu(), floats.cpu().contiguous().view(torch.int32)], dim=1).contiguous()
     return out.to(device) if device is not None else out
+
+
+AFFINE_COLUMNS = ("matrix", "tan_half", "zoom", "events", "pad_value")
+
+
+def split_affine(affine):
+    """``affine`` (fp32 [B, 16]) as (matrix fp32 [B, 3, 3]: source offset = matrix @ output offset; tan_half fp32 [B, 3]: the
+    tangent of half the rotation angle about d, h, w; zoom fp32 [B]; events int32 [B]: bit 0 rotation, bit 1 zoom; pad_value
+    fp32 [B])."""
+    assert affine.dtype == torch.float32 and affine.dim() == 2 and affine.shape[1] == nv.AUG_AFFINE_WORDS
+    events = affine[:, nv.AUG_AFFINE_EVENTS:nv.AUG_AFFINE_EVENTS + 1].contiguous().view(torch.int32)[:, 0]
+    return (affine[:, :nv.AUG_AFFINE_T].reshape(-1, 3, 3), affine[:, nv.AUG_AFFINE_T:nv.AUG_AFFINE_ZOOM],
+            affine[:, nv.AUG_AFFINE_ZOOM], events, affine[:, nv.AUG_AFFINE_PAD])
 
 
 @dataclasses.dataclass(frozen=True)
@@ -178,10 +200,22 @@ class DeviceBatchProducer:
     ``smoothing`` (a ``LabelSmoothing``) makes ``labels`` the centroid-distance smoothed channels of ``class_ids`` instead of
     the one-hot ones: same launches, same ``params``, and ``apply`` of a logged row reproduces the smoothed batch.  Every volume
     then needs ``num_classes`` (one value for all).  ``class_ids=range(1, K)`` gives the channels the reference trains on
-    (``labels[:, 1:]``, engine.py:159-160).  Crop centres come from the hard label map either way."""
+    (``labels[:, 1:]``, engine.py:159-160).  Crop centres come from the hard label map either way.
+
+    ``rotate_prob`` / ``zoom_prob`` above 0 turn on the augmentations that resample, about the centre of the cropped window and
+    on voxel indices (not millimetres), before the flips and the 90-degree rotation: with probability ``rotate_prob`` a rotation
+    about each axis d, h, w by an angle within ``+-rotate_range[axis]`` (radians, each in [0, pi / 2]); with probability
+    ``zoom_prob`` a zoom drawn uniformly from ``zoom_range = (min, max)`` (above 1 magnifies).  The image is interpolated
+    trilinearly, the label map taken at the nearest voxel (class 0 outside the volume), and a voxel outside the volume holds
+    ``pad_value`` (0 is air after the intensity window).  The rotation is drawn as the tangent of half its angle, uniformly, so
+    that the matrix needs no sine or cosine and is reproducible bit for bit: the angle is therefore not uniform, its density
+    rises by tan(angle / 2)^2 towards the ends of the range (7 % at +-30 degrees).  Then ``draw`` returns ``(params, affine)``
+    (``split_affine`` names the columns of the second), ``apply`` takes both, and a logged pair replays its batch.  With both
+    probabilities 0 (the default) nothing changes: the same launches, the same objects, the same bits."""
 
     def __init__(self, volumes, roi=(96, 96, 96), class_ids=range(16), pos=1, neg=1, flip_prob=0.1, rot90_prob=0.1, max_k=3,
-                 scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0, smoothing=None):
+                 scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0, smoothing=None, rotate_prob=0.0,
+                 rotate_range=(0.0, 0.0, 0.0), zoom_prob=0.0, zoom_range=(1.0, 1.0), pad_value=0.0):
         volumes = list(volumes)
         if not volumes or not all(isinstance(v, DeviceVolume) for v in volumes):
             raise ValueError("DeviceBatchProducer: a non-empty list of DeviceVolume")
@@ -199,7 +233,8 @@ class DeviceBatchProducer:
             raise ValueError(f"DeviceBatchProducer: 1 .. {nv.AUG_MAX_CLASSES} class ids, got {len(class_ids)}")
         if any(c < 0 or c > 255 for c in class_ids):
             raise ValueError("DeviceBatchProducer: class ids are values of a uint8 label map (0 .. 255)")
-        probs = dict(flip_prob=flip_prob, rot90_prob=rot90_prob, scale_prob=scale_prob, shift_prob=shift_prob)
+        probs = dict(flip_prob=flip_prob, rot90_prob=rot90_prob, scale_prob=scale_prob, shift_prob=shift_prob,
+                     rotate_prob=rotate_prob, zoom_prob=zoom_prob)
         for name, p in probs.items():
             if not 0.0 <= float(p) <= 1.0:
                 raise ValueError(f"DeviceBatchProducer: {name} is a probability, got {p}")
@@ -212,6 +247,24 @@ class DeviceBatchProducer:
         if float(rot90_prob) > 0 and roi[0] != roi[1]:
             raise ValueError(f"DeviceBatchProducer: the rotation is in the plane of the first two axes and needs roi[0] == roi[1] "
                              f"(roi = {roi}); pass rot90_prob=0")
+        try:
+            rotate_range = tuple(float(r) for r in rotate_range)
+            zoom_range = tuple(float(z) for z in zoom_range)
+            pad_value = float(pad_value)
+        except (TypeError, ValueError):
+            raise ValueError("DeviceBatchProducer: rotate_range is three angles, zoom_range two factors, pad_value a number") from None
+        if len(rotate_range) != 3 or not all(0.0 <= r <= math.pi / 2 for r in rotate_range):
+            raise ValueError(f"DeviceBatchProducer: rotate_range is three angles in radians, each in [0, pi / 2], got {rotate_range}")
+        if len(zoom_range) != 2 or not (0.0 < zoom_range[0] <= zoom_range[1] and math.isfinite(zoom_range[1])):
+            raise ValueError(f"DeviceBatchProducer: zoom_range is (min, max) with 0 < min <= max, finite, got {zoom_range}")
+        if not math.isfinite(pad_value) or abs(pad_value) > 3.0e38:
+            raise ValueError(f"DeviceBatchProducer: pad_value is a finite fp32 number, got {pad_value}")
+        self.affine = float(rotate_prob) > 0 or float(zoom_prob) > 0
+        if self.affine and max(max(v.shape) for v in volumes) > 2 ** 22:
+            raise ValueError("DeviceBatchProducer: rotation and zoom take voxel indices in fp32: extents up to 2^22")
+        # tan(angle / 2) in fp64, rounded once (at most 1 for pi / 2); fp32(max - min) likewise
+        self.affine_cfg = nv.AugAffineConfig(float(rotate_prob), (C.c_float * 3)(*[min(math.tan(r / 2), 1.0) for r in rotate_range]),
+                                             float(zoom_prob), zoom_range[0], zoom_range[1] - zoom_range[0], pad_value, 0)
         if smoothing is not None:
             if not isinstance(smoothing, LabelSmoothing):
                 raise ValueError("DeviceBatchProducer: smoothing is a LabelSmoothing or None")
@@ -266,26 +319,44 @@ class DeviceBatchProducer:
 
     def draw(self, volume_ids, counter=None):
         """The random decisions of one batch as ``params`` (int32 [B, 8] on the device; ``split_params`` names the columns).
-        ``counter=None`` uses and advances the producer's device-resident call counter; an integer is used for this call only."""
+        ``counter=None`` uses and advances the producer's device-resident call counter; an integer is used for this call only.
+        A producer with rotation or zoom returns ``(params, affine)``: the same ``params`` and fp32 [B, 16] rows that
+        ``split_affine`` names."""
         ids = self._ids(volume_ids)
         params = torch.empty((ids.numel(), nv.AUG_PARAM_WORDS), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
+            if self.affine:
+                affine = torch.empty((ids.numel(), nv.AUG_AFFINE_WORDS), dtype=torch.float32, device=self.device)
+                return ops.aug_draw_affine(self.table, ids, self.cfg, self.affine_cfg, self.seed, self._counter, params, affine,
+                                           self._status, counter_value=counter)
             return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter)
 
-    def apply(self, params, out_images=None, out_labels=None):
+    def apply(self, params, out_images=None, out_labels=None, affine=None):
         """The batch ``params`` describes: (images fp32 [B, 1, *roi], labels fp32 [B, len(class_ids), *roi]); the labels are
-        one-hot, or smoothed when the producer was built with ``smoothing``."""
+        one-hot, or smoothed when the producer was built with ``smoothing``.  A producer with rotation or zoom needs the
+        ``affine`` rows of the same ``draw``; any producer resamples through rows it is given."""
         assert torch.is_tensor(params) and params.is_cuda and params.device == self.device, "params: a tensor on the producer's device"
+        if self.affine and affine is None:
+            raise ValueError("DeviceBatchProducer.apply: this producer rotates or zooms: pass the affine rows of draw() as affine=")
         B = params.shape[0]
         if out_images is None:
             out_images = torch.empty((B, 1) + self.roi, dtype=torch.float32, device=self.device)
         if out_labels is None:
             out_labels = torch.empty((B, len(self.class_ids)) + self.roi, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
+            if affine is not None:
+                assert torch.is_tensor(affine) and affine.is_cuda and affine.device == self.device, \
+                    "affine: a tensor on the producer's device"
+                smooth = dict(centroids=self.centroids, smoothing=self._smoothing) if self.smoothing is not None else {}
+                return ops.aug_apply_affine(self.table, params, affine, self.roi, self.class_table, out_images, out_labels,
+                                            self._status, **smooth)
             if self.smoothing is not None:
                 return ops.aug_apply_smoothed(self.table, self.centroids, self._smoothing, params, self.roi, self.class_table,
                                               out_images, out_labels, self._status)
             return ops.aug_apply(self.table, params, self.roi, self.class_table, out_images, out_labels, self._status)
 
     def next(self, volume_ids, out_images=None, out_labels=None):
+        if self.affine:
+            params, affine = self.draw(volume_ids)
+            return self.apply(params, out_images, out_labels, affine=affine)
         return self.apply(self.draw(volume_ids), out_images, out_labels)

@@ -21,6 +21,14 @@
 //   smoothed apply : the apply kernel with another body for the label planes (template parameter MODE): the same index code
 //            gives the source index of a lane's 4 voxels, the centroids of the row's volume sit in LDS (one broadcast read per
 //            channel), and a channel costs 4 x (sub, fma, sqrt, add, rcp, mul, sub, min) before its 16-byte store.
+//   affine : random rotation and zoom.  The draw kernel's AFFINE form takes two more Philox blocks and writes, beside the params
+//            row, the matrix M = R / z from half-angle tangents in fp64 (no sine, no cosine: a numpy restatement has its bits).
+//            The affine apply keeps the store side of apply and reads by gather: 8 image loads and 1 label byte per voxel from
+//            a source region of a few MB that neighbouring lanes share.  A workgroup covers a compact 4 x 8 x 32 tile of the
+//            output (a wave one 8 x 32 piece of a plane, a 128-byte line per row and store), not a run of 1 024 voxels: under
+//            a rotation an output row crosses a source line every few voxels, and it is the rows beside, above and below it
+//            that use the rest of those lines (measured: DESIGN.md 10c-1).  The flip / rot90 index code, the row checks and
+//            the smoothed channel are device functions all apply kernels share.
 // -ffp-contract=off (csrc/Makefile) keeps the three fp32 operations of the intensity transform, and the two of each drawn
 // value, separately rounded; the pragma below says so for this file whatever the command line.
 #include "common.hpp"
@@ -93,11 +101,40 @@ __device__ __forceinline__ float symmetric(float half_width, uint32_t x) {
   return t + (-half_width);
 }
 
+// one row of dua_aug_draw_affine's second output: M = R_d R_h R_w / z from the half-angle tangents, every operation one IEEE
+// fp64 operation in the order include/dua_hip.h writes them (this file compiles without contraction), rounded once to fp32
+__device__ void aug_affine_row(float* __restrict__ dst, const float t[3], float z, int events, float pad) {
+  double c[3], s[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double td = (double)t[a], q = td * td, n = 1.0 + q;
+    c[a] = (1.0 - q) / n;
+    s[a] = (td + td) / n;
+  }
+  const double cd = c[0], ch = c[1], cw = c[2], sd = s[0], sh = s[1], sw = s[2];
+  const double R[9] = {ch * cw, 0.0 - (ch * sw), sh,
+                       (cd * sw) + (sd * (sh * cw)), (cd * cw) - (sd * (sh * sw)), 0.0 - (sd * ch),
+                       (sd * sw) - (cd * (sh * cw)), (sd * cw) + (cd * (sh * sw)), cd * ch};
+  const double g = 1.0 / (double)z;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) dst[DUA_AUG_AFFINE_M + j] = (float)(R[j] * g);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) dst[DUA_AUG_AFFINE_T + a] = t[a];
+  dst[DUA_AUG_AFFINE_ZOOM] = z;
+  reinterpret_cast<int*>(dst)[DUA_AUG_AFFINE_EVENTS] = events;
+  dst[DUA_AUG_AFFINE_PAD] = pad;
+  dst[DUA_AUG_AFFINE_PAD + 1] = 0.f;
+}
+
+// AFFINE: dua_aug_draw_affine -- two more Philox blocks per sample and the affine row beside the params row, which keeps its bits
+template <bool AFFINE>
 __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua_aug_volume* __restrict__ table, int nvol,
                                                                       const int* __restrict__ ids, int B, dua_aug_config cfg,
                                                                       unsigned long long seed, unsigned long long* counter,
                                                                       int use_counter, unsigned long long counter_value,
-                                                                      int* __restrict__ params, int* status) {
+                                                                      int* __restrict__ params, int* status,
+                                                                      dua_aug_affine_config acfg, float* __restrict__ affine) {
+  const float no_turn[3] = {0.f, 0.f, 0.f};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long call = use_counter ? counter_value : *counter;
   __syncthreads();                                        // every wave holds the call counter before one lane moves it on
@@ -105,11 +142,13 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
   for (int b = wave; b < B; b += AUG_DRAW_WAVES) {
     int* row = params + (long)b * DUA_AUG_PARAM_WORDS;
     const int vid = ids[b];
+    float* arow = AFFINE ? affine + (long)b * DUA_AUG_AFFINE_WORDS : nullptr;
     if (vid < 0 || vid >= nvol) {
       if (lane == 0) {
         row[DUA_AUG_VOLUME] = -1;
         for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
         if (status) *status = 1;
+        if constexpr (AFFINE) aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
       }
       continue;
     }
@@ -131,11 +170,32 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
     const int k = unit_float(w[1][1]) < cfg.rot90_prob ? 1 + (int)below(w[1][2], (uint32_t)cfg.max_k) : 0;
     const float scale = unit_float(w[1][3]) < cfg.scale_prob ? symmetric(cfg.scale_factors, w[2][0]) : 0.f;
     const float shift = unit_float(w[2][1]) < cfg.shift_prob ? symmetric(cfg.shift_offsets, w[2][2]) : 0.f;
+    float turn[3] = {0.f, 0.f, 0.f}, zoom = 1.f;
+    int events = 0;
+    if constexpr (AFFINE) {
+      uint32_t x[2][4];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        x[j][0] = (uint32_t)call; x[j][1] = (uint32_t)(call >> 32); x[j][2] = (uint32_t)b; x[j][3] = (uint32_t)(3 + j);
+        philox4x32_10(x[j], (uint32_t)seed, (uint32_t)(seed >> 32));
+      }
+      if (unit_float(x[0][0]) < acfg.rotate_prob) {
+        events |= 1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) turn[a] = symmetric(acfg.rotate_tan_half[a], x[0][1 + a]);
+      }
+      if (unit_float(x[1][0]) < acfg.zoom_prob) {
+        events |= 2;
+        const float t = acfg.zoom_span * unit_float(x[1][1]);
+        zoom = t + acfg.zoom_min;
+      }
+    }
     if (count == 0) {                                     // a table row the host should never have built
       if (lane == 0) {
         row[DUA_AUG_VOLUME] = -1;
         for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
         if (status) *status = 1;
+        if constexpr (AFFINE) aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
       }
       continue;
     }
@@ -183,6 +243,12 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
       for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
       if (status) *status = 1;
     }
+    if constexpr (AFFINE) {
+      if (lane == 0) {
+        if (written) aug_affine_row(arow, turn, zoom, events, acfg.pad_value);
+        else aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
+      }
+    }
   }
 }
 
@@ -197,6 +263,66 @@ struct AugSmooth {
   float alpha, order, epsilon, max_value;
 };
 enum { SMOOTH_NONE = 0, SMOOTH_ORDER1 = 1, SMOOTH_POW = 2 };
+
+// what every apply kernel checks of its params row before it reads or writes anything (block-uniform); vol = the row's volume
+__device__ __forceinline__ bool aug_row_ok(const dua_aug_volume* __restrict__ table, int nvol, const int* __restrict__ row, int Rd,
+                                           int Rh, int Rw, dua_aug_volume& vol) {
+  const int vid = row[DUA_AUG_VOLUME], sd0 = row[DUA_AUG_START_D], sh0 = row[DUA_AUG_START_H], sw0 = row[DUA_AUG_START_W];
+  const int flip = row[DUA_AUG_FLIP], k = row[DUA_AUG_K];
+  bool ok = vid >= 0 && vid < nvol && (unsigned)flip < 8u && (unsigned)k < 4u && (!(k & 1) || Rd == Rh);
+  if (ok) {
+    vol = table[vid];
+    ok = sd0 >= 0 && sh0 >= 0 && sw0 >= 0 && sd0 <= vol.D - Rd && sh0 <= vol.H - Rh && sw0 <= vol.W - Rw;
+  }
+  return ok;
+}
+
+// the smoothed forms: the centroid of class_ids[ch] in volume vid into cen[ch]; false (block-uniform) for an id without a row
+__device__ __forceinline__ bool aug_stage_centroids(float (*cen)[4], int* bad_id, int vid, const unsigned char* __restrict__ class_ids,
+                                                    int C, const AugSmooth& sm) {
+  if (threadIdx.x == 0) *bad_id = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < C) {                             // C <= DUA_AUG_MAX_CLASSES < AUG_THREADS
+    const int id = class_ids[threadIdx.x];
+    if (id < sm.K) {
+      const float* c3 = sm.centroids + ((long)vid * sm.K + id) * 3;
+      cen[threadIdx.x][0] = c3[0]; cen[threadIdx.x][1] = c3[1]; cen[threadIdx.x][2] = c3[2];
+    } else {
+      *bad_id = 1;
+    }
+  }
+  __syncthreads();
+  return *bad_id == 0;
+}
+
+// linear output voxel o -> its position (od, oh, ow)
+__device__ __forceinline__ void aug_output_position(unsigned o, int Rh, int Rw, int& od, int& oh, int& ow) {
+  const unsigned orow = o / (unsigned)Rw;
+  ow = (int)(o - orow * (unsigned)Rw); od = (int)(orow / (unsigned)Rh); oh = (int)(orow - (unsigned)od * (unsigned)Rh);
+}
+
+// output row (od, oh) -> the window indices (a, c) along d and h of the source row it comes from, for every (flip, k); along w the
+// row runs forwards, or backwards with flip bit 2.  The one copy of the flip / rot90 index code.
+__device__ __forceinline__ void aug_window_row(int od, int oh, int k, int flip, int Rd, int Rh, int& a, int& c) {
+  // inverse of rot90(., k, (0, 1)): k = 1: out[i][j] = x[j][n - 1 - i]; k = 2: x[n0 - 1 - i][n1 - 1 - j]; k = 3: x[n - 1 - j][i]
+  switch (k) {
+    case 1: a = oh; c = Rh - 1 - od; break;
+    case 2: a = Rd - 1 - od; c = Rh - 1 - oh; break;
+    case 3: a = Rd - 1 - oh; c = od; break;
+    default: a = od; c = oh; break;
+  }
+  if (flip & 1) a = Rd - 1 - a;
+  if (flip & 2) c = Rh - 1 - c;
+}
+
+// one smoothed label value: onehot = [label == class], (dw, t) = the w difference and dd^2 + dh^2 against the class centroid
+template <int MODE>
+__device__ __forceinline__ float aug_smoothed(float onehot, float dw, float t, const AugSmooth& sm) {
+  const float dist = __builtin_amdgcn_sqrtf(__builtin_fmaf(dw, dw, t));
+  const float p = MODE == SMOOTH_POW ? powf(dist, sm.order) : dist;
+  const float s = __builtin_amdgcn_rcpf(p + sm.epsilon) * sm.alpha;
+  return fminf(fabsf(onehot - s), sm.max_value);
+}
 
 // V output voxels per lane (4: roi_w is a multiple of 4, so a group never crosses a row and every store is 16-byte aligned).
 // MODE: what a label plane holds -- SMOOTH_NONE: the one-hot channel; SMOOTH_ORDER1 / SMOOTH_POW: the centroid-distance
@@ -214,30 +340,13 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
   const int* row = params + (long)b * DUA_AUG_PARAM_WORDS;
   const int vid = row[DUA_AUG_VOLUME], sd0 = row[DUA_AUG_START_D], sh0 = row[DUA_AUG_START_H], sw0 = row[DUA_AUG_START_W];
   const int flip = row[DUA_AUG_FLIP], k = row[DUA_AUG_K];
-  bool ok = vid >= 0 && vid < nvol && (unsigned)flip < 8u && (unsigned)k < 4u && (!(k & 1) || Rd == Rh);
   dua_aug_volume vol = {};
-  if (ok) {
-    vol = table[vid];
-    ok = sd0 >= 0 && sh0 >= 0 && sw0 >= 0 && sd0 <= vol.D - Rd && sh0 <= vol.H - Rh && sw0 <= vol.W - Rw;
-  }
-  if (!ok) {                                              // block-uniform: nothing is read, nothing is written
+  if (!aug_row_ok(table, nvol, row, Rd, Rh, Rw, vol)) {   // block-uniform: nothing is read, nothing is written
     if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
     return;
   }
   if constexpr (MODE != SMOOTH_NONE) {
-    if (threadIdx.x == 0) bad_id = 0;
-    __syncthreads();
-    if ((int)threadIdx.x < C) {                           // C <= DUA_AUG_MAX_CLASSES < AUG_THREADS
-      const int id = class_ids[threadIdx.x];
-      if (id < sm.K) {
-        const float* c3 = sm.centroids + ((long)vid * sm.K + id) * 3;
-        cen[threadIdx.x][0] = c3[0]; cen[threadIdx.x][1] = c3[1]; cen[threadIdx.x][2] = c3[2];
-      } else {
-        bad_id = 1;
-      }
-    }
-    __syncthreads();
-    if (bad_id) {                                         // block-uniform again: a class id without a centroid row
+    if (!aug_stage_centroids(cen, &bad_id, vid, class_ids, C, sm)) {       // block-uniform again: a class id without a centroid row
       if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
       return;
     }
@@ -245,18 +354,9 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
   const long vox = (long)Rd * Rh * Rw;
   const unsigned o = (blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x) * V;   // first output voxel of this lane (vox < 2^31)
   if (o >= vox) return;
-  const unsigned orow = o / (unsigned)Rw;
-  const int ow = (int)(o - orow * (unsigned)Rw), od = (int)(orow / (unsigned)Rh), oh = (int)(orow - (unsigned)od * (unsigned)Rh);
-  // inverse of rot90(., k, (0, 1)): k = 1: out[i][j] = x[j][n - 1 - i]; k = 2: x[n0 - 1 - i][n1 - 1 - j]; k = 3: x[n - 1 - j][i]
-  int a, c;
-  switch (k) {
-    case 1: a = oh; c = Rh - 1 - od; break;
-    case 2: a = Rd - 1 - od; c = Rh - 1 - oh; break;
-    case 3: a = Rd - 1 - oh; c = od; break;
-    default: a = od; c = oh; break;
-  }
-  if (flip & 1) a = Rd - 1 - a;
-  if (flip & 2) c = Rh - 1 - c;
+  int od, oh, ow, a, c;
+  aug_output_position(o, Rh, Rw, od, oh, ow);
+  aug_window_row(od, oh, k, flip, Rd, Rh, a, c);
   const bool fw = (flip & 4) != 0;
   const long src = ((long)(sd0 + a) * vol.H + (sh0 + c)) * vol.W + sw0;     // start of the source row's window
   const float factor = 1.f + __int_as_float(row[DUA_AUG_SCALE]);
@@ -305,11 +405,7 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
       float m[V];
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        const float dw = fx[e] - cw;
-        const float dist = __builtin_amdgcn_sqrtf(__builtin_fmaf(dw, dw, t));
-        const float p = MODE == SMOOTH_POW ? powf(dist, sm.order) : dist;
-        const float s = __builtin_amdgcn_rcpf(p + sm.epsilon) * sm.alpha;
-        m[e] = fminf(fabsf((lb[e] == id ? 1.f : 0.f) - s), sm.max_value);
+        m[e] = aug_smoothed<MODE>(lb[e] == id ? 1.f : 0.f, fx[e] - cw, t, sm);
       }
       if constexpr (V == 4) {
         Vec mv;
@@ -319,6 +415,141 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
       } else {
         *(lab + (long)ch * vox) = m[0];
       }
+    }
+  }
+}
+
+constexpr int AFF_TILE_D = 4, AFF_TILE_H = 8, AFF_TILE_W = 32;
+static_assert(AFF_TILE_D * AFF_TILE_H * AFF_TILE_W == 4 * AUG_THREADS && AFF_TILE_W % 4 == 0, "one tile per workgroup, 4 voxels per lane");
+
+// floorf(s) as an index that can be compared and incremented: clamped to [-2, 2^31 - 128] first, where the clamp only moves an
+// index that lies outside every volume to another one that does (a NaN becomes -2)
+__device__ __forceinline__ int aug_floor_index(float fl) { return (int)fminf(fmaxf(fl, -2.f), 2147483520.f); }
+
+// dua_aug_apply_affine: the store side of aug_apply_kernel (a lane owns V consecutive output voxels of a row along w, one store
+// per plane), the read side a gather -- per voxel the 8 corners of the trilinear cell around s = M r + c and the label byte at
+// the nearest voxel.  The window index p of an output voxel comes from the same index code, so flips and k apply after the
+// resampling.  The products with r_d and r_h and their sum are the same numbers for the V voxels of a lane: computed once,
+// they are the bits each voxel would get from scratch; nothing is carried along the row.
+template <int V, int MODE>
+__global__ void __launch_bounds__(AUG_THREADS) aug_apply_affine_kernel(const dua_aug_volume* __restrict__ table, int nvol,
+                                                                      const int* __restrict__ params,
+                                                                      const float* __restrict__ affine, int Rd, int Rh, int Rw,
+                                                                      const unsigned char* __restrict__ class_ids, int C,
+                                                                      float* __restrict__ images, float* __restrict__ labels,
+                                                                      int* status, AugSmooth sm) {
+  using Vec = typename OutVec<V>::T;
+  __shared__ float cen[MODE == SMOOTH_NONE ? 1 : DUA_AUG_MAX_CLASSES][4];
+  __shared__ int bad_id;
+  const int b = blockIdx.y;
+  const int* row = params + (long)b * DUA_AUG_PARAM_WORDS;
+  const int vid = row[DUA_AUG_VOLUME], sd0 = row[DUA_AUG_START_D], sh0 = row[DUA_AUG_START_H], sw0 = row[DUA_AUG_START_W];
+  const int flip = row[DUA_AUG_FLIP], k = row[DUA_AUG_K];
+  dua_aug_volume vol = {};
+  if (!aug_row_ok(table, nvol, row, Rd, Rh, Rw, vol)) {
+    if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
+    return;
+  }
+  if constexpr (MODE != SMOOTH_NONE) {
+    if (!aug_stage_centroids(cen, &bad_id, vid, class_ids, C, sm)) {
+      if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
+      return;
+    }
+  }
+  const long vox = (long)Rd * Rh * Rw;
+  int od, oh, ow, a, c;
+  unsigned o;
+  if constexpr (V == 4) {
+    // a workgroup covers a compact AFF_TILE_D x AFF_TILE_H x AFF_TILE_W tile of the output, a wave one 8 x 32 piece of a plane:
+    // under a rotation the rows of a tile read neighbouring source lines, which the CU's L1 then holds for all of them
+    const unsigned tiles_w = (Rw + AFF_TILE_W - 1) / AFF_TILE_W, tiles_h = (Rh + AFF_TILE_H - 1) / AFF_TILE_H;
+    const unsigned tw = blockIdx.x % tiles_w, trow = blockIdx.x / tiles_w, th = trow % tiles_h, td = trow / tiles_h;
+    const unsigned lw = threadIdx.x % (AFF_TILE_W / 4), lrow = threadIdx.x / (AFF_TILE_W / 4);
+    ow = (int)(tw * AFF_TILE_W + lw * 4); oh = (int)(th * AFF_TILE_H + lrow % AFF_TILE_H); od = (int)(td * AFF_TILE_D + lrow / AFF_TILE_H);
+    if (od >= Rd || oh >= Rh || ow >= Rw) return;          // roi_w is a multiple of 4: a lane's voxels are all inside or all outside
+    o = ((unsigned)od * (unsigned)Rh + (unsigned)oh) * (unsigned)Rw + (unsigned)ow;
+  } else {
+    o = blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x;
+    if (o >= vox) return;
+    aug_output_position(o, Rh, Rw, od, oh, ow);
+  }
+  aug_window_row(od, oh, k, flip, Rd, Rh, a, c);
+  const bool fw = (flip & 4) != 0;
+  const float* arow = affine + (long)b * DUA_AUG_AFFINE_WORDS;
+  float m[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) m[j] = arow[DUA_AUG_AFFINE_M + j];
+  const float pad = arow[DUA_AUG_AFFINE_PAD];
+  const float hd = 0.5f * (float)(Rd - 1), hh = 0.5f * (float)(Rh - 1), hw = 0.5f * (float)(Rw - 1);      // exact
+  const float cd = (float)sd0 + hd, chh = (float)sh0 + hh, cw = (float)sw0 + hw;
+  const float rd = (float)a - hd, rh = (float)c - hh;
+  const float qd = m[0] * rd + m[1] * rh, qh = m[3] * rd + m[4] * rh, qw = m[6] * rd + m[7] * rh;
+  const float factor = 1.f + __int_as_float(row[DUA_AUG_SCALE]);
+  const float shift = __int_as_float(row[DUA_AUG_SHIFT]);
+  const unsigned D = (unsigned)vol.D, H = (unsigned)vol.H, W = (unsigned)vol.W;
+  float px[V], jd[V], jh[V], jw[V];
+  unsigned char lb[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    const float rw = (float)(fw ? Rw - 1 - (ow + e) : ow + e) - hw;
+    const float s0 = (qd + m[2] * rw) + cd, s1 = (qh + m[5] * rw) + chh, s2 = (qw + m[8] * rw) + cw;
+    const float l0 = floorf(s0), l1 = floorf(s1), l2 = floorf(s2);
+    const float f0 = s0 - l0, f1 = s1 - l1, f2 = s2 - l2;
+    const int i0 = aug_floor_index(l0), i1 = aug_floor_index(l1), i2 = aug_floor_index(l2);
+    float cor[2][2][2];
+#pragma unroll
+    for (int ed = 0; ed < 2; ++ed)
+#pragma unroll
+      for (int eh = 0; eh < 2; ++eh)
+#pragma unroll
+        for (int ew = 0; ew < 2; ++ew) {
+          const unsigned d = (unsigned)(i0 + ed), h = (unsigned)(i1 + eh), w = (unsigned)(i2 + ew);
+          const bool in = d < D && h < H && w < W;        // a negative index is a huge unsigned one
+          cor[ed][eh][ew] = in ? vol.image[((long)d * vol.H + h) * vol.W + w] : pad;
+        }
+    float y[2];
+#pragma unroll
+    for (int ed = 0; ed < 2; ++ed) {
+      const float x0 = __builtin_fmaf(f2, cor[ed][0][1] - cor[ed][0][0], cor[ed][0][0]);
+      const float x1 = __builtin_fmaf(f2, cor[ed][1][1] - cor[ed][1][0], cor[ed][1][0]);
+      y[ed] = __builtin_fmaf(f1, x1 - x0, x0);
+    }
+    px[e] = __builtin_fmaf(f0, y[1] - y[0], y[0]);
+    const int n0 = f0 >= 0.5f ? 1 : 0, n1 = f1 >= 0.5f ? 1 : 0, n2 = f2 >= 0.5f ? 1 : 0;
+    const unsigned d = (unsigned)(i0 + n0), h = (unsigned)(i1 + n1), w = (unsigned)(i2 + n2);
+    lb[e] = (d < D && h < H && w < W) ? vol.label[((long)d * vol.H + h) * vol.W + w] : (unsigned char)0;
+    jd[e] = l0 + (float)n0; jh[e] = l1 + (float)n1; jw[e] = l2 + (float)n2;      // the position the smoothed forms take: unclamped
+  }
+  Vec v;
+  if constexpr (V == 4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = px[e] * factor + shift;
+  } else {
+    v = px[0] * factor + shift;
+  }
+  *reinterpret_cast<Vec*>(images + (long)b * vox + o) = v;
+  float* lab = labels + (long)b * C * vox + o;
+#pragma unroll 2
+  for (int ch = 0; ch < C; ++ch) {
+    const unsigned char id = class_ids[ch];
+    float mv[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float onehot = lb[e] == id ? 1.f : 0.f;
+      if constexpr (MODE == SMOOTH_NONE) {
+        mv[e] = onehot;
+      } else {
+        const float dd = jd[e] - cen[ch][0], dh = jh[e] - cen[ch][1];
+        mv[e] = aug_smoothed<MODE>(onehot, jw[e] - cen[ch][2], dd * dd + dh * dh, sm);
+      }
+    }
+    if constexpr (V == 4) {
+      Vec out;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) out[e] = mv[e];
+      *reinterpret_cast<Vec*>(lab + (long)ch * vox) = out;
+    } else {
+      *(lab + (long)ch * vox) = mv[0];
     }
   }
 }
@@ -413,8 +644,8 @@ int dua_aug_draw(const dua_aug_volume* table, int nvol, const int* ids, int B, c
       !(cfg->shift_offsets >= 0.f) || (cfg->rot90_prob > 0.f && cfg->roi[0] != cfg->roi[1]))
     return DUA_ERR_ARG;
   const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
-  hipLaunchKernelGGL(dua::aug_draw_kernel, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg, seed,
-                     counter, use_counter, counter_value, params, status);
+  hipLaunchKernelGGL(dua::aug_draw_kernel<false>, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg,
+                     seed, counter, use_counter, counter_value, params, status, dua_aug_affine_config{}, (float*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -487,6 +718,70 @@ int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* c
   else if (!pw) DUA_AUG_SMOOTHED(1, dua::SMOOTH_ORDER1);
   else DUA_AUG_SMOOTHED(1, dua::SMOOTH_POW);
 #undef DUA_AUG_SMOOTHED
+  return (int)hipGetLastError();
+}
+
+int dua_aug_draw_affine(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                        const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
+                        int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
+                        void* stream) {
+  if (!table || nvol < 1 || !ids || B < 1 || !cfg || !affine_cfg || !params || !affine || (!use_counter && !counter))
+    return DUA_ERR_ARG;
+  if (cfg->roi[0] < 1 || cfg->roi[1] < 1 || cfg->roi[2] < 1 || cfg->max_k < 1 || cfg->max_k > 3) return DUA_ERR_ARG;
+  if (!dua::prob_ok(cfg->pos_fraction) || !dua::prob_ok(cfg->flip_prob) || !dua::prob_ok(cfg->rot90_prob) ||
+      !dua::prob_ok(cfg->scale_prob) || !dua::prob_ok(cfg->shift_prob) || !(cfg->scale_factors >= 0.f) ||
+      !(cfg->shift_offsets >= 0.f) || (cfg->rot90_prob > 0.f && cfg->roi[0] != cfg->roi[1]))
+    return DUA_ERR_ARG;
+  const dua_aug_affine_config a = *affine_cfg;
+  // every comparison is false for a NaN
+  if (!dua::prob_ok(a.rotate_prob) || !dua::prob_ok(a.zoom_prob) || !(a.zoom_min > 0.f && a.zoom_min <= 3.0e38f) ||
+      !(a.zoom_span >= 0.f && a.zoom_span <= 3.0e38f) || !(a.pad_value >= -3.0e38f && a.pad_value <= 3.0e38f))
+    return DUA_ERR_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (!(a.rotate_tan_half[i] >= 0.f && a.rotate_tan_half[i] <= 1.f)) return DUA_ERR_ARG;
+  const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
+  hipLaunchKernelGGL(dua::aug_draw_kernel<true>, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg,
+                     seed, counter, use_counter, counter_value, params, status, a, affine);
+  return (int)hipGetLastError();
+}
+
+int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
+                         const dua_aug_smoothing* smoothing, const int* params, const float* affine, int B, int roi_d,
+                         int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
+                         int* status, void* stream) {
+  constexpr int max_extent = 1 << 22;                     // r and c of the contract are exact in fp32
+  if (!table || nvol < 1 || !params || !affine || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 ||
+      roi_d > max_extent || roi_h > max_extent || roi_w > max_extent || !class_ids || C < 1 || C > DUA_AUG_MAX_CLASSES ||
+      !images || !labels || (centroids == nullptr) != (smoothing == nullptr))
+    return DUA_ERR_ARG;
+  dua::AugSmooth sm{};
+  bool pw = false;
+  if (smoothing) {
+    const dua_aug_smoothing p = *smoothing;
+    if (num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES || !(p.alpha >= 0.f && p.alpha <= 3.0e38f) ||
+        !(p.order > 0.f && p.order <= 3.0e38f) || !(p.epsilon >= 1.17549435e-38f && p.epsilon <= 3.0e38f) || !(p.max_value > 0.f))
+      return DUA_ERR_ARG;
+    sm = dua::AugSmooth{centroids, num_classes, p.alpha, p.order, p.epsilon, p.max_value};
+    pw = p.order != 1.f;
+  }
+  const long vox = (long)roi_d * roi_h * roi_w;
+  if (vox >= (1L << 31)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
+  const long tiles = (long)((roi_d + dua::AFF_TILE_D - 1) / dua::AFF_TILE_D) * ((roi_h + dua::AFF_TILE_H - 1) / dua::AFF_TILE_H) *
+                     ((roi_w + dua::AFF_TILE_W - 1) / dua::AFF_TILE_W);       // at most vox, which is below 2^31
+  const dim3 grid((unsigned)(wide ? tiles : (vox + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
+#define DUA_AUG_AFFINE(V, MODE)                                                                                                \
+  hipLaunchKernelGGL((dua::aug_apply_affine_kernel<V, MODE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, affine, \
+                     roi_d, roi_h, roi_w, class_ids, C, images, labels, status, sm)
+  if (!smoothing) {
+    if (wide) DUA_AUG_AFFINE(4, dua::SMOOTH_NONE);
+    else DUA_AUG_AFFINE(1, dua::SMOOTH_NONE);
+  } else if (wide && !pw) DUA_AUG_AFFINE(4, dua::SMOOTH_ORDER1);
+  else if (wide) DUA_AUG_AFFINE(4, dua::SMOOTH_POW);
+  else if (!pw) DUA_AUG_AFFINE(1, dua::SMOOTH_ORDER1);
+  else DUA_AUG_AFFINE(1, dua::SMOOTH_POW);
+#undef DUA_AUG_AFFINE
   return (int)hipGetLastError();
 }
 

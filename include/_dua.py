@@ -49,6 +49,27 @@ _L.dua_blend_finish_labelmap.restype = C.c_int
 _L.dua_blend_finish_labelmap.argtypes = ([C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p] * 6 +
                                          [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 4)
 
+# random rotation and zoom in the device batch producer: dua_aug_draw_affine draws, beside the params rows of dua_aug_draw (the
+# same bits), one affine row per sample; dua_aug_apply_affine resamples the patch through it (trilinear image, nearest label, the
+# row's pad value outside the volume; centroids / smoothing None = one-hot labels).  The contract is in dua_hip.h
+class AugConfig(C.Structure):                    # dua_aug_config
+    _fields_ = [("roi", C.c_int * 3), ("max_k", C.c_int), ("pos_fraction", C.c_float), ("flip_prob", C.c_float),
+                ("rot90_prob", C.c_float), ("scale_prob", C.c_float), ("scale_factors", C.c_float), ("shift_prob", C.c_float),
+                ("shift_offsets", C.c_float), ("reserved", C.c_int)]
+
+
+class AugAffineConfig(C.Structure):              # dua_aug_affine_config: tan(max angle / 2) per axis, fp32(zoom_max - zoom_min)
+    _fields_ = [("rotate_prob", C.c_float), ("rotate_tan_half", C.c_float * 3), ("zoom_prob", C.c_float), ("zoom_min", C.c_float),
+                ("zoom_span", C.c_float), ("pad_value", C.c_float), ("reserved", C.c_int)]
+
+
+_L.dua_aug_draw_affine.restype = C.c_int
+_L.dua_aug_draw_affine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(AugConfig), C.POINTER(AugAffineConfig),
+                                   C.c_ulonglong, C.c_void_p, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_L.dua_aug_apply_affine.restype = C.c_int
+_L.dua_aug_apply_affine.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                                    [C.c_void_p, C.c_int] + [C.c_void_p] * 4)
+
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream

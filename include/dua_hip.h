@@ -1042,6 +1042,81 @@ int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* c
                            const dua_aug_smoothing* smoothing, const int* params, int B, int roi_d, int roi_h, int roi_w,
                            const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream);
 
+/* ---- training input: random rotation and zoom ------------------------------------------------------------------------
+ * The two spatial augmentations that resample (nnU-Net's rotation and scaling, MONAI's RandAffined / RandZoomd; the reference
+ * only gestures at one, utils.py:137-141), in the same two launches: dua_aug_draw_affine for dua_aug_draw, dua_aug_apply_affine
+ * for dua_aug_apply[_smoothed].  Rotation and zoom act on voxel indices, not on millimetres.  The semantics are fixed HERE.
+ *
+ * dua_aug_draw_affine: params comes out bit-identical to dua_aug_draw's for the same table, ids, cfg, seed and counter (blocks
+ * 0 - 2 keep every role; the call-counter rule is the same).  Two more Philox blocks per sample:
+ *   3.0 rotation event   3.1, 3.2, 3.3 t_a for axis a = d, h, w
+ *   4.0 zoom event       4.1 zoom value       4.2, 4.3 unused
+ * (every word keeps its role whether or not an event happened).  fp32, no contraction:
+ *   t_a = fadd(fmul(2 rotate_tan_half[a], u), -rotate_tan_half[a]) iff u(3.0) < rotate_prob, else 0   (in [-tan_half, tan_half))
+ *   z   = fadd(fmul(zoom_span, u(4.1)), zoom_min)                  iff u(4.0) < zoom_prob, else 1
+ *         (in [zoom_min, fadd(zoom_span, zoom_min)])
+ * t_a is the tangent of HALF the rotation angle about axis a: the angle 2 atan(t_a) is not uniform, its density is
+ * proportional to 1 + t^2, i.e. it RISES by t^2 from the middle to the ends of the range: 7 % at +-30 degrees, 17 % at
+ * +-45.  That is the price of a matrix without sine or cosine: with every t_a, z and the 1, 2 and 0
+ * below converted to fp64 (exact), and every + - * / ONE IEEE fp64 operation in the order written,
+ *   q_a = t_a * t_a;  n_a = 1 + q_a;  c_a = (1 - q_a) / n_a;  s_a = (t_a + t_a) / n_a          (a = d, h, w)
+ *   R = R_d R_h R_w, R_d rotating the (h, w) plane, R_h the (d, w) plane, R_w the (d, h) plane:
+ *     R00 = c_h * c_w                                R01 = 0 - (c_h * s_w)                          R02 = s_h
+ *     R10 = (c_d * s_w) + (s_d * (s_h * c_w))        R11 = (c_d * c_w) - (s_d * (s_h * s_w))        R12 = 0 - (s_d * c_h)
+ *     R20 = (s_d * s_w) - (c_d * (s_h * c_w))        R21 = (s_d * c_w) + (c_d * (s_h * s_w))        R22 = c_d * c_h
+ *   g = 1 / z;   M[i][j] = fp32(R[i][j] * g)         (one rounding to fp32 per entry)
+ * so a numpy float64 restatement reproduces M bit for bit, and with no event M is exactly the identity (all zeros +0).
+ *
+ * affine (WRITTEN, [B][DUA_AUG_AFFINE_WORDS] 32-bit words, the bits of an fp32 unless said otherwise): words 0 - 8 M row-major;
+ * DUA_AUG_AFFINE_T + a = t_a;  DUA_AUG_AFFINE_ZOOM = z;  DUA_AUG_AFFINE_EVENTS = int32, bit 0 rotation event, bit 1 zoom event;
+ * DUA_AUG_AFFINE_PAD = affine_cfg->pad_value, so that a logged (params, affine) pair replays its batch from dua_aug_apply_affine
+ * alone, which takes no configuration;  word 15 = 0.  A sample whose params row gets volume -1 gets the row of no event.
+ *
+ * dua_aug_apply_affine: centroids == NULL and smoothing == NULL: one-hot labels; both given: labels smoothed as in
+ * dua_aug_apply_smoothed (num_classes is ignored without them).  For an output voxel let p = (p_d, p_h, p_w) be the index inside
+ * the un-flipped, un-rotated window that dua_aug_apply would read for it (so flips and k compose exactly as there: they apply
+ * AFTER the resampling), roi = (roi_d, roi_h, roi_w), start = the row's start.  In fp32, no contraction:
+ *   1. r_a = p_a - (roi_a - 1) / 2;   c_a = start_a + (roi_a - 1) / 2           (both exact: extents up to 2^22 are required)
+ *   2. s_a = ((M[a][0] r_d + M[a][1] r_h) + M[a][2] r_w) + c_a                   (three products, three sums, each rounded)
+ *   3. i_a = floorf(s_a);   f_a = s_a - i_a                                      (exact)
+ *   4. corner(e_d, e_h, e_w) = image[i_d + e_d][i_h + e_h][i_w + e_w] when all three indices are inside the volume, else the
+ *      row's pad value: decided per corner
+ *   5. along w, then h, then d:  x(e_d, e_h) = fmaf(f_w, corner(e_d, e_h, 1) - corner(e_d, e_h, 0), corner(e_d, e_h, 0));
+ *      y(e_d) = fmaf(f_h, x(e_d, 1) - x(e_d, 0), x(e_d, 0));   value = fmaf(f_d, y(1) - y(0), y(0))
+ *   6. images[b, 0] = (value * (1 + scale)) + shift, as in dua_aug_apply
+ *   7. the label is the one at the nearest voxel j_a = i_a + (f_a >= 0.5 ? 1 : 0), class id 0 when j is outside the volume;
+ *      smoothed channels: the formula of dua_aug_apply_smoothed with j (wherever it lies) as the position and the one-hot of
+ *      that label.
+ * Rows are skipped exactly as in dua_aug_apply (volume, start, flip or k out of range; odd k with roi_d != roi_h); reading
+ * outside the volume through M is no reason to skip, that is what the pad value is for.  A row whose M is the identity gives
+ * the bits of dua_aug_apply (of dua_aug_apply_smoothed) for a finite image; labels are reproducible bit for bit from an fp32
+ * restatement of s; only the image carries rounding error (the lerp tree and the intensity transform).  M is taken as it
+ * stands (it need not be a rotation); entries that are not finite give unspecified values, never a read outside the volume.
+ * Arguments of dua_aug_draw_affine beyond dua_aug_draw's: rotate_prob, zoom_prob in [0, 1]; 0 <= rotate_tan_half[a] <= 1 (angles
+ * up to 90 degrees); zoom_min > 0, zoom_span >= 0, pad_value: finite. */
+#define DUA_AUG_AFFINE_M 0
+#define DUA_AUG_AFFINE_T 9
+#define DUA_AUG_AFFINE_ZOOM 12
+#define DUA_AUG_AFFINE_EVENTS 13
+#define DUA_AUG_AFFINE_PAD 14
+#define DUA_AUG_AFFINE_WORDS 16
+typedef struct {
+  float rotate_prob;
+  float rotate_tan_half[3];      /* fp32(tan(max angle / 2)) per axis d, h, w: computed in fp64 by the host, rounded once */
+  float zoom_prob, zoom_min;
+  float zoom_span;               /* fp32(zoom_max - zoom_min) */
+  float pad_value;               /* what a corner outside the volume holds */
+  int reserved;
+} dua_aug_affine_config;
+int dua_aug_draw_affine(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                        const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
+                        int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
+                        void* stream);
+int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
+                         const dua_aug_smoothing* smoothing, const int* params, const float* affine, int B, int roi_d,
+                         int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
+                         int* status, void* stream);
+
 /* ---- evaluation: streamed sliding-window blend ----------------------------------------------------------------------
  * The blend of monai.inferers.sliding_window_inference as Engine.infer calls it (engine.py:173-177; Tester, test.py:119-159:
  * constant importance map, sum / count), the binarisation that follows it (engine.py:179-180) and the three voxel counts of

@@ -20,6 +20,15 @@ process.  The one-hot side is ``dua_aug_apply`` of ``--onehot-lib`` (default: th
 package's own), loaded next to the package's library, so that the smoothed kernel of this tree is measured against the one-hot
 kernel of another build.  Both write the same bytes, 4 (1 + C) per voxel.  It also times the once-per-volume centroid pass
 (``dua_aug_class_centroids``) next to ``dua_aug_count_candidates`` on a 512 x 512 x 150 label map.
+
+    python tools/bench_augment.py --affine [--rounds 21] [--repeats 200]
+
+``--affine`` times, at the producer's own shape (B = 2, roi 96^3, 15 channels, ``class_ids = range(1, 16)``), the plain ``apply``
+(``dua_aug_apply``), the resampling ``apply`` with a rotation of up to 30 degrees about every axis and a zoom from (0.7, 1.4) in
+every row (``dua_aug_apply_affine``), and the same batch from torch operators (``affine_grid`` + ``grid_sample`` on the whole
+volume, bilinear for the image and nearest for a float copy of the label map made beforehand, then flips, rot90, the intensity
+operations and a stacked == for the one-hot), alternating rounds in one process.  All three write the same bytes, 4 (1 + C) per
+voxel; each time is printed beside the bandwidth that makes of them.
 """
 import argparse
 import ctypes
@@ -175,6 +184,79 @@ def smoothing_bench(args):
     return result
 
 
+def affine_bench(args):
+    import math
+    import torch.nn.functional as F
+    B, K = 2, 16
+    vols = volumes(args.volumes, classes=K)
+    ids = torch.tensor([i % len(vols) for i in range(B)], dtype=torch.int32, device=DEV)
+    kw = dict(roi=ROI, class_ids=range(1, K), flip_prob=0.5, rot90_prob=0.5, scale_prob=0.5, seed=2)
+    plain = augment.DeviceBatchProducer(vols, **kw)
+    turned = augment.DeviceBatchProducer(vols, rotate_prob=1.0, rotate_range=(math.radians(30),) * 3, zoom_prob=1.0,
+                                         zoom_range=(0.7, 1.4), **kw)
+    params, affine = turned.draw(ids)
+    out_images = torch.empty((B, 1) + ROI, device=DEV)
+    out_labels = torch.empty((B, K - 1) + ROI, device=DEV)
+    ref_images, ref_labels = torch.empty_like(out_images), torch.empty_like(out_labels)
+    class_ids = torch.arange(1, K, dtype=torch.float32, device=DEV).view(-1, 1, 1, 1)
+    # what a torch user prepares once: float label maps, and per sample the theta of affine_grid from the host rows
+    label_f = [v.label.float()[None, None] for v in vols]
+    ints, floats = augment.split_params(params.cpu())
+    matrix = augment.split_affine(affine.cpu())[0].double()
+    rows = []
+    for (vid, sd, sh, sw, flip, k), (scale, shift), m in zip(ints.tolist(), floats.tolist(), matrix):
+        size, start = vols[vid].shape, (sd, sh, sw)
+        theta = torch.zeros(3, 4, dtype=torch.float64)
+        for a in range(3):                                  # index order d, h, w; affine_grid wants x = w first
+            for c in range(3):
+                theta[2 - a, 2 - c] = m[a, c] * (ROI[c] - 1) / (size[a] - 1)
+            theta[2 - a, 3] = 2.0 * (start[a] + (ROI[a] - 1) / 2) / (size[a] - 1) - 1.0
+        rows.append((vid, flip, k, scale, shift, theta.float()[None].to(DEV)))
+
+    def torch_fn():
+        for b, (vid, flip, k, scale, shift, theta) in enumerate(rows):
+            grid = F.affine_grid(theta, (1, 1) + ROI, align_corners=True)
+            p = F.grid_sample(vols[vid].image[None, None], grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0, 0]
+            q = F.grid_sample(label_f[vid], grid, mode="nearest", padding_mode="zeros", align_corners=True)[0, 0]
+            dims = [a for a in (0, 1, 2) if flip >> a & 1]
+            if dims:
+                p, q = p.flip(dims), q.flip(dims)
+            if k:
+                p, q = torch.rot90(p, k, (0, 1)), torch.rot90(q, k, (0, 1))
+            ref_images[b, 0] = p * (1.0 + scale) + shift
+            ref_labels[b] = q[None] == class_ids
+
+    def apply_fn():
+        plain.apply(params, out_images, out_labels)
+
+    def affine_fn():
+        turned.apply(params, out_images, out_labels, affine=affine)
+
+    affine_fn(); torch_fn()
+    image_gap = float((out_images - ref_images).abs().max())
+    label_gap = float((out_labels != ref_labels).float().mean())
+    for _ in range(args.warmup):
+        apply_fn(); affine_fn(); torch_fn()
+    torch.cuda.synchronize()
+    ms_apply, ms_affine, ms_torch = timed_rounds((apply_fn, affine_fn, torch_fn), args.repeats, args.rounds)
+    nbytes = 4 * K * B * ROI[0] * ROI[1] * ROI[2]
+    result = {"metric": "augment_affine_apply_time", "unit": "ms", "box": socket.gethostname(), "device": torch.cuda.get_device_name(0),
+              "roi": ROI, "B": B, "channels": K - 1, "repeats": args.repeats, "rounds": args.rounds, "bytes_written": nbytes,
+              "apply": summary(ms_apply), "affine_apply": summary(ms_affine), "torch_grid_sample": summary(ms_torch),
+              "max_image_gap_to_torch": image_gap, "label_fraction_differing_from_torch": label_gap}
+    for name in ("apply", "affine_apply", "torch_grid_sample"):
+        result[name]["write_GBps"] = nbytes / (result[name]["median_ms"] * 1e-3) / 1e9
+        print(f"{name}: {result[name]['median_ms']:.4f} ms ({result[name]['min_ms']:.4f} .. {result[name]['max_ms']:.4f}) for "
+              f"{nbytes} bytes written = {result[name]['write_GBps']:.0f} GB/s", flush=True)
+    result["affine_over_apply"] = result["affine_apply"]["median_ms"] / result["apply"]["median_ms"]
+    result["torch_over_affine"] = result["torch_grid_sample"]["median_ms"] / result["affine_apply"]["median_ms"]
+    print(f"affine / apply = {result['affine_over_apply']:.3f}; torch / affine = {result['torch_over_affine']:.1f}; against torch: max "
+          f"image gap {image_gap:.2e}, {100 * label_gap:.4f} % of the label values differ (nearest-voxel ties)", flush=True)
+    assert plain.status == 0 and turned.status == 0
+    result["value"] = result["affine_apply"]["median_ms"]
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=1000)
@@ -185,11 +267,12 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--smoothing", action="store_true", help="smoothed apply next to the one-hot apply, and the centroid pass")
     ap.add_argument("--onehot-lib", default="", help="with --smoothing: the build whose dua_aug_apply is the one-hot side")
+    ap.add_argument("--affine", action="store_true", help="resampling apply next to the plain apply and to torch's grid_sample")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_augment.py measures on the GPU; none is visible")
-    if args.smoothing:
-        line = json.dumps(smoothing_bench(args))
+    if args.smoothing or args.affine:
+        line = json.dumps(smoothing_bench(args) if args.smoothing else affine_bench(args))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(line + "\n")
