@@ -156,8 +156,8 @@ class SwinPlan(SamplerDriver):
         self.raw1b, self.raw2b, self.res3b = (torch.zeros(big, dtype=dtype, device=device) for _ in range(3))   # side stream
         self.side_stream = torch.cuda.Stream(device=device)
         self.two_streams = True
-        # which encoder blocks the side stream takes once hidden_states_out[i] is enqueued (encoder_k reads hidden state k - 1;
-        # encoder1, k = 0, reads the input only)
+        # which encoder blocks the side stream takes once hidden_states_out[i] is enqueued: block k (0-based, enc(k) of
+        # denoiser_body) reads hidden state k - 1, block 0 the input only; a block listed before its input waits for it
         self.side_plan = {2: (3, 2, 1, 0)}
         # the memory-bound tail of a side-stream block (conv3 + sums, residual_norm_act) also runs one workgroup per CU: at full
         # width encoder1's two 96^3 passes held the main stream's split-K finish kernels at 40-55 us instead of 6
@@ -542,10 +542,13 @@ class SwinPlan(SamplerDriver):
             self._res_block(r, srcs[k][0], srcs[k][1], cat[k], r.cout, post_add=self.e_enc[k], side=two)
 
         def ready(i):                                   # hidden_states_out[i] has been enqueued on the main stream
-            if two and self.side_plan.get(i):
+            # enc(k) reads hidden_states_out[k - 1]: a block that side_plan lists at an earlier stage starts once its input is
+            # enqueued, not before (it would read the previous step's hidden state with nothing ordering it against this step's)
+            ks = [k for j in sorted(self.side_plan) for k in self.side_plan[j] if max(j, k - 1) == i] if two else []
+            if ks:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    for k in self.side_plan[i]:
+                    for k in ks:
                         enc(k)
                         self.enc_done[k].record(side)
 
