@@ -1,4 +1,4 @@
-"""Descriptors of the launch-form checks: every 3x3x3 and transposed convolution of the three plans tests/test_launch_sequence_fp64.py
+"""Descriptors of the launch-form checks: every 3x3x3 and transposed convolution of the plans tests/test_launch_sequence_fp64.py
 pins (built from the plan's geometry on the host, no device needed) and the regimes of tests/test_kernels_gpu.py.  Shared by
 tests/test_conv3_form.py (CPU: the library's form query) and tools/conv_form_trace.py (GPU: what the launchers really launch)."""
 import itertools
@@ -24,7 +24,9 @@ def desc(dtype, N, dims, cin, cout, cin_stride=None, cin_off=0, cout_stride=None
 def plan_launches(case, expected):
     """[(name, 'conv' | 'deconv', descriptor fields, fused, output dims or None)] of one EXPECTED entry of
     tests/test_launch_sequence_fp64.py: diff_unet_amos_amd.engine.Plan.denoiser_body written as descriptors (level extents floor,
-    the transposed convolution writes the upper channels of the concat buffer, the first layer takes the tap form in fp16)."""
+    the transposed convolution writes the upper channels of the concat buffer, the first layer takes the tap form in fp16).  A
+    level whose ``fold`` entry is set (any of the four) has neither its transposed convolution nor its first convolution in the
+    list: the folded launch is no dua_conv3_desc."""
     import torch
     f, N = FEATURES, expected["N"]
     dt = F16 if expected["dtype"] == torch.float16 else F32
@@ -76,7 +78,7 @@ def voxels(d):
 
 
 def conv_descriptors(expected_table):
-    """Every distinct convolution descriptor (policy 0) of the three plans and the regimes, with the name it was first seen under."""
+    """Every distinct convolution descriptor (policy 0) of the pinned plans and the regimes, with the name it was first seen under."""
     seen = {}
     for case, exp in expected_table.items():
         for name, kind, d, _, _ in plan_launches(case, exp):

@@ -1,6 +1,6 @@
 """The launch form of every convolution is decided by one host function (csrc/conv3_form.hpp) that the launchers run and
 dua_conv3d_k3_form / dua_deconv_k2s2_form export.  No GPU needed: the queries answer for 256 compute units without a device.
-Pins which kernel, tile depth and split the launches of the three plans of tests/test_launch_sequence_fp64.py and the regimes of
+Pins which kernel, tile depth and split the launches of the plans of tests/test_launch_sequence_fp64.py and the regimes of
 tests/test_kernels_gpu.py take, and holds the properties that tie the form to the other queries (kernel kind, workspace size,
 registered LDS limits) and to the launcher's rejections."""
 import ctypes as C
@@ -8,7 +8,7 @@ import ctypes as C
 import pytest
 
 import conv_form_cases as K
-from test_launch_sequence_fp64 import EXPECTED, KIND_NAMES
+from test_launch_sequence_fp64 import EXPECTED, FORMS, KIND_NAMES, form_names
 
 CUS = 256
 HUGE = 1 << 40
@@ -44,17 +44,23 @@ def _workspace(nv, d):
 
 @pytest.mark.parametrize("case", list(EXPECTED))
 def test_plan_launches_take_the_pinned_kind_and_split(nv, case):
-    """Kind and split of every convolution / transposed convolution of a plan equal its EXPECTED rows, asked with the workspace the
-    plan allocates (the largest dua_conv3d_k3_workspace of its layers)."""
+    """Kind and split of every convolution / transposed convolution of a plan equal its EXPECTED rows, and kernel, tile depth and
+    ksplit of every convolution its FORMS row, asked with the workspace the plan allocates (the largest dua_conv3d_k3_workspace of
+    its layers): a policy change that moves a launch of a batched plan fails here, without a GPU."""
     launches = K.plan_launches(case, EXPECTED[case])
     ws = max([16] + [_workspace(nv, d) for _, kind, d, _, _ in launches if kind == "conv"])
     want = {name: (kind, split) for name, kind, split in EXPECTED[case]["seq"]}
+    names = form_names(nv)
+    assert sorted(FORMS[case]) == sorted(name for name, kind, _, _, _ in launches if kind == "conv")
     checked = 0
     for name, kind, d, fused, dims in launches:
         if kind == "conv":
             rc, f = _form(nv, d, fused, ws)
             assert rc == 0, name
             assert (KIND_NAMES[_kind(nv, f)], f.ksplit > 1) == want[name], (case, name)
+            assert (names[f.kernel], f.tile_depth, f.ksplit) == FORMS[case][name], (case, name)
+            if f.kernel != nv.CONV3_FIRST:                          # (the first-layer kernel walks all samples from one grid)
+                assert f.grid_z == d[1] * f.ksplit, (case, name)      # one slice of the grid per sample and split
             assert f.finish == (1 if f.ksplit > 1 else 0)
         else:
             rc, f = _dform(nv, d, fused, dims)
@@ -63,6 +69,19 @@ def test_plan_launches_take_the_pinned_kind_and_split(nv, case):
             assert int(nv.lib().dua_deconv_k2s2_kernel_kind(C.byref(nv.Conv3Desc(*d)))) == min(f.kernel, 2)
         checked += 1
     assert checked == sum(1 for _, kind, _ in EXPECTED[case]["seq"] if kind in ("v2", "first", "wide") or kind.startswith("deconv"))
+
+
+def test_plan_launches_drop_the_two_launches_of_a_folded_level_at_any_level():
+    """A fold takes the transposed convolution and the convolution behind it out of the descriptor list at the level it is set
+    for -- level 2 as well as 0 and 1 (no shipped plan folds level 2 today: its coarse tensor is 256 channels wide, the folded
+    kernel takes 128) -- and leaves every other descriptor as it was."""
+    base = dict(EXPECTED["fp16-96-b4"], fold=[False] * 4)
+    plain = K.plan_launches("", base)
+    for level in range(4):
+        fold = [l == level for l in range(4)]
+        got = K.plan_launches("", dict(base, fold=fold))
+        assert got == [row for row in plain if row[0] not in (f"up{level}", f"u{level}a")]
+        assert [row[0] for row in got].count(f"u{level}b") == 1 and len(got) == len(plain) - 2
 
 
 def test_tile_depth_and_kd_plane_regimes(nv):

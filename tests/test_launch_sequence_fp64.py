@@ -4,11 +4,19 @@ written down -- and the head in logits mode, with ops.conv3d_k3 / upconv_k3 / de
 wrapped so that each call is launched, synchronised, sampled on the device and checked per element against its bound, and the
 InstanceNorm statistics words a convolution leaves against fp64 sums of what it stored.
 
-Three plans at default widths (64, 64, 128, 256, 512, 64), 16 classes: the benchmarked fp16 96^3 patch; fp16 at batch 2 with
+Six plans at default widths (64, 64, 128, 256, 512, 64), 16 classes: the benchmarked fp16 96^3 patch; fp16 at batch 2 with
 an odd extent (replicate-padded transposed convolutions, floor pooling, per-sample statistics rows); the exact-fp32 companion
-plan the last DDPM steps run on, at 64^3.  Which kernel every launch takes is pinned below, as the policy is written today: a
-policy change that moves a launch makes this test fail instead of quietly testing another kernel."""
+plan the last DDPM steps run on, at 64^3; and the 96^3 patch at batch 2, 3 and 4 (sliding-window batches, balanced batches of
+three, step-uncertainty runs in adjacent rows), whose launch forms are functions of the workgroup count N x 96^3 gives: other
+kernels, tile depths and splits than at N = 1.  The samples of these three differ in scale and timestep, so that a row of
+statistics, scale / shift or embedding add taken from a neighbouring sample is far outside every bound.  Which kernel every
+launch takes is pinned below, as the policy is written today -- the coarse kind and, in FORMS, the kernel of the form query with
+its tile depth and split: a policy change that moves a launch makes this test fail instead of quietly testing another kernel.
+
+test_rows_of_a_batch_do_not_see_each_other runs the batch-4 plan twice, the second time with another image, state and timestep
+in row 2 only: every other row of every buffer the plan exposes and of the logits keeps its bits."""
 import ctypes
+import math
 import os
 import zlib
 
@@ -62,6 +70,90 @@ EXPECTED = {
              ("up0", "deconv2", False), ("u0a", "v2", False), ("u0b", "v2", False), ("head", "tail", False)]),
 }
 KIND_NAMES = {0: "v2", 1: "first", 2: "wide"}
+# The batched cases must be able to tell the samples of a batch apart (case_inputs).  Two measures, both in units of what a check
+# allows: an elementwise consumer (materialise, the head, the transposed convolution's input) rounds at 2^-11 of a value, so the
+# scale and add rows of neighbouring samples are held 8 x 2^-11 apart in the typical channel (median relative distance, APART);
+# a convolution sums thousands of terms, so for every fused convolution the reference is evaluated once more with the next sample's
+# rows and must lie more than twice the bound away (column "rows n+1" of the table, as tests/test_batched_forms_defects.py).
+APART = 2.0 ** -8
+TIMESTEPS = (500, 37, 811, 203)            # one per sample of a batch; the first two are what the batch-1 and batch-2 cases always used
+
+
+def _batched_96(N, level1, level2, level3, split4):
+    """EXPECTED entry and FORMS row of the fp16 96^3 plan at batch N > 1: (kind, kernel, tile depth) of the convolutions at 48^3,
+    24^3 and 12^3 and the split of the two at 6^3; the rest does not move with N."""
+    k1, k2, k3 = level1[0], level2[0], level3[0]
+    seq = [("d0a", "first", False), ("d0b", "wide", False), ("m0", "mat", False),
+           ("d1a", k1, False), ("d1b", k1, False), ("m1", "mat", False),
+           ("d2a", k2, False), ("d2b", k2, False), ("m2", "mat", False),
+           ("d3a", k3, False), ("d3b", k3, False), ("m3", "mat", False),
+           ("d4a", "v2", True), ("d4b", "v2", True), ("m4", "mat", False),
+           ("up3", "deconv1", False), ("u3a", k3, False), ("u3b", k3, False),
+           ("up2", "deconv1", False), ("u2a", k2, False), ("u2b", k2, False),
+           ("u1a", "fold", False), ("u1b", k1, False),
+           ("u0a", "fold", False), ("u0b", "wide", False), ("head", "tail", False)]
+    forms = {"d0a": ("FIRST", 4, 1), "d0b": ("WIDE", 8, 1), "u0b": ("WIDE", 8, 1), "d4a": ("V2_4_KD", 4, split4), "d4b": ("V2_4_KD", 4, split4)}
+    for names, (_, kernel, depth) in ((("d1a", "d1b", "u1b"), level1), (("d2a", "d2b", "u2a", "u2b"), level2),
+                                      (("d3a", "d3b", "u3a", "u3b"), level3)):
+        forms.update({n: (kernel, depth, 1) for n in names})
+    return dict(N=N, dims=(96, 96, 96), dtype=torch.float16, fold=[True, True, False, False], layout=(True, True, True), seq=seq,
+                distinct=True), forms
+
+
+# launch -> (kernel of dua_conv3d_k3_form without its DUA_CONV3_ prefix, tile depth, ksplit): the coarse kind above cannot tell a
+# two-deep tile from a four-deep one, a kd-plane kernel from a plain one, or one split from another
+FORMS = {
+    "fp16-96": {"d0a": ("FIRST", 4, 1), "d0b": ("WIDE", 8, 1), "d1a": ("V2_4", 4, 1), "d1b": ("V2_4", 4, 1),
+                "d2a": ("V2_2_KD", 2, 1), "d2b": ("V2_2_KD", 2, 1), "d3a": ("V2_4_KD", 4, 4), "d3b": ("V2_4_KD", 4, 5),
+                "d4a": ("V2_4_KD", 4, 12), "d4b": ("V2_4_KD", 4, 16), "u3a": ("V2_4_KD", 4, 5), "u3b": ("V2_4_KD", 4, 5),
+                "u2a": ("V2_2_KD", 2, 1), "u2b": ("V2_2_KD", 2, 1), "u1b": ("V2_4", 4, 1), "u0b": ("WIDE", 8, 1)},
+    "fp16-b2-odd": {"d0a": ("FIRST", 4, 1), "d0b": ("V2_4", 4, 1), "d1a": ("V2_2", 2, 1), "d1b": ("V2_2", 2, 1),
+                    "d2a": ("V2_4_KD", 4, 3), "d2b": ("V2_4_KD", 4, 4), "d3a": ("V2_4_KD", 4, 12), "d3b": ("V2_4_KD", 4, 12),
+                    "d4a": ("V2_4_KD", 4, 12), "d4b": ("V2_4_KD", 4, 16), "u3a": ("V2_4_KD", 4, 16), "u3b": ("V2_4_KD", 4, 12),
+                    "u2a": ("V2_4_KD", 4, 4), "u2b": ("V2_4_KD", 4, 4), "u1a": ("V2_2", 2, 1), "u1b": ("V2_2", 2, 1),
+                    "u0a": ("V2_4", 4, 1), "u0b": ("V2_4", 4, 1)},
+    "fp32-64": {"d0a": ("V2_4", 4, 1), "d0b": ("V2_4", 4, 1), "d1a": ("V2_2_KD", 2, 1), "d1b": ("V2_2_KD", 2, 1),
+                "d2a": ("V2_4_KD", 4, 6), "d2b": ("V2_4_KD", 4, 8), "d3a": ("V2_4_KD", 4, 24), "d3b": ("V2_4_KD", 4, 24),
+                "d4a": ("V2_4_KD", 4, 24), "d4b": ("V2_4_KD", 4, 32), "u3a": ("V2_4_KD", 4, 32), "u3b": ("V2_4_KD", 4, 24),
+                "u2a": ("V2_4_KD", 4, 8), "u2b": ("V2_4_KD", 4, 8), "u1a": ("V2_2_KD", 2, 1), "u1b": ("V2_2_KD", 2, 1),
+                "u0a": ("V2_4", 4, 1), "u0b": ("V2_4", 4, 1)},
+}
+# The batched 96^3 plans.  The level-2 fold stays off at every batch: its coarse tensor has 256 channels and dua_upconv_k3_supported
+# takes at most 128, so u2a is a plain convolution also at N = 4, where 27 * 4 * 2 = 216 tiles pass Plan.UPCONV_MIN_TILES.
+for _n, _args in ((2, (("v2", "V2_4", 4), ("v2", "V2_4", 4), ("v2", "V2_2_KD", 2), 8)),
+                  (3, (("wide", "WIDE", 8), ("v2", "V2_4", 4), ("v2", "V2_2", 2), 5)),
+                  (4, (("wide", "WIDE", 8), ("v2", "V2_4", 4), ("v2", "V2_2", 2), 4))):
+    EXPECTED[f"fp16-96-b{_n}"], FORMS[f"fp16-96-b{_n}"] = _batched_96(_n, *_args)
+
+
+def form_names(nv):
+    """dua_conv3_form.kernel -> its name without the prefix"""
+    return {getattr(nv, n): n[len("CONV3_"):] for n in dir(nv) if n.startswith("CONV3_")}
+
+
+def case_inputs(case):
+    """(image [N, 1, D, H, W], x [N, classes, D, H, W], timesteps [N]) of a case, on the host.  The cases marked ``distinct`` make
+    the samples of a batch differ in what InstanceNorm does not remove.  A factor on a sample is not enough: the network is
+    positively homogeneous up to its biases, the first normalisation divides the factor out, and the scale rows of two samples
+    of white noise then agree to 1e-3 (measured: 7.6e-4 at the first materialise with factors 1 and 1.5).  So sample n's state
+    and image are noise in blocks of (n + 1)^3 equal voxels -- another spatial correlation, so other variances behind every
+    convolution -- scaled by 1 + 0.5 n (state) and 1 - 0.2 n (image) and moved by 0.25 n; with the distinct timesteps every scale,
+    shift and add row of a sample is far from its neighbours' (_Checker._consts asserts it at every launch)."""
+    exp = EXPECTED[case]
+    N, dims = exp["N"], exp["dims"]
+    g = torch.Generator().manual_seed(len(case))
+    image = torch.rand(N, 1, *dims, generator=g)
+    x = torch.randn(N, CLASSES, *dims, generator=g)
+    if exp.get("distinct"):
+        for n in range(N):
+            k = n + 1
+            assert all(s % k == 0 for s in dims)
+            for t in (x, image):
+                coarse = t[n, :, :dims[0] // k, :dims[1] // k, :dims[2] // k]
+                t[n] = coarse.repeat_interleave(k, 1).repeat_interleave(k, 2).repeat_interleave(k, 3)
+            x[n] = x[n] * (1 + 0.5 * n) + 0.25 * n
+            image[n] *= 1 - 0.2 * n
+    return image, x, torch.tensor(TIMESTEPS[:N])
 
 
 def _net():
@@ -80,7 +172,7 @@ class _Checker:
 
     def __init__(self, plan, case):
         from diff_unet_amos_amd import ops
-        self.ops, self.plan, self.case, self.rows = ops, plan, case, []
+        self.ops, self.plan, self.case, self.rows, self.apart = ops, plan, case, [], []
         self.dt = plan.dtype
         self.orig = dict(conv3d_k3=ops.conv3d_k3, upconv_k3=ops.upconv_k3, deconv_k2s2=ops.deconv_k2s2,
                          materialize=ops.materialize, final_conv_sampler=ops.final_conv_sampler)
@@ -98,7 +190,13 @@ class _Checker:
 
     # ---- shared pieces ---------------------------------------------------------------------------------------------------
     def _pts(self, name, N, dims):
-        return R.sample_voxels(N, dims, n_random=2000, seed=zlib.crc32(f"{self.case}/{name}".encode()))
+        pts = R.sample_voxels(N, dims, n_random=2000, seed=zlib.crc32(f"{self.case}/{name}".encode()))
+        # the structured points of the sampler are per sample: both faces of every axis of EVERY sample are among them
+        for n in range(N):
+            p = pts[pts[:, 0] == n]
+            for ax, S in enumerate(dims):
+                assert bool((p[:, 1 + ax] == 0).any()) and bool((p[:, 1 + ax] == S - 1).any()), (self.case, name, n, ax)
+        return pts
 
     def _consts(self, norm, N):
         """fp32 scale, shift, add [N, C] of a producer descriptor as the consumers' preamble forms them (ops.instnorm_finalize:
@@ -115,6 +213,10 @@ class _Checker:
         else:
             stride = norm.c.add_stride or C
             ad = torch.stack([add[n * stride:n * stride + C].cpu() for n in range(N)])
+        if EXPECTED[self.case].get("distinct"):
+            # how far apart the rows of neighbouring samples are, in the typical channel (_run_case holds it to APART)
+            rel = lambda v: float(((v - v.roll(1, 0)).abs() / v.abs().clamp_min(1e-30)).median())      # noqa: E731
+            self.apart.append((C, rel(sc), rel(ad) if add is not None else math.inf))      # asserted once the table is printed
         return sc, sh, ad
 
     def _act(self, raw, n_idx, norm, N, ok=None):
@@ -141,9 +243,9 @@ class _Checker:
         rq = ((words[..., 1] - Q).abs() / bq).max()
         return float(torch.maximum(rs, rq))
 
-    def _row(self, name, kind, split, shape, npts, res, stats_ratio=None):
+    def _row(self, name, kind, split, shape, npts, res, stats_ratio=None, form=None, tell=None):
         self.rows.append(dict(name=name, kind=kind, split=split, shape=shape, n=npts, ratio=res.ratio, where=res.where,
-                              res=res, stats=stats_ratio))
+                              res=res, stats=stats_ratio, form=form, tell=tell))
 
     def _blocked(self, t, flag):
         return self.ops.from_blocked(t) if flag else t
@@ -159,7 +261,10 @@ class _Checker:
                          0 if tap_channel is None else tap_channel + 1, 0,
                          (nv.IN_BLOCKED if in_blocked else 0) | (nv.OUT_BLOCKED if out_blocked else 0), ops.CONV_POLICY)
         ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-        split = ops.conv3_form(d, norm is not None, ws_bytes).ksplit > 1           # the launcher's own answer for this call
+        f = ops.conv3_form(d, norm is not None, ws_bytes)                          # the launcher's own answer for this call
+        split = f.ksplit > 1
+        form = (form_names(nv)[f.kernel], f.tile_depth, f.ksplit)
+        assert form == FORMS[self.case][name], f"{self.case} {name}: the launch form moved: {form}, pinned {FORMS[self.case][name]}"
         kind = KIND_NAMES[int(nv.lib().dua_conv3d_k3_kernel_kind(ctypes.byref(d), 1 if norm is not None else 0, 1 if split else 0))]
         xs = x.clone()
         self.orig["conv3d_k3"](x, cin, cin_off, w_packed, bias_pad, cout, y, cout_off, out_stats, norm=norm, workspace=workspace,
@@ -167,8 +272,8 @@ class _Checker:
         torch.cuda.synchronize()
         xc, yc = self._blocked(xs, in_blocked), self._blocked(y, out_blocked)
         pts = self._pts(name, N, (D, H, W))
-        A, ok = R.gather_taps(xc, pts, cin_off, cin)
-        A = self._act(A, pts[:, 0], norm, N, ok)
+        A_raw, ok = R.gather_taps(xc, pts, cin_off, cin)
+        A = self._act(A_raw, pts[:, 0], norm, N, ok)
         w = layer.w.detach().float().cpu()
         if layer.perm is not None:                 # packed input channel j holds source channel perm[j] (or zero padding)
             wp = torch.zeros(w.shape[0], cin, 3, 3, 3)
@@ -176,12 +281,20 @@ class _Checker:
                 if s >= 0:
                     wp[:, j] = w[:, s]
             w = wp
-        ref, ab, sq = R.conv3_ref(A, R.conv3_weights(w, self.dt), layer.b)
+        Wm = R.conv3_weights(w, self.dt)
+        ref, ab, sq = R.conv3_ref(A, Wm, layer.b)
         parts = 3 * -(-cin // ops.chunk_elems(self.dt)) if split else 0
         bnd = R.bound(ref, ab, sq, R.chain_length(27 * cin, self.dt, parts), self.dt,
                       emulated_in=self.dt if norm is not None else None)
         res = R.check(R.gather_points(yc, pts, cout_off, cout), ref, bnd, pts)
-        self._row(name, kind, split, f"{N}x{D}x{H}x{W} {cin}->{cout}", len(pts), res, self._stats_ratio(yc, cout_off, cout, out_stats))
+        tell = None
+        if norm is not None and EXPECTED[self.case].get("distinct"):
+            # would this check notice the scale / shift / add rows of the next sample?  The same reference with those rows, in
+            # units of the bound (the largest element): a kernel that read them would land about there
+            mixed = R.conv3_ref(self._act(A_raw, (pts[:, 0] + 1) % N, norm, N, ok), Wm, layer.b)[0]
+            tell = float(((mixed - ref).abs() / bnd).max())
+        self._row(name, kind, split, f"{N}x{D}x{H}x{W} {cin}->{cout}", len(pts), res, self._stats_ratio(yc, cout_off, cout, out_stats),
+                  form=form, tell=tell)
 
     def upconv_k3(self, xs, cskip, cskip_off, u, cu, cu_off, norm, w_skip, wu, btab, cout, y, cout_off, out_stats, in_blocked=False,
                   out_blocked=False):
@@ -309,10 +422,7 @@ def _run_case(case, monkeypatch):
     plan.refresh_weights()
     assert [plan._fold_level(l) for l in range(4)] == exp["fold"], f"{case}: fold levels moved"
     assert plan._level0_layout() == exp["layout"], f"{case}: level-0 layouts moved"
-    g = torch.Generator().manual_seed(len(case))
-    image = torch.rand(N, 1, *dims, generator=g)
-    x = torch.randn(N, CLASSES, *dims, generator=g)
-    t = torch.tensor([500, 37][:N])
+    image, x, t = case_inputs(case)
     with torch.no_grad():
         plan.run_encoder(image.cuda())
         ops.to_channels_last(x.cuda().contiguous(), plan.xin, 0, CLASSES)
@@ -325,12 +435,22 @@ def _run_case(case, monkeypatch):
         plan.tail(nv.MODE_LOGITS, logits=logits)
         monkeypatch.undo()
     print(f"\n[{case}] {len(chk.rows)} launches; max |err| / bound per launch, statistics words likewise")
-    print(f"  {'launch':<6} {'kind':<8} {'split':<5} {'shape':<34} {'samples':>7} {'err/bound':>10} {'stats':>8}  worst at")
+    print(f"  {'launch':<6} {'kind':<8} {'split':<5} {'form (kernel, depth, ksplit)':<28} {'shape':<34} {'samples':>7} {'err/bound':>10} {'stats':>8} {'rows n+1':>9}  worst at")
     for r in chk.rows:
         st = "" if r["stats"] is None else f"{r['stats']:.3f}"
-        print(f"  {r['name']:<6} {r['kind']:<8} {str(r['split']):<5} {r['shape']:<34} {r['n']:>7} {r['ratio']:>10.4f} {st:>8}  {r['where']}")
+        fm = "" if r["form"] is None else "{} d{} k{}".format(*r["form"])
+        tl = "" if r["tell"] is None else f"{r['tell']:.0f}"
+        print(f"  {r['name']:<6} {r['kind']:<8} {str(r['split']):<5} {fm:<28} {r['shape']:<34} {r['n']:>7} {r['ratio']:>10.4f} {st:>8} {tl:>9}  {r['where']}")
+    if exp.get("distinct"):
+        near = min(chk.apart, key=lambda a: min(a[1:]))
+        print(f"  median relative distance between the rows of neighbouring samples, smallest of {len(chk.apart)} descriptors read: "
+              f"scale {near[1]:.3f}, add {near[2]:.3f} ({near[0]} channels)")
+        assert min(near[1:]) > APART, f"{case}: scale / add rows of neighbouring samples nearly equal: {sorted(set(chk.apart))}"
+        blind = [(r["name"], r["tell"]) for r in chk.rows if r["tell"] is not None and not r["tell"] > 2]
+        assert not blind and sum(r["tell"] is not None for r in chk.rows) == 9, f"{case}: a neighbour's rows would pass: {blind}"
     seq = [(r["name"], r["kind"], r["split"]) for r in chk.rows]
     assert seq == exp["seq"], f"{case}: the launch sequence or its dispatch moved:\n got {seq}\nwant {exp['seq']}"
+    assert {r["name"]: r["form"] for r in chk.rows if r["form"] is not None} == FORMS[case], f"{case}: not every pinned form was launched"
     bad = [(r["name"], r["res"]) for r in chk.rows if not r["ratio"] <= 1]
     assert not bad, f"{case}: launches over their fp64 bound: {bad}"
     bad = [(r["name"], r["stats"]) for r in chk.rows if r["stats"] is not None and not r["stats"] <= 1]
@@ -340,3 +460,56 @@ def _run_case(case, monkeypatch):
 @pytest.mark.parametrize("case", list(EXPECTED))
 def test_every_launch_within_its_fp64_bound(case, monkeypatch):
     _run_case(case, monkeypatch)
+
+
+def _evaluate(plan, image, x, t):
+    """One evaluation as _run_case stages it, unwrapped: (logits, copies of every buffer the plan exposes and of the statistics
+    words of every convolution of the denoiser)."""
+    from diff_unet_amos_amd import _native as nv
+    from diff_unet_amos_amd import ops
+    dev = plan.dev
+    with torch.no_grad():
+        plan.run_encoder(image.to(dev))
+        ops.to_channels_last(x.to(dev).contiguous(), plan.xin, 0, CLASSES)
+        plan.cur_add.copy_(plan.temb_table[t.to(dev).long()])
+        plan.denoiser_body()
+        logits = torch.zeros((plan.N, CLASSES, *plan.dims), dtype=torch.float32, device=dev)
+        plan.tail(nv.MODE_LOGITS, logits=logits)
+    torch.cuda.synchronize()
+    snap = {"x4": plan.x4.clone(), "logits": logits}
+    for key in ("rawA", "rawB", "uA", "uB", "cat"):
+        for l, buf in enumerate(getattr(plan, key)):
+            snap[f"{key}[{l}]"] = buf.clone()
+    for pair in plan.den + plan.dec:
+        for c in pair:
+            snap[f"stats {c.name}"] = c.stats.clone()
+    return snap
+
+
+def test_rows_of_a_batch_do_not_see_each_other():
+    """The fp16-96-b4 plan evaluated twice, the second time with another image, state and timestep in row 2 and nothing else
+    changed: rows 0, 1 and 3 of the logits, of rawA, rawB, uA, uB, cat (every level), x4 and of every convolution's statistics
+    words keep their bits, row 2 of each changes.  Every voxel, where the per-launch check samples.  Bit equality is the contract:
+    a sample's workgroups read its own rows only, the statistics are integer atomics per sample and split-K partials are summed
+    in a fixed order; a halo read across a sample boundary, a row of statistics / scale / add of a neighbour, or a mis-decoded
+    blockIdx of the batched grids would carry row 2's change into another row.  (A buffer in 16-channel blocks keeps the sample
+    outermost, so indexing the sample holds there too.)"""
+    case, changed = "fp16-96-b4", 2
+    exp = EXPECTED[case]
+    N, dims = exp["N"], exp["dims"]
+    net = _net()
+    plan = net._rt.plan(N, dims, torch.device("cuda", 0))
+    plan.refresh_weights()
+    assert [plan._fold_level(l) for l in range(4)] == exp["fold"] and plan._level0_layout() == exp["layout"]
+    image, x, t = case_inputs(case)
+    before = _evaluate(plan, image, x, t)
+    g = torch.Generator().manual_seed(20)
+    image[changed] = torch.rand(1, *dims, generator=g) * 0.45
+    x[changed] = torch.randn(CLASSES, *dims, generator=g) * 0.7
+    t[changed] = 999
+    after = _evaluate(plan, image, x, t)
+    assert before.keys() == after.keys() and len(before) == 2 + 5 + 5 + 4 + 4 + 4 + 18
+    leaked = [(k, n) for k in before for n in range(N) if n != changed and not torch.equal(before[k][n], after[k][n])]
+    assert not leaked, f"rows other than {changed} changed with it: {leaked}"
+    same = [k for k in before if torch.equal(before[k][changed], after[k][changed])]
+    assert not same, f"row {changed} did not change in {same}"

@@ -24,7 +24,7 @@ import conv_form_cases as K
 import glue_fp64ref as GR
 import step_ref as SR
 from test_glue_fp64 import LAYOUTS
-from test_launch_sequence_fp64 import EXPECTED
+from test_launch_sequence_fp64 import EXPECTED, TIMESTEPS
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -538,7 +538,7 @@ def test_one_call_step_leaves_the_bits_of_the_launch_sequence(step_plans, name, 
 @pytest.mark.parametrize("case", list(EXPECTED))
 def test_recorded_ops_carry_the_pinned_descriptors(case):
     """The OP_CONV3 / OP_DECONV / OP_DECONV_PAD entries of the op list dua_denoiser_step executes carry, field by field and in
-    order, the descriptors tests/conv_form_cases.plan_launches writes by hand for the three plans of
+    order, the descriptors tests/conv_form_cases.plan_launches writes by hand for the plans of
     tests/test_launch_sequence_fp64.py; the plan hands every convolution the whole split-K workspace."""
     nv, ops = _nv(), _ops()
     from diff_unet_amos_amd.engine import Plan
@@ -551,7 +551,7 @@ def test_recorded_ops_carry_the_pinned_descriptors(case):
     assert [plan._fold_level(l) for l in range(4)] == exp["fold"] and plan._level0_layout() == exp["layout"]
     logits = torch.zeros((N, plan.C, *dims), dtype=F32, device=dev)
     with torch.no_grad():
-        plan.native_step(nv.MODE_LOGITS, rows_per_sample=torch.tensor([500, 37][:N], dtype=I32, device=dev), logits=logits)
+        plan.native_step(nv.MODE_LOGITS, rows_per_sample=torch.tensor(TIMESTEPS[:N], dtype=I32, device=dev), logits=logits)
     torch.cuda.synchronize()
     assert int(plan.err_word) == 0
     recorded = list(plan._step_ops)
