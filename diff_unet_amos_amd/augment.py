@@ -324,12 +324,10 @@ class DeviceBatchProducer:
         ``split_affine`` names."""
         ids = self._ids(volume_ids)
         params = torch.empty((ids.numel(), nv.AUG_PARAM_WORDS), dtype=torch.int32, device=self.device)
+        affine = torch.empty((ids.numel(), nv.AUG_AFFINE_WORDS), dtype=torch.float32, device=self.device) if self.affine else None
         with torch.cuda.device(self.device):
-            if self.affine:
-                affine = torch.empty((ids.numel(), nv.AUG_AFFINE_WORDS), dtype=torch.float32, device=self.device)
-                return ops.aug_draw_affine(self.table, ids, self.cfg, self.affine_cfg, self.seed, self._counter, params, affine,
-                                           self._status, counter_value=counter)
-            return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter)
+            return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter,
+                                affine_cfg=self.affine_cfg if self.affine else None, affine=affine)
 
     def apply(self, params, out_images=None, out_labels=None, affine=None):
         """The batch ``params`` describes: (images fp32 [B, 1, *roi], labels fp32 [B, len(class_ids), *roi]); the labels are
@@ -343,20 +341,14 @@ class DeviceBatchProducer:
             out_images = torch.empty((B, 1) + self.roi, dtype=torch.float32, device=self.device)
         if out_labels is None:
             out_labels = torch.empty((B, len(self.class_ids)) + self.roi, dtype=torch.float32, device=self.device)
+        assert affine is None or (torch.is_tensor(affine) and affine.is_cuda and affine.device == self.device), \
+            "affine: a tensor on the producer's device"
+        centroids, smoothing = (self.centroids, self._smoothing) if self.smoothing is not None else (None, None)
         with torch.cuda.device(self.device):
-            if affine is not None:
-                assert torch.is_tensor(affine) and affine.is_cuda and affine.device == self.device, \
-                    "affine: a tensor on the producer's device"
-                smooth = dict(centroids=self.centroids, smoothing=self._smoothing) if self.smoothing is not None else {}
-                return ops.aug_apply_affine(self.table, params, affine, self.roi, self.class_table, out_images, out_labels,
-                                            self._status, **smooth)
-            if self.smoothing is not None:
-                return ops.aug_apply_smoothed(self.table, self.centroids, self._smoothing, params, self.roi, self.class_table,
-                                              out_images, out_labels, self._status)
-            return ops.aug_apply(self.table, params, self.roi, self.class_table, out_images, out_labels, self._status)
+            return ops.aug_apply(self.table, params, self.roi, self.class_table, out_images, out_labels, self._status,
+                                 affine=affine, centroids=centroids, smoothing=smoothing)
 
     def next(self, volume_ids, out_images=None, out_labels=None):
-        if self.affine:
-            params, affine = self.draw(volume_ids)
-            return self.apply(params, out_images, out_labels, affine=affine)
-        return self.apply(self.draw(volume_ids), out_images, out_labels)
+        drawn = self.draw(volume_ids)
+        params, affine = drawn if self.affine else (drawn, None)
+        return self.apply(params, out_images, out_labels, affine=affine)

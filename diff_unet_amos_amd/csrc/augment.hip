@@ -11,24 +11,27 @@
 //            where a binary search takes thirteen) and a ballot / popcount scan of the one chunk found; the lane that holds
 //            the candidate writes the row.  One workgroup, because the call counter is read by every sample and advanced by
 //            one lane of the same launch: a workgroup barrier orders the two, which no grid of independent workgroups could.
-//   apply  : a pure store-bandwidth kernel (per voxel: 4 + 1 bytes read, 4 (1 + C) written).  The rotation is in the (d, h)
-//            plane, so an output row along w is always one source row, forwards or backwards: a lane owns 4 consecutive
-//            output voxels, reads their 4 floats and 4 label bytes and writes one 16-byte store into the image plane and
-//            into each of the C label planes; a wave-instruction covers 1 KiB of one plane.
+//   apply  : ONE kernel template, aug_apply_kernel<V, MODE, AFFINE>, behind every apply entry point; one host launcher holds the
+//            argument checks and chooses the instantiation.  All forms share the store side: a lane owns 4 consecutive output
+//            voxels along w (1 where roi_w or an output pointer rules out 16-byte stores) and writes one 16-byte store into the
+//            image plane and into each of the C label planes; a wave-instruction covers 1 KiB of one plane.  The flip / rot90
+//            index code, the row checks and the smoothed channel are device functions.  Two read sides (AFFINE):
+//            rows   : a pure store-bandwidth kernel (per voxel: 4 + 1 bytes read, 4 (1 + C) written).  The rotation by k is in the
+//                     (d, h) plane, so an output row along w is always one source row, forwards or backwards: a lane reads the
+//                     4 floats and 4 label bytes of its voxels.
+//            gather : random rotation and zoom, through the affine rows of the draw.  8 image loads and 1 label byte per voxel
+//                     from a source region of a few MB that neighbouring lanes share.  A workgroup covers a compact 4 x 8 x 32
+//                     tile of the output (a wave one 8 x 32 piece of a plane, a 128-byte line per row and store), not a run of
+//                     1 024 voxels: under a rotation an output row crosses a source line every few voxels, and it is the rows
+//                     beside, above and below it that use the rest of those lines (measured: DESIGN.md 10c-1).
+//            Three label bodies (MODE): the one-hot channel, or the centroid-distance smoothed channel with or without pow.  The
+//            read side leaves the source position of each voxel; the centroids of the row's volume sit in LDS (one broadcast
+//            read per channel), and a channel costs 4 x (sub, fma, sqrt, add, rcp, mul, sub, min) before its 16-byte store.
 //   centroids : once per volume, for label smoothing (dataset/cache_dataset.py:105-153).  One pass over the label map, 16 bytes
 //            per thread and step; count and index sums per class as 64-bit integers, LDS atomics inside a workgroup, one
 //            global integer atomic per class and workgroup: exact, so identical between runs.  A finish launch divides in fp64.
-//   smoothed apply : the apply kernel with another body for the label planes (template parameter MODE): the same index code
-//            gives the source index of a lane's 4 voxels, the centroids of the row's volume sit in LDS (one broadcast read per
-//            channel), and a channel costs 4 x (sub, fma, sqrt, add, rcp, mul, sub, min) before its 16-byte store.
-//   affine : random rotation and zoom.  The draw kernel's AFFINE form takes two more Philox blocks and writes, beside the params
-//            row, the matrix M = R / z from half-angle tangents in fp64 (no sine, no cosine: a numpy restatement has its bits).
-//            The affine apply keeps the store side of apply and reads by gather: 8 image loads and 1 label byte per voxel from
-//            a source region of a few MB that neighbouring lanes share.  A workgroup covers a compact 4 x 8 x 32 tile of the
-//            output (a wave one 8 x 32 piece of a plane, a 128-byte line per row and store), not a run of 1 024 voxels: under
-//            a rotation an output row crosses a source line every few voxels, and it is the rows beside, above and below it
-//            that use the rest of those lines (measured: DESIGN.md 10c-1).  The flip / rot90 index code, the row checks and
-//            the smoothed channel are device functions all apply kernels share.
+//   affine draw : the draw kernel's AFFINE form takes two more Philox blocks and writes, beside the params row, the matrix
+//            M = R / z from half-angle tangents in fp64 (no sine, no cosine: a numpy restatement has its bits).
 // -ffp-contract=off (csrc/Makefile) keeps the three fp32 operations of the intensity transform, and the two of each drawn
 // value, separately rounded; the pragma below says so for this file whatever the command line.
 #include "common.hpp"
@@ -324,14 +327,27 @@ __device__ __forceinline__ float aug_smoothed(float onehot, float dw, float t, c
   return fminf(fabsf(onehot - s), sm.max_value);
 }
 
-// V output voxels per lane (4: roi_w is a multiple of 4, so a group never crosses a row and every store is 16-byte aligned).
+constexpr int AFF_TILE_D = 4, AFF_TILE_H = 8, AFF_TILE_W = 32;
+static_assert(AFF_TILE_D * AFF_TILE_H * AFF_TILE_W == 4 * AUG_THREADS && AFF_TILE_W % 4 == 0, "one tile per workgroup, 4 voxels per lane");
+
+// floorf(s) as an index that can be compared and incremented: clamped to [-2, 2^31 - 128] first, where the clamp only moves an
+// index that lies outside every volume to another one that does (a NaN becomes -2)
+__device__ __forceinline__ int aug_floor_index(float fl) { return (int)fminf(fmaxf(fl, -2.f), 2147483520.f); }
+
+// The one apply kernel.  A lane owns V consecutive output voxels of a row along w (4: roi_w is a multiple of 4, so a group never
+// crosses a row and every store is 16-byte aligned) and writes one store into the image plane and into each label plane.
 // MODE: what a label plane holds -- SMOOTH_NONE: the one-hot channel; SMOOTH_ORDER1 / SMOOTH_POW: the centroid-distance
-// smoothed channel (order == 1 without pow), evaluated at the source index that the index code, shared by all, finds.
-template <int V, int MODE>
+// smoothed channel (order == 1 without pow), evaluated at the source position (jd, jh, jw) of each voxel.
+// AFFINE: how an output voxel finds its source values.  false: the index code gives the source row, 1 float and 1 label byte per
+// voxel, forwards or backwards along it; `affine` is unread.  true: a gather -- per voxel the 8 corners of the trilinear cell
+// around s = M r + c and the label byte at the nearest voxel.  The window index p of an output voxel comes from the same index
+// code, so flips and k apply after the resampling.  The products with r_d and r_h and their sum are the same numbers for the V
+// voxels of a lane: computed once, they are the bits each voxel would get from scratch; nothing is carried along the row.
+template <int V, int MODE, bool AFFINE>
 __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_volume* __restrict__ table, int nvol,
-                                                               const int* __restrict__ params, int Rd, int Rh, int Rw,
-                                                               const unsigned char* __restrict__ class_ids, int C,
-                                                               float* __restrict__ images, float* __restrict__ labels,
+                                                               const int* __restrict__ params, const float* __restrict__ affine,
+                                                               int Rd, int Rh, int Rw, const unsigned char* __restrict__ class_ids,
+                                                               int C, float* __restrict__ images, float* __restrict__ labels,
                                                                int* status, AugSmooth sm) {
   using Vec = typename OutVec<V>::T;
   __shared__ float cen[MODE == SMOOTH_NONE ? 1 : DUA_AUG_MAX_CLASSES][4];      // centroid of class_ids[ch] in the row's volume
@@ -352,114 +368,9 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(const dua_aug_vo
     }
   }
   const long vox = (long)Rd * Rh * Rw;
-  const unsigned o = (blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x) * V;   // first output voxel of this lane (vox < 2^31)
-  if (o >= vox) return;
   int od, oh, ow, a, c;
-  aug_output_position(o, Rh, Rw, od, oh, ow);
-  aug_window_row(od, oh, k, flip, Rd, Rh, a, c);
-  const bool fw = (flip & 4) != 0;
-  const long src = ((long)(sd0 + a) * vol.H + (sh0 + c)) * vol.W + sw0;     // start of the source row's window
-  const float factor = 1.f + __int_as_float(row[DUA_AUG_SCALE]);
-  const float shift = __int_as_float(row[DUA_AUG_SHIFT]);
-  float px[V];
-  unsigned char lb[V];
-#pragma unroll
-  for (int e = 0; e < V; ++e) {
-    const int sw = fw ? Rw - 1 - (ow + e) : ow + e;
-    px[e] = vol.image[src + sw];
-    lb[e] = vol.label[src + sw];
-  }
-  Vec v;
-  if constexpr (V == 4) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = px[e] * factor + shift;
-  } else {
-    v = px[0] * factor + shift;
-  }
-  *reinterpret_cast<Vec*>(images + (long)b * vox + o) = v;
-  float* lab = labels + (long)b * C * vox + o;
-  if constexpr (MODE == SMOOTH_NONE) {
-#pragma unroll 4
-    for (int ch = 0; ch < C; ++ch) {
-      const unsigned char id = class_ids[ch];
-      Vec m;
-      if constexpr (V == 4) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = lb[e] == id ? 1.f : 0.f;
-      } else {
-        m = lb[0] == id ? 1.f : 0.f;
-      }
-      *reinterpret_cast<Vec*>(lab + (long)ch * vox) = m;
-    }
-  } else {
-    // the source index of the lane's voxels is (sd0 + a, sh0 + c, sw0 + sw_e); fp32 holds it exactly for extents up to 2^24
-    const float fd = (float)(sd0 + a), fh = (float)(sh0 + c);
-    float fx[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) fx[e] = (float)(sw0 + (fw ? Rw - 1 - (ow + e) : ow + e));
-#pragma unroll 2
-    for (int ch = 0; ch < C; ++ch) {
-      const unsigned char id = class_ids[ch];
-      const float dd = fd - cen[ch][0], dh = fh - cen[ch][1], cw = cen[ch][2];
-      const float t = dd * dd + dh * dh;
-      float m[V];
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        m[e] = aug_smoothed<MODE>(lb[e] == id ? 1.f : 0.f, fx[e] - cw, t, sm);
-      }
-      if constexpr (V == 4) {
-        Vec mv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mv[e] = m[e];
-        *reinterpret_cast<Vec*>(lab + (long)ch * vox) = mv;
-      } else {
-        *(lab + (long)ch * vox) = m[0];
-      }
-    }
-  }
-}
-
-constexpr int AFF_TILE_D = 4, AFF_TILE_H = 8, AFF_TILE_W = 32;
-static_assert(AFF_TILE_D * AFF_TILE_H * AFF_TILE_W == 4 * AUG_THREADS && AFF_TILE_W % 4 == 0, "one tile per workgroup, 4 voxels per lane");
-
-// floorf(s) as an index that can be compared and incremented: clamped to [-2, 2^31 - 128] first, where the clamp only moves an
-// index that lies outside every volume to another one that does (a NaN becomes -2)
-__device__ __forceinline__ int aug_floor_index(float fl) { return (int)fminf(fmaxf(fl, -2.f), 2147483520.f); }
-
-// dua_aug_apply_affine: the store side of aug_apply_kernel (a lane owns V consecutive output voxels of a row along w, one store
-// per plane), the read side a gather -- per voxel the 8 corners of the trilinear cell around s = M r + c and the label byte at
-// the nearest voxel.  The window index p of an output voxel comes from the same index code, so flips and k apply after the
-// resampling.  The products with r_d and r_h and their sum are the same numbers for the V voxels of a lane: computed once,
-// they are the bits each voxel would get from scratch; nothing is carried along the row.
-template <int V, int MODE>
-__global__ void __launch_bounds__(AUG_THREADS) aug_apply_affine_kernel(const dua_aug_volume* __restrict__ table, int nvol,
-                                                                      const int* __restrict__ params,
-                                                                      const float* __restrict__ affine, int Rd, int Rh, int Rw,
-                                                                      const unsigned char* __restrict__ class_ids, int C,
-                                                                      float* __restrict__ images, float* __restrict__ labels,
-                                                                      int* status, AugSmooth sm) {
-  using Vec = typename OutVec<V>::T;
-  __shared__ float cen[MODE == SMOOTH_NONE ? 1 : DUA_AUG_MAX_CLASSES][4];
-  __shared__ int bad_id;
-  const int b = blockIdx.y;
-  const int* row = params + (long)b * DUA_AUG_PARAM_WORDS;
-  const int vid = row[DUA_AUG_VOLUME], sd0 = row[DUA_AUG_START_D], sh0 = row[DUA_AUG_START_H], sw0 = row[DUA_AUG_START_W];
-  const int flip = row[DUA_AUG_FLIP], k = row[DUA_AUG_K];
-  dua_aug_volume vol = {};
-  if (!aug_row_ok(table, nvol, row, Rd, Rh, Rw, vol)) {
-    if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
-    return;
-  }
-  if constexpr (MODE != SMOOTH_NONE) {
-    if (!aug_stage_centroids(cen, &bad_id, vid, class_ids, C, sm)) {
-      if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = 1;
-      return;
-    }
-  }
-  const long vox = (long)Rd * Rh * Rw;
-  int od, oh, ow, a, c;
-  unsigned o;
-  if constexpr (V == 4) {
+  unsigned o;                                             // first output voxel of this lane (vox < 2^31)
+  if constexpr (AFFINE && V == 4) {
     // a workgroup covers a compact AFF_TILE_D x AFF_TILE_H x AFF_TILE_W tile of the output, a wave one 8 x 32 piece of a plane:
     // under a rotation the rows of a tile read neighbouring source lines, which the CU's L1 then holds for all of them
     const unsigned tiles_w = (Rw + AFF_TILE_W - 1) / AFF_TILE_W, tiles_h = (Rh + AFF_TILE_H - 1) / AFF_TILE_H;
@@ -469,56 +380,68 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_affine_kernel(const dua
     if (od >= Rd || oh >= Rh || ow >= Rw) return;          // roi_w is a multiple of 4: a lane's voxels are all inside or all outside
     o = ((unsigned)od * (unsigned)Rh + (unsigned)oh) * (unsigned)Rw + (unsigned)ow;
   } else {
-    o = blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x;
+    o = (blockIdx.x * (unsigned)AUG_THREADS + threadIdx.x) * V;
     if (o >= vox) return;
     aug_output_position(o, Rh, Rw, od, oh, ow);
   }
   aug_window_row(od, oh, k, flip, Rd, Rh, a, c);
   const bool fw = (flip & 4) != 0;
-  const float* arow = affine + (long)b * DUA_AUG_AFFINE_WORDS;
-  float m[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) m[j] = arow[DUA_AUG_AFFINE_M + j];
-  const float pad = arow[DUA_AUG_AFFINE_PAD];
-  const float hd = 0.5f * (float)(Rd - 1), hh = 0.5f * (float)(Rh - 1), hw = 0.5f * (float)(Rw - 1);      // exact
-  const float cd = (float)sd0 + hd, chh = (float)sh0 + hh, cw = (float)sw0 + hw;
-  const float rd = (float)a - hd, rh = (float)c - hh;
-  const float qd = m[0] * rd + m[1] * rh, qh = m[3] * rd + m[4] * rh, qw = m[6] * rd + m[7] * rh;
   const float factor = 1.f + __int_as_float(row[DUA_AUG_SCALE]);
   const float shift = __int_as_float(row[DUA_AUG_SHIFT]);
-  const unsigned D = (unsigned)vol.D, H = (unsigned)vol.H, W = (unsigned)vol.W;
-  float px[V], jd[V], jh[V], jw[V];
+  float px[V], jd[V], jh[V], jw[V];                       // the source value and the position the smoothed forms take
   unsigned char lb[V];
+  if constexpr (AFFINE) {
+    const float* arow = affine + (long)b * DUA_AUG_AFFINE_WORDS;
+    float m[9];
 #pragma unroll
-  for (int e = 0; e < V; ++e) {
-    const float rw = (float)(fw ? Rw - 1 - (ow + e) : ow + e) - hw;
-    const float s0 = (qd + m[2] * rw) + cd, s1 = (qh + m[5] * rw) + chh, s2 = (qw + m[8] * rw) + cw;
-    const float l0 = floorf(s0), l1 = floorf(s1), l2 = floorf(s2);
-    const float f0 = s0 - l0, f1 = s1 - l1, f2 = s2 - l2;
-    const int i0 = aug_floor_index(l0), i1 = aug_floor_index(l1), i2 = aug_floor_index(l2);
-    float cor[2][2][2];
+    for (int j = 0; j < 9; ++j) m[j] = arow[DUA_AUG_AFFINE_M + j];
+    const float pad = arow[DUA_AUG_AFFINE_PAD];
+    const float hd = 0.5f * (float)(Rd - 1), hh = 0.5f * (float)(Rh - 1), hw = 0.5f * (float)(Rw - 1);      // exact
+    const float cd = (float)sd0 + hd, chh = (float)sh0 + hh, cw = (float)sw0 + hw;
+    const float rd = (float)a - hd, rh = (float)c - hh;
+    const float qd = m[0] * rd + m[1] * rh, qh = m[3] * rd + m[4] * rh, qw = m[6] * rd + m[7] * rh;
+    const unsigned D = (unsigned)vol.D, H = (unsigned)vol.H, W = (unsigned)vol.W;
 #pragma unroll
-    for (int ed = 0; ed < 2; ++ed)
+    for (int e = 0; e < V; ++e) {
+      const float rw = (float)(fw ? Rw - 1 - (ow + e) : ow + e) - hw;
+      const float s0 = (qd + m[2] * rw) + cd, s1 = (qh + m[5] * rw) + chh, s2 = (qw + m[8] * rw) + cw;
+      const float l0 = floorf(s0), l1 = floorf(s1), l2 = floorf(s2);
+      const float f0 = s0 - l0, f1 = s1 - l1, f2 = s2 - l2;
+      const int i0 = aug_floor_index(l0), i1 = aug_floor_index(l1), i2 = aug_floor_index(l2);
+      float cor[2][2][2];
 #pragma unroll
-      for (int eh = 0; eh < 2; ++eh)
+      for (int ed = 0; ed < 2; ++ed)
 #pragma unroll
-        for (int ew = 0; ew < 2; ++ew) {
-          const unsigned d = (unsigned)(i0 + ed), h = (unsigned)(i1 + eh), w = (unsigned)(i2 + ew);
-          const bool in = d < D && h < H && w < W;        // a negative index is a huge unsigned one
-          cor[ed][eh][ew] = in ? vol.image[((long)d * vol.H + h) * vol.W + w] : pad;
-        }
-    float y[2];
+        for (int eh = 0; eh < 2; ++eh)
 #pragma unroll
-    for (int ed = 0; ed < 2; ++ed) {
-      const float x0 = __builtin_fmaf(f2, cor[ed][0][1] - cor[ed][0][0], cor[ed][0][0]);
-      const float x1 = __builtin_fmaf(f2, cor[ed][1][1] - cor[ed][1][0], cor[ed][1][0]);
-      y[ed] = __builtin_fmaf(f1, x1 - x0, x0);
+          for (int ew = 0; ew < 2; ++ew) {
+            const unsigned d = (unsigned)(i0 + ed), h = (unsigned)(i1 + eh), w = (unsigned)(i2 + ew);
+            const bool in = d < D && h < H && w < W;      // a negative index is a huge unsigned one
+            cor[ed][eh][ew] = in ? vol.image[((long)d * vol.H + h) * vol.W + w] : pad;
+          }
+      float y[2];
+#pragma unroll
+      for (int ed = 0; ed < 2; ++ed) {
+        const float x0 = __builtin_fmaf(f2, cor[ed][0][1] - cor[ed][0][0], cor[ed][0][0]);
+        const float x1 = __builtin_fmaf(f2, cor[ed][1][1] - cor[ed][1][0], cor[ed][1][0]);
+        y[ed] = __builtin_fmaf(f1, x1 - x0, x0);
+      }
+      px[e] = __builtin_fmaf(f0, y[1] - y[0], y[0]);
+      const int n0 = f0 >= 0.5f ? 1 : 0, n1 = f1 >= 0.5f ? 1 : 0, n2 = f2 >= 0.5f ? 1 : 0;
+      const unsigned d = (unsigned)(i0 + n0), h = (unsigned)(i1 + n1), w = (unsigned)(i2 + n2);
+      lb[e] = (d < D && h < H && w < W) ? vol.label[((long)d * vol.H + h) * vol.W + w] : (unsigned char)0;
+      jd[e] = l0 + (float)n0; jh[e] = l1 + (float)n1; jw[e] = l2 + (float)n2;      // the nearest voxel, unclamped
     }
-    px[e] = __builtin_fmaf(f0, y[1] - y[0], y[0]);
-    const int n0 = f0 >= 0.5f ? 1 : 0, n1 = f1 >= 0.5f ? 1 : 0, n2 = f2 >= 0.5f ? 1 : 0;
-    const unsigned d = (unsigned)(i0 + n0), h = (unsigned)(i1 + n1), w = (unsigned)(i2 + n2);
-    lb[e] = (d < D && h < H && w < W) ? vol.label[((long)d * vol.H + h) * vol.W + w] : (unsigned char)0;
-    jd[e] = l0 + (float)n0; jh[e] = l1 + (float)n1; jw[e] = l2 + (float)n2;      // the position the smoothed forms take: unclamped
+  } else {
+    const long src = ((long)(sd0 + a) * vol.H + (sh0 + c)) * vol.W + sw0;   // start of the source row's window
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int sw = fw ? Rw - 1 - (ow + e) : ow + e;
+      px[e] = vol.image[src + sw];
+      lb[e] = vol.label[src + sw];
+      // the source index (sd0 + a, sh0 + c, sw0 + sw); fp32 holds it exactly for extents up to 2^24
+      jd[e] = (float)(sd0 + a); jh[e] = (float)(sh0 + c); jw[e] = (float)(sw0 + sw);
+    }
   }
   Vec v;
   if constexpr (V == 4) {
@@ -529,7 +452,8 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_affine_kernel(const dua
   }
   *reinterpret_cast<Vec*>(images + (long)b * vox + o) = v;
   float* lab = labels + (long)b * C * vox + o;
-#pragma unroll 2
+  constexpr int PLANES_UNROLL = MODE == SMOOTH_NONE && !AFFINE ? 4 : 2;
+#pragma unroll PLANES_UNROLL
   for (int ch = 0; ch < C; ++ch) {
     const unsigned char id = class_ids[ch];
     float mv[V];
@@ -620,6 +544,81 @@ static bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }
 
 }  // namespace dua
 
+// dua_aug_draw (affine_cfg == NULL and affine == NULL) and dua_aug_draw_affine (both given)
+static int aug_draw_launch(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                           const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
+                           int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
+                           void* stream) {
+  if (!table || nvol < 1 || !ids || B < 1 || !cfg || !params || (!use_counter && !counter)) return DUA_ERR_ARG;
+  if (cfg->roi[0] < 1 || cfg->roi[1] < 1 || cfg->roi[2] < 1 || cfg->max_k < 1 || cfg->max_k > 3) return DUA_ERR_ARG;
+  if (!dua::prob_ok(cfg->pos_fraction) || !dua::prob_ok(cfg->flip_prob) || !dua::prob_ok(cfg->rot90_prob) ||
+      !dua::prob_ok(cfg->scale_prob) || !dua::prob_ok(cfg->shift_prob) || !(cfg->scale_factors >= 0.f) ||
+      !(cfg->shift_offsets >= 0.f) || (cfg->rot90_prob > 0.f && cfg->roi[0] != cfg->roi[1]))
+    return DUA_ERR_ARG;
+  dua_aug_affine_config a{};
+  if (affine_cfg) {
+    a = *affine_cfg;
+    // every comparison is false for a NaN
+    if (!dua::prob_ok(a.rotate_prob) || !dua::prob_ok(a.zoom_prob) || !(a.zoom_min > 0.f && a.zoom_min <= 3.0e38f) ||
+        !(a.zoom_span >= 0.f && a.zoom_span <= 3.0e38f) || !(a.pad_value >= -3.0e38f && a.pad_value <= 3.0e38f))
+      return DUA_ERR_ARG;
+    for (int i = 0; i < 3; ++i)
+      if (!(a.rotate_tan_half[i] >= 0.f && a.rotate_tan_half[i] <= 1.f)) return DUA_ERR_ARG;
+  }
+  const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
+  const auto kernel = affine_cfg ? dua::aug_draw_kernel<true> : dua::aug_draw_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg, seed, counter,
+                     use_counter, counter_value, params, status, a, affine);
+  return (int)hipGetLastError();
+}
+
+// every apply entry point: affine == NULL reads whole source rows, otherwise through the affine rows; smoothing == NULL gives
+// one-hot label planes, otherwise the smoothed ones from centroids
+static int aug_apply_launch(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
+                            const dua_aug_smoothing* smoothing, const int* params, const float* affine, int B, int roi_d,
+                            int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
+                            int* status, void* stream) {
+  if (!table || nvol < 1 || !params || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 || !class_ids || C < 1 ||
+      C > DUA_AUG_MAX_CLASSES || !images || !labels)
+    return DUA_ERR_ARG;
+  dua::AugSmooth sm{};
+  int mode = dua::SMOOTH_NONE;
+  if (smoothing) {
+    const dua_aug_smoothing p = *smoothing;
+    // every comparison is false for a NaN.  epsilon is a normal number, so that 1 / (dist^order + epsilon) stays finite and
+    // alpha = 0 gives exactly 0
+    if (num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES || !(p.alpha >= 0.f && p.alpha <= 3.0e38f) ||
+        !(p.order > 0.f && p.order <= 3.0e38f) || !(p.epsilon >= 1.17549435e-38f && p.epsilon <= 3.0e38f) || !(p.max_value > 0.f))
+      return DUA_ERR_ARG;
+    sm = dua::AugSmooth{centroids, num_classes, p.alpha, p.order, p.epsilon, p.max_value};
+    mode = p.order != 1.f ? dua::SMOOTH_POW : dua::SMOOTH_ORDER1;
+  }
+  const long vox = (long)roi_d * roi_h * roi_w;
+  if (vox >= (1L << 31)) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  // 16-byte stores need every plane and every row to start on a 16-byte boundary
+  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
+  long blocks = ((wide ? vox / 4 : vox) + dua::AUG_THREADS - 1) / dua::AUG_THREADS;     // a lane per 4 (1) voxels in linear order
+  if (wide && affine)                                     // a tile per workgroup: at most vox, which is below 2^31
+    blocks = (long)((roi_d + dua::AFF_TILE_D - 1) / dua::AFF_TILE_D) * ((roi_h + dua::AFF_TILE_H - 1) / dua::AFF_TILE_H) *
+             ((roi_w + dua::AFF_TILE_W - 1) / dua::AFF_TILE_W);
+  const dim3 grid((unsigned)blocks, B);
+#define DUA_AUG_APPLY(V, MODE, AFFINE)                                                                                          \
+  hipLaunchKernelGGL((dua::aug_apply_kernel<V, MODE, AFFINE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, affine, \
+                     roi_d, roi_h, roi_w, class_ids, C, images, labels, status, sm)
+#define DUA_AUG_APPLY_A(V, MODE) if (affine) DUA_AUG_APPLY(V, MODE, true); else DUA_AUG_APPLY(V, MODE, false)
+#define DUA_AUG_APPLY_V(MODE) if (wide) { DUA_AUG_APPLY_A(4, MODE); } else { DUA_AUG_APPLY_A(1, MODE); }
+  switch (mode) {
+    case dua::SMOOTH_NONE: DUA_AUG_APPLY_V(dua::SMOOTH_NONE) break;
+    case dua::SMOOTH_ORDER1: DUA_AUG_APPLY_V(dua::SMOOTH_ORDER1) break;
+    default: DUA_AUG_APPLY_V(dua::SMOOTH_POW) break;
+  }
+#undef DUA_AUG_APPLY_V
+#undef DUA_AUG_APPLY_A
+#undef DUA_AUG_APPLY
+  return (int)hipGetLastError();
+}
+
 extern "C" {
 
 int dua_aug_count_candidates(const float* image, const unsigned char* label, long voxels, float image_threshold,
@@ -637,38 +636,14 @@ int dua_aug_count_candidates(const float* image, const unsigned char* label, lon
 int dua_aug_draw(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
                  unsigned long long seed, unsigned long long* counter, int use_counter, unsigned long long counter_value,
                  int* params, int* status, void* stream) {
-  if (!table || nvol < 1 || !ids || B < 1 || !cfg || !params || (!use_counter && !counter)) return DUA_ERR_ARG;
-  if (cfg->roi[0] < 1 || cfg->roi[1] < 1 || cfg->roi[2] < 1 || cfg->max_k < 1 || cfg->max_k > 3) return DUA_ERR_ARG;
-  if (!dua::prob_ok(cfg->pos_fraction) || !dua::prob_ok(cfg->flip_prob) || !dua::prob_ok(cfg->rot90_prob) ||
-      !dua::prob_ok(cfg->scale_prob) || !dua::prob_ok(cfg->shift_prob) || !(cfg->scale_factors >= 0.f) ||
-      !(cfg->shift_offsets >= 0.f) || (cfg->rot90_prob > 0.f && cfg->roi[0] != cfg->roi[1]))
-    return DUA_ERR_ARG;
-  const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
-  hipLaunchKernelGGL(dua::aug_draw_kernel<false>, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg,
-                     seed, counter, use_counter, counter_value, params, status, dua_aug_affine_config{}, (float*)nullptr);
-  return (int)hipGetLastError();
+  return aug_draw_launch(table, nvol, ids, B, cfg, nullptr, seed, counter, use_counter, counter_value, params, nullptr, status,
+                         stream);
 }
 
 int dua_aug_apply(const dua_aug_volume* table, int nvol, const int* params, int B, int roi_d, int roi_h, int roi_w,
                   const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream) {
-  if (!table || nvol < 1 || !params || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 || !class_ids || C < 1 ||
-      C > DUA_AUG_MAX_CLASSES || !images || !labels)
-    return DUA_ERR_ARG;
-  const long vox = (long)roi_d * roi_h * roi_w;
-  if (vox >= (1L << 31)) return DUA_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  // 16-byte stores need every plane and every row to start on a 16-byte boundary
-  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
-  if (wide) {
-    const dim3 grid((unsigned)((vox / 4 + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-    hipLaunchKernelGGL((dua::aug_apply_kernel<4, dua::SMOOTH_NONE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params,
-                       roi_d, roi_h, roi_w, class_ids, C, images, labels, status, dua::AugSmooth{});
-  } else {
-    const dim3 grid((unsigned)((vox + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-    hipLaunchKernelGGL((dua::aug_apply_kernel<1, dua::SMOOTH_NONE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params,
-                       roi_d, roi_h, roi_w, class_ids, C, images, labels, status, dua::AugSmooth{});
-  }
-  return (int)hipGetLastError();
+  return aug_apply_launch(table, nvol, nullptr, 0, nullptr, params, nullptr, B, roi_d, roi_h, roi_w, class_ids, C, images, labels,
+                          status, stream);
 }
 
 int dua_aug_class_centroids(const unsigned char* label, int D, int H, int W, int num_classes, unsigned long long* sums,
@@ -693,56 +668,18 @@ int dua_aug_class_centroids(const unsigned char* label, int D, int H, int W, int
 int dua_aug_apply_smoothed(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
                            const dua_aug_smoothing* smoothing, const int* params, int B, int roi_d, int roi_h, int roi_w,
                            const unsigned char* class_ids, int C, float* images, float* labels, int* status, void* stream) {
-  if (!table || nvol < 1 || !params || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 || !class_ids || C < 1 ||
-      C > DUA_AUG_MAX_CLASSES || !images || !labels || !centroids || num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES ||
-      !smoothing)
-    return DUA_ERR_ARG;
-  const dua_aug_smoothing p = *smoothing;
-  // every comparison is false for a NaN.  epsilon is a normal number, so that 1 / (dist^order + epsilon) stays finite and
-  // alpha = 0 gives exactly 0
-  if (!(p.alpha >= 0.f && p.alpha <= 3.0e38f) || !(p.order > 0.f && p.order <= 3.0e38f) ||
-      !(p.epsilon >= 1.17549435e-38f && p.epsilon <= 3.0e38f) || !(p.max_value > 0.f))
-    return DUA_ERR_ARG;
-  const long vox = (long)roi_d * roi_h * roi_w;
-  if (vox >= (1L << 31)) return DUA_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const dua::AugSmooth sm{centroids, num_classes, p.alpha, p.order, p.epsilon, p.max_value};
-  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
-  const bool pw = p.order != 1.f;
-  const dim3 grid((unsigned)(((wide ? vox / 4 : vox) + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-#define DUA_AUG_SMOOTHED(V, MODE)                                                                                              \
-  hipLaunchKernelGGL((dua::aug_apply_kernel<V, MODE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, roi_d, roi_h, \
-                     roi_w, class_ids, C, images, labels, status, sm)
-  if (wide && !pw) DUA_AUG_SMOOTHED(4, dua::SMOOTH_ORDER1);
-  else if (wide) DUA_AUG_SMOOTHED(4, dua::SMOOTH_POW);
-  else if (!pw) DUA_AUG_SMOOTHED(1, dua::SMOOTH_ORDER1);
-  else DUA_AUG_SMOOTHED(1, dua::SMOOTH_POW);
-#undef DUA_AUG_SMOOTHED
-  return (int)hipGetLastError();
+  if (!centroids || !smoothing) return DUA_ERR_ARG;
+  return aug_apply_launch(table, nvol, centroids, num_classes, smoothing, params, nullptr, B, roi_d, roi_h, roi_w, class_ids, C,
+                          images, labels, status, stream);
 }
 
 int dua_aug_draw_affine(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
                         const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
                         int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
                         void* stream) {
-  if (!table || nvol < 1 || !ids || B < 1 || !cfg || !affine_cfg || !params || !affine || (!use_counter && !counter))
-    return DUA_ERR_ARG;
-  if (cfg->roi[0] < 1 || cfg->roi[1] < 1 || cfg->roi[2] < 1 || cfg->max_k < 1 || cfg->max_k > 3) return DUA_ERR_ARG;
-  if (!dua::prob_ok(cfg->pos_fraction) || !dua::prob_ok(cfg->flip_prob) || !dua::prob_ok(cfg->rot90_prob) ||
-      !dua::prob_ok(cfg->scale_prob) || !dua::prob_ok(cfg->shift_prob) || !(cfg->scale_factors >= 0.f) ||
-      !(cfg->shift_offsets >= 0.f) || (cfg->rot90_prob > 0.f && cfg->roi[0] != cfg->roi[1]))
-    return DUA_ERR_ARG;
-  const dua_aug_affine_config a = *affine_cfg;
-  // every comparison is false for a NaN
-  if (!dua::prob_ok(a.rotate_prob) || !dua::prob_ok(a.zoom_prob) || !(a.zoom_min > 0.f && a.zoom_min <= 3.0e38f) ||
-      !(a.zoom_span >= 0.f && a.zoom_span <= 3.0e38f) || !(a.pad_value >= -3.0e38f && a.pad_value <= 3.0e38f))
-    return DUA_ERR_ARG;
-  for (int i = 0; i < 3; ++i)
-    if (!(a.rotate_tan_half[i] >= 0.f && a.rotate_tan_half[i] <= 1.f)) return DUA_ERR_ARG;
-  const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
-  hipLaunchKernelGGL(dua::aug_draw_kernel<true>, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg,
-                     seed, counter, use_counter, counter_value, params, status, a, affine);
-  return (int)hipGetLastError();
+  if (!affine_cfg || !affine) return DUA_ERR_ARG;
+  return aug_draw_launch(table, nvol, ids, B, cfg, affine_cfg, seed, counter, use_counter, counter_value, params, affine, status,
+                         stream);
 }
 
 int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
@@ -750,39 +687,10 @@ int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* cen
                          int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
                          int* status, void* stream) {
   constexpr int max_extent = 1 << 22;                     // r and c of the contract are exact in fp32
-  if (!table || nvol < 1 || !params || !affine || B < 1 || B > 65535 || roi_d < 1 || roi_h < 1 || roi_w < 1 ||
-      roi_d > max_extent || roi_h > max_extent || roi_w > max_extent || !class_ids || C < 1 || C > DUA_AUG_MAX_CLASSES ||
-      !images || !labels || (centroids == nullptr) != (smoothing == nullptr))
+  if (!affine || roi_d > max_extent || roi_h > max_extent || roi_w > max_extent || (centroids == nullptr) != (smoothing == nullptr))
     return DUA_ERR_ARG;
-  dua::AugSmooth sm{};
-  bool pw = false;
-  if (smoothing) {
-    const dua_aug_smoothing p = *smoothing;
-    if (num_classes < 1 || num_classes > dua::CEN_MAX_CLASSES || !(p.alpha >= 0.f && p.alpha <= 3.0e38f) ||
-        !(p.order > 0.f && p.order <= 3.0e38f) || !(p.epsilon >= 1.17549435e-38f && p.epsilon <= 3.0e38f) || !(p.max_value > 0.f))
-      return DUA_ERR_ARG;
-    sm = dua::AugSmooth{centroids, num_classes, p.alpha, p.order, p.epsilon, p.max_value};
-    pw = p.order != 1.f;
-  }
-  const long vox = (long)roi_d * roi_h * roi_w;
-  if (vox >= (1L << 31)) return DUA_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wide = roi_w % 4 == 0 && ((size_t)images & 15) == 0 && ((size_t)labels & 15) == 0;
-  const long tiles = (long)((roi_d + dua::AFF_TILE_D - 1) / dua::AFF_TILE_D) * ((roi_h + dua::AFF_TILE_H - 1) / dua::AFF_TILE_H) *
-                     ((roi_w + dua::AFF_TILE_W - 1) / dua::AFF_TILE_W);       // at most vox, which is below 2^31
-  const dim3 grid((unsigned)(wide ? tiles : (vox + dua::AUG_THREADS - 1) / dua::AUG_THREADS), B);
-#define DUA_AUG_AFFINE(V, MODE)                                                                                                \
-  hipLaunchKernelGGL((dua::aug_apply_affine_kernel<V, MODE>), grid, dim3(dua::AUG_THREADS), 0, s, table, nvol, params, affine, \
-                     roi_d, roi_h, roi_w, class_ids, C, images, labels, status, sm)
-  if (!smoothing) {
-    if (wide) DUA_AUG_AFFINE(4, dua::SMOOTH_NONE);
-    else DUA_AUG_AFFINE(1, dua::SMOOTH_NONE);
-  } else if (wide && !pw) DUA_AUG_AFFINE(4, dua::SMOOTH_ORDER1);
-  else if (wide) DUA_AUG_AFFINE(4, dua::SMOOTH_POW);
-  else if (!pw) DUA_AUG_AFFINE(1, dua::SMOOTH_ORDER1);
-  else DUA_AUG_AFFINE(1, dua::SMOOTH_POW);
-#undef DUA_AUG_AFFINE
-  return (int)hipGetLastError();
+  return aug_apply_launch(table, nvol, centroids, num_classes, smoothing, params, affine, B, roi_d, roi_h, roi_w, class_ids, C,
+                          images, labels, status, stream);
 }
 
 }  // extern "C"

@@ -1812,38 +1812,77 @@ def _aug_table(table, name="table"):
     return table.shape[0]
 
 
-def aug_draw(table, ids, cfg, seed, counter, params, status, counter_value=None):
+def _aug_affine_rows(affine, B):
+    _f32c(affine, "affine")
+    assert tuple(affine.shape) == (B, nv.AUG_AFFINE_WORDS), f"affine: fp32 [{B}, {nv.AUG_AFFINE_WORDS}], got {tuple(affine.shape)}"
+
+
+def aug_draw(table, ids, cfg, seed, counter, params, status, counter_value=None, affine_cfg=None, affine=None):
     """dua_aug_draw: one row of ``params`` (int32 [B, 8]) per entry of ``ids`` (int32 [B]); ``counter`` (int64 [1]) is the
-    device-resident call counter the launch reads and advances, unless ``counter_value`` overrides it for this call."""
+    device-resident call counter the launch reads and advances, unless ``counter_value`` overrides it for this call.  With
+    ``affine_cfg`` (an ``nv.AugAffineConfig``) and ``affine`` (fp32 [B, 16], WRITTEN; both or neither) dua_aug_draw_affine: the
+    same bits in ``params`` plus one row of the matrix, the half-angle tangents, the zoom, the event bits and the pad value per
+    sample; returns ``(params, affine)``."""
     nvol = _aug_table(table)
     _i32c(ids, "volume_ids"); _i32c(params, "params"); _i32c(status, "status")
     assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1, "counter: int64 [1] device tensor"
     B = ids.numel()
     assert ids.dim() == 1 and B >= 1 and tuple(params.shape) == (B, nv.AUG_PARAM_WORDS) and status.numel() == 1
-    assert all(t.device == table.device for t in (ids, params, status, counter)), "every tensor on the volumes' device"
+    assert (affine_cfg is None) == (affine is None), "affine_cfg and affine: both or neither"
+    tensors = [ids, params, status, counter]
+    if affine is not None:
+        _aug_affine_rows(affine, B)
+        assert isinstance(affine_cfg, nv.AugAffineConfig)
+        tensors.append(affine)
+    assert all(t.device == table.device for t in tensors), "every tensor on the volumes' device"
     assert isinstance(cfg, nv.AugConfig)
     use = counter_value is not None
-    nv.check(nv.lib().dua_aug_draw(nv.ptr(table), nvol, nv.ptr(ids), B, C.byref(cfg), int(seed) & (2 ** 64 - 1), nv.ptr(counter),
-                                   int(use), (int(counter_value) & (2 ** 64 - 1)) if use else 0, nv.ptr(params), nv.ptr(status),
-                                   nv.stream_ptr()), "dua_aug_draw")
-    return params
+    if affine is None:
+        name, cfgs, outs = "dua_aug_draw", (C.byref(cfg),), (nv.ptr(params),)
+    else:
+        name, cfgs, outs = "dua_aug_draw_affine", (C.byref(cfg), C.byref(affine_cfg)), (nv.ptr(params), nv.ptr(affine))
+    nv.check(getattr(nv.lib(), name)(nv.ptr(table), nvol, nv.ptr(ids), B, *cfgs, int(seed) & (2 ** 64 - 1), nv.ptr(counter), int(use),
+                                     (int(counter_value) & (2 ** 64 - 1)) if use else 0, *outs, nv.ptr(status), nv.stream_ptr()), name)
+    return params if affine is None else (params, affine)
 
 
-def aug_apply(table, params, roi, class_ids, images, labels, status):
+def aug_apply(table, params, roi, class_ids, images, labels, status, affine=None, centroids=None, smoothing=None):
     """dua_aug_apply: images fp32 [B, 1, *roi] and labels fp32 [B, C, *roi] (both WRITTEN) from ``params`` (int32 [B, 8]);
-    ``class_ids``: uint8 [C] device tensor."""
+    ``class_ids``: uint8 [C] device tensor.  With ``centroids`` (fp32 [volumes, num_classes, 3]) and ``smoothing`` (an
+    ``nv.AugSmoothing``; both or neither) the label channels are the centroid-distance smoothed ones (dua_aug_apply_smoothed);
+    with ``affine`` (fp32 [B, 16]) the patch is resampled through its rows, trilinear image, nearest label
+    (dua_aug_apply_affine, smoothed or not)."""
     nvol = _aug_table(table)
     _i32c(params, "params"); _i32c(status, "status"); _u8c(class_ids, "class_ids")
     _f32c(images, "images"); _f32c(labels, "labels")
     B, Cn = params.shape[0], class_ids.numel()
     assert params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS and B >= 1 and status.numel() == 1
     assert 1 <= Cn <= nv.AUG_MAX_CLASSES, f"1 .. {nv.AUG_MAX_CLASSES} classes"
+    assert (centroids is None) == (smoothing is None), "centroids and smoothing: both or neither"
+    tensors = [params, status, class_ids, images, labels]
+    if affine is not None:
+        _aug_affine_rows(affine, B)
+        tensors.append(affine)
+    K = 0
+    if smoothing is not None:
+        _f32c(centroids, "centroids")
+        assert centroids.dim() == 3 and centroids.shape[0] == nvol and centroids.shape[2] == 3, "centroids: [volumes, num_classes, 3]"
+        assert isinstance(smoothing, nv.AugSmoothing)
+        tensors.append(centroids)
+        K = centroids.shape[1]
     rd, rh, rw = (int(r) for r in roi)
     assert tuple(images.shape) == (B, 1, rd, rh, rw), f"images: [{B}, 1, {rd}, {rh}, {rw}], got {tuple(images.shape)}"
     assert tuple(labels.shape) == (B, Cn, rd, rh, rw), f"labels: [{B}, {Cn}, {rd}, {rh}, {rw}], got {tuple(labels.shape)}"
-    assert all(t.device == table.device for t in (params, status, class_ids, images, labels)), "every tensor on the volumes' device"
-    nv.check(nv.lib().dua_aug_apply(nv.ptr(table), nvol, nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
-                                    nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply")
+    assert all(t.device == table.device for t in tensors), "every tensor on the volumes' device"
+    smooth = (nv.ptr(centroids), K, C.byref(smoothing) if smoothing is not None else None)
+    if affine is not None:
+        name, head = "dua_aug_apply_affine", (*smooth, nv.ptr(params), nv.ptr(affine))
+    elif smoothing is not None:
+        name, head = "dua_aug_apply_smoothed", (*smooth, nv.ptr(params))
+    else:
+        name, head = "dua_aug_apply", (nv.ptr(params),)
+    nv.check(getattr(nv.lib(), name)(nv.ptr(table), nvol, *head, B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images), nv.ptr(labels),
+                                     nv.ptr(status), nv.stream_ptr()), name)
     return images, labels
 
 
@@ -1863,84 +1902,6 @@ def aug_class_centroids(label, num_classes):
         nv.check(nv.lib().dua_aug_class_centroids(nv.ptr(label), D, H, W, K, nv.ptr(sums), nv.ptr(centroids), nv.stream_ptr()),
                  "dua_aug_class_centroids")
     return sums, centroids
-
-
-def aug_apply_smoothed(table, centroids, smoothing, params, roi, class_ids, images, labels, status):
-    """dua_aug_apply_smoothed: ``aug_apply`` with centroid-distance smoothed label channels; ``centroids`` fp32
-    [volumes, num_classes, 3], ``smoothing`` an ``nv.AugSmoothing``."""
-    nvol = _aug_table(table)
-    _i32c(params, "params"); _i32c(status, "status"); _u8c(class_ids, "class_ids")
-    _f32c(images, "images"); _f32c(labels, "labels"); _f32c(centroids, "centroids")
-    B, Cn = params.shape[0], class_ids.numel()
-    assert params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS and B >= 1 and status.numel() == 1
-    assert 1 <= Cn <= nv.AUG_MAX_CLASSES, f"1 .. {nv.AUG_MAX_CLASSES} classes"
-    assert centroids.dim() == 3 and centroids.shape[0] == nvol and centroids.shape[2] == 3, "centroids: [volumes, num_classes, 3]"
-    assert isinstance(smoothing, nv.AugSmoothing)
-    rd, rh, rw = (int(r) for r in roi)
-    assert tuple(images.shape) == (B, 1, rd, rh, rw), f"images: [{B}, 1, {rd}, {rh}, {rw}], got {tuple(images.shape)}"
-    assert tuple(labels.shape) == (B, Cn, rd, rh, rw), f"labels: [{B}, {Cn}, {rd}, {rh}, {rw}], got {tuple(labels.shape)}"
-    assert all(t.device == table.device for t in (params, status, class_ids, images, labels, centroids)), \
-        "every tensor on the volumes' device"
-    nv.check(nv.lib().dua_aug_apply_smoothed(nv.ptr(table), nvol, nv.ptr(centroids), centroids.shape[1], C.byref(smoothing),
-                                             nv.ptr(params), B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images),
-                                             nv.ptr(labels), nv.ptr(status), nv.stream_ptr()), "dua_aug_apply_smoothed")
-    return images, labels
-
-
-# ---- random rotation and zoom of the training input (csrc/augment.hip; include/dua_hip.h "random rotation and zoom") ----
-
-def _aug_affine_rows(affine, B):
-    _f32c(affine, "affine")
-    assert tuple(affine.shape) == (B, nv.AUG_AFFINE_WORDS), f"affine: fp32 [{B}, {nv.AUG_AFFINE_WORDS}], got {tuple(affine.shape)}"
-
-
-def aug_draw_affine(table, ids, cfg, affine_cfg, seed, counter, params, affine, status, counter_value=None):
-    """dua_aug_draw_affine: ``aug_draw`` (the same bits in ``params``) plus one row of ``affine`` (fp32 [B, 16]: the matrix, the
-    half-angle tangents, the zoom, the event bits and the pad value) per sample; ``affine_cfg`` an ``nv.AugAffineConfig``."""
-    nvol = _aug_table(table)
-    _i32c(ids, "volume_ids"); _i32c(params, "params"); _i32c(status, "status")
-    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1, "counter: int64 [1] device tensor"
-    B = ids.numel()
-    assert ids.dim() == 1 and B >= 1 and tuple(params.shape) == (B, nv.AUG_PARAM_WORDS) and status.numel() == 1
-    _aug_affine_rows(affine, B)
-    assert all(t.device == table.device for t in (ids, params, affine, status, counter)), "every tensor on the volumes' device"
-    assert isinstance(cfg, nv.AugConfig) and isinstance(affine_cfg, nv.AugAffineConfig)
-    use = counter_value is not None
-    nv.check(nv.lib().dua_aug_draw_affine(nv.ptr(table), nvol, nv.ptr(ids), B, C.byref(cfg), C.byref(affine_cfg),
-                                          int(seed) & (2 ** 64 - 1), nv.ptr(counter), int(use),
-                                          (int(counter_value) & (2 ** 64 - 1)) if use else 0, nv.ptr(params), nv.ptr(affine),
-                                          nv.ptr(status), nv.stream_ptr()), "dua_aug_draw_affine")
-    return params, affine
-
-
-def aug_apply_affine(table, params, affine, roi, class_ids, images, labels, status, centroids=None, smoothing=None):
-    """dua_aug_apply_affine: ``aug_apply`` resampled through the rows of ``affine`` (trilinear image, nearest label); with
-    ``centroids`` and ``smoothing`` the label channels are smoothed as in ``aug_apply_smoothed``."""
-    nvol = _aug_table(table)
-    _i32c(params, "params"); _i32c(status, "status"); _u8c(class_ids, "class_ids")
-    _f32c(images, "images"); _f32c(labels, "labels")
-    B, Cn = params.shape[0], class_ids.numel()
-    assert params.dim() == 2 and params.shape[1] == nv.AUG_PARAM_WORDS and B >= 1 and status.numel() == 1
-    _aug_affine_rows(affine, B)
-    assert 1 <= Cn <= nv.AUG_MAX_CLASSES, f"1 .. {nv.AUG_MAX_CLASSES} classes"
-    assert (centroids is None) == (smoothing is None), "centroids and smoothing: both or neither"
-    tensors = [params, affine, status, class_ids, images, labels]
-    K = 0
-    if smoothing is not None:
-        _f32c(centroids, "centroids")
-        assert centroids.dim() == 3 and centroids.shape[0] == nvol and centroids.shape[2] == 3, "centroids: [volumes, num_classes, 3]"
-        assert isinstance(smoothing, nv.AugSmoothing)
-        tensors.append(centroids)
-        K = centroids.shape[1]
-    rd, rh, rw = (int(r) for r in roi)
-    assert tuple(images.shape) == (B, 1, rd, rh, rw), f"images: [{B}, 1, {rd}, {rh}, {rw}], got {tuple(images.shape)}"
-    assert tuple(labels.shape) == (B, Cn, rd, rh, rw), f"labels: [{B}, {Cn}, {rd}, {rh}, {rw}], got {tuple(labels.shape)}"
-    assert all(t.device == table.device for t in tensors), "every tensor on the volumes' device"
-    nv.check(nv.lib().dua_aug_apply_affine(nv.ptr(table), nvol, nv.ptr(centroids), K,
-                                           C.byref(smoothing) if smoothing is not None else None, nv.ptr(params), nv.ptr(affine),
-                                           B, rd, rh, rw, nv.ptr(class_ids), Cn, nv.ptr(images), nv.ptr(labels), nv.ptr(status),
-                                           nv.stream_ptr()), "dua_aug_apply_affine")
-    return images, labels
 
 
 # ---- evaluation: streamed sliding-window blend (csrc/blend.hip; engine.py:173-180, metric.py:37-49) ----

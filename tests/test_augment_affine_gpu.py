@@ -123,7 +123,7 @@ def test_smoothing_composed_with_the_resampling_stays_within_its_bound(apply_cas
     tests/label_smoothing_ref.py derives for the plain apply holds as it stands."""
     aug = _aug()
     K, alpha, eps = 16, 0.3, 1e-6
-    for name in ("cube16", "volume_of_roi_size"):
+    for name in ("cube16", "narrow_4_byte_stores", "volume_of_roi_size"):
         case, volumes, ref_vols, want = apply_cases[name]
         dev_vols, _ = _pairs(volumes, num_classes=K)
         ids = list(case["class_ids"])
