@@ -177,6 +177,14 @@ class AugAffineConfig(C.Structure):
                 ("zoom_span", C.c_float), ("pad_value", C.c_float), ("reserved", C.c_int)]
 
 
+class AugIntensityConfig(C.Structure):
+    """dua_aug_intensity_config."""
+    _fields_ = [(n, C.c_float) for n in ("noise_prob", "noise_std_min", "noise_std_span", "blur_prob", "blur_sigma_min",
+                                         "blur_sigma_span", "brightness_prob", "brightness_min", "brightness_span",
+                                         "contrast_prob", "contrast_min", "contrast_span", "gamma_prob", "gamma_min",
+                                         "gamma_span_below", "gamma_span_above", "gamma_invert_prob")] + [("reserved", C.c_int)]
+
+
 class PrepGeom(C.Structure):
     """dua_prep_geom."""
     _fields_ = [("n_in", C.c_int * 3), ("n_out", C.c_int * 3), ("stride", C.c_long * 3), ("base", C.c_long),
@@ -189,6 +197,12 @@ CC_MAX_CAP = 65536       # DUA_CC_MAX_CAP
 SUF_MAX_RUNS = 16        # DUA_SUF_MAX_RUNS
 AUG_VOLUME, AUG_START_D, AUG_START_H, AUG_START_W, AUG_FLIP, AUG_K, AUG_SCALE, AUG_SHIFT = range(8)
 AUG_AFFINE_M, AUG_AFFINE_T, AUG_AFFINE_ZOOM, AUG_AFFINE_EVENTS, AUG_AFFINE_PAD, AUG_AFFINE_WORDS = 0, 9, 12, 13, 14, 16
+# dua_aug_intensity_*: event bits, row columns, row length, largest blur radius
+(AUG_INTENSITY_NOISE, AUG_INTENSITY_BLUR, AUG_INTENSITY_BRIGHTNESS, AUG_INTENSITY_CONTRAST, AUG_INTENSITY_GAMMA,
+ AUG_INTENSITY_INVERT) = (1 << i for i in range(6))
+(AUG_INTENSITY_EVENTS, AUG_INTENSITY_STD, AUG_INTENSITY_SIGMA, AUG_INTENSITY_BRIGHT, AUG_INTENSITY_CONTRAST_F, AUG_INTENSITY_GAMMA_V,
+ AUG_INTENSITY_CALL_LO, AUG_INTENSITY_CALL_HI, AUG_INTENSITY_SAMPLE) = range(9)
+AUG_INTENSITY_WORDS, AUG_INTENSITY_MAX_RADIUS = 16, 4
 
 _P = C.c_void_p
 ABI_VERSION = 8          # DUA_ABI_VERSION of include/dua_hip.h this binding was written against
@@ -306,6 +320,9 @@ _SIGS = {
                                       C.c_int, C.c_ulonglong, _P, _P, _P, _P]),
     "dua_aug_apply_affine": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _P, C.c_int, _P, _P, _P, _P]),
+    "dua_aug_intensity_scratch_bytes": (C.c_long, [C.c_int] * 4),
+    "dua_aug_intensity_draw": (C.c_int, [C.POINTER(AugIntensityConfig), C.c_int, C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P]),
+    "dua_aug_intensity_apply": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _P, _P, C.c_long, _P]),
     "dua_blend_accumulate": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P] + [C.c_int] * 4 + [_P, _P]),
     "dua_blend_finish": (C.c_int, [_P] + [C.c_int] * 5 + [_P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "dua_blend_accumulate_weighted": (C.c_int, [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P] +

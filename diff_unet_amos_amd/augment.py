@@ -30,6 +30,17 @@ RandAffined / RandZoomd apply them by default), come from the same two launches 
     images, labels = producer.next(ids)          # trilinear image, nearest label, pad_value outside the volume
 
 include/dua_hip.h ("random rotation and zoom") fixes them; tests/augment_affine_ref.py restates that text.
+
+The intensity half of that recipe (nnU-Net's defaults: Gaussian noise, Gaussian blur, multiplicative brightness, contrast, gamma
+with and without inversion) is a stage of its own after ``apply``, on the images alone (csrc/augment_intensity.hip: one draw
+launch, one tiled noise-and-blur pass, four pointwise passes separated by deterministic reductions)::
+
+    aug = IntensityAugmenter(roi=(96, 96, 96), seed=7)
+    producer = DeviceBatchProducer(volumes, intensity=aug)
+    images, labels = producer.next(ids)          # labels untouched; producer.intensity_rows holds the rows, for logging
+    images = aug(images)                         # or on any fp32 [B, 1, *roi] batch, without a producer
+
+include/dua_hip.h ("training input: intensity augmentation") fixes it; tests/augment_intensity_ref.py restates that text.
 """
 from __future__ import annotations
 
@@ -72,6 +83,127 @@ def split_affine(affine):
     events = affine[:, nv.AUG_AFFINE_EVENTS:nv.AUG_AFFINE_EVENTS + 1].contiguous().view(torch.int32)[:, 0]
     return (affine[:, :nv.AUG_AFFINE_T].reshape(-1, 3, 3), affine[:, nv.AUG_AFFINE_T:nv.AUG_AFFINE_ZOOM],
             affine[:, nv.AUG_AFFINE_ZOOM], events, affine[:, nv.AUG_AFFINE_PAD])
+
+
+INTENSITY_COLUMNS = ("events", "noise_std", "blur_sigma", "brightness", "contrast", "gamma", "call", "sample")
+INTENSITY_EVENTS = ("noise", "blur", "brightness", "contrast", "gamma", "invert")
+
+
+def split_intensity(rows):
+    """``rows`` (fp32 [B, 16]) as a dict on the host: ``events`` int32 [B] (bit i = ``INTENSITY_EVENTS[i]``), ``noise_std``,
+    ``blur_sigma``, ``brightness``, ``contrast``, ``gamma`` fp32 [B], ``call`` (a list of Python integers: the 64-bit call counter
+    the row was drawn with) and ``sample`` int32 [B] (its index in that call).  Reads the rows: a host synchronisation."""
+    assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == nv.AUG_INTENSITY_WORDS
+    r = rows.detach().cpu().contiguous()
+    bits = r.view(torch.int32)
+    lo, hi = bits[:, nv.AUG_INTENSITY_CALL_LO].tolist(), bits[:, nv.AUG_INTENSITY_CALL_HI].tolist()
+    return {"events": bits[:, nv.AUG_INTENSITY_EVENTS].clone(), "noise_std": r[:, nv.AUG_INTENSITY_STD].clone(),
+            "blur_sigma": r[:, nv.AUG_INTENSITY_SIGMA].clone(), "brightness": r[:, nv.AUG_INTENSITY_BRIGHT].clone(),
+            "contrast": r[:, nv.AUG_INTENSITY_CONTRAST_F].clone(), "gamma": r[:, nv.AUG_INTENSITY_GAMMA_V].clone(),
+            "call": [((h & 0xFFFFFFFF) << 32) | (l & 0xFFFFFFFF) for l, h in zip(lo, hi)],
+            "sample": bits[:, nv.AUG_INTENSITY_SAMPLE].clone()}
+
+
+class IntensityAugmenter:
+    """Gaussian noise, Gaussian blur, brightness, contrast and gamma (with and without inversion) on ``images`` fp32
+    [B, 1, *roi], each with its own probability per sample, in that order; the defaults are nnU-Net's.  ``draw(B)`` returns the
+    decisions as ``rows`` (fp32 [B, 16] on the device; ``split_intensity`` names the columns), ``apply(images, rows)`` the
+    transformed images, ``aug(images)`` both.  Deterministic for a given (seed, call counter): the call counter is a 64-bit
+    device word the draw launch itself advances, so a captured call moves on with every replay, and a logged ``rows`` tensor
+    with the seed replays its batch bit for bit, the noise included.  No host read, no allocation inside ``apply`` once the
+    scratch for a batch size exists (call ``apply`` once before capturing it).
+
+    noise: x += N(0, std^2), std from ``noise_std``; blur: ``scipy.ndimage.gaussian_filter(x, sigma, mode="reflect")`` with
+    sigma from ``blur_sigma`` (at most 1: a radius of 4 voxels); brightness: x *= f; contrast: x = clamp((x - mean) f + mean,
+    min, max); gamma: batchgenerators' gamma transform with ``retain_stats``, the exponent from the part of ``gamma_range``
+    below 1 half of the time, on -x with probability ``gamma_invert_prob``.  Statistics are per patch."""
+
+    def __init__(self, roi, seed=0, noise_prob=0.1, noise_std=(0.0, 0.1), blur_prob=0.2, blur_sigma=(0.5, 1.0), brightness_prob=0.15,
+                 brightness_range=(0.75, 1.25), contrast_prob=0.15, contrast_range=(0.75, 1.25), gamma_prob=0.3,
+                 gamma_range=(0.7, 1.5), gamma_invert_prob=0.25, device="cuda"):
+        try:
+            roi = tuple(int(r) for r in roi)
+        except (TypeError, ValueError):
+            raise ValueError(f"IntensityAugmenter: roi is three extents, got {roi}") from None
+        if len(roi) != 3 or min(roi) < 4 or roi[0] * roi[1] * roi[2] >= 2 ** 31:
+            raise ValueError(f"IntensityAugmenter: roi is three extents, each at least 4, fewer than 2^31 voxels, got {roi}")
+        probs = dict(noise_prob=noise_prob, blur_prob=blur_prob, brightness_prob=brightness_prob, contrast_prob=contrast_prob,
+                     gamma_prob=gamma_prob, gamma_invert_prob=gamma_invert_prob)
+        for name, p in probs.items():
+            try:
+                ok = 0.0 <= float(p) <= 1.0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"IntensityAugmenter: {name} is a probability, got {p}")
+        ranges = dict(noise_std=noise_std, blur_sigma=blur_sigma, brightness_range=brightness_range, contrast_range=contrast_range,
+                      gamma_range=gamma_range)
+        for name, r in ranges.items():
+            try:
+                r = tuple(float(v) for v in r)
+            except (TypeError, ValueError):
+                r = ()
+            if len(r) != 2 or not (math.isfinite(r[0]) and math.isfinite(r[1]) and r[0] <= r[1] and abs(r[1]) <= 3.0e38):
+                raise ValueError(f"IntensityAugmenter: {name} is (min, max) with min <= max, finite, got {ranges[name]}")
+            ranges[name] = r
+        if ranges["noise_std"][0] < 0:
+            raise ValueError(f"IntensityAugmenter: noise_std is not negative, got {noise_std}")
+        if not 0 < ranges["blur_sigma"][0] or ranges["blur_sigma"][1] > 1.0:
+            raise ValueError(f"IntensityAugmenter: blur_sigma lies in (0, 1] (a radius of at most {nv.AUG_INTENSITY_MAX_RADIUS} voxels), "
+                             f"got {blur_sigma}")
+        for name in ("brightness_range", "contrast_range", "gamma_range"):
+            if not ranges[name][0] > 0:
+                raise ValueError(f"IntensityAugmenter: {name} is positive, got {ranges[name]}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"IntensityAugmenter: a GPU device, not {device}")
+        self.roi, self.seed, self.device = roi, int(seed), device
+        self.settings = dict(probs, **ranges)
+        g0, g1 = ranges["gamma_range"]
+        span = lambda r: r[1] - r[0]                          # in fp64, rounded to fp32 once by the structure
+        self.cfg = nv.AugIntensityConfig(
+            float(noise_prob), ranges["noise_std"][0], span(ranges["noise_std"]),
+            float(blur_prob), ranges["blur_sigma"][0], span(ranges["blur_sigma"]),
+            float(brightness_prob), ranges["brightness_range"][0], span(ranges["brightness_range"]),
+            float(contrast_prob), ranges["contrast_range"][0], span(ranges["contrast_range"]),
+            float(gamma_prob), g0, min(g1, 1.0) - g0, g1 - max(g0, 1.0), float(gamma_invert_prob), 0)
+        self._counter = self._scratch = None
+
+    def _state(self):
+        if self._counter is None:
+            self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._counter
+
+    @property
+    def counter(self):
+        """The call counter the next ``draw`` will use (reads the device word: a host synchronisation)."""
+        return int(self._state().item()) & (2 ** 64 - 1)
+
+    def draw(self, B, counter=None):
+        """The decisions of one batch as ``rows`` (fp32 [B, 16] on the device).  ``counter=None`` uses and advances the
+        augmenter's device-resident call counter; an integer is used for this call only."""
+        B = int(B)
+        if B < 1:
+            raise ValueError(f"IntensityAugmenter.draw: at least one sample, got B = {B}")
+        rows = torch.empty((B, nv.AUG_INTENSITY_WORDS), dtype=torch.float32, device=self.device)
+        return ops.aug_intensity_draw(self.cfg, self.seed, self._state(), rows, counter_value=counter)
+
+    def apply(self, images, rows, out=None):
+        """``images`` (fp32 [B, 1, *roi]) through ``rows``; ``out`` may be ``images`` (in place), default a new tensor."""
+        if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.float32 and images.dim() == 5 and
+                tuple(images.shape[1:]) == (1,) + self.roi):
+            raise ValueError(f"IntensityAugmenter.apply: images is a float32 device tensor [B, 1, {self.roi[0]}, {self.roi[1]}, "
+                             f"{self.roi[2]}]")
+        B = images.shape[0]
+        need = ops.aug_intensity_scratch_bytes(B, self.roi)
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != images.device:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=images.device)
+        if out is None:
+            out = torch.empty_like(images)
+        return ops.aug_intensity_apply(images, rows, self.seed, out, self._scratch)
+
+    def __call__(self, images, out=None):
+        return self.apply(images, self.draw(images.shape[0]), out=out)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -211,11 +343,15 @@ class DeviceBatchProducer:
     that the matrix needs no sine or cosine and is reproducible bit for bit: the angle is therefore not uniform, its density
     rises by tan(angle / 2)^2 towards the ends of the range (7 % at +-30 degrees).  Then ``draw`` returns ``(params, affine)``
     (``split_affine`` names the columns of the second), ``apply`` takes both, and a logged pair replays its batch.  With both
-    probabilities 0 (the default) nothing changes: the same launches, the same objects, the same bits."""
+    probabilities 0 (the default) nothing changes: the same launches, the same objects, the same bits.
+
+    ``intensity`` (an ``IntensityAugmenter`` of the producer's roi and device) makes ``next`` run it, in place, on the images
+    ``apply`` wrote; the rows of that call stay in ``producer.intensity_rows`` for logging.  ``draw`` and ``apply`` of the producer
+    do not change, and ``None`` (the default) changes nothing."""
 
     def __init__(self, volumes, roi=(96, 96, 96), class_ids=range(16), pos=1, neg=1, flip_prob=0.1, rot90_prob=0.1, max_k=3,
                  scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0, smoothing=None, rotate_prob=0.0,
-                 rotate_range=(0.0, 0.0, 0.0), zoom_prob=0.0, zoom_range=(1.0, 1.0), pad_value=0.0):
+                 rotate_range=(0.0, 0.0, 0.0), zoom_prob=0.0, zoom_range=(1.0, 1.0), pad_value=0.0, intensity=None):
         volumes = list(volumes)
         if not volumes or not all(isinstance(v, DeviceVolume) for v in volumes):
             raise ValueError("DeviceBatchProducer: a non-empty list of DeviceVolume")
@@ -278,6 +414,14 @@ class DeviceBatchProducer:
             if max(class_ids) >= volumes[0].num_classes:
                 raise ValueError(f"DeviceBatchProducer: class id {max(class_ids)} has no centroid (num_classes = "
                                  f"{volumes[0].num_classes})")
+        if intensity is not None:
+            if not isinstance(intensity, IntensityAugmenter):
+                raise ValueError("DeviceBatchProducer: intensity is an IntensityAugmenter or None")
+            same_device = intensity.device.type == self.device.type and intensity.device.index in (None, self.device.index)
+            if intensity.roi != roi or not same_device:
+                raise ValueError(f"DeviceBatchProducer: intensity was built for roi {intensity.roi} on {intensity.device}, the "
+                                 f"producer has roi {roi} on {self.device}")
+        self.intensity, self.intensity_rows = intensity, None
         self.smoothing = smoothing
         self.volumes, self.roi, self.class_ids, self.seed = volumes, roi, tuple(class_ids), int(seed)
         self.cfg = nv.AugConfig((C.c_int * 3)(*roi), int(max_k), float(pos) / (float(pos) + float(neg)), float(flip_prob),
@@ -351,4 +495,8 @@ class DeviceBatchProducer:
     def next(self, volume_ids, out_images=None, out_labels=None):
         drawn = self.draw(volume_ids)
         params, affine = drawn if self.affine else (drawn, None)
-        return self.apply(params, out_images, out_labels, affine=affine)
+        images, labels = self.apply(params, out_images, out_labels, affine=affine)
+        if self.intensity is not None:
+            self.intensity_rows = self.intensity.draw(images.shape[0])
+            self.intensity.apply(images, self.intensity_rows, out=images)
+        return images, labels

@@ -1904,6 +1904,51 @@ def aug_class_centroids(label, num_classes):
     return sums, centroids
 
 
+# ---- intensity augmentation of the training input (csrc/augment_intensity.hip) ----
+
+def aug_intensity_scratch_bytes(B, roi):
+    """dua_aug_intensity_scratch_bytes: what ``aug_intensity_apply`` needs as scratch for ``B`` patches of ``roi``."""
+    rd, rh, rw = (int(r) for r in roi)
+    n = nv.lib().dua_aug_intensity_scratch_bytes(int(B), rd, rh, rw)
+    if n < 0:
+        raise ValueError(f"aug_intensity_scratch_bytes: B in 1 .. 65535 and three extents of at least 4, got B = {B}, roi = {roi}")
+    return n
+
+
+def aug_intensity_draw(cfg, seed, counter, rows, counter_value=None):
+    """dua_aug_intensity_draw: one row of ``rows`` (fp32 [B, 16], WRITTEN) per sample; ``counter`` (int64 [1]) is the
+    device-resident call counter the launch reads and advances, unless ``counter_value`` overrides it for this call."""
+    _f32c(rows, "rows")
+    assert rows.dim() == 2 and rows.shape[1] == nv.AUG_INTENSITY_WORDS and rows.shape[0] >= 1, f"rows: fp32 [B, {nv.AUG_INTENSITY_WORDS}]"
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1 and counter.device == rows.device, \
+        "counter: int64 [1] tensor on the rows' device"
+    assert isinstance(cfg, nv.AugIntensityConfig)
+    use = counter_value is not None
+    with torch.cuda.device(rows.device):
+        nv.check(nv.lib().dua_aug_intensity_draw(C.byref(cfg), rows.shape[0], int(seed) & (2 ** 64 - 1), nv.ptr(counter), int(use),
+                                                 (int(counter_value) & (2 ** 64 - 1)) if use else 0, nv.ptr(rows), nv.stream_ptr()),
+                 "dua_aug_intensity_draw")
+    return rows
+
+
+def aug_intensity_apply(images, rows, seed, out, scratch):
+    """dua_aug_intensity_apply: ``out`` (fp32 [B, 1, *roi], WRITTEN; may be ``images``) = ``images`` through ``rows`` (fp32
+    [B, 16]); ``scratch``: a uint8 device tensor of at least ``aug_intensity_scratch_bytes(B, roi)`` bytes."""
+    _f32c(images, "images"); _f32c(out, "out"); _f32c(rows, "rows"); _u8c(scratch, "scratch")
+    assert images.dim() == 5 and images.shape[1] == 1 and out.shape == images.shape, "images, out: fp32 [B, 1, D, H, W] of one shape"
+    B = images.shape[0]
+    assert tuple(rows.shape) == (B, nv.AUG_INTENSITY_WORDS), f"rows: fp32 [{B}, {nv.AUG_INTENSITY_WORDS}], got {tuple(rows.shape)}"
+    assert all(t.device == images.device for t in (out, rows, scratch)), "every tensor on the images' device"
+    assert out is images or out.data_ptr() == images.data_ptr() or \
+        out.data_ptr() + out.numel() * 4 <= images.data_ptr() or images.data_ptr() + images.numel() * 4 <= out.data_ptr(), \
+        "out: images itself or a tensor that does not overlap it"
+    rd, rh, rw = (int(r) for r in images.shape[2:])
+    with torch.cuda.device(images.device):
+        nv.check(nv.lib().dua_aug_intensity_apply(nv.ptr(images), nv.ptr(rows), B, rd, rh, rw, int(seed) & (2 ** 64 - 1), nv.ptr(out),
+                                                  nv.ptr(scratch), scratch.numel(), nv.stream_ptr()), "dua_aug_intensity_apply")
+    return out
+
+
 # ---- evaluation: streamed sliding-window blend (csrc/blend.hip; engine.py:173-180, metric.py:37-49) ----
 
 def _flip_mask(flip):

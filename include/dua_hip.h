@@ -1117,6 +1117,98 @@ int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* cen
                          int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
                          int* status, void* stream);
 
+/* ---- training input: intensity augmentation ---------------------------------------------------------------------------
+ * The intensity half of a CT augmentation recipe (nnU-Net's default pipeline: Gaussian noise, Gaussian blur, multiplicative
+ * brightness, contrast, gamma with and without inversion; the reference has none of them), as a stage after dua_aug_apply*:
+ * dua_aug_intensity_draw writes one row per sample, dua_aug_intensity_apply transforms images fp32 [B][roi_d][roi_h][roi_w]
+ * (one channel) through those rows.  No host read, capturable.  The semantics are fixed HERE (nnU-Net / batchgenerators are no
+ * dependency).
+ *
+ * dua_aug_intensity_draw.  Random words: Philox4x32-10, key = (seed lo, seed hi), counter = (call lo, call hi, b,
+ * 0x40000000 + j) for block j = 0, 1, 2 of sample b; the noise of dua_aug_intensity_apply takes counter = (call lo, call hi, b,
+ * 0x80000000 + q) for voxels 4q .. 4q + 3 of the patch in linear order.  The two tags keep these words apart from each other
+ * and from dua_aug_draw's blocks (.., b, j) when both are given one seed.  u(x) and the event rule u(x) < p are dua_aug_draw's.
+ *   0.0 noise event        0.1 noise std      0.2 blur event       0.3 blur sigma
+ *   1.0 brightness event   1.1 brightness     1.2 contrast event   1.3 contrast
+ *   2.0 gamma event        2.1 gamma branch   2.2 gamma value      2.3 invert event
+ * (every word keeps its role whether or not the event before it happened).  A value in (min, max) is
+ * fadd(fmul(span, u), min) with span = fp32(max - min) rounded once by the host, no contraction.  Gamma is drawn from
+ * (gamma_min, min(gamma_max, 1)) [span gamma_span_below] iff u(2.1) < 0.5 and gamma_min < 1, otherwise from
+ * (max(gamma_min, 1), gamma_max) [span gamma_span_above, taken as it stands].  Invert happens iff there is a gamma event and
+ * u(2.3) < gamma_invert_prob.  Without its event a value is neutral: std 0, sigma 0, factors 1, gamma 1.
+ * The call counter is dua_aug_draw's: use_counter == 0 reads *counter in every sample and advances it by one (ONE workgroup, a
+ * wave per sample, one lane after a barrier), so a captured launch moves on with every replay; otherwise counter_value is used.
+ *
+ * rows (WRITTEN, [B][DUA_AUG_INTENSITY_WORDS] 32-bit words, the bits of an fp32 unless said otherwise): _EVENTS = int32, bits
+ * DUA_AUG_INTENSITY_NOISE .. _INVERT; _STD, _SIGMA, _BRIGHT, _CONTRAST_F, _GAMMA_V = the five values; _CALL_LO, _CALL_HI, _SAMPLE
+ * = the call counter and b as int32 bits, so that a logged row carries its noise key and replays its sample, noise included,
+ * from dua_aug_intensity_apply and the seed alone; words 9 - 15 = 0.
+ *
+ * dua_aug_intensity_apply, for one sample: x = its patch of n = roi_d roi_h roi_w voxels; every fp32 operation below is rounded
+ * separately (no contraction); a stage whose event bit is clear is skipped exactly, so a row with no bit set gives out the bits
+ * of images.  In this order:
+ *  1. noise: x_i = x_i + std z_i.  Normals pairwise from the words (a, b) = (word 0, word 1) and (word 2, word 3) of the voxel's
+ *     block: u1 = ((a >> 8) + 1) 2^-24, u2 = (b >> 8) 2^-24, r = sqrt(-2 ln u1), z = (r cos 2 pi u2, r sin 2 pi u2); words 0, 1
+ *     give voxels 4q and 4q + 1, words 2, 3 voxels 4q + 2 and 4q + 3.  (logf, sqrtf, sincosf of fp32(2 pi) u2.)
+ *  2. blur: separable Gaussian along w, then h, then d.  R = floor(4 sigma + 0.5) (at most DUA_AUG_INTENSITY_MAX_RADIUS; a row
+ *     that asks for more gets that), taps exp(-i^2 / (2 sigma^2)), i = -R .. R, normalised by their sum, computed in fp64 from
+ *     the fp32 sigma and rounded to fp32 once; the boundary reflected as index -1 - j below and 2 n - 1 - j above
+ *     (scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=4.0)).  The blur reads the noisy patch everywhere, its
+ *     reflected halo included.
+ *  3. brightness: x = x f.
+ *  4. contrast: m, lo, hi = mean, minimum, maximum of x as it stands;  x = min(max(((x - m) f) + m, lo), hi).
+ *  5. gamma: if invert, x = -x.  m, s, lo, hi = mean, population standard deviation, minimum, maximum of x;  g = hi - lo;
+ *     y = (powf((x - lo) / (g + 1e-7f), gamma) g) + lo;  m', s' = mean and deviation of y;
+ *     x = (((y - m') / (s' + 1e-8f)) s) + m;  if invert, x = -x.  (batchgenerators' gamma with retain_stats.)
+ * Statistics: sum, sum of squares, minimum and maximum over the stored fp32 values, accumulated in fp64: one partial per
+ * workgroup, the partials combined in a fixed order, no floating-point atomic; mean = sum / n, deviation = sqrt(max(sum of
+ * squares / n - mean^2, 0)) in fp64, each statistic rounded to fp32 once.  The bits are the same from run to run.  A constant
+ * patch stays finite and comes out as the constant (x f after brightness).
+ *
+ * out may be images (in place).  scratch: dua_aug_intensity_scratch_bytes(B, roi) bytes, 16-byte aligned, contents irrelevant
+ * before and after; nothing is allocated by the call.  16-byte accesses when roi_w is a multiple of 4 and images and out are
+ * 16-byte aligned, 4-byte ones otherwise.  Values of a hand-built row are taken as they stand; a sigma that is not positive
+ * blurs with R = 0.
+ * Arguments (DUA_ERR_ARG before any launch): NULL pointers; roi extents below 4 (a reflection then needs a second step) or a
+ * patch of 2^31 voxels or more; B < 1, and B > 65535 where a grid dimension holds it (apply, scratch_bytes); probabilities
+ * outside [0, 1]; noise_std_min, the spans of std, sigma, brightness and contrast negative; blur_sigma_min, brightness_min,
+ * contrast_min, gamma_min or either end of a gamma branch not positive; floor(4 (blur_sigma_min + blur_sigma_span) + 0.5) above
+ * DUA_AUG_INTENSITY_MAX_RADIUS; anything not finite; scratch_bytes below the size asked for.
+ * dua_aug_intensity_scratch_bytes returns DUA_ERR_ARG (negative) for arguments dua_aug_intensity_apply would refuse. */
+#define DUA_AUG_INTENSITY_MAX_RADIUS 4
+#define DUA_AUG_INTENSITY_NOISE 1
+#define DUA_AUG_INTENSITY_BLUR 2
+#define DUA_AUG_INTENSITY_BRIGHTNESS 4
+#define DUA_AUG_INTENSITY_CONTRAST 8
+#define DUA_AUG_INTENSITY_GAMMA 16
+#define DUA_AUG_INTENSITY_INVERT 32
+#define DUA_AUG_INTENSITY_EVENTS 0
+#define DUA_AUG_INTENSITY_STD 1
+#define DUA_AUG_INTENSITY_SIGMA 2
+#define DUA_AUG_INTENSITY_BRIGHT 3
+#define DUA_AUG_INTENSITY_CONTRAST_F 4
+#define DUA_AUG_INTENSITY_GAMMA_V 5
+#define DUA_AUG_INTENSITY_CALL_LO 6
+#define DUA_AUG_INTENSITY_CALL_HI 7
+#define DUA_AUG_INTENSITY_SAMPLE 8
+#define DUA_AUG_INTENSITY_WORDS 16
+typedef struct {
+  float noise_prob, noise_std_min, noise_std_span;
+  float blur_prob, blur_sigma_min, blur_sigma_span;
+  float brightness_prob, brightness_min, brightness_span;
+  float contrast_prob, contrast_min, contrast_span;
+  float gamma_prob, gamma_min;
+  float gamma_span_below;          /* fp32(min(gamma_max, 1) - gamma_min) */
+  float gamma_span_above;          /* fp32(gamma_max - max(gamma_min, 1)) */
+  float gamma_invert_prob;
+  int reserved;
+} dua_aug_intensity_config;
+long dua_aug_intensity_scratch_bytes(int B, int roi_d, int roi_h, int roi_w);
+int dua_aug_intensity_draw(const dua_aug_intensity_config* cfg, int B, unsigned long long seed, unsigned long long* counter,
+                           int use_counter, unsigned long long counter_value, float* rows, void* stream);
+int dua_aug_intensity_apply(const float* images, const float* rows, int B, int roi_d, int roi_h, int roi_w,
+                            unsigned long long seed, float* out, void* scratch, long scratch_bytes, void* stream);
+
 /* ---- evaluation: streamed sliding-window blend ----------------------------------------------------------------------
  * The blend of monai.inferers.sliding_window_inference as Engine.infer calls it (engine.py:173-177; Tester, test.py:119-159:
  * constant importance map, sum / count), the binarisation that follows it (engine.py:179-180) and the three voxel counts of

@@ -29,6 +29,16 @@ every row (``dua_aug_apply_affine``), and the same batch from torch operators (`
 volume, bilinear for the image and nearest for a float copy of the label map made beforehand, then flips, rot90, the intensity
 operations and a stacked == for the one-hot), alternating rounds in one process.  All three write the same bytes, 4 (1 + C) per
 voxel; each time is printed beside the bandwidth that makes of them.
+
+    python tools/bench_augment.py --intensity [--rounds 21] [--repeats 200] [--with-step] [--out profiles/augment_bench.json]
+
+``--intensity`` times the intensity stage (``IntensityAugmenter``, csrc/augment_intensity.hip) at roi 96^3 for B = 2 and B = 4:
+``next`` of a producer without it, with every event forced on in every row, and with nnU-Net's default probabilities; the stage
+alone (``apply`` on fixed all-on rows, out of place); and the same contract from torch operators on the same rows, device and
+process (``randn`` for the noise, three ``conv3d`` over a symmetrically padded patch for the blur, reductions for the statistics,
+``pow``), alternating rounds.  The torch form's output is compared with the kernels' on rows without noise (torch's generator
+draws other normals).  ``--with-step`` relates the all-on cost to one config-4 training step.  With ``--out`` naming the file of
+the plain run, the result is stored under its key ``intensity``.
 """
 import argparse
 import ctypes
@@ -257,6 +267,98 @@ def affine_bench(args):
     return result
 
 
+def torch_intensity(images, rows, out):
+    """The contract of dua_aug_intensity_apply in whole-tensor torch operators, one sample at a time, from host rows
+    (events, std, sigma, brightness, contrast, gamma)."""
+    import torch.nn.functional as F
+    for b, (mask, std, sigma, bright, contrast, gamma) in enumerate(rows):
+        x = images[b:b + 1]
+        if mask & 1:
+            x = x + std * torch.randn_like(x)
+        if mask & 2:
+            R = int(4.0 * sigma + 0.5)
+            i = torch.arange(-R, R + 1, dtype=torch.float64)
+            k = torch.exp(-(i * i) / (2.0 * sigma * sigma))
+            k = (k / k.sum()).float().to(x.device)
+            for dim in (4, 3, 2):
+                n, shape = x.shape[dim], [1, 1, 1, 1, 1]
+                shape[dim] = 2 * R + 1
+                x = torch.cat([x.narrow(dim, 0, R).flip(dim), x, x.narrow(dim, n - R, R).flip(dim)], dim=dim)
+                x = F.conv3d(x, k.reshape(shape))
+        if mask & 4:
+            x = x * bright
+        if mask & 8:
+            m, lo, hi = x.mean(), x.min(), x.max()
+            x = torch.minimum(torch.maximum((x - m) * contrast + m, lo), hi)
+        if mask & 16:
+            if mask & 32:
+                x = -x
+            m, s, lo, hi = x.mean(), x.std(unbiased=False), x.min(), x.max()
+            y = torch.pow((x - lo) / ((hi - lo) + 1e-7), gamma) * (hi - lo) + lo
+            x = (y - y.mean()) / (y.std(unbiased=False) + 1e-8) * s + m
+            if mask & 32:
+                x = -x
+        out[b:b + 1] = x
+    return out
+
+
+def intensity_bench(args):
+    forced = dict(noise_prob=1.0, blur_prob=1.0, brightness_prob=1.0, contrast_prob=1.0, gamma_prob=1.0)
+    vols = volumes(args.volumes)
+    result = {"metric": "augment_intensity_time", "unit": "ms", "box": socket.gethostname(), "device": torch.cuda.get_device_name(0),
+              "roi": ROI, "classes": CLASSES, "repeats": args.repeats, "rounds": args.rounds, "batches": {}}
+    for B in (2, 4):
+        ids = torch.tensor([i % len(vols) for i in range(B)], dtype=torch.int32, device=DEV)
+        kw = dict(roi=ROI, class_ids=range(CLASSES), seed=1)
+        plain = augment.DeviceBatchProducer(vols, **kw)
+        all_on = augment.DeviceBatchProducer(vols, intensity=augment.IntensityAugmenter(ROI, seed=3, device=DEV, **forced), **kw)
+        default = augment.DeviceBatchProducer(vols, intensity=augment.IntensityAugmenter(ROI, seed=3, device=DEV), **kw)
+        out_images = torch.empty((B, 1) + ROI, device=DEV)
+        out_labels = torch.empty((B, CLASSES) + ROI, device=DEV)
+        images = plain.next(ids)[0].clone()
+        stage = augment.IntensityAugmenter(ROI, seed=3, device=DEV, **forced)
+        rows = stage.draw(B)
+        stage_out, torch_out = torch.empty_like(images), torch.empty_like(images)
+        names = augment.split_intensity(rows)
+        host = list(zip(names["events"].tolist(), *[names[k].tolist() for k in ("noise_std", "blur_sigma", "brightness", "contrast", "gamma")]))
+        # the two forms on the same rows without the noise: what remains is rounding
+        quiet = rows.clone()
+        quiet_bits = quiet.view(torch.int32)
+        quiet_bits[:, 0] &= ~1
+        stage.apply(images, quiet, out=stage_out)
+        torch_intensity(images, [(m & ~1, *r) for (m, *r) in host], torch_out)
+        gap = float((stage_out - torch_out).abs().max())
+
+        fns = (lambda: plain.next(ids, out_images, out_labels), lambda: all_on.next(ids, out_images, out_labels),
+               lambda: default.next(ids, out_images, out_labels), lambda: stage.apply(images, rows, out=stage_out),
+               lambda: torch_intensity(images, host, torch_out))
+        for _ in range(args.warmup):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        ms = timed_rounds(fns, args.repeats, args.rounds)
+        keys = ("next_plain", "next_all_on", "next_default_probabilities", "stage_all_on", "torch_operators_all_on")
+        entry = {k: summary(m) for k, m in zip(keys, ms)}
+        entry["all_on_cost_ms"] = entry["next_all_on"]["median_ms"] - entry["next_plain"]["median_ms"]
+        entry["default_cost_ms"] = entry["next_default_probabilities"]["median_ms"] - entry["next_plain"]["median_ms"]
+        entry["torch_over_stage"] = entry["torch_operators_all_on"]["median_ms"] / entry["stage_all_on"]["median_ms"]
+        entry["max_gap_to_torch_without_noise"] = gap
+        result["batches"][str(B)] = entry
+        for k in keys:
+            print(f"B={B} {k}: {entry[k]['median_ms']:.4f} ms ({entry[k]['min_ms']:.4f} .. {entry[k]['max_ms']:.4f})", flush=True)
+        print(f"B={B}: all-on stage inside next costs {entry['all_on_cost_ms']:.4f} ms, with the default probabilities "
+              f"{entry['default_cost_ms']:.4f} ms; torch operators / stage = {entry['torch_over_stage']:.1f}; max gap to torch without "
+              f"noise {gap:.2e}", flush=True)
+        assert plain.status == 0 and all_on.status == 0 and default.status == 0
+    if args.with_step:
+        result["train_step"] = train_step_ms(5, 20)
+        result["all_on_B2_share_of_step"] = result["batches"]["2"]["all_on_cost_ms"] / result["train_step"]["median_ms"]
+        print(f"training step (graph, fp16, batch 2): {result['train_step']['median_ms']:.2f} ms; the all-on stage at B=2 is "
+              f"{100 * result['all_on_B2_share_of_step']:.2f} % of it", flush=True)
+    result["value"] = result["batches"]["2"]["stage_all_on"]["median_ms"]
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=1000)
@@ -268,9 +370,23 @@ def main():
     ap.add_argument("--smoothing", action="store_true", help="smoothed apply next to the one-hot apply, and the centroid pass")
     ap.add_argument("--onehot-lib", default="", help="with --smoothing: the build whose dua_aug_apply is the one-hot side")
     ap.add_argument("--affine", action="store_true", help="resampling apply next to the plain apply and to torch's grid_sample")
+    ap.add_argument("--intensity", action="store_true", help="the intensity stage next to next() without it and to torch operators")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_augment.py measures on the GPU; none is visible")
+    if args.intensity:
+        result = intensity_bench(args)
+        if args.out:
+            merged = result
+            if os.path.exists(args.out):
+                with open(args.out) as f:
+                    before = json.loads(f.read() or "{}")
+                if before.get("metric") == "augment_next_time":
+                    merged = dict(before, intensity=result)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(merged) + "\n")
+        print(json.dumps(result))
+        return
     if args.smoothing or args.affine:
         line = json.dumps(smoothing_bench(args) if args.smoothing else affine_bench(args))
         if args.out:
