@@ -177,6 +177,11 @@ class AugAffineConfig(C.Structure):
                 ("zoom_span", C.c_float), ("pad_value", C.c_float), ("reserved", C.c_int)]
 
 
+class AugClassVolume(C.Structure):
+    """dua_aug_class_volume: one 16-byte row of the device table of per-volume class tables."""
+    _fields_ = [("prefix", C.c_void_p), ("cum", C.c_void_p)]
+
+
 class AugIntensityConfig(C.Structure):
     """dua_aug_intensity_config."""
     _fields_ = [(n, C.c_float) for n in ("noise_prob", "noise_std_min", "noise_std_span", "blur_prob", "blur_sigma_min",
@@ -320,6 +325,9 @@ _SIGS = {
                                       C.c_int, C.c_ulonglong, _P, _P, _P, _P]),
     "dua_aug_apply_affine": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugSmoothing), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _P, C.c_int, _P, _P, _P, _P]),
+    "dua_aug_count_class_candidates": (C.c_int, [_P, _P, C.c_long, C.c_float, C.c_int, _P, _P]),
+    "dua_aug_draw_classes": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.POINTER(AugAffineConfig), C.c_ulonglong, _P,
+                                       C.c_int, C.c_ulonglong, _P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
     "dua_aug_intensity_scratch_bytes": (C.c_long, [C.c_int] * 4),
     "dua_aug_intensity_draw": (C.c_int, [C.POINTER(AugIntensityConfig), C.c_int, C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P]),
     "dua_aug_intensity_apply": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _P, _P, C.c_long, _P]),

@@ -41,6 +41,18 @@ launch, one tiled noise-and-blur pass, four pointwise passes separated by determ
     images = aug(images)                         # or on any fp32 [B, 1, *roi] batch, without a producer
 
 include/dua_hip.h ("training input: intensity augmentation") fixes it; tests/augment_intensity_ref.py restates that text.
+
+Crop centres can be balanced by class instead of by foreground and background: a class is drawn first, then a voxel of that
+class, so that a small organ is the centre of a patch as often as a large one (MONAI's ``RandCropByLabelClassesd(ratios=...)``;
+nnU-Net's oversampling picks among the classes that occur in the case and otherwise crops anywhere)::
+
+    volumes = [DeviceVolume(image, label, num_classes=16) for image, label in cases]
+    producer = DeviceBatchProducer(volumes, class_ratios=[0, 1, 1, 4, ...])               # MONAI's ratios, one per class
+    producer = DeviceBatchProducer(volumes, class_ratios="present", uniform_prob=0.67)    # nnU-Net's rule
+    images, labels = producer.next(ids)          # producer.chosen_classes, producer.class_tally: what was drawn, on the device
+
+Still one draw launch and one apply launch; a row drawn this way is an ordinary ``params`` row.  include/dua_hip.h ("training
+input: class-balanced crop centres") fixes it; tests/augment_classes_ref.py restates that text.
 """
 from __future__ import annotations
 
@@ -235,6 +247,24 @@ class LabelSmoothing:
         return nv.AugSmoothing(self.alpha, self.order, self.epsilon, math.inf if self.max_value is None else self.max_value)
 
 
+def class_cum(ratios, counts):
+    """The ``cum`` row of include/dua_hip.h ("class-balanced crop centres") as a list of K Python floats, to be rounded to fp32
+    once: ``ratios`` where the class has candidates (``counts`` > 0) and 0 elsewhere, summed in class order in fp64, the running
+    sum divided by the total, and exactly 1.0 from the last weighted class on.  None when no weighted class has a candidate."""
+    e = [float(r) if int(n) > 0 else 0.0 for r, n in zip(ratios, counts)]
+    total = 0.0
+    for x in e:
+        total += x
+    if total == 0.0:
+        return None
+    last = max(k for k, x in enumerate(e) if x > 0.0)
+    run, cum = 0.0, []
+    for k, x in enumerate(e):
+        run += x
+        cum.append(1.0 if k >= last else run / total)
+    return cum
+
+
 class DeviceVolume:
     """One cached case on the device: ``image`` fp32 [D, H, W] (or [1, D, H, W]) and ``label`` uint8 [D, H, W] of class ids,
     with the candidate sets of RandCropByPosNegLabel counted once (foreground = label > 0; background = label == 0 and
@@ -271,6 +301,7 @@ class DeviceVolume:
         self.prefix = ops.aug_count_candidates(self.image, self.label, self.image_threshold)
         self.num_classes = None if num_classes is None else int(num_classes)
         self.centroids = self.class_counts = self.class_sums = None
+        self.class_prefix = self.class_candidate_counts = self._class_candidate_totals = None
         totals = self.prefix[:, -1].to(torch.int64)
         if self.num_classes is not None:
             sums, self.centroids = ops.aug_class_centroids(self.label, self.num_classes)
@@ -316,6 +347,23 @@ class DeviceVolume:
     def device(self):
         return self.image.device
 
+    def class_candidates(self):
+        """The candidate sets per class for class-balanced crop centres (class 0 = label == 0 and image > image_threshold,
+        class k = label == k), counted once, on first use: ``class_prefix`` int32 [num_classes, nchunks + 1], the per-chunk
+        exclusive prefix table of every class, which is returned, and ``class_candidate_counts`` int64 [num_classes], both on the
+        device.  Reads the counts once (a host synchronisation at that point)."""
+        if self.class_prefix is None:
+            if self.num_classes is None:
+                raise ValueError("DeviceVolume.class_candidates: the volume was built without num_classes")
+            if self.num_classes > nv.AUG_MAX_CLASSES:
+                raise ValueError(f"DeviceVolume.class_candidates: at most {nv.AUG_MAX_CLASSES} classes, the volume has num_classes = "
+                                 f"{self.num_classes}")
+            prefix = ops.aug_count_class_candidates(self.image, self.label, self.num_classes, self.image_threshold)
+            counts = prefix[:, -1].to(torch.int64)
+            self._class_candidate_totals = counts.tolist()    # the one host read
+            self.class_prefix, self.class_candidate_counts = prefix, counts
+        return self.class_prefix
+
     def table_row(self):
         D, H, W = self.shape
         n = self.prefix.shape[1]
@@ -347,11 +395,24 @@ class DeviceBatchProducer:
 
     ``intensity`` (an ``IntensityAugmenter`` of the producer's roi and device) makes ``next`` run it, in place, on the images
     ``apply`` wrote; the rows of that call stay in ``producer.intensity_rows`` for logging.  ``draw`` and ``apply`` of the producer
-    do not change, and ``None`` (the default) changes nothing."""
+    do not change, and ``None`` (the default) changes nothing.
+
+    ``class_ratios`` draws the crop centre by class instead of by ``pos`` / ``neg`` (which must then keep their defaults): a
+    sequence of ``num_classes`` non-negative numbers, MONAI's ``ratios`` -- class k is chosen with a probability proportional to
+    ``class_ratios[k]`` among the classes that occur in the volume (class 0 = background above ``image_threshold``), then a voxel
+    of it uniformly -- or the string ``"present"`` for ``(0, 1, .., 1)``, nnU-Net's uniform choice among the foreground classes
+    of the case.  Every volume needs one ``num_classes`` (at most 64); a volume in which no class with a positive ratio occurs
+    is refused.  ``uniform_prob`` is the probability that the centre is instead any voxel of the volume (nnU-Net: 0.67; works
+    without ``class_ratios`` too).  Same two launches; ``draw`` returns what it returns otherwise and a row is an ordinary row.
+    ``chosen_classes`` (int32 [B], device) holds the classes of the last draw, -1 for a uniform centre; ``class_tally`` (int64
+    [num_classes + 1], device, the last entry the uniform centres) counts every draw since ``reset_class_tally()``; the producer
+    reads neither.  ``chosen_classes`` is allocated by the first draw of a batch size: draw once before capturing ``next``.  With
+    ``class_ratios=None, uniform_prob=0`` (the default) nothing changes: the same launch, the same objects, the same bits."""
 
     def __init__(self, volumes, roi=(96, 96, 96), class_ids=range(16), pos=1, neg=1, flip_prob=0.1, rot90_prob=0.1, max_k=3,
                  scale_prob=0.1, scale_factors=0.1, shift_prob=0.5, shift_offsets=0.1, seed=0, smoothing=None, rotate_prob=0.0,
-                 rotate_range=(0.0, 0.0, 0.0), zoom_prob=0.0, zoom_range=(1.0, 1.0), pad_value=0.0, intensity=None):
+                 rotate_range=(0.0, 0.0, 0.0), zoom_prob=0.0, zoom_range=(1.0, 1.0), pad_value=0.0, intensity=None,
+                 class_ratios=None, uniform_prob=0.0):
         volumes = list(volumes)
         if not volumes or not all(isinstance(v, DeviceVolume) for v in volumes):
             raise ValueError("DeviceBatchProducer: a non-empty list of DeviceVolume")
@@ -421,6 +482,49 @@ class DeviceBatchProducer:
             if intensity.roi != roi or not same_device:
                 raise ValueError(f"DeviceBatchProducer: intensity was built for roi {intensity.roi} on {intensity.device}, the "
                                  f"producer has roi {roi} on {self.device}")
+        try:
+            uniform_prob = float(uniform_prob)
+        except (TypeError, ValueError):
+            uniform_prob = math.nan
+        if not 0.0 <= uniform_prob <= 1.0:
+            raise ValueError(f"DeviceBatchProducer: uniform_prob is a probability, got {uniform_prob}")
+        self.uniform_prob = uniform_prob
+        self.class_ratios = self.class_cum = self.class_draw_table = self.chosen_classes = self.class_tally = None
+        if class_ratios is not None:
+            if float(pos) != 1.0 or float(neg) != 1.0:
+                raise ValueError("DeviceBatchProducer: class_ratios replaces the pos / neg rule: leave pos and neg at their defaults, "
+                                 f"got pos = {pos}, neg = {neg}")
+            missing = [i for i, v in enumerate(volumes) if v.num_classes is None]
+            if missing:
+                raise ValueError(f"DeviceBatchProducer: class_ratios needs num_classes, volumes {missing} were built without it")
+            if len({v.num_classes for v in volumes}) != 1:
+                raise ValueError("DeviceBatchProducer: class_ratios needs one num_classes for every volume, got "
+                                 f"{sorted({v.num_classes for v in volumes})}")
+            K = volumes[0].num_classes
+            if K > nv.AUG_MAX_CLASSES:
+                raise ValueError(f"DeviceBatchProducer: class_ratios takes at most {nv.AUG_MAX_CLASSES} classes, the volumes have {K}")
+            if isinstance(class_ratios, str):
+                if class_ratios != "present":
+                    raise ValueError(f"DeviceBatchProducer: class_ratios is a sequence of numbers or \"present\", got {class_ratios!r}")
+                ratios = [0.0] + [1.0] * (K - 1)
+            else:
+                try:
+                    ratios = [float(r) for r in class_ratios]
+                except (TypeError, ValueError):
+                    raise ValueError("DeviceBatchProducer: class_ratios is a sequence of numbers or \"present\"") from None
+            if len(ratios) != K:
+                raise ValueError(f"DeviceBatchProducer: class_ratios has one entry per class: {K} for num_classes = {K}, got {len(ratios)}")
+            if not all(math.isfinite(r) and r >= 0.0 for r in ratios) or not math.isfinite(sum(ratios)):
+                raise ValueError(f"DeviceBatchProducer: class_ratios are non-negative and finite (and so is their sum), got {ratios}")
+            cums = []
+            for i, v in enumerate(volumes):
+                v.class_candidates()
+                cum = class_cum(ratios, v._class_candidate_totals)
+                if cum is None:
+                    raise ValueError(f"DeviceBatchProducer: volume {i} holds no voxel of a class with a positive ratio (class_ratios = "
+                                     f"{ratios}, candidates per class = {v._class_candidate_totals})")
+                cums.append(cum)
+            self.class_ratios = tuple(ratios)
         self.intensity, self.intensity_rows = intensity, None
         self.smoothing = smoothing
         self.volumes, self.roi, self.class_ids, self.seed = volumes, roi, tuple(class_ids), int(seed)
@@ -432,6 +536,13 @@ class DeviceBatchProducer:
         self.class_table = torch.tensor(class_ids, dtype=torch.uint8).to(self.device)
         self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.class_ratios is not None:
+            self.class_cum = torch.tensor(cums, dtype=torch.float64).to(torch.float32).to(self.device)     # fp32 [volumes, K]: rounded once
+            K = len(self.class_ratios)
+            crows = (nv.AugClassVolume * len(volumes))(*[nv.AugClassVolume(v.class_prefix.data_ptr(), self.class_cum.data_ptr() + 4 * K * i)
+                                                          for i, v in enumerate(volumes)])
+            self.class_draw_table = torch.frombuffer(bytearray(bytes(crows)), dtype=torch.uint8).reshape(len(volumes), -1).to(self.device)
+            self.class_tally = torch.zeros(K + 1, dtype=torch.int64, device=self.device)
         if smoothing is not None:
             self.centroids = torch.stack([v.centroids for v in volumes]).contiguous()       # fp32 [volumes, num_classes, 3]
             self._smoothing = smoothing.native()
@@ -446,6 +557,12 @@ class DeviceBatchProducer:
         """Non-zero once any launch met a row it had to skip: a volume id outside the table, or a params row that would read
         outside its volume (reads the device word: a host synchronisation)."""
         return int(self._status.item())
+
+    def reset_class_tally(self):
+        """Zero ``class_tally`` (a producer with ``class_ratios``)."""
+        if self.class_tally is None:
+            raise ValueError("DeviceBatchProducer.reset_class_tally: the producer was built without class_ratios")
+        self.class_tally.zero_()
 
     def _ids(self, volume_ids):
         if torch.is_tensor(volume_ids):
@@ -469,6 +586,15 @@ class DeviceBatchProducer:
         ids = self._ids(volume_ids)
         params = torch.empty((ids.numel(), nv.AUG_PARAM_WORDS), dtype=torch.int32, device=self.device)
         affine = torch.empty((ids.numel(), nv.AUG_AFFINE_WORDS), dtype=torch.float32, device=self.device) if self.affine else None
+        if self.class_ratios is not None or self.uniform_prob > 0.0:
+            K = len(self.class_ratios) if self.class_ratios is not None else 0
+            if K and (self.chosen_classes is None or self.chosen_classes.numel() != ids.numel()):
+                self.chosen_classes = torch.empty(ids.numel(), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                return ops.aug_draw_classes(self.table, ids, self.cfg, self.seed, self._counter, params, self._status,
+                                            counter_value=counter, affine_cfg=self.affine_cfg if self.affine else None, affine=affine,
+                                            class_table=self.class_draw_table, num_classes=K, uniform_prob=self.uniform_prob,
+                                            chosen=self.chosen_classes if K else None, tally=self.class_tally)
         with torch.cuda.device(self.device):
             return ops.aug_draw(self.table, ids, self.cfg, self.seed, self._counter, params, self._status, counter_value=counter,
                                 affine_cfg=self.affine_cfg if self.affine else None, affine=affine)

@@ -30,6 +30,8 @@
 //   centroids : once per volume, for label smoothing (dataset/cache_dataset.py:105-153).  One pass over the label map, 16 bytes
 //            per thread and step; count and index sums per class as 64-bit integers, LDS atomics inside a workgroup, one
 //            global integer atomic per class and workgroup: exact, so identical between runs.  A finish launch divides in fp64.
+//   class count : once per volume, when crop centres are drawn by class: the same chunks, one prefix row per class, one pass.
+//   class draw : the draw kernel's CLASSES form: a ballot over cum picks the class, the same search runs on that class's row.
 //   affine draw : the draw kernel's AFFINE form takes two more Philox blocks and writes, beside the params row, the matrix
 //            M = R / z from half-angle tangents in fp64 (no sine, no cosine: a numpy restatement has its bits).
 // -ffp-contract=off (csrc/Makefile) keeps the three fp32 operations of the intensity transform, and the two of each drawn
@@ -74,6 +76,43 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_chunk_counts_kernel(const flo
     for (int w = 0; w < AUG_THREADS / 64; ++w) s += part[tid][w];
     prefix[(long)tid * (nchunks + 1) + c] = s;
   }
+}
+
+__device__ __forceinline__ bool is_class_candidate(int k, unsigned char l, float v, float thr) {
+  return (int)l == k && (k != 0 || v > thr);
+}
+
+// counts[k][c] = candidates of class k in chunk c, all K rows from one pass over label and image.  Ballots, but over the ids
+// a wave actually holds, not over all K: the lowest lane still to be counted names an id, one ballot finds every lane with
+// that id, its popcount goes to the workgroup's LDS row in ONE integer add from that lane.  A label map is piecewise constant,
+// so 64 consecutive voxels hold one to three ids and a step costs that many ballots, where a ballot per class would cost K = 64
+// of them for every 64 voxels; a per-lane LDS histogram would send the 64 adds of a wave to the same word (same-address LDS
+// atomics are taken one after another).  Integer adds: the counts do not depend on the order of arrival.
+__global__ void __launch_bounds__(AUG_THREADS) aug_class_chunk_counts_kernel(const float* __restrict__ image,
+                                                                             const unsigned char* __restrict__ label, long voxels,
+                                                                             float thr, int nchunks, int K,
+                                                                             unsigned* __restrict__ prefix) {
+  __shared__ unsigned hist[DUA_AUG_MAX_CLASSES];
+  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (tid < K) hist[tid] = 0;                             // K <= DUA_AUG_MAX_CLASSES < AUG_THREADS
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < DUA_AUG_CHUNK / AUG_THREADS; ++j) {
+    const long i = (long)c * DUA_AUG_CHUNK + j * AUG_THREADS + tid;
+    int id = i < voxels ? (int)label[i] : -1;             // -1: in no set
+    if (id == 0 && !(image[i] > thr)) id = -1;
+    if (id >= K) id = -1;
+    unsigned long long todo = __ballot(id >= 0);
+    while (todo) {                                        // wave-uniform
+      const int leader = __ffsll((long long)todo) - 1;
+      const int cur = __shfl(id, leader);
+      const unsigned long long same = __ballot(id == cur);
+      if (lane == leader) atomicAdd(&hist[cur], (unsigned)__popcll(same));       // 0 <= cur < K
+      todo &= ~same;
+    }
+  }
+  __syncthreads();
+  if (tid < K) prefix[(long)tid * (nchunks + 1) + c] = hist[tid];
 }
 
 // in place, per row: counts [nchunks] -> exclusive prefix [nchunks + 1] (the last entry is the total).  One block per row;
@@ -129,14 +168,51 @@ __device__ void aug_affine_row(float* __restrict__ dst, const float t[3], float 
   dst[DUA_AUG_AFFINE_PAD + 1] = 0.f;
 }
 
+// what dua_aug_draw_classes adds to a draw (unread by the other entries)
+struct AugClassDraw {
+  const dua_aug_class_volume* classes;                    // may be NULL: the pos / neg rule
+  int K;
+  float uniform_prob;
+  int* chosen;                                            // [B], may be NULL
+  unsigned long long* tally;                              // [K + 1], may be NULL
+};
+
+// a row that cannot be drawn: volume -1, zeros, *status
+__device__ __forceinline__ void aug_bad_row(int* __restrict__ row, int* status) {
+  row[DUA_AUG_VOLUME] = -1;
+  for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
+  if (status) *status = 1;
+}
+
+// the params row of a sample whose centre is the voxel with linear index i of its volume
+__device__ __forceinline__ void aug_write_row(int* __restrict__ row, int vid, long i, const dua_aug_volume& vol,
+                                              const dua_aug_config& cfg, int flip, int k, float scale, float shift) {
+  const unsigned line = (unsigned)i / (unsigned)vol.W;    // voxels < 2^31
+  const int cw = (int)((unsigned)i - line * (unsigned)vol.W), cd = (int)(line / (unsigned)vol.H);
+  const int ch = (int)(line - (unsigned)cd * (unsigned)vol.H);
+  row[DUA_AUG_VOLUME] = vid;
+  row[DUA_AUG_START_D] = min(max(cd - cfg.roi[0] / 2, 0), vol.D - cfg.roi[0]);
+  row[DUA_AUG_START_H] = min(max(ch - cfg.roi[1] / 2, 0), vol.H - cfg.roi[1]);
+  row[DUA_AUG_START_W] = min(max(cw - cfg.roi[2] / 2, 0), vol.W - cfg.roi[2]);
+  row[DUA_AUG_FLIP] = flip;
+  row[DUA_AUG_K] = k;
+  row[DUA_AUG_SCALE] = __float_as_int(scale);
+  row[DUA_AUG_SHIFT] = __float_as_int(shift);
+}
+
 // AFFINE: dua_aug_draw_affine -- two more Philox blocks per sample and the affine row beside the params row, which keeps its bits
-template <bool AFFINE>
+// CLASSES: dua_aug_draw_classes -- word 2.3 decides the uniform event (a voxel of the whole volume, no table), otherwise the
+// candidate set is a class: lane k holds cum[k], one ballot of u < cum[k] and its lowest bit give the class, and the search below
+// runs on row k of the volume's class table.  Every branch on these is wave-uniform.  Without a class table the set is the pos /
+// neg one, and with uniform_prob = 0 besides, the row has the bits of the CLASSES = false form.
+template <bool AFFINE, bool CLASSES>
 __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua_aug_volume* __restrict__ table, int nvol,
                                                                       const int* __restrict__ ids, int B, dua_aug_config cfg,
                                                                       unsigned long long seed, unsigned long long* counter,
                                                                       int use_counter, unsigned long long counter_value,
                                                                       int* __restrict__ params, int* status,
-                                                                      dua_aug_affine_config acfg, float* __restrict__ affine) {
+                                                                      dua_aug_affine_config acfg, float* __restrict__ affine,
+                                                                      AugClassDraw cls) {
   const float no_turn[3] = {0.f, 0.f, 0.f};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long call = use_counter ? counter_value : *counter;
@@ -148,10 +224,9 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
     float* arow = AFFINE ? affine + (long)b * DUA_AUG_AFFINE_WORDS : nullptr;
     if (vid < 0 || vid >= nvol) {
       if (lane == 0) {
-        row[DUA_AUG_VOLUME] = -1;
-        for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
-        if (status) *status = 1;
+        aug_bad_row(row, status);
         if constexpr (AFFINE) aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
+        if constexpr (CLASSES) if (cls.chosen) cls.chosen[b] = -2;
       }
       continue;
     }
@@ -163,9 +238,24 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
       philox4x32_10(w[j], (uint32_t)seed, (uint32_t)(seed >> 32));
     }
     const bool fg = vol.fg_count > 0 && (vol.bg_count == 0 || unit_float(w[0][0]) < cfg.pos_fraction);
-    const uint32_t count = fg ? vol.fg_count : vol.bg_count;
+    uint32_t count = fg ? vol.fg_count : vol.bg_count;
     const unsigned* prefix = fg ? vol.fg_prefix : vol.bg_prefix;
-    const uint32_t r = below(w[0][1], count);
+    int cclass = -1;                                      // the chosen class; -1: the pos / neg set
+    bool uniform = false;
+    if constexpr (CLASSES) {
+      uniform = unit_float(w[2][3]) < cls.uniform_prob;
+      if (!uniform && cls.classes) {
+        const dua_aug_class_volume cv = cls.classes[vid];
+        const float u = unit_float(w[0][0]);
+        const bool below_cum = lane < cls.K && u < cv.cum[lane < cls.K ? lane : 0];      // K <= 64: a lane per class
+        const unsigned long long m = __ballot(below_cum);
+        cclass = m ? __ffsll((long long)m) - 1 : cls.K;   // K: a cum that chooses nothing
+        prefix = cv.prefix + (long)min(cclass, cls.K - 1) * (vol.nchunks + 1);
+        count = cclass < cls.K ? prefix[vol.nchunks] : 0u;
+      }
+    }
+    const long voxels = (long)vol.D * vol.H * vol.W;
+    const uint32_t r = below(w[0][1], uniform ? (uint32_t)voxels : count);
     int flip = 0;
     flip |= unit_float(w[0][2]) < cfg.flip_prob ? 1 : 0;
     flip |= unit_float(w[0][3]) < cfg.flip_prob ? 2 : 0;
@@ -193,63 +283,49 @@ __global__ void __launch_bounds__(AUG_DRAW_WAVES * 64) aug_draw_kernel(const dua
         zoom = t + acfg.zoom_min;
       }
     }
-    if (count == 0) {                                     // a table row the host should never have built
-      if (lane == 0) {
-        row[DUA_AUG_VOLUME] = -1;
-        for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
-        if (status) *status = 1;
-        if constexpr (AFFINE) aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
-      }
-      continue;
-    }
-    // the chunk c with prefix[c] <= r < prefix[c + 1]: prefix is non-decreasing, prefix[0] = 0 <= r < total = prefix[nchunks]
-    int lo = 0, hi = vol.nchunks;
-    while (hi - lo > 1) {
-      const int step = (hi - lo + 63) >> 6;
-      const long idx = (long)lo + (long)lane * step;
-      const unsigned v = idx < hi ? prefix[idx] : 0xFFFFFFFFu;
-      const int seg = __popcll(__ballot(idx < hi && v <= r)) - 1;      // lane 0 probes prefix[lo] <= r: seg >= 0
-      lo += max(seg, 0) * step;
-      hi = min(lo + step, hi);
-    }
-    uint32_t rem = r - prefix[lo];
-    const long voxels = (long)vol.D * vol.H * vol.W;
     bool written = false;
-    for (int j = 0; j < DUA_AUG_CHUNK / 64; ++j) {
-      const long i = (long)lo * DUA_AUG_CHUNK + j * 64 + lane;
-      const bool in = i < voxels;
-      const bool cand = in && is_candidate(fg, vol.label[in ? i : 0], vol.image[in ? i : 0], vol.image_threshold);
-      const unsigned long long m = __ballot(cand);
-      const uint32_t n = __popcll(m);
-      if (rem < n) {
-        const uint32_t rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (cand && rank == rem) {
-          const unsigned line = (unsigned)i / (unsigned)vol.W;                  // voxels < 2^31
-          const int cw = (int)((unsigned)i - line * (unsigned)vol.W), cd = (int)(line / (unsigned)vol.H);
-          const int ch = (int)(line - (unsigned)cd * (unsigned)vol.H);
-          row[DUA_AUG_VOLUME] = vid;
-          row[DUA_AUG_START_D] = min(max(cd - cfg.roi[0] / 2, 0), vol.D - cfg.roi[0]);
-          row[DUA_AUG_START_H] = min(max(ch - cfg.roi[1] / 2, 0), vol.H - cfg.roi[1]);
-          row[DUA_AUG_START_W] = min(max(cw - cfg.roi[2] / 2, 0), vol.W - cfg.roi[2]);
-          row[DUA_AUG_FLIP] = flip;
-          row[DUA_AUG_K] = k;
-          row[DUA_AUG_SCALE] = __float_as_int(scale);
-          row[DUA_AUG_SHIFT] = __float_as_int(shift);
-        }
-        written = true;
-        break;
+    if (uniform) {                                        // voxel number r of the whole volume: no table, no scan
+      if (lane == 0) aug_write_row(row, vid, (long)r, vol, cfg, flip, k, scale, shift);
+      written = true;
+    } else if (count > 0) {                               // count == 0: a table row the host should never have built
+      // the chunk c with prefix[c] <= r < prefix[c + 1]: prefix is non-decreasing, prefix[0] = 0 <= r < total = prefix[nchunks]
+      int lo = 0, hi = vol.nchunks;
+      while (hi - lo > 1) {
+        const int step = (hi - lo + 63) >> 6;
+        const long idx = (long)lo + (long)lane * step;
+        const unsigned v = idx < hi ? prefix[idx] : 0xFFFFFFFFu;
+        const int seg = __popcll(__ballot(idx < hi && v <= r)) - 1;      // lane 0 probes prefix[lo] <= r: seg >= 0
+        lo += max(seg, 0) * step;
+        hi = min(lo + step, hi);
       }
-      rem -= n;
+      uint32_t rem = r - prefix[lo];
+      for (int j = 0; j < DUA_AUG_CHUNK / 64; ++j) {
+        const long i = (long)lo * DUA_AUG_CHUNK + j * 64 + lane;
+        const bool in = i < voxels;
+        const unsigned char l = vol.label[in ? i : 0];
+        const float v = vol.image[in ? i : 0];
+        const bool cand = in && (CLASSES && cclass >= 0 ? is_class_candidate(cclass, l, v, vol.image_threshold)
+                                                        : is_candidate(fg, l, v, vol.image_threshold));
+        const unsigned long long m = __ballot(cand);
+        const uint32_t n = __popcll(m);
+        if (rem < n) {
+          const uint32_t rank = __popcll(m & ((1ull << lane) - 1ull));
+          if (cand && rank == rem) aug_write_row(row, vid, i, vol, cfg, flip, k, scale, shift);
+          written = true;
+          break;
+        }
+        rem -= n;
+      }
     }
-    if (!written && lane == 0) {                          // the prefix table and the volume disagree
-      row[DUA_AUG_VOLUME] = -1;
-      for (int j = 1; j < DUA_AUG_PARAM_WORDS; ++j) row[j] = 0;
-      if (status) *status = 1;
-    }
-    if constexpr (AFFINE) {
-      if (lane == 0) {
+    if (lane == 0) {
+      if (!written) aug_bad_row(row, status);             // an empty set, or the prefix table and the volume disagree
+      if constexpr (AFFINE) {
         if (written) aug_affine_row(arow, turn, zoom, events, acfg.pad_value);
         else aug_affine_row(arow, no_turn, 1.f, 0, acfg.pad_value);
+      }
+      if constexpr (CLASSES) {
+        if (cls.chosen) cls.chosen[b] = !written ? -2 : uniform ? -1 : cclass;
+        if (cls.tally && written && (uniform || cclass >= 0)) atomicAdd(&cls.tally[uniform ? cls.K : cclass], 1ull);
       }
     }
   }
@@ -544,11 +620,12 @@ static bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }
 
 }  // namespace dua
 
-// dua_aug_draw (affine_cfg == NULL and affine == NULL) and dua_aug_draw_affine (both given)
+// dua_aug_draw (affine_cfg == NULL and affine == NULL), dua_aug_draw_affine (both given) and, with cls, dua_aug_draw_classes
+// (either)
 static int aug_draw_launch(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
                            const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
                            int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
-                           void* stream) {
+                           const dua::AugClassDraw* cls, void* stream) {
   if (!table || nvol < 1 || !ids || B < 1 || !cfg || !params || (!use_counter && !counter)) return DUA_ERR_ARG;
   if (cfg->roi[0] < 1 || cfg->roi[1] < 1 || cfg->roi[2] < 1 || cfg->max_k < 1 || cfg->max_k > 3) return DUA_ERR_ARG;
   if (!dua::prob_ok(cfg->pos_fraction) || !dua::prob_ok(cfg->flip_prob) || !dua::prob_ok(cfg->rot90_prob) ||
@@ -566,9 +643,10 @@ static int aug_draw_launch(const dua_aug_volume* table, int nvol, const int* ids
       if (!(a.rotate_tan_half[i] >= 0.f && a.rotate_tan_half[i] <= 1.f)) return DUA_ERR_ARG;
   }
   const int waves = B < dua::AUG_DRAW_WAVES ? B : dua::AUG_DRAW_WAVES;
-  const auto kernel = affine_cfg ? dua::aug_draw_kernel<true> : dua::aug_draw_kernel<false>;
+  const auto kernel = cls ? (affine_cfg ? dua::aug_draw_kernel<true, true> : dua::aug_draw_kernel<false, true>)
+                          : (affine_cfg ? dua::aug_draw_kernel<true, false> : dua::aug_draw_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(1), dim3(waves * 64), 0, (hipStream_t)stream, table, nvol, ids, B, *cfg, seed, counter,
-                     use_counter, counter_value, params, status, a, affine);
+                     use_counter, counter_value, params, status, a, affine, cls ? *cls : dua::AugClassDraw{});
   return (int)hipGetLastError();
 }
 
@@ -637,7 +715,7 @@ int dua_aug_draw(const dua_aug_volume* table, int nvol, const int* ids, int B, c
                  unsigned long long seed, unsigned long long* counter, int use_counter, unsigned long long counter_value,
                  int* params, int* status, void* stream) {
   return aug_draw_launch(table, nvol, ids, B, cfg, nullptr, seed, counter, use_counter, counter_value, params, nullptr, status,
-                         stream);
+                         nullptr, stream);
 }
 
 int dua_aug_apply(const dua_aug_volume* table, int nvol, const int* params, int B, int roi_d, int roi_h, int roi_w,
@@ -679,7 +757,7 @@ int dua_aug_draw_affine(const dua_aug_volume* table, int nvol, const int* ids, i
                         void* stream) {
   if (!affine_cfg || !affine) return DUA_ERR_ARG;
   return aug_draw_launch(table, nvol, ids, B, cfg, affine_cfg, seed, counter, use_counter, counter_value, params, affine, status,
-                         stream);
+                         nullptr, stream);
 }
 
 int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* centroids, int num_classes,
@@ -691,6 +769,31 @@ int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* cen
     return DUA_ERR_ARG;
   return aug_apply_launch(table, nvol, centroids, num_classes, smoothing, params, affine, B, roi_d, roi_h, roi_w, class_ids, C,
                           images, labels, status, stream);
+}
+
+int dua_aug_count_class_candidates(const float* image, const unsigned char* label, long voxels, float image_threshold,
+                                   int num_classes, unsigned* prefix, void* stream) {
+  if (!image || !label || !prefix || voxels <= 0 || voxels >= (1L << 31) || image_threshold != image_threshold ||
+      num_classes < 1 || num_classes > DUA_AUG_MAX_CLASSES)
+    return DUA_ERR_ARG;
+  const int nchunks = (int)((voxels + DUA_AUG_CHUNK - 1) / DUA_AUG_CHUNK);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(dua::aug_class_chunk_counts_kernel, dim3(nchunks), dim3(dua::AUG_THREADS), 0, s, image, label, voxels,
+                     image_threshold, nchunks, num_classes, prefix);
+  hipLaunchKernelGGL(dua::aug_prefix_scan_kernel, dim3(num_classes), dim3(dua::AUG_THREADS), 0, s, nchunks, prefix);
+  return (int)hipGetLastError();
+}
+
+int dua_aug_draw_classes(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                         const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
+                         int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
+                         const dua_aug_class_volume* classes, int num_classes, float uniform_prob, int* chosen,
+                         unsigned long long* tally, void* stream) {
+  if ((affine_cfg == nullptr) != (affine == nullptr) || !dua::prob_ok(uniform_prob)) return DUA_ERR_ARG;
+  if (classes ? (num_classes < 1 || num_classes > DUA_AUG_MAX_CLASSES) : (chosen || tally)) return DUA_ERR_ARG;
+  const dua::AugClassDraw cls{classes, classes ? num_classes : 0, uniform_prob, chosen, tally};
+  return aug_draw_launch(table, nvol, ids, B, cfg, affine_cfg, seed, counter, use_counter, counter_value, params, affine, status,
+                         &cls, stream);
 }
 
 }  // extern "C"

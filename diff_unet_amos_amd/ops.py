@@ -1846,6 +1846,67 @@ def aug_draw(table, ids, cfg, seed, counter, params, status, counter_value=None,
     return params if affine is None else (params, affine)
 
 
+def aug_count_class_candidates(image, label, num_classes, image_threshold=0.0):
+    """dua_aug_count_class_candidates: int32 [num_classes, nchunks + 1] exclusive prefix tables of the per-chunk candidate
+    counts of every class of one volume (row 0 = label == 0 and image > image_threshold, row k = label == k; the last entry of
+    a row is the class's total)."""
+    _f32c(image, "image"); _u8c(label, "label")
+    assert image.dim() == 3 and image.shape == label.shape and image.device == label.device, "image / label: [D, H, W], same device"
+    vox, K = image.numel(), int(num_classes)
+    assert 0 < vox < 2 ** 31, "a volume holds fewer than 2^31 voxels"
+    assert 1 <= K <= nv.AUG_MAX_CLASSES, f"num_classes: 1 .. {nv.AUG_MAX_CLASSES}"
+    prefix = torch.empty((K, -(-vox // nv.AUG_CHUNK) + 1), dtype=torch.int32, device=image.device)
+    with torch.cuda.device(image.device):
+        nv.check(nv.lib().dua_aug_count_class_candidates(nv.ptr(image), nv.ptr(label), vox, float(image_threshold), K,
+                                                         nv.ptr(prefix), nv.stream_ptr()), "dua_aug_count_class_candidates")
+    return prefix
+
+
+def aug_draw_classes(table, ids, cfg, seed, counter, params, status, counter_value=None, affine_cfg=None, affine=None,
+                     class_table=None, num_classes=0, uniform_prob=0.0, chosen=None, tally=None):
+    """dua_aug_draw_classes: ``aug_draw`` with the crop centre drawn from a class.  ``class_table`` (uint8 [volumes, 16]: one
+    ``nv.AugClassVolume`` per volume, or None for the pos / neg rule), ``num_classes``, ``uniform_prob`` (the probability of a
+    centre anywhere in the volume), ``chosen`` (int32 [B], WRITTEN: the class, -1 for the uniform event, -2 for a row that could
+    not be drawn) and ``tally`` (int64 [num_classes + 1], ADDED to); ``chosen`` and ``tally`` need ``class_table``.  Returns what
+    ``aug_draw`` returns."""
+    nvol = _aug_table(table)
+    _i32c(ids, "volume_ids"); _i32c(params, "params"); _i32c(status, "status")
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1, "counter: int64 [1] device tensor"
+    B = ids.numel()
+    assert ids.dim() == 1 and B >= 1 and tuple(params.shape) == (B, nv.AUG_PARAM_WORDS) and status.numel() == 1
+    assert (affine_cfg is None) == (affine is None), "affine_cfg and affine: both or neither"
+    tensors = [ids, params, status, counter]
+    if affine is not None:
+        _aug_affine_rows(affine, B)
+        assert isinstance(affine_cfg, nv.AugAffineConfig)
+        tensors.append(affine)
+    K = int(num_classes)
+    if class_table is not None:
+        _u8c(class_table, "class_table")
+        assert tuple(class_table.shape) == (nvol, C.sizeof(nv.AugClassVolume)), f"class_table: uint8 [{nvol}, 16], a row per volume"
+        assert 1 <= K <= nv.AUG_MAX_CLASSES, f"num_classes: 1 .. {nv.AUG_MAX_CLASSES}"
+        tensors.append(class_table)
+    else:
+        assert chosen is None and tally is None, "chosen and tally report classes: they need class_table"
+    if chosen is not None:
+        _i32c(chosen, "chosen")
+        assert tuple(chosen.shape) == (B,), f"chosen: int32 [{B}]"
+        tensors.append(chosen)
+    if tally is not None:
+        assert tally.is_cuda and tally.dtype == torch.int64 and tally.is_contiguous() and tuple(tally.shape) == (K + 1,), \
+            f"tally: contiguous int64 [{K + 1}] device tensor"
+        tensors.append(tally)
+    assert all(t.device == table.device for t in tensors), "every tensor on the volumes' device"
+    assert isinstance(cfg, nv.AugConfig)
+    use = counter_value is not None
+    nv.check(nv.lib().dua_aug_draw_classes(nv.ptr(table), nvol, nv.ptr(ids), B, C.byref(cfg),
+                                           C.byref(affine_cfg) if affine_cfg is not None else None, int(seed) & (2 ** 64 - 1),
+                                           nv.ptr(counter), int(use), (int(counter_value) & (2 ** 64 - 1)) if use else 0,
+                                           nv.ptr(params), nv.ptr(affine), nv.ptr(status), nv.ptr(class_table), K,
+                                           float(uniform_prob), nv.ptr(chosen), nv.ptr(tally), nv.stream_ptr()), "dua_aug_draw_classes")
+    return params if affine is None else (params, affine)
+
+
 def aug_apply(table, params, roi, class_ids, images, labels, status, affine=None, centroids=None, smoothing=None):
     """dua_aug_apply: images fp32 [B, 1, *roi] and labels fp32 [B, C, *roi] (both WRITTEN) from ``params`` (int32 [B, 8]);
     ``class_ids``: uint8 [C] device tensor.  With ``centroids`` (fp32 [volumes, num_classes, 3]) and ``smoothing`` (an

@@ -69,6 +69,19 @@ _L.dua_aug_draw_affine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.P
 _L.dua_aug_apply_affine.restype = C.c_int
 _L.dua_aug_apply_affine.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                                     [C.c_void_p, C.c_int] + [C.c_void_p] * 4)
+# class-balanced crop centres: dua_aug_count_class_candidates builds, once per volume, one prefix row per class;
+# dua_aug_draw_classes is dua_aug_draw_affine (affine_cfg / affine may both be None) with the centre drawn from a class chosen by
+# the volume's cum row, or, with probability uniform_prob, from the whole volume.  The contract is in dua_hip.h
+class AugClassVolume(C.Structure):               # dua_aug_class_volume: device pointers to the class prefix table and to cum
+    _fields_ = [("prefix", C.c_void_p), ("cum", C.c_void_p)]
+
+
+_L.dua_aug_count_class_candidates.restype = C.c_int
+_L.dua_aug_count_class_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+_L.dua_aug_draw_classes.restype = C.c_int
+_L.dua_aug_draw_classes.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(AugConfig), C.POINTER(AugAffineConfig),
+                                     C.c_ulonglong, C.c_void_p, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4 +
+                                    [C.c_int, C.c_float] + [C.c_void_p] * 3)
 
 
 def _stream():

@@ -941,7 +941,7 @@ int dua_cc_filter(int V, int D, int H, int W, const int* labels, const int* coun
  * counter = (call counter lo, call counter hi, b, j); block j yields words j.0 .. j.3:
  *   0.0 set choice   0.1 candidate index   0.2 flip axis 0   0.3 flip axis 1
  *   1.0 flip axis 2  1.1 rotation event    1.2 rotation k    1.3 scale event
- *   2.0 scale value  2.1 shift event       2.2 shift value   2.3 unused
+ *   2.0 scale value  2.1 shift event       2.2 shift value   2.3 unused (dua_aug_draw_classes: uniform event)
  * (every word keeps its role whether or not the event before it happened).  With x a 32-bit word:
  *   integer in [0, n): mulhi(x, n) = (x * n) >> 32;   u(x) = (x >> 8) * 2^-24 (exact in fp32);   event of probability p
  *   (fp32): u(x) < p;
@@ -1116,6 +1116,66 @@ int dua_aug_apply_affine(const dua_aug_volume* table, int nvol, const float* cen
                          const dua_aug_smoothing* smoothing, const int* params, const float* affine, int B, int roi_d,
                          int roi_h, int roi_w, const unsigned char* class_ids, int C, float* images, float* labels,
                          int* status, void* stream);
+
+/* ---- training input: class-balanced crop centres ---------------------------------------------------------------------
+ * A third way of choosing the crop centre, beside the pos / neg rule of dua_aug_draw: first a class, then a voxel of that
+ * class (nnU-Net's per-class oversampling; MONAI's RandCropByLabelClassesd(ratios=...)), or, with a probability of its own, any
+ * voxel of the volume.  Uniform foreground voxels of a scan with organs of very different volumes are voxels of the largest
+ * organ nearly always.  The semantics are fixed HERE (MONAI is not a dependency).
+ *
+ * Candidate sets per class, for a label map with ids in [0, K), K = num_classes <= DUA_AUG_MAX_CLASSES:
+ *   class 0      = label == 0 and image > image_threshold       (the background set of dua_aug_count_candidates)
+ *   class k >= 1 = label == k
+ * each ordered by ascending linear voxel index.  dua_aug_count_class_candidates writes prefix = unsigned [K][nchunks + 1], the
+ * chunks (DUA_AUG_CHUNK) and the exclusive-prefix convention of dua_aug_count_candidates: row k, contiguous, belongs to class k;
+ * entry c = number of its candidates in chunks [0, c), entry nchunks = n_k, the total.  A voxel whose id is >= K is in no set.
+ * Integer counts only: identical between runs.  Row 0 equals row 1 of dua_aug_count_candidates' table, and the entry-wise sum
+ * of rows 1 .. K - 1 its row 0 when no id is >= K.
+ *
+ * Class choice.  Per volume the host supplies cum = fp32 [K] from ratios r_k >= 0 (finite): the effective weight is e_k = r_k
+ * where n_k > 0 and 0 where the class has no candidate; E = e_0 + .. + e_(K-1) summed in fp64 in class order; cum_k =
+ * fp32((e_0 + .. + e_k) / E), the running sum and the one division in fp64, rounded once; the last class with e_k > 0 and every
+ * class after it get cum_k = 1.0 exactly.  The chosen class is the smallest k with u(0.0) < cum_k: a class with e_k = 0 has
+ * cum_k == cum_(k-1) (cum_(-1) = 0) and cannot be chosen, and u <= 1 - 2^-24 < 1, so the rule always chooses.  E == 0 leaves no
+ * class to choose: the host refuses such a volume.
+ *
+ * Uniform event.  Word 2.3, unused by dua_aug_draw and dua_aug_draw_affine, gets a role in dua_aug_draw_classes only:
+ *   u(2.3) < uniform_prob:  centre = voxel number mulhi(0.1, D H W) of the whole volume (linear index); no table is read
+ *   otherwise:              centre = candidate number mulhi(0.1, n_k) of the chosen class k
+ * The start clamp and every other word and column of params are dua_aug_draw's; the call-counter rule is unchanged (one
+ * workgroup, a wave per sample).
+ *
+ * dua_aug_draw_classes takes the arguments of dua_aug_draw_affine and, before the stream:
+ *   classes       DEVICE table, one dua_aug_class_volume per volume of `table` (the prefix of
+ *                 dua_aug_count_class_candidates for that volume and its cum); may be NULL
+ *   num_classes   K, 1 .. DUA_AUG_MAX_CLASSES, one value for every volume (not read when classes is NULL)
+ *   uniform_prob  in [0, 1]
+ *   chosen        int [B], WRITTEN, may be NULL: the chosen class of sample b, -1 for the uniform event, -2 for a sample whose
+ *                 params row gets volume -1
+ *   tally         unsigned long long [K + 1], ADDED to by integer atomics (one per sample), may be NULL: entry k counts the
+ *                 samples of class k, entry K the uniform events; a sample whose row gets volume -1 is not counted.  The
+ *                 caller zeroes it when it wants to.
+ * It composes with the other options and leaves their words alone: affine_cfg and affine may both be NULL (no affine rows are
+ * written; blocks 3 and 4 are not drawn) or both be given, as in dua_aug_draw_affine.  With classes == NULL the set is chosen by
+ * dua_aug_draw's pos / neg rule and uniform_prob still works; with classes == NULL and uniform_prob == 0, params (and affine)
+ * are bit-identical to dua_aug_draw[_affine] for the same inputs.  With classes given, cfg->pos_fraction is not used.
+ * A chosen class whose row holds no candidate, a cum that lets no class be chosen (all zero, NaN), or a row that disagrees
+ * with the volume gives a volume -1 row (and the affine row of no event) and sets *status, as in dua_aug_draw.
+ * Refused with DUA_ERR_ARG before any launch: whatever dua_aug_draw[_affine] refuses; uniform_prob outside [0, 1] or NaN;
+ * classes given with num_classes outside 1 .. DUA_AUG_MAX_CLASSES; classes == NULL with chosen or tally given (the pos / neg
+ * rule has no class to report); one of affine_cfg and affine without the other.  dua_aug_count_class_candidates refuses what
+ * dua_aug_count_candidates does, and num_classes outside 1 .. DUA_AUG_MAX_CLASSES. */
+typedef struct {                 /* one row of the device table of per-volume class tables (16 bytes) */
+  const unsigned* prefix;        /* unsigned [num_classes][nchunks + 1] of dua_aug_count_class_candidates */
+  const float* cum;              /* fp32 [num_classes] */
+} dua_aug_class_volume;
+int dua_aug_count_class_candidates(const float* image, const unsigned char* label, long voxels, float image_threshold,
+                                   int num_classes, unsigned* prefix, void* stream);
+int dua_aug_draw_classes(const dua_aug_volume* table, int nvol, const int* ids, int B, const dua_aug_config* cfg,
+                         const dua_aug_affine_config* affine_cfg, unsigned long long seed, unsigned long long* counter,
+                         int use_counter, unsigned long long counter_value, int* params, float* affine, int* status,
+                         const dua_aug_class_volume* classes, int num_classes, float uniform_prob, int* chosen,
+                         unsigned long long* tally, void* stream);
 
 /* ---- training input: intensity augmentation ---------------------------------------------------------------------------
  * The intensity half of a CT augmentation recipe (nnU-Net's default pipeline: Gaussian noise, Gaussian blur, multiplicative

@@ -39,6 +39,16 @@ process (``randn`` for the noise, three ``conv3d`` over a symmetrically padded p
 ``pow``), alternating rounds.  The torch form's output is compared with the kernels' on rows without noise (torch's generator
 draws other normals).  ``--with-step`` relates the all-on cost to one config-4 training step.  With ``--out`` naming the file of
 the plain run, the result is stored under its key ``intensity``.
+
+    python tools/bench_augment.py --classes [--parent-lib other/libdua_hip.so] [--rounds 21] [--repeats 200]
+
+``--classes`` times the draw alone (one workgroup, no voxel is moved) at B = 2 and B = 16 over the same 16-class volumes in one
+process: today's draw (``dua_aug_draw``), the draw with ``class_ratios="present", uniform_prob=0.67`` and with sixteen equal
+ratios and no uniform event (``dua_aug_draw_classes``), and, with ``--parent-lib``, ``dua_aug_draw`` of another build of the
+library loaded next to this one (the parent commit's), on the same table.  Two figures per form: the time of a call through
+``ops`` into preallocated rows, which is mostly the host's, and the time per draw of a captured graph of 100 draws in a row,
+which is the device's.  It also times the once-per-volume ``dua_aug_count_class_candidates`` beside ``dua_aug_count_candidates``
+on one of the volumes and on a 512 x 512 x 150 label map.
 """
 import argparse
 import ctypes
@@ -267,6 +277,92 @@ def affine_bench(args):
     return result
 
 
+def classes_bench(args):
+    from diff_unet_amos_amd import _native as nv
+    from diff_unet_amos_amd import ops
+    K, GRAPH_DRAWS = 16, 100
+    vols = volumes(args.volumes, classes=K, num_classes=K)
+    kw = dict(roi=ROI, class_ids=range(1, K), seed=2)
+    plain = augment.DeviceBatchProducer(vols, **kw)
+    present = augment.DeviceBatchProducer(vols, class_ratios="present", uniform_prob=0.67, **kw)
+    equal = augment.DeviceBatchProducer(vols, class_ratios=[1.0] * K, **kw)
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        parent.dua_aug_draw.restype, parent.dua_aug_draw.argtypes = nv._SIGS["dua_aug_draw"]
+    result = {"metric": "augment_class_draw_time", "unit": "ms", "box": socket.gethostname(), "device": torch.cuda.get_device_name(0),
+              "classes": K, "volumes": len(vols), "repeats": args.repeats, "rounds": args.rounds, "graph_draws": GRAPH_DRAWS,
+              "parent_lib": os.path.relpath(args.parent_lib) if args.parent_lib else None, "batches": {}}
+    for B in (2, 16):
+        ids = torch.tensor([i % len(vols) for i in range(B)], dtype=torch.int32, device=DEV)
+        params = torch.empty((B, 8), dtype=torch.int32, device=DEV)
+        chosen = torch.empty(B, dtype=torch.int32, device=DEV)
+
+        def plain_fn():
+            ops.aug_draw(plain.table, ids, plain.cfg, plain.seed, plain._counter, params, plain._status)
+
+        def class_fn(p):
+            return lambda: ops.aug_draw_classes(p.table, ids, p.cfg, p.seed, p._counter, params, p._status, class_table=p.class_draw_table,
+                                                num_classes=K, uniform_prob=p.uniform_prob, chosen=chosen, tally=p.class_tally)
+
+        def parent_fn():
+            nv.check(parent.dua_aug_draw(nv.ptr(plain.table), len(vols), nv.ptr(ids), B, ctypes.byref(plain.cfg), plain.seed,
+                                         nv.ptr(plain._counter), 0, 0, nv.ptr(params), nv.ptr(plain._status), nv.stream_ptr()), "dua_aug_draw")
+
+        fns = {"draw": plain_fn, "draw_classes_present_uniform_0.67": class_fn(present), "draw_classes_equal_ratios": class_fn(equal)}
+        if parent is not None:
+            fns["parent_draw"] = parent_fn
+        if parent is not None:                                 # the two builds write the same rows for one counter
+            plain._counter.zero_(); plain_fn(); mine = params.clone()
+            plain._counter.zero_(); parent_fn()
+            assert torch.equal(mine, params), "dua_aug_draw differs between the two builds"
+        graphs = {}
+        for name, fn in fns.items():
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            graph, stream = torch.cuda.CUDAGraph(), torch.cuda.Stream(device=DEV)
+            stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(stream):
+                with torch.cuda.graph(graph, stream=stream):
+                    for _ in range(GRAPH_DRAWS):
+                        fn()
+            torch.cuda.current_stream().wait_stream(stream)
+            graph.replay()
+            graphs[name] = graph
+        torch.cuda.synchronize()
+        names = list(fns)
+        ms_call = timed_rounds([fns[n] for n in names], args.repeats, args.rounds)
+        ms_graph = timed_rounds([graphs[n].replay for n in names], max(args.repeats // GRAPH_DRAWS, 2), args.rounds)
+        entry = {}
+        for n, c, g in zip(names, ms_call, ms_graph):
+            entry[n] = {"call": summary(c), "in_graph": summary([x / GRAPH_DRAWS for x in g])}
+            print(f"B={B} {n}: call {entry[n]['call']['median_ms'] * 1e3:.2f} us ({entry[n]['call']['min_ms'] * 1e3:.2f} .. "
+                  f"{entry[n]['call']['max_ms'] * 1e3:.2f}); per draw inside a graph of {GRAPH_DRAWS}: "
+                  f"{entry[n]['in_graph']['median_ms'] * 1e3:.2f} us ({entry[n]['in_graph']['min_ms'] * 1e3:.2f} .. "
+                  f"{entry[n]['in_graph']['max_ms'] * 1e3:.2f})", flush=True)
+        result["batches"][str(B)] = entry
+        assert plain.status == 0 and present.status == 0 and equal.status == 0
+    # once per case: the class tables beside the pos / neg tables, on a producer volume and on a label map of the size of a scan
+    g = torch.Generator().manual_seed(7)
+    shape = (150, 512, 512)
+    big_label = block_labels(shape, K, g).to(DEV)
+    big_image = (torch.rand(shape, generator=g) - 0.3).to(DEV)
+    result["per_volume"] = {}
+    for name, image, label in (("producer_volume", vols[0].image, vols[0].label), ("scan", big_image, big_label)):
+        fns = (lambda: ops.aug_count_class_candidates(image, label, K, 0.0), lambda: ops.aug_count_candidates(image, label, 0.0))
+        for fn in fns:
+            fn()
+        torch.cuda.synchronize()
+        ms_cls, ms_cnt = timed_rounds(fns, 20, args.rounds)
+        result["per_volume"][name] = {"shape": tuple(image.shape), "count_class_candidates": summary(ms_cls),
+                                      "count_candidates": summary(ms_cnt)}
+        print(f"{tuple(image.shape)}: class tables {statistics.median(ms_cls):.4f} ms ({min(ms_cls):.4f} .. {max(ms_cls):.4f}), pos / neg "
+              f"tables {statistics.median(ms_cnt):.4f} ms ({min(ms_cnt):.4f} .. {max(ms_cnt):.4f})", flush=True)
+    result["value"] = result["batches"]["2"]["draw_classes_present_uniform_0.67"]["in_graph"]["median_ms"]
+    return result
+
+
 def torch_intensity(images, rows, out):
     """The contract of dua_aug_intensity_apply in whole-tensor torch operators, one sample at a time, from host rows
     (events, std, sigma, brightness, contrast, gamma)."""
@@ -370,6 +466,8 @@ def main():
     ap.add_argument("--smoothing", action="store_true", help="smoothed apply next to the one-hot apply, and the centroid pass")
     ap.add_argument("--onehot-lib", default="", help="with --smoothing: the build whose dua_aug_apply is the one-hot side")
     ap.add_argument("--affine", action="store_true", help="resampling apply next to the plain apply and to torch's grid_sample")
+    ap.add_argument("--classes", action="store_true", help="the draw with class ratios next to the draw without, and the class tables")
+    ap.add_argument("--parent-lib", default="", help="with --classes: another build of the library whose dua_aug_draw is timed beside")
     ap.add_argument("--intensity", action="store_true", help="the intensity stage next to next() without it and to torch operators")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -387,8 +485,8 @@ def main():
                 f.write(json.dumps(merged) + "\n")
         print(json.dumps(result))
         return
-    if args.smoothing or args.affine:
-        line = json.dumps(smoothing_bench(args) if args.smoothing else affine_bench(args))
+    if args.smoothing or args.affine or args.classes:
+        line = json.dumps(smoothing_bench(args) if args.smoothing else affine_bench(args) if args.affine else classes_bench(args))
         if args.out:
             with open(args.out, "w") as f:
                 f.write(line + "\n")
