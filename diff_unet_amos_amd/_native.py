@@ -290,6 +290,12 @@ _SIGS = {
     "dua_multi_neighbor_angles": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
     "dua_seg_loss_finish_mn": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P,
                                          _P]),
+    "dua_seg_loss_terms_scratch_bytes": (C.c_long, [C.c_int, C.c_int, C.c_long]),
+    "dua_seg_loss_terms_reduce": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P, C.c_long, _P]),
+    "dua_seg_loss_terms_finish": (C.c_int, [C.c_int, C.c_int, C.c_long] + [C.c_int] * 6 + [C.c_int, _P, C.c_int, _P, _P, _P, _P,
+                                            _P]),
+    "dua_seg_loss_terms_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P] + [C.c_int] * 6 +
+                                [_P, C.c_int, _P]),
     "dua_temb_train_fwd": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(TembBlocks), _P, _P, _P]),
     "dua_temb_train_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(TembBlocks), _P, _P, _P, _P, _P, _P, _P, _P]),
     "dua_grads_nonfinite": (C.c_int, [C.POINTER(AdamWList), _P, _P]),

@@ -695,8 +695,9 @@ LOSS_NAMES = ("mse", "bce", "dice")
 
 def seg_loss_reduce(logits, labels, names=LOSS_NAMES, combine="sum"):
     """logits: channels-last [N, D, H, W, Cs] (first C = labels.shape[1] channels); labels fp32 [N, C, D, H, W].
-    Loss of losses/loss.py:25-86 for ``names`` (a subset of SEG_LOSS_NAMES: mse / bce / dice / multi_neighbor, the last
-    with K = C classes) combined by "sum" / "mean" / "log".
+    Loss of losses/loss.py:25-86 for ``names`` (a subset of ALL_LOSS_NAMES: mse / bce / dice / multi_neighbor, the last
+    with K = C classes, and ce / dice_ce / generalized_dice) combined by "sum" / "mean" / "log".  A name set within
+    SEG_LOSS_NAMES takes the three-term kernels (csrc/seg_loss.hip); any of EXT_LOSS_NAMES takes csrc/seg_loss_terms.hip.
     Returns (L as a 0-dim fp32 tensor, the fp64 sums the gradient kernel needs, d L / d (sum of terms) as a 0-dim fp32
     device tensor -- 1 for "sum", 1/len(names) for "mean", 1/(1 + sum) for "log")."""
     assert logits.is_cuda and logits.is_contiguous() and logits.dim() == 5
@@ -704,7 +705,9 @@ def seg_loss_reduce(logits, labels, names=LOSS_NAMES, combine="sum"):
     V = labels.shape[2] * labels.shape[3] * labels.shape[4]
     assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous()
     assert tuple(logits.shape[:4]) == (N, *labels.shape[2:]) and logits.shape[-1] >= Cc
-    assert names and all(n_ in SEG_LOSS_NAMES for n_ in names) and combine in ("sum", "mean", "log")
+    assert names and all(n_ in ALL_LOSS_NAMES for n_ in names) and combine in ("sum", "mean", "log")
+    if any(n_ in EXT_LOSS_NAMES for n_ in names):
+        return _seg_loss_terms_reduce(logits, labels, names, combine)
     sums = zeros((N * Cc * 4 + 2,), torch.float64, logits.device)
     nv.check(nv.lib().dua_seg_loss_reduce(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1], nv.ptr(labels),
                                           nv.ptr(sums), nv.stream_ptr()), "dua_seg_loss_reduce")
@@ -716,11 +719,47 @@ def seg_loss_reduce(logits, labels, names=LOSS_NAMES, combine="sum"):
 # every name seg_loss_reduce accepts: LOSS_NAMES (the terms with a gradient, in seg_loss_grad's weight order) and
 # "multi_neighbor" (losses/loss.py:234-301: no gradient, it adds to the value and to the combine's count / total)
 SEG_LOSS_NAMES = LOSS_NAMES + ("multi_neighbor",)
+# the names only csrc/seg_loss_terms.hip computes (include/dua_hip.h, dua_seg_loss_terms_*), and every accepted name
+EXT_LOSS_NAMES = ("ce", "dice_ce", "generalized_dice")
+ALL_LOSS_NAMES = SEG_LOSS_NAMES + EXT_LOSS_NAMES
+TERM_LOSS_NAMES = LOSS_NAMES + EXT_LOSS_NAMES          # the gradient-carrying names in the order of the use_* flags
+
+
+def _terms_use(names):
+    return [int(n_ in names) for n_ in TERM_LOSS_NAMES]
+
+
+def _terms_consts(sums, N, Cc):
+    """The fp32 [N, C, 2] gradient constants that ride behind the N C 4 + 3 sums of the seg_loss_terms path (one buffer, so
+    that seg_loss_finish / seg_loss_grad keep their arguments)."""
+    assert sums.dtype == torch.float64 and sums.numel() == N * Cc * 5 + 3, "sums of another name set"
+    return sums[N * Cc * 4 + 3:].view(torch.float32)
+
+
+def _seg_loss_terms_reduce(logits, labels, names, combine):
+    N, Cc = labels.shape[:2]
+    V = labels.shape[2] * labels.shape[3] * labels.shape[4]
+    sums = zeros((N * Cc * 5 + 3,), torch.float64, logits.device)          # N C 4 + 3 sums, then N C 2 fp32 constants
+    nbytes = int(nv.lib().dua_seg_loss_terms_scratch_bytes(N, Cc, V))
+    assert nbytes > 0, "seg_loss: 1..64 channels, 1..65535 samples"
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    nv.check(nv.lib().dua_seg_loss_terms_reduce(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1],
+                                                nv.ptr(labels), nv.ptr(sums), nv.ptr(scratch), nbytes, nv.stream_ptr()),
+             "dua_seg_loss_terms_reduce")
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    return out[0], sums, seg_loss_finish(N, Cc, V, names, combine, sums, out,
+                                         multi_neighbor_partials(logits, labels) if "multi_neighbor" in names else None)
 
 
 def seg_loss_finish(N, Cc, V, names, combine, sums, out, mn=None):
     """The loss tail (losses/loss.py:64-86) into ``out`` = fp32 (L, d L / d total); ``mn``: multi_neighbor_partials(...) to
     count the multi_neighbor term among the terms, or None.  Returns out[1], d L / d total (0-dim)."""
+    if any(n_ in EXT_LOSS_NAMES for n_ in names):
+        nv.check(nv.lib().dua_seg_loss_terms_finish(N, Cc, V, *_terms_use(names), mn.shape[1] - 1 if mn is not None else 0,
+                                                    nv.ptr(mn), ("sum", "mean", "log").index(combine), nv.ptr(sums),
+                                                    nv.ptr(out[0:]), nv.ptr(out[1:]), nv.ptr(_terms_consts(sums, N, Cc)),
+                                                    nv.stream_ptr()), "dua_seg_loss_terms_finish")
+        return out[1]
     use = [int(n_ in names) for n_ in LOSS_NAMES]
     if mn is None:
         nv.check(nv.lib().dua_seg_loss_finish(N, Cc, V, *use, ("sum", "mean", "log").index(combine), nv.ptr(sums),
@@ -759,6 +798,12 @@ def seg_loss_grad(logits, labels, sums, gscale, names=LOSS_NAMES):
     V = labels.shape[2] * labels.shape[3] * labels.shape[4]
     out = zeros(tuple(logits.shape), logits.dtype, logits.device) if logits.shape[-1] > Cc else torch.empty_like(logits)
     g = gscale.detach().float().reshape(1).contiguous() if gscale is not None else None
+    if any(n_ in EXT_LOSS_NAMES for n_ in names):
+        nv.check(nv.lib().dua_seg_loss_terms_grad(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1],
+                                                  nv.ptr(labels), nv.ptr(_terms_consts(sums, N, Cc)), nv.ptr(g),
+                                                  *_terms_use(names), nv.ptr(out), out.shape[-1], nv.stream_ptr()),
+                 "dua_seg_loss_terms_grad")
+        return out
     w = [1.0 if n_ in names else 0.0 for n_ in LOSS_NAMES]
     nv.check(nv.lib().dua_seg_loss_grad(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1], nv.ptr(labels),
                                         nv.ptr(sums), nv.ptr(g), w[0], w[1], w[2], nv.ptr(out), out.shape[-1],

@@ -67,11 +67,12 @@ class _TembAdds(torch.autograd.Function):
 
 def parse_losses(losses="mse,bce,dice", loss_combine="sum"):
     """losses/loss.py:25-62: comma-separated loss names and the combine rule; the names the HIP loss kernels cover
-    (ops.SEG_LOSS_NAMES: mse, bce, dice and multi_neighbor, in any order -- cfg/amos/train.yaml's set is all four)."""
+    (ops.ALL_LOSS_NAMES: mse, bce, dice and multi_neighbor -- cfg/amos/train.yaml's set is all four -- and ce, dice_ce,
+    generalized_dice, in any order); every other name of loss.py:40-54 is refused with the reference's message."""
     names = tuple(losses.split(","))
-    from .ops import SEG_LOSS_NAMES
+    from .ops import ALL_LOSS_NAMES
     for n in names:
-        if n not in SEG_LOSS_NAMES:
+        if n not in ALL_LOSS_NAMES:
             raise NotImplementedError(f"Loss ({n}) is not listed yet")
     if loss_combine not in ("sum", "mean", "log"):
         raise NotImplementedError("Unsupported value for loss_combine. Please choose from 'sum', 'mean', or 'log'.")
@@ -389,8 +390,8 @@ class _Head(torch.autograd.Function):
 
 
 class _SegLoss(torch.autograd.Function):
-    """losses/loss.py:25-86 for any subset of mse / bce / dice / multi_neighbor under "sum" / "mean" / "log" on channels-last
-    logits: one reduce pass forward (plus the two multi_neighbor launches when that name is in use), one gradient pass
+    """losses/loss.py:25-86 for any subset of mse / bce / dice / multi_neighbor / ce / dice_ce / generalized_dice under "sum" /
+    "mean" / "log" on channels-last logits: one reduce pass forward (plus the two multi_neighbor launches when that name is in use), one gradient pass
     backward.  multi_neighbor has no gradient (its argmax cuts the graph): it reaches the backward only through dcomb, the
     derivative of the combine (1/count under "mean", 1/(1 + total) under "log")."""
 

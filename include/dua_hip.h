@@ -355,6 +355,54 @@ int dua_multi_neighbor_angles(int N, int K, const unsigned long long* csums, dou
 int dua_seg_loss_finish_mn(int N, int C, long voxels, int use_mse, int use_bce, int use_dice, int K, const double* mn_partials,
                            int combine, const double* sums, float* loss, float* dcomb, void* stream);
 
+/* The fused loss with "ce", "dice_ce" and "generalized_dice" (losses/loss.py:40-54) beside mse / bce / dice, forward and
+ * backward (csrc/seg_loss_terms.hip).  The entries above stay as they are; these are taken when one of the three names is in use.
+ *
+ * Operands as above: logits p channels-last [N][V][stride] (first C used, fp16 or fp32), labels y fp32 NCDHW [N][C][V],
+ * C <= 64.  Labels may be one-hot, all-zero at a voxel (background under include_background: false) or soft (the producer's
+ * label smoothing): NOTHING below assumes sum_c y_c = 1.
+ *
+ * ce = torch.nn.CrossEntropyLoss() with class-probability targets (what loss.py:42,75 calls for float labels of the logits'
+ *   shape):  ce = 1/(N V) sum_{n,v} [ Y_v lse_v - sum_c y_c p_c ],  Y_v = sum_c y_c,  lse_v = m + log sum_c exp(p_c - m),
+ *   m = max_c p_c;  d ce / d p_c = (Y_v softmax_c - y_c) / (N V).  The divisor is N V, not N C V.
+ * dice_ce = MONAI DiceCELoss(sigmoid=True) defaults: the dice term above plus ce (lambda_dice = lambda_ce = 1).  A float target
+ *   with the logits' channel count reaches CrossEntropyLoss as probabilities (MONAI >= 1.0; older releases took its argmax --
+ *   not implemented).  It is ONE term of the combine: under "mean" it counts once, alone it is returned as it is.  With
+ *   "dice" also selected the Dice part is in the total, and in the gradient, twice; likewise ce.
+ * generalized_dice = MONAI GeneralizedDiceLoss(sigmoid=True) defaults (w_type square, smooth_nr = smooth_dr = e = 1e-5,
+ *   batch=False, mean reduction) from the same I, S, Y per (n, c):  w_{n,c} = 1 / Y_{n,c}^2; where that is inf (class absent
+ *   from the sample) it is set to 0 and then replaced by the largest finite weight of the SAME sample (all stay 0 when every
+ *   weight of the sample was inf);  A_n = 2 sum_c w I + e,  B_n = sum_c w (S + Y) + e,  f_n = 1 - A_n / B_n,  mean over n.
+ *   w depends on labels only:  d / d p_{c,v} = s (1 - s) (k0 y + k1),  k0 = -2 w / (B N),  k1 = A w / (B^2 N).  A, B, w, k0, k1
+ *   are formed in fp64 from the fp64 sums and rounded ONCE to fp32 (a soft-label Y of 1e-3 gives w = 1e6).
+ * The combine ("sum" / "mean" / "log"), dcomb and the multi_neighbor term mean what they mean above.
+ *
+ * dua_seg_loss_terms_scratch_bytes: bytes of scratch the reduce needs: N * min(512, ceil(voxels / 256)) * (3 C + 3) doubles
+ *   (one row of partials per workgroup), or DUA_ERR_ARG.
+ * dua_seg_loss_terms_reduce: sums (fp64 [N C 4 + 3], WRITTEN, no need to zero) = per (n, c) (I, S, Y, 0), then (sum (s-y)^2,
+ *   sum of BCE terms, sum_{n,v} of the cross-entropy bracket) in ONE pass over logits and labels; lse by a running maximum over
+ *   the channel groups (exp only sees p - m <= 0).  Each workgroup writes its partials to scratch and a second launch adds them
+ *   in workgroup order: no floating-point atomics, the same inputs give the same bits.
+ * dua_seg_loss_terms_finish: loss[0] = L, dcomb[0] = dL/d(total) from sums for the selected names (use_* = 0 / 1 each, in the
+ *   order mse, bce, dice, ce, dice_ce, generalized_dice) and, when mn_partials is not NULL, the multi_neighbor term (fp64
+ *   [N][K + 1] of dua_multi_neighbor_angles) as one more term; consts (fp32 [N][C][2], written when dice, dice_ce or
+ *   generalized_dice is selected; may be NULL otherwise) = (k0, k1) of the gradient's (k0 y + k1) s (1 - s), the Dice part
+ *   (counted once per selecting name) and the generalized-Dice part added in fp64.  sums may be NULL when no use_* is set.
+ * dua_seg_loss_terms_grad: dlogits = *gscale * [ mse' + bce' + (k0 y + k1) s (1 - s) + ce' ] for the selected names (same
+ *   flags), same layout as logits; channels past C are not written.  A part whose names are not selected is skipped by a
+ *   branch, so its inf / NaN cannot reach the output.
+ * DUA_ERR_ARG: C > 64, N > 65535, a NULL operand, a flag other than 0 / 1, no term selected, a bad combine, stride < C,
+ *   scratch_bytes too small. */
+long dua_seg_loss_terms_scratch_bytes(int N, int C, long voxels);
+int dua_seg_loss_terms_reduce(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                              double* sums, void* scratch, long scratch_bytes, void* stream);
+int dua_seg_loss_terms_finish(int N, int C, long voxels, int use_mse, int use_bce, int use_dice, int use_ce, int use_dice_ce,
+                              int use_gdice, int K, const double* mn_partials, int combine, const double* sums, float* loss,
+                              float* dcomb, float* consts, void* stream);
+int dua_seg_loss_terms_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                            const float* consts, const float* gscale, int use_mse, int use_bce, int use_dice, int use_ce,
+                            int use_dice_ce, int use_gdice, void* dlogits, int dlogits_stride, void* stream);
+
 /* Timestep embedding under training (models/diffusion/utils.py:5-54, denoiser.py:51-52,65): for sample n
  *   e = [sin | cos](t[n] * freqs), z1 = W0 e + b0, h1 = swish(z1), z2 = W1 h1 + b1, s = swish(z2), add_b = Wp_b s + bp_b
  * for every TwoConv block b (its temb_proj).  ``add`` / ``dadd`` are BLOCK-MAJOR: block b's [N][cout_b] rows are contiguous

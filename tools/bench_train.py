@@ -1,6 +1,6 @@
 """Config 4 (training step, batch 2, 96^3, 16 classes) on the HIP training path (training.NativeConvTrainer): eager or
 as one replayed HIP graph.  One JSON line.
-Usage: python tools/bench_train.py [--steps K] [--graph] [--losses mse,bce,multi_neighbor,dice] [--loss-combine sum]"""
+Usage: python tools/bench_train.py [--steps K] [--graph] [--losses mse,bce,multi_neighbor,dice | mse,dice_ce,generalized_dice | ...] [--loss-combine sum]"""
 import argparse
 import json
 import os
@@ -21,7 +21,8 @@ ap.add_argument("--classes", type=int, default=16)
 ap.add_argument("--size", type=int, default=96)
 ap.add_argument("--dtype", default="float16")
 ap.add_argument("--graph", action="store_true", help="replay the whole training step as one HIP graph")
-ap.add_argument("--losses", default="mse,bce,dice", help="loss names (losses/loss.py); cfg/amos/train.yaml: mse,bce,multi_neighbor,dice")
+ap.add_argument("--losses", default="mse,bce,dice", help="loss names (losses/loss.py): any of mse, bce, dice, multi_neighbor, ce, dice_ce, generalized_dice; "
+                "cfg/amos/train.yaml: mse,bce,multi_neighbor,dice")
 ap.add_argument("--loss-combine", default="sum", choices=("sum", "mean", "log"))
 ap.add_argument("--no-gc", action="store_true", help="disable the Python cyclic GC during the timed loop (diagnosis)")
 ap.add_argument("--ab-wgrad", default="", help="comma list of weight-gradient launch forms (dua_conv3_desc.policy, ops.WGRAD_POLICY): time the loop once per value, same process")
