@@ -440,6 +440,18 @@ def wgrad_3kd_chain(P, total, dtype, partials):
     return main + (_cdiv(P, 4) + 3 if partials else P)
 
 
+def _tall_gemm(a, b):
+    """a^T b for a [V, m], b [V, n] with V in the hundreds of thousands: the long axis in up to 256 pieces (one batched GEMM, the pieces
+    added in fp64), since a library GEMM with an m x n output of a few tiles walks all of V on a few compute units."""
+    V = a.shape[0]
+    S = min(256, V // 4096)
+    if S < 2:
+        return a.t() @ b
+    V0 = V // S * S
+    out = torch.bmm(a[:V0].view(S, V0 // S, -1).transpose(1, 2), b[:V0].view(S, V0 // S, -1)).sum(0)
+    return out + a[V0:].t() @ b[V0:] if V0 < V else out
+
+
 def wgrad_ref(x, c_off, cin, dy, co_off, cout, cin_src=None, perm=None):
     """fp64 weight gradient of the 3x3x3 convolution as 27 shifted GEMMs on x's device (no fp64 convolution), in the
     reference layout [cout, cin_src, 3, 3, 3], and sum |x| |dy| per element.  x, dy: channels-last buffers (the kernel's exact
@@ -453,8 +465,8 @@ def wgrad_ref(x, c_off, cin, dy, co_off, cout, cin_src=None, perm=None):
     ab = torch.empty_like(ref)
     for t, (kd, kh, kw) in enumerate(itertools.product(range(3), repeat=3)):
         xs = xp[:, kd:kd + D, kh:kh + H, kw:kw + W].reshape(-1, cin)
-        ref[t] = g.t() @ xs
-        ab[t] = ga.t() @ xs.abs()
+        ref[t] = _tall_gemm(g, xs)
+        ab[t] = _tall_gemm(ga, xs.abs())
     ref, ab = ref.permute(1, 2, 0), ab.permute(1, 2, 0)          # [cout, cin packed, 27]
     if perm is None:
         cs = cin if cin_src is None else cin_src

@@ -1,7 +1,11 @@
 """Training side of the hot path (training.py): the reference's training step (train.py:258-268) runs through the
 drop-in boundary ``DiffUNet.forward`` on the HIP forward + backward kernels; its logits, loss and every parameter
 gradient match the CPU oracle under torch autograd; the fused loss covers the reference's loss configurations; the
-one-process-per-rank gradient averaging equals single-process training on the union batch."""
+one-process-per-rank gradient averaging equals single-process training on the union batch.
+
+The fp16 path's aggregates here (whole-gradient relative L2, lowest cosine) are end-to-end smoke: they are dominated by the large
+weight tensors and blind to scale.  The per-tensor guarantee for that path lives in tests/test_train_step_fp64.py: every launch of a
+step against fp64 on the operands it read, and the wiring of every operand and of every parameter's gradient (tests/train_trace.py)."""
 import os
 import re
 
