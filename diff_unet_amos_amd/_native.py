@@ -152,6 +152,15 @@ class AdamWList(C.Structure):
     _fields_ = [("count", C.c_int), ("numel", C.c_long * ADAMW_MAX_TENSORS), ("p", C.c_void_p * ADAMW_MAX_TENSORS),
                 ("g", C.c_void_p * ADAMW_MAX_TENSORS), ("m", C.c_void_p * ADAMW_MAX_TENSORS), ("v", C.c_void_p * ADAMW_MAX_TENSORS)]
 
+
+ADAMW_CHUNK = 4096        # DUA_ADAMW_CHUNK
+
+
+class AdamWEma(C.Structure):
+    """dua_adamw_ema."""
+    _fields_ = [("e", C.c_void_p * ADAMW_MAX_TENSORS)]
+
+
 class AugVolume(C.Structure):
     """dua_aug_volume: one 64-byte row of the device table of volumes."""
     _fields_ = [("image", C.c_void_p), ("label", C.c_void_p), ("fg_prefix", C.c_void_p), ("bg_prefix", C.c_void_p),
@@ -302,6 +311,11 @@ _SIGS = {
     "dua_adamw_step": (C.c_int, [C.POINTER(AdamWList), C.c_float, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
                                  C.c_int, _P]),
     "dua_adamw_advance": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_int, _P, _P]),
+    "dua_adamw_blocks": (C.c_long, [C.POINTER(AdamWList)]),
+    "dua_grads_sumsq": (C.c_int, [C.POINTER(AdamWList), _P, _P]),
+    "dua_grad_norm_finish": (C.c_int, [_P, C.c_long, _P, C.c_float, _P, _P, _P, _P]),
+    "dua_adamw_step_ex": (C.c_int, [C.POINTER(AdamWList), C.c_float, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P,
+                                    C.c_int, _P, C.POINTER(AdamWEma), C.c_float, _P]),
     "dua_surface_scratch_bytes": (C.c_long, [C.c_int] * 4),
     "dua_surface_masks": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, _P, C.c_int, C.c_long, C.c_int, _P, C.c_long, _P, _P]),
     "dua_surface_edt_sq": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P]),

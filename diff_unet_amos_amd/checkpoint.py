@@ -65,3 +65,23 @@ def load_checkpoint(model_path, model, optimizer=None, scheduler=None, map_locat
             obj.load_state_dict(state[key])
     return {"start_epoch": state["epoch"], "noise_ratio": state["noise_ratio"], "project_name": state["project_name"],
             "global_step": state["global_step"], "best_mean_dice": state["best_mean_dice"], "wandb_id": state["id"]}
+
+
+def ema_filename(rate, step) -> str:
+    """guided_diffusion/train_util.py:232-246: the EMA weights of rate ``rate`` after ``step`` steps."""
+    return f"ema_{rate}_{step:06d}.pt"
+
+
+def save_ema(save_dir, ema_state, rate, step) -> str:
+    """Writes an EMA state dict (``NativeConvTrainer.ema_state_dict()``) under the reference's file name; returns the path.  The
+    file is a plain state dict, as the reference's: it loads into the model with ``load_state_dict``."""
+    if save_dir:
+        os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, ema_filename(rate, step))
+    torch.save(dict(ema_state), path)
+    return path
+
+
+def load_ema(path, map_location=None) -> dict:
+    """The state dict ``save_ema`` wrote (tensors only: read with ``weights_only=True``)."""
+    return torch.load(path, map_location=map_location, weights_only=True)

@@ -9,6 +9,8 @@
 //   temb_train_*         TimeStepEmbedder + swish + the nine temb_proj (utils.py:5-54, denoiser.py:51-52,65), forward and
 //                        backward (eleven Linear layers = 33 library GEMMs, their bias reductions and gradient sums before)
 //   grads_nonfinite / adamw_* torch.cuda.amp's unscale + inf check, torch.optim.AdamW and the loss-scale update (train.py:121-126,264-268)
+//   grads_sumsq / grad_norm_finish / adamw_step_ex  the global gradient norm (which is also the overflow test), clip_grad_norm_'s
+//                        coefficient and the EMA of the weights (guided_diffusion's update_ema) inside the AdamW launch
 // All of it is fp32 (fp64 where the torch code it replaces was), bandwidth- or latency-bound, deterministic (no floating-point atomics).
 #include "common.hpp"
 #include "../../include/dua_hip.h"
@@ -342,7 +344,7 @@ __global__ __launch_bounds__(256) void temb_bwd_outer_kernel(int N, int half, in
 }
 
 // ---- AdamW over a list of tensors ---------------------------------------------------------------------------------------------
-constexpr int AD_CHUNK = 4096;          // elements per workgroup: 256 threads x 4 x 16-byte pieces
+constexpr int AD_CHUNK = DUA_ADAMW_CHUNK;          // elements per workgroup: 256 threads x 4 x 16-byte pieces
 struct AdamArgs {
   dua_adamw_list l;
   int first_block[DUA_ADAMW_MAX_TENSORS + 1];
@@ -385,9 +387,14 @@ __device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, 
   p -= step_size * m / denom;
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, float lr, const float* lr_dev, float beta1, float beta2, float eps,
-                                                    float wd, const float* grad_scale, const float* found_inf, const int* step,
-                                                    int store_grad) {
+// adamw_kernel with two compile-time options.  CLIP: g' = fl(fl(g inv) c) with c = *clip_coef (unscale, clip, step: the order of
+// torch's unscale_ + clip_grad_norm_ + step).  EMA: e' = fl(e + fl(w fl(p' - e))) on the updated p (update_ema of the reference,
+// guided_diffusion/nn.py:55-65, in the lerp form the first moment uses: rate * e at rate 0.9999 would lose w e to rounding).
+// <false, false> is adamw_kernel as it was: the same operations on the same operands in the same order.
+template <bool CLIP, bool EMA>
+__device__ __forceinline__ void adamw_body(const AdamArgs& a, float lr, const float* lr_dev, float beta1, float beta2, float eps, float wd,
+                                           const float* grad_scale, const float* found_inf, const int* step, int store_grad,
+                                           const float* clip_coef, float* const* ema, float ema_w) {
   if (found_inf && *found_inf != 0.f) return;
   __shared__ float cst[2];
   if (threadIdx.x == 0) {
@@ -398,6 +405,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, float lr, const 
   __syncthreads();
   if (lr_dev) lr = *lr_dev;
   const float inv = grad_scale ? 1.f / *grad_scale : 1.f;
+  const float c = CLIP ? *clip_coef : 1.f;
   const float lr_wd = lr * wd, w1 = 1.f - beta1, w2 = 1.f - beta2, step_size = lr / cst[0], bc2s = cst[1];
   const int ti = adam_find(a, blockIdx.x);
   const long off = (long)(blockIdx.x - a.first_block[ti]) * AD_CHUNK;
@@ -406,29 +414,123 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, float lr, const 
   float* g = a.l.g[ti] + off;
   float* m = a.l.m[ti] + off;
   float* v = a.l.v[ti] + off;
+  float* e = EMA ? ema[ti] + off : nullptr;
   long done = 0;
-  if (((((size_t)p) | ((size_t)g) | ((size_t)m) | ((size_t)v)) & 15) == 0) {
+  if (((((size_t)p) | ((size_t)g) | ((size_t)m) | ((size_t)v) | ((size_t)e)) & 15) == 0) {
     const long n4 = n >> 2;
     for (long i = threadIdx.x; i < n4; i += 256) {
       f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], gv = ((const f32x4*)g)[i];
+      f32x4 ev;
+      if (EMA) ev = ((f32x4*)e)[i];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float gq = gv[q] * inv;
+        float gq = gv[q] * inv;
+        if (CLIP) gq = gq * c;
         float pq = pv[q], mq = mv[q], vq = vv[q];
         adam_one(pq, mq, vq, gq, lr_wd, w1, beta2, w2, step_size, bc2s, eps);
         pv[q] = pq; mv[q] = mq; vv[q] = vq; gv[q] = gq;
+        if (EMA) ev[q] = ev[q] + ema_w * (pq - ev[q]);
       }
       ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
       if (store_grad) ((f32x4*)g)[i] = gv;
+      if (EMA) ((f32x4*)e)[i] = ev;
     }
     done = n4 << 2;
   }
   for (long i = done + threadIdx.x; i < n; i += 256) {
     float pv = p[i], mv = m[i], vv = v[i];
-    const float gv = g[i] * inv;
+    float gv = g[i] * inv;
+    if (CLIP) gv = gv * c;
     adam_one(pv, mv, vv, gv, lr_wd, w1, beta2, w2, step_size, bc2s, eps);
     p[i] = pv; m[i] = mv; v[i] = vv;
     if (store_grad) g[i] = gv;
+    if (EMA) { const float ev = e[i]; e[i] = ev + ema_w * (pv - ev); }
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                                    float wd, const float* grad_scale, const float* found_inf, const int* step,
+                                                    int store_grad) {
+  adamw_body<false, false>(a, lr, lr_dev, beta1, beta2, eps, wd, grad_scale, found_inf, step, store_grad, nullptr, nullptr, 0.f);
+}
+
+// the list and the EMA pointers by value: 2 832 + 512 bytes of the 4 KB a launch may carry (one EMA rate per launch)
+struct AdamExArgs {
+  AdamArgs a;
+  dua_adamw_ema e;
+};
+// + 96: the scalars and pointers after the struct; + 256: the implicit arguments the runtime appends
+static_assert(sizeof(AdamExArgs) + 96 + 256 <= 4096, "kernel arguments of adamw_ex_kernel");
+
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adamw_ex_kernel(AdamExArgs x, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                                       float wd, const float* grad_scale, const float* found_inf, const int* step,
+                                                       int store_grad, const float* clip_coef, float ema_w) {
+  adamw_body<CLIP, EMA>(x.a, lr, lr_dev, beta1, beta2, eps, wd, grad_scale, found_inf, step, store_grad, clip_coef, x.e.e, ema_w);
+}
+
+// ---- global gradient norm ----------------------------------------------------------------------------------------------------
+// partials[b] = sum of (double)g (double)g over workgroup b's chunk (grads_nonfinite_kernel's grid; every product is exact in
+// fp64).  The value depends on the chunk's element values only, never on the address: lane t owns the elements i of the chunk
+// with (i >> 2) & 255 == t, adds them in ascending i whether they arrive as one 16-byte piece or as four scalars, then the
+// fixed wave butterfly and the wave-order LDS combine -- every rank derives the same clip coefficient to the bit.
+__device__ __forceinline__ double tg_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void grads_sumsq_kernel(AdamArgs a, double* __restrict__ partials) {
+  __shared__ double ws[4];
+  const int ti = adam_find(a, blockIdx.x);
+  const long off = (long)(blockIdx.x - a.first_block[ti]) * AD_CHUNK;
+  const int n = (int)min((long)AD_CHUNK, a.l.numel[ti] - off);
+  const float* g = a.l.g[ti] + off;
+  const bool vec = (((size_t)g) & 15) == 0;
+  float x[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e0 = (j * 256 + (int)threadIdx.x) * 4;
+    if (vec && e0 + 4 <= n) {
+      const f32x4 v = *(const f32x4*)(g + e0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[j][q] = v[q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[j][q] = e0 + q < n ? g[e0 + q] : 0.f;
+    }
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc += (double)x[j][q] * (double)x[j][q];
+  acc = tg_wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// S = the partials in a fixed order (thread t: t, t + 256, ..; butterfly; waves in order);  norm = (float)(sqrt(S) / scale);
+// coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_);  S not finite: the overflow flag, coef = 0
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, long count, const float* grad_scale,
+                                                               float max_norm, float* norm, float* coef, float* found_inf) {
+  __shared__ double ws[4];
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < count; i += 256) acc += partials[i];
+  acc = tg_wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double S = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+  const double scale = grad_scale ? (double)*grad_scale : 1.0;
+  const float nf = (float)(sqrt(S) / scale);
+  *norm = nf;
+  if (!isfinite(S)) {
+    if (found_inf) *found_inf = 1.f;
+    *coef = 0.f;
+  } else {
+    *coef = fminf(1.f, max_norm / (nf + 1e-6f));
   }
 }
 
@@ -576,6 +678,57 @@ int dua_adamw_step(const dua_adamw_list* list, float lr, const float* lr_dev, fl
     if (!list->p[i] || !list->m[i] || !list->v[i]) return DUA_ERR_ARG;
   hipLaunchKernelGGL(dua::adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, lr, lr_dev, beta1, beta2, eps,
                      weight_decay, grad_scale, found_inf, step, store_grad);
+  return (int)hipGetLastError();
+}
+
+long dua_adamw_blocks(const dua_adamw_list* list) {
+  dua::AdamArgs a;
+  const int blocks = dua::adam_args(list, a);
+  return blocks <= 0 ? (long)DUA_ERR_ARG : (long)blocks;
+}
+
+int dua_grads_sumsq(const dua_adamw_list* list, double* partials, void* stream) {
+  dua::AdamArgs a;
+  const int blocks = dua::adam_args(list, a);
+  if (blocks <= 0 || !partials) return DUA_ERR_ARG;
+  hipLaunchKernelGGL(dua::grads_sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, partials);
+  return (int)hipGetLastError();
+}
+
+int dua_grad_norm_finish(const double* partials, long count, const float* grad_scale, float max_norm, float* norm, float* coef,
+                         float* found_inf, void* stream) {
+  if (!partials || count <= 0 || !(max_norm > 0.f) || !norm || !coef) return DUA_ERR_ARG;
+  hipLaunchKernelGGL(dua::grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, count, grad_scale, max_norm,
+                     norm, coef, found_inf);
+  return (int)hipGetLastError();
+}
+
+int dua_adamw_step_ex(const dua_adamw_list* list, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                      float weight_decay, const float* grad_scale, const float* found_inf, const int* step, int store_grad,
+                      const float* clip_coef, const dua_adamw_ema* ema, float ema_weight, void* stream) {
+  if (!clip_coef && !ema)
+    return dua_adamw_step(list, lr, lr_dev, beta1, beta2, eps, weight_decay, grad_scale, found_inf, step, store_grad, stream);
+  dua::AdamExArgs x;
+  const int blocks = dua::adam_args(list, x.a);
+  if (blocks <= 0 || !step || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f)) return DUA_ERR_ARG;
+  for (int i = 0; i < list->count; ++i)
+    if (!list->p[i] || !list->m[i] || !list->v[i]) return DUA_ERR_ARG;
+  if (ema) {
+    if (!(ema_weight > 0.f && ema_weight <= 1.f)) return DUA_ERR_ARG;
+    for (int i = 0; i < list->count; ++i)
+      if (!ema->e[i]) return DUA_ERR_ARG;
+    x.e = *ema;
+  } else {
+    x.e = dua_adamw_ema{};
+  }
+  const hipStream_t st = (hipStream_t)stream;
+#define DUA_ADAMW_EX(CLIP, EMA)                                                                                                  \
+  hipLaunchKernelGGL((dua::adamw_ex_kernel<CLIP, EMA>), dim3(blocks), dim3(256), 0, st, x, lr, lr_dev, beta1, beta2, eps, weight_decay, \
+                     grad_scale, found_inf, step, store_grad, clip_coef, ema_weight)
+  if (clip_coef && ema) DUA_ADAMW_EX(true, true);
+  else if (clip_coef) DUA_ADAMW_EX(true, false);
+  else DUA_ADAMW_EX(false, true);
+#undef DUA_ADAMW_EX
   return (int)hipGetLastError();
 }
 

@@ -1144,16 +1144,72 @@ def grads_nonfinite(grads, found_inf):
         nv.check(L.dua_grads_nonfinite(C.byref(l), nv.ptr(found_inf), nv.stream_ptr()), "dua_grads_nonfinite")
 
 
+def grad_norm_partials(grads):
+    """How many fp64 partials ``grad_norm`` needs for ``grads``: one per 4096-element chunk of every tensor."""
+    return sum(-(-g.numel() // nv.ADAMW_CHUNK) for g in grads)
+
+
+def grad_norm(grads, max_norm, grad_scale=None, found_inf=None, norm=None, coef=None, partials=None):
+    """(norm, coef), fp32 device scalars: the global L2 norm of ``grads`` / grad_scale and torch.nn.utils.clip_grad_norm_'s
+    coefficient min(1, max_norm / (norm + 1e-6)) (``max_norm`` = inf: 1, the norm as a logged quantity).  An Inf / NaN element
+    sets ``found_inf`` (never written otherwise) and coef = 0: this pass is also the overflow check of a loss-scaled step, in
+    place of grads_nonfinite.  Deterministic and independent of the tensors' alignment.  What is not passed is allocated;
+    callers inside a stream capture pass ``norm``, ``coef`` and ``partials`` (fp64, >= grad_norm_partials(grads))."""
+    dev = grads[0].device
+    count = grad_norm_partials(grads)
+    norm = torch.empty((), dtype=torch.float32, device=dev) if norm is None else norm
+    coef = torch.empty((), dtype=torch.float32, device=dev) if coef is None else coef
+    partials = torch.empty(count, dtype=torch.float64, device=dev) if partials is None else partials
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= count
+    for t in (norm, coef, found_inf, grad_scale):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32)
+    L = nv.lib()
+    done = 0
+    for l in _adamw_lists([None] * len(grads), grads, None, None):
+        nv.check(L.dua_grads_sumsq(C.byref(l), C.c_void_p(partials.data_ptr() + 8 * done), nv.stream_ptr()), "dua_grads_sumsq")
+        done += L.dua_adamw_blocks(C.byref(l))
+    assert done == count
+    nv.check(L.dua_grad_norm_finish(nv.ptr(partials), count, nv.ptr(grad_scale), float(max_norm), nv.ptr(norm), nv.ptr(coef),
+                                    nv.ptr(found_inf), nv.stream_ptr()), "dua_grad_norm_finish")
+    return norm, coef
+
+
+def ema_weight(rate):
+    """1 - rate of an EMA, formed in double (the C ABI rounds it to fp32 once; 1.f - rate in fp32 is 1.7e-4 off at 0.9999)."""
+    return 1.0 - float(rate)
+
+
 def adamw_step(params, grads, ms, vs, step, lr, betas, eps, weight_decay, lr_dev=None, grad_scale=None, found_inf=None,
-               store_grad=False):
+               store_grad=False, clip_coef=None, ema=None, ema_rate=None):
     """One AdamW update of every tensor (torch.optim.AdamW's arithmetic, train.py:121-122) with k = step + 1; ``step``: int32
-    device scalar, not advanced here (adamw_advance)."""
+    device scalar, not advanced here (adamw_advance).  ``clip_coef`` (fp32 device scalar, grad_norm's): multiplies the
+    unscaled gradient; ``ema`` (tensors parallel to ``params``) with ``ema_rate``: e += (1 - rate)(p - e) on the updated p, in
+    the same launch (skipped with the update when ``found_inf`` is set)."""
     assert step.is_cuda and step.dtype == torch.int32
     L = nv.lib()
-    for l in _adamw_lists(params, grads, ms, vs):
-        nv.check(L.dua_adamw_step(C.byref(l), float(lr), nv.ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps),
-                                  float(weight_decay), nv.ptr(grad_scale), nv.ptr(found_inf), nv.ptr(step), int(store_grad),
-                                  nv.stream_ptr()), "dua_adamw_step")
+    if clip_coef is None and ema is None:
+        for l in _adamw_lists(params, grads, ms, vs):
+            nv.check(L.dua_adamw_step(C.byref(l), float(lr), nv.ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps),
+                                      float(weight_decay), nv.ptr(grad_scale), nv.ptr(found_inf), nv.ptr(step), int(store_grad),
+                                      nv.stream_ptr()), "dua_adamw_step")
+        return
+    assert clip_coef is None or (clip_coef.is_cuda and clip_coef.dtype == torch.float32)
+    w = 0.0
+    if ema is not None:
+        assert ema_rate is not None and 0.0 <= float(ema_rate) < 1.0 and len(ema) == len(params)
+        w = ema_weight(ema_rate)
+    for n, l in enumerate(_adamw_lists(params, grads, ms, vs)):
+        e = None
+        if ema is not None:
+            e = nv.AdamWEma()
+            for j in range(l.count):
+                t = ema[n * nv.ADAMW_MAX_TENSORS + j]
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == l.numel[j]
+                e.e[j] = t.data_ptr()
+        nv.check(L.dua_adamw_step_ex(C.byref(l), float(lr), nv.ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps),
+                                     float(weight_decay), nv.ptr(grad_scale), nv.ptr(found_inf), nv.ptr(step), int(store_grad),
+                                     nv.ptr(clip_coef), C.byref(e) if e is not None else None, w, nv.stream_ptr()),
+                 "dua_adamw_step_ex")
 
 
 def adamw_advance(step, found_inf=None, scale=None, growth=None, growth_factor=2.0, backoff=0.5, interval=200, seen=None):

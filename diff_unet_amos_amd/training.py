@@ -529,12 +529,21 @@ class NativeAdamW(torch.optim.Optimizer):
                     self._counter(p.device)
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=None, found_inf=None, store_grad=False, advance=True):
+    def step(self, closure=None, grad_scale=None, found_inf=None, store_grad=False, advance=True, clip_coef=None, ema=None,
+             ema_rate=None):
         """``grad_scale`` / ``found_inf``: fp32 device scalars of a loss-scaled step (see ops.adamw_step); ``advance=False`` leaves
-        the update counter to the caller's ops.adamw_advance (which also applies the loss-scale rule)."""
+        the update counter to the caller's ops.adamw_advance (which also applies the loss-scale rule).  ``clip_coef``: fp32
+        device scalar of ops.grad_norm; ``ema``: one tensor per parameter of the groups, in their order, updated at ``ema_rate``
+        in the same launch.  The EMA tensors belong to the caller: they are no optimizer state, ``state_dict()`` keeps
+        torch.optim.AdamW's layout."""
         from . import ops
         assert closure is None
         count = None
+        shadow = None
+        if ema is not None:
+            every = [p for group in self.param_groups for p in group["params"]]
+            assert len(ema) == len(every)
+            shadow = {p: e for p, e in zip(every, ema)}
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -543,7 +552,8 @@ class NativeAdamW(torch.optim.Optimizer):
             count = self._counter(ps[0].device)
             ops.adamw_step([p.data for p in ps], [p.grad for p in ps], [m for m, _ in mv], [v for _, v in mv], count, group["lr"],
                            group["betas"], group["eps"], group["weight_decay"], lr_dev=self.lr_dev, grad_scale=grad_scale,
-                           found_inf=found_inf, store_grad=store_grad)
+                           found_inf=found_inf, store_grad=store_grad, clip_coef=clip_coef,
+                           ema=None if shadow is None else [shadow[p] for p in ps], ema_rate=ema_rate)
         if advance and count is not None:
             ops.adamw_advance(count)
 
@@ -603,11 +613,17 @@ class NativeConvTrainer:
     runs; RCCL on a GPU node) or by one flat all-reduce after backward (``overlap=False``).
     ``graph=True`` replays the step from HIP graphs: one graph single-process; under torch.distributed TWO graphs
     (forward + backward | unscale + AdamW + loss-scale update) with the flat gradient all-reduce between them -- the
-    collective stays an ordinary call, so any backend works (RCCL on a node, gloo in the tests)."""
+    collective stays an ordinary call, so any backend works (RCCL on a node, gloo in the tests).
+    ``max_grad_norm``: clip the global L2 norm of the (averaged, unscaled) gradient as torch.nn.utils.clip_grad_norm_ does;
+    ``float("inf")`` only measures it (``grad_norm()``).  ``ema_rate``: keep an exponential moving average of the weights
+    (``self.ema``, parallel to ``self.params``; guided_diffusion/train_util.py:86-89, 216-218), updated only on steps that are
+    taken.  On the library's optimizer both ride in the step's own launches (ops.grad_norm takes the place of the overflow
+    check, ops.adamw_step clips and averages), so a captured step replays them; ``fused_optimizer=False`` runs them in torch
+    operators.  Both default to None: the step is then launch for launch what it was."""
 
     def __init__(self, net, lr=2e-4, weight_decay=1e-4, losses="mse,bce,dice", loss_combine="sum",
                  dtype=torch.float16, init_scale=2.0 ** 12, overlap=True, graph=False, fused_optimizer=True,
-                 wgrad_overlap=True):
+                 wgrad_overlap=True, max_grad_norm=None, ema_rate=None):
         import torch.distributed as dist
         self.net, self.dtype = net, dtype
         self.lr, self.weight_decay, self.init_scale = lr, weight_decay, init_scale
@@ -627,6 +643,15 @@ class NativeConvTrainer:
             raise ValueError("losses='multi_neighbor' alone has no gradient (its argmax cuts the graph): nothing to train; "
                              "combine it with mse / bce / dice")
         self.params = [p for p in net.parameters() if p.requires_grad]
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be positive (inf: measure only), got {max_grad_norm}")
+        if ema_rate is not None and not 0.0 <= float(ema_rate) < 1.0:
+            raise ValueError(f"ema_rate must be in [0, 1), got {ema_rate}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_rate = None if ema_rate is None else float(ema_rate)
+        self._param_names = [k for k, p in net.named_parameters() if p.requires_grad]
+        self.ema = [p.detach().clone() for p in self.params] if ema_rate is not None else None
+        self._gn, self._torch_norm, self._torch_coef = None, None, None
         # graph mode always uses the library's AdamW; ``fused_optimizer=False`` selects torch.optim.AdamW for eager steps
         self.native_opt = bool(fused_optimizer or graph)
         self.optimizer = (NativeAdamW(self.params, lr=lr, weight_decay=weight_decay) if self.native_opt
@@ -640,6 +665,10 @@ class NativeConvTrainer:
             from . import _native
             _native.prepare(dev)         # every kernel's function attributes: before the first launch, before any capture, and
                                          # before autograd's worker thread (which issues the backward launches) exists
+        if self.max_grad_norm is not None and self.native_opt and dev.type == "cuda":
+            # the norm, the clip coefficient and the per-chunk partials: allocated here, before any capture
+            self._gn = dict(norm=torch.zeros((), device=dev), coef=torch.ones((), device=dev),
+                            partials=torch.zeros(ops.grad_norm_partials(self.params), dtype=torch.float64, device=dev))
         self.arena = ops.ZeroArena(sum(p.numel() for p in self.params) * 4 + (96 << 20), dev) if dev.type == "cuda" else None
         # weight gradients on a side stream (see _wgrad); not under the DDP reducer, whose hooks read them on the main stream --
         # and NOT in graph mode: a captured fork / join makes the step a multi-branch HIP graph, and hipGraphLaunch of such a
@@ -676,14 +705,26 @@ class NativeConvTrainer:
                     (loss * g["scale"]).backward()
         return loss.detach()
 
+    def _native_update(self, scale, flag, growth, seen, store_grad=False):
+        """Overflow check (or, with ``max_grad_norm``, the norm pass that is also the overflow check), AdamW with the unscale,
+        the clip and the EMA in its launch, then the counter and the loss-scale rule: after the all-reduce, so the norm is the
+        averaged gradient's and every rank derives the same coefficient."""
+        from . import ops
+        grads = [p.grad for p in self.params]
+        clip = None
+        if self._gn is not None:
+            _, clip = ops.grad_norm(grads, self.max_grad_norm, grad_scale=scale, found_inf=flag, **self._gn)
+        else:
+            ops.grads_nonfinite(grads, flag)
+        self.optimizer.step(grad_scale=scale, found_inf=flag, store_grad=store_grad, advance=False, clip_coef=clip, ema=self.ema,
+                            ema_rate=self.ema_rate)
+        ops.adamw_advance(self.optimizer._count, flag, scale, growth, 2.0, 0.5, 200, seen=seen)
+
     def _graph_update(self):
         g = self._g
-        from . import ops
         # found_inf is zero on entry (zero-initialised, cleared again by adamw_advance at the end of every step)
         # (g["found_inf"] is what the host reads: the flag the last completed step saw)
-        ops.grads_nonfinite([p.grad for p in self.params], g["found_flag"])
-        self.optimizer.step(grad_scale=g["scale"], found_inf=g["found_flag"], advance=False)
-        ops.adamw_advance(self.optimizer._count, g["found_flag"], g["scale"], g["growth"], 2.0, 0.5, 200, seen=g["found_inf"])
+        self._native_update(g["scale"], g["found_flag"], g["growth"], g["found_inf"])
 
     def _graph_body(self):
         loss = self._graph_fwd_bwd()
@@ -710,6 +751,7 @@ class NativeConvTrainer:
         # ... and the optimizer state as it is NOW: a checkpoint loaded before the first step (load_checkpoint ->
         # optimizer.load_state_dict) must survive the warm-up updates below
         saved_opt = self.optimizer.snapshot_state()
+        saved_ema = [e.clone() for e in self.ema] if self.ema is not None else None
         # Warm-up ON the capture stream: the per-(device, stream) scratch buffers of ops (split-K, weight-gradient partials)
         # are then allocated here, from the ordinary pool, and the capture finds them -- allocated inside the capture they
         # would live in this graph's private pool while the module-level cache hands them to every later capture.
@@ -739,6 +781,9 @@ class NativeConvTrainer:
             for p, q in zip(self.params, saved):
                 p.copy_(q)
             self.optimizer.restore_state(saved_opt)
+            if saved_ema is not None:
+                for e, q in zip(self.ema, saved_ema):
+                    e.copy_(q)
             self._g["found_inf"].zero_(); self._g["found_flag"].zero_()
             self._g["scale"].fill_(self.init_scale if self.dtype == torch.float16 else 1.0)
             self._g["growth"].zero_()
@@ -766,11 +811,14 @@ class NativeConvTrainer:
         return g["loss"]
 
     def _amp_state(self):
-        """Device-resident loss-scaling state of eager fp16 steps on the library's AdamW: scale, growth counter, this step's
-        overflow flag and the flag the last completed step saw (``loss_scale()`` / ``last_step_overflowed()`` read them back)."""
+        """Device-resident loss-scaling state of eager steps on the library's AdamW: scale, growth counter, this step's
+        overflow flag and the flag the last completed step saw (``loss_scale()`` / ``last_step_overflowed()`` read them back).
+        fp16 steps use all of it; fp32 steps with ``max_grad_norm`` or ``ema_rate`` use the two flags only (a non-finite
+        gradient skips the update and the EMA there too), the scale stays 1."""
         if self._amp is None:
             dev = self.params[0].device
-            self._amp = dict(scale=torch.full((), float(self.init_scale), device=dev), growth=torch.zeros((), dtype=torch.int32, device=dev),
+            scale = float(self.init_scale) if self.dtype == torch.float16 else 1.0      # fp32 steps use the flags only
+            self._amp = dict(scale=torch.full((), scale, device=dev), growth=torch.zeros((), dtype=torch.int32, device=dev),
                              flag=torch.zeros((), device=dev), seen=torch.zeros((), device=dev))
         return self._amp
 
@@ -820,10 +868,13 @@ class NativeConvTrainer:
             # dynamic loss scaling without a host decision (the eager step used to read found_inf back -- one synchronisation per
             # step, which also kept the host from running ahead of the device under the DDP reducer): overflow flag, skipped update,
             # scale and growth counter live on the device exactly as in the captured step
-            from . import ops
-            ops.grads_nonfinite([p.grad for p in self.params], amp["flag"])
-            self.optimizer.step(grad_scale=amp["scale"], found_inf=amp["flag"], store_grad=True, advance=False)
-            ops.adamw_advance(self.optimizer._count, amp["flag"], amp["scale"], amp["growth"], 2.0, 0.5, 200, seen=amp["seen"])
+            self._native_update(amp["scale"], amp["flag"], amp["growth"], amp["seen"], store_grad=True)
+            return loss.detach()
+        extras = self.max_grad_norm is not None or self.ema is not None
+        if extras and self.native_opt:
+            # fp32 on the library's optimizer: no loss scale, but the norm pass still raises the flag that skips a non-finite step
+            st = self._amp_state()
+            self._native_update(None, st["flag"], None, st["seen"])
             return loss.detach()
         if self.dtype == torch.float16:
             dev = self.params[0].device
@@ -833,9 +884,78 @@ class NativeConvTrainer:
             torch._amp_foreach_non_finite_check_and_unscale_(grads, found_inf, inv)      # torch.optim.AdamW path (fused_optimizer=False)
             if bool(found_inf.item()):                                           # overflow: skip, halve the scale
                 self.scale, self.good_steps = max(self.scale / 2, 2.0 ** -14), 0
+                self._torch_norm, self._torch_coef = float("nan"), 0.0
                 return loss.detach()
             self.good_steps += 1
             if self.good_steps >= 200:
                 self.scale, self.good_steps = self.scale * 2, 0
+        if self.max_grad_norm is not None:
+            # the torch-operator form: clip_grad_norm_ on the unscaled gradients ...
+            total = torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+            self._torch_norm = float(total)
+            self._torch_coef = min(1.0, self.max_grad_norm / (self._torch_norm + 1e-6))
         self.optimizer.step()
+        if self.ema is not None:
+            # ... and update_ema (guided_diffusion/nn.py:55-65) after the step
+            with torch.no_grad():
+                for e, p in zip(self.ema, self.params):
+                    e.mul_(self.ema_rate).add_(p.detach(), alpha=1 - self.ema_rate)
         return loss.detach()
+
+    def grad_norm(self):
+        """The last step's global gradient norm: unscaled, after the all-reduce, before clipping (a host read; not finite on an
+        overflow step)."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("grad_norm() needs max_grad_norm (float('inf') measures without clipping)")
+        return float(self._gn["norm"]) if self._gn is not None else self._torch_norm
+
+    def clip_coef(self):
+        """The coefficient the last step multiplied its gradient by: min(1, max_grad_norm / (grad_norm + 1e-6)); 0 on overflow."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("clip_coef() needs max_grad_norm")
+        return float(self._gn["coef"]) if self._gn is not None else self._torch_coef
+
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("this trainer keeps no EMA (ema_rate=None)")
+
+    def ema_state_dict(self):
+        """The network's state_dict with every trained parameter replaced by its EMA (buffers and frozen parameters as they are):
+        what the reference saves as ema_{rate}_{step:06d}.pt and evaluates with."""
+        self._need_ema()
+        sd = self.net.state_dict()
+        for k, e in zip(self._param_names, self.ema):
+            sd[k] = e.detach().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        """Copies INTO the live EMA tensors: a captured step keeps updating the same addresses."""
+        self._need_ema()
+        for k, e in zip(self._param_names, self.ema):
+            e.copy_(sd[k])
+
+    def ema_weights(self):
+        """``with trainer.ema_weights():`` the network holds the EMA weights (evaluation); the training weights come back on exit.
+        Values are swapped in place -- addresses stay (a captured step), the parameters' versions move (engines repack)."""
+        import contextlib
+        self._need_ema()
+
+        @torch.no_grad()
+        def swap():
+            if self.params[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ema_weights() cannot swap the weights during a stream capture")
+            for p, e in zip(self.params, self.ema):
+                t = p.detach().clone()
+                p.copy_(e)
+                e.copy_(t)
+
+        @contextlib.contextmanager
+        def block():
+            swap()
+            try:
+                yield self.net
+            finally:
+                swap()
+
+        return block()

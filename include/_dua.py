@@ -83,6 +83,32 @@ _L.dua_aug_draw_classes.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int, C
                                      C.c_ulonglong, C.c_void_p, C.c_int, C.c_ulonglong] + [C.c_void_p] * 4 +
                                     [C.c_int, C.c_float] + [C.c_void_p] * 3)
 
+# gradient-norm clipping and an EMA of the weights in the AdamW launch: dua_grads_sumsq writes one fp64 partial per 4096-element
+# chunk (dua_adamw_blocks of them per list), dua_grad_norm_finish turns them into the norm and clip_grad_norm_'s coefficient and
+# raises the overflow flag, dua_adamw_step_ex is dua_adamw_step with that coefficient and  e += w (p - e),  w = (float)(1.0 - rate)
+# formed in double.  Lists of <= 64 tensors go in by value.  The contract is in dua_hip.h
+DUA_ADAMW_MAX_TENSORS, DUA_ADAMW_CHUNK = 64, 4096
+
+
+class AdamWList(C.Structure):                    # dua_adamw_list: device pointers of parameters, gradients and the two moments
+    _fields_ = [("count", C.c_int), ("numel", C.c_long * DUA_ADAMW_MAX_TENSORS)] + [(n, C.c_void_p * DUA_ADAMW_MAX_TENSORS)
+                                                                                      for n in ("p", "g", "m", "v")]
+
+
+class AdamWEma(C.Structure):                     # dua_adamw_ema: one EMA tensor per entry of the list
+    _fields_ = [("e", C.c_void_p * DUA_ADAMW_MAX_TENSORS)]
+
+
+_L.dua_adamw_blocks.restype = C.c_long
+_L.dua_adamw_blocks.argtypes = [C.POINTER(AdamWList)]
+_L.dua_grads_sumsq.restype = C.c_int
+_L.dua_grads_sumsq.argtypes = [C.POINTER(AdamWList), C.c_void_p, C.c_void_p]
+_L.dua_grad_norm_finish.restype = C.c_int
+_L.dua_grad_norm_finish.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_float] + [C.c_void_p] * 4
+_L.dua_adamw_step_ex.restype = C.c_int
+_L.dua_adamw_step_ex.argtypes = ([C.POINTER(AdamWList), C.c_float, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3 +
+                                 [C.c_int, C.c_void_p, C.POINTER(AdamWEma), C.c_float, C.c_void_p])
+
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream

@@ -453,6 +453,32 @@ int dua_adamw_step(const dua_adamw_list* list, float lr, const float* lr_dev, fl
 int dua_adamw_advance(int* step, float* found_inf, float* scale, int* growth, float growth_factor, float backoff, int interval,
                       float* seen, void* stream);
 
+/* Global gradient-norm clipping and an EMA of the weights inside the AdamW step (torch.nn.utils.clip_grad_norm_; update_ema of
+ * guided_diffusion/nn.py:55-65, train_util.py:216-218).  The norm pass replaces dua_grads_nonfinite: it reads the same 4 bytes
+ * per parameter, and a sum of squares is non-finite exactly when an element is.
+ *   dua_adamw_blocks (host only): the workgroups, = partials, a list takes: sum of ceil(numel / DUA_ADAMW_CHUNK); < 0 on a bad list.
+ *   dua_grads_sumsq: partials[b] = sum over chunk b of (double)g * (double)g (needs only numel and g of the list).  A partial
+ *     depends on the element values of its chunk alone, not on the alignment of g: the same bits from every rank and every
+ *     allocation.  No atomics.  Several lists of a step write consecutive ranges of one buffer (offset by dua_adamw_blocks).
+ *   dua_grad_norm_finish: S = the count partials in a fixed order, fp64;  *norm = (float)(sqrt(S) / *grad_scale) (NULL: 1), the
+ *     norm of the unscaled gradient before clipping;  *coef = fminf(1, max_norm / (*norm + 1e-6f)).  max_norm = +inf gives coef 1
+ *     (the norm as a logged quantity, no clipping); max_norm <= 0 or NaN: DUA_ERR_ARG.  S not finite: *found_inf = 1.0f (never
+ *     written otherwise; may be NULL), *coef = 0, *norm as computed.  norm / coef / found_inf: device fp32 scalars.
+ *   dua_adamw_step_ex: dua_adamw_step with  g' = (g * (1 / *grad_scale)) * *clip_coef  (clip_coef NULL: 1; unscale, clip, step;
+ *     store_grad writes this g') and, after the update of p,  e += ema_weight * (p - e)  per tensor (ema NULL: none; else e[i]
+ *     non-NULL for every tensor of the list, numel[i] fp32 each).  ema_weight = (float)(1.0 - rate) formed in double by the
+ *     caller (1.f - rate in fp32 is off by 1.7e-4 relative at rate 0.9999), in (0, 1].  A set found_inf returns before touching
+ *     p, m, v, e and g.  One EMA rate per launch.  clip_coef == NULL && ema == NULL is dua_adamw_step itself. */
+#define DUA_ADAMW_CHUNK 4096                       /* elements per workgroup of the list kernels */
+typedef struct { float* e[DUA_ADAMW_MAX_TENSORS]; } dua_adamw_ema;
+long dua_adamw_blocks(const dua_adamw_list* list);
+int dua_grads_sumsq(const dua_adamw_list* list, double* partials, void* stream);
+int dua_grad_norm_finish(const double* partials, long count, const float* grad_scale, float max_norm, float* norm, float* coef,
+                         float* found_inf, void* stream);
+int dua_adamw_step_ex(const dua_adamw_list* list, float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                      float weight_decay, const float* grad_scale, const float* found_inf, const int* step, int store_grad,
+                      const float* clip_coef, const dua_adamw_ema* ema, float ema_weight, void* stream);
+
 /* ---- library state ---------------------------------------------------------------------------------------------
  * dua_abi_version(): DUA_ABI_VERSION of the library that is loaded.  It changes whenever a struct of this header, the size
  * or layout of a buffer a caller allocates (e.g. the statistics words of dua_in_norm) or a signature changes; a binding

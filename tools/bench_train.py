@@ -1,6 +1,7 @@
 """Config 4 (training step, batch 2, 96^3, 16 classes) on the HIP training path (training.NativeConvTrainer): eager or
 as one replayed HIP graph.  One JSON line.
-Usage: python tools/bench_train.py [--steps K] [--graph] [--losses mse,bce,multi_neighbor,dice | mse,dice_ce,generalized_dice | ...] [--loss-combine sum]"""
+Usage: python tools/bench_train.py [--steps K] [--graph] [--losses mse,bce,multi_neighbor,dice | mse,dice_ce,generalized_dice | ...] [--loss-combine sum]
+       [--max-grad-norm 12] [--ema-rate 0.9999]"""
 import argparse
 import json
 import os
@@ -24,13 +25,16 @@ ap.add_argument("--graph", action="store_true", help="replay the whole training 
 ap.add_argument("--losses", default="mse,bce,dice", help="loss names (losses/loss.py): any of mse, bce, dice, multi_neighbor, ce, dice_ce, generalized_dice; "
                 "cfg/amos/train.yaml: mse,bce,multi_neighbor,dice")
 ap.add_argument("--loss-combine", default="sum", choices=("sum", "mean", "log"))
+ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm (inf: measure it only)")
+ap.add_argument("--ema-rate", type=float, default=None, help="keep an EMA of the weights at this rate")
 ap.add_argument("--no-gc", action="store_true", help="disable the Python cyclic GC during the timed loop (diagnosis)")
 ap.add_argument("--ab-wgrad", default="", help="comma list of weight-gradient launch forms (dua_conv3_desc.policy, ops.WGRAD_POLICY): time the loop once per value, same process")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 net = DiffUNet(in_channels=1, out_channels=a.classes).to(dev)
-tr = NativeConvTrainer(net, dtype=getattr(torch, a.dtype), graph=a.graph, losses=a.losses, loss_combine=a.loss_combine)
+tr = NativeConvTrainer(net, dtype=getattr(torch, a.dtype), graph=a.graph, losses=a.losses, loss_combine=a.loss_combine,
+                       max_grad_norm=a.max_grad_norm, ema_rate=a.ema_rate)
 image = torch.rand(a.batch, 1, a.size, a.size, a.size, device=dev)
 labels = (torch.rand(a.batch, a.classes, a.size, a.size, a.size, device=dev) > 0.8).float()
 for _ in range(a.warmup):
@@ -65,5 +69,6 @@ if a.ab_wgrad:
 print(json.dumps({"metric": "train_step_time", "value": dt * 1e3, "unit": "ms", "median_ms": sorted(per)[len(per) // 2] * 1e3, "per_step_ms": [round(x * 1e3, 2) for x in per], "ab_wgrad_median_ms": ab, "native": True,
                   "path": "HIP conv fwd/dgrad/wgrad + fused InstanceNorm/LeakyReLU/add fwd/bwd under autograd; fused loss, pooling, 1x1-head and transposed-conv (in-place concat) kernels; AdamW = torch; " + a.dtype,
                   "graph": a.graph, "batch": a.batch,
-                  "size": a.size, "classes": a.classes, "losses": a.losses, "loss_combine": a.loss_combine, "loss": float(loss),
+                  "size": a.size, "classes": a.classes, "max_grad_norm": a.max_grad_norm, "ema_rate": a.ema_rate,
+                  "grad_norm": tr.grad_norm() if a.max_grad_norm is not None else None, "losses": a.losses, "loss_combine": a.loss_combine, "loss": float(loss),
                   "max_mem_GiB": torch.cuda.max_memory_allocated() / 2**30}))
