@@ -334,6 +334,15 @@ _SIGS = {
     "dua_cc_sizes": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, _P, _P]),
     "dua_cc_filter": (C.c_int, [C.c_int] * 4 + [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_long, _P, _P, C.c_int,
                                 C.c_int, C.c_int, _P, _P, C.c_long, _P]),
+    "dua_cc_map_scratch_bytes": (C.c_long, [C.c_int] * 5),
+    "dua_cc_label_map": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_int, _P, _P, _P, C.c_long, _P]),
+    "dua_cc_filter_map": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                    _P, C.c_long, _P]),
+    "dua_surface_map_boxes": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, _P, C.c_long, C.c_int, _P, _P]),
+    "dua_surface_map_scratch_bytes": (C.c_long, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
+    "dua_surface_map_report": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, _P, C.c_long, C.c_int, C.POINTER(C.c_int),
+                                                         C.POINTER(C.c_int), C.c_int] + [C.c_double] * 3 +
+                               [C.c_int, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P, C.c_long, _P]),
     "dua_aug_count_candidates": (C.c_int, [_P, _P, C.c_long, C.c_float, _P, _P]),
     "dua_aug_draw": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(AugConfig), C.c_ulonglong, _P, C.c_int, C.c_ulonglong, _P, _P,
                                _P]),

@@ -72,6 +72,14 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
   }
 }
 
+// the parent the init writes: the first voxel of the lane's run inside its wave (`starts` has a bit per run start), CC_BG for
+// background
+__device__ __forceinline__ int cc_run_parent(bool fg, unsigned long long starts, int lane, long p) {
+  if (!fg) return CC_BG;
+  const unsigned long long below = starts & (~0ull >> (63 - lane));         // bits 0 .. lane: never empty for a foreground lane
+  return (int)p - (lane - (63 - __clzll((long long)below)));
+}
+
 // grid (ceil(vox / 256), V).  A wave holds 64 consecutive voxels: every lane takes part in the ballots.  A volume with
 // select[v] == 0 is all background to everything that follows.
 __global__ __launch_bounds__(CC_THREADS) void cc_init_kernel(const void* __restrict__ mask, int is_f32, long mvs,
@@ -87,26 +95,48 @@ __global__ __launch_bounds__(CC_THREADS) void cc_init_kernel(const void* __restr
   // a run starts at a foreground lane that is lane 0, follows a background lane, or is the first voxel of a row
   const unsigned long long starts = f & (~(f << 1) | row0);
   if (p >= vox) return;
-  int par = CC_BG;
-  if (fg) {
-    const unsigned long long below = starts & (~0ull >> (63 - lane));       // bits 0 .. lane: never empty for a foreground lane
-    par = (int)p - (lane - (63 - __clzll((long long)below)));
-  }
-  parent[(size_t)v * pvs + (size_t)p] = par;
+  parent[(size_t)v * pvs + (size_t)p] = cc_run_parent(fg, starts, lane, p);
 }
 
-// grid (ceil(vox / 256), V), one voxel per thread
+// The label-map form of the init: grid as above, V = N maps.  A voxel is foreground when its value lies in 1 .. C - 1, and a run
+// also starts where the value changes: a run holds one value, so the unions the init stands for are all between equal values.
+__global__ __launch_bounds__(CC_THREADS) void cc_init_map_kernel(const unsigned char* __restrict__ map, long mvs, int C, int vox,
+                                                                 int W, int* __restrict__ parent, long pvs) {
+  const int v = blockIdx.y;
+  const long p = (long)blockIdx.x * CC_THREADS + threadIdx.x;
+  const int val = p < vox ? map[(size_t)v * mvs + (size_t)p] : 0;
+  const bool fg = val >= 1 && val < C;
+  const int lane = threadIdx.x & 63;
+  const int prev = __shfl_up(val, 1, 64);                        // every lane takes part; lane 0 starts a run anyway
+  const unsigned long long f = __ballot(fg);
+  const unsigned long long row0 = __ballot(fg && p % W == 0);
+  const unsigned long long change = __ballot(fg && lane > 0 && prev != val);
+  const unsigned long long starts = f & (~(f << 1) | row0 | change);
+  if (p >= vox) return;
+  parent[(size_t)v * pvs + (size_t)p] = cc_run_parent(fg, starts, lane, p);
+}
+
+// grid (ceil(vox / 256), V), one voxel per thread.  MAP (the label-map form): two voxels are joined only when they carry the same
+// value, so "q is foreground" reads "q carries p's value" everywhere below; the redundancy arguments hold word for word with
+// that reading, because every voxel they name then carries p's value.
+template <bool MAP>
 __global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(int* __restrict__ parent_all, long pvs, int D, int H, int W,
-                                                              int conn) {
+                                                              int conn, const unsigned char* __restrict__ map_all, long mvs) {
   int* parent = parent_all + (size_t)blockIdx.y * pvs;
   const long vox = (long)D * H * W;
   const long pl = (long)blockIdx.x * CC_THREADS + threadIdx.x;
   if (pl >= vox) return;
   const int p = (int)pl;
   if (parent[p] < 0) return;                                    // the sign of a slot never changes
+  const unsigned char* map = MAP ? map_all + (size_t)blockIdx.y * mvs : nullptr;
+  const int val = MAP ? map[p] : 0;
+  auto joined = [&](int i) {                                    // i is foreground (of p's class)
+    if constexpr (MAP) return map[i] == val;
+    else return parent[i] >= 0;
+  };
   const int HW = H * W;
   const int w = p % W, h = (p / W) % H, d = p / HW;
-  const bool left = w > 0 && parent[p - 1] >= 0;
+  const bool left = w > 0 && joined(p - 1);
   // -x: lanes 1..63 were joined to their run by the init; lane 0 joins the run that ends in the wave before
   if (left && (threadIdx.x & 63) == 0) cc_union(parent, p, p - 1);
 #pragma unroll
@@ -123,15 +153,15 @@ __global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(int* __restrict__ 
         const int xx = w + dx;
         if (xx < 0 || xx >= W) continue;
         const int q = p + dz * HW + dy * W + dx;
-        if (parent[q] < 0) continue;
+        if (!joined(q)) continue;
         if (dx == 0) {
           // p - 1 and q - 1 are both foreground: p ~ p - 1 and q ~ q - 1 along x, and p - 1 makes (or skips for the same
           // reason, down to the start of the run) this union with q - 1
-          if (left && parent[q - 1] >= 0) continue;
+          if (left && joined(q - 1)) continue;
         } else {
           // r = p + (dz, dy, 0) is foreground: q ~ r along x, and p ~ r is this voxel's own union at dx == 0 (an offset with
           // one non-zero component fewer, so inside the footprint)
-          if (parent[q - dx] >= 0) continue;
+          if (joined(q - dx)) continue;
         }
         cc_union(parent, p, q);
       }
@@ -262,25 +292,32 @@ __global__ __launch_bounds__(CC_THREADS) void cc_sizes_kernel(const int* __restr
 // grid (ceil(cap / 256), V): keep[v][l - 1] for the labels 1 .. n = min(counts[v], cap).  The position of label l in
 // np.argsort(-sizes, kind="stable") is the number of labels that are larger, or equal and smaller in number; l is kept when
 // that position is below k (k == 0: no limit on the number) and its size is at least min_size.
+// MAP (the label-map form): cls[v][l - 1] is the class of label l, and the position is taken among the labels of l's class.
+template <bool MAP>
 __global__ __launch_bounds__(CC_THREADS) void cc_select_kernel(const int* __restrict__ sizes, const int* __restrict__ counts,
-                                                               int cap, int k, int min_size, unsigned char* __restrict__ keep) {
+                                                               int cap, int k, int min_size, unsigned char* __restrict__ keep,
+                                                               const unsigned char* __restrict__ cls_all) {
   __shared__ int tile[CC_THREADS];
+  __shared__ unsigned char ctile[MAP ? CC_THREADS : 1];
+  const unsigned char* cls = MAP ? cls_all + (size_t)blockIdx.y * cap : nullptr;
   const int v = blockIdx.y;
   const int* sz = sizes + (size_t)v * cap;
   int n = counts[v];
   n = n < 0 ? 0 : (n > cap ? cap : n);
   const int l = blockIdx.x * CC_THREADS + threadIdx.x;           // label l + 1
   const int mine = l < n ? sz[l] : 0;
+  const int myc = MAP && l < n ? cls[l] : 0;
   int pos = 0;
   if (k > 0 && (int)(blockIdx.x * CC_THREADS) < n) {             // block-uniform
     for (int base = 0; base < n; base += CC_THREADS) {
       __syncthreads();
       tile[threadIdx.x] = base + (int)threadIdx.x < n ? sz[base + threadIdx.x] : -1;
+      if constexpr (MAP) ctile[threadIdx.x] = base + (int)threadIdx.x < n ? cls[base + threadIdx.x] : 0;
       __syncthreads();
       const int m = n - base < CC_THREADS ? n - base : CC_THREADS;
       for (int t = 0; t < m; ++t) {
         const int s = tile[t];
-        pos += (s > mine) || (s == mine && base + t < l);
+        pos += (!MAP || ctile[t] == myc) && ((s > mine) || (s == mine && base + t < l));
       }
     }
   }
@@ -332,6 +369,86 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const int* __rest
   }
 }
 
+// ---- the label-map form of the filter ------------------------------------------------------------------------------------
+
+// grid (nb, V): cls[v][l - 1] = the class of label l, 1 <= l <= cap.  A component carries one value, the value at its root; every
+// voxel that starts a run of its label along W stores that same byte (identical stores: the order does not matter).
+__global__ __launch_bounds__(CC_THREADS) void cc_class_kernel(const int* __restrict__ labels, const unsigned char* __restrict__ map,
+                                                              long mvs, int vox, int W, int cap, unsigned char* __restrict__ cls) {
+  const int v = blockIdx.y;
+  const int* lab = labels + (size_t)v * (size_t)vox;
+#pragma unroll
+  for (int j = 0; j < CC_PER_THREAD; ++j) {
+    const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
+    if (p >= vox) continue;
+    const int l = lab[p];
+    if (l < 1 || l > cap) continue;
+    if (p % W != 0 && lab[p - 1] == l) continue;
+    cls[(size_t)v * cap + (l - 1)] = map[(size_t)v * mvs + (size_t)p];
+  }
+}
+
+// grid (nb, V): out[v][p] = map[v][p] where the value is 0 or >= C, where its class is passed through (apply[value] == 0) or
+// where the voxel's component is kept; 0 otherwise.  TALLY: (|A & B|, |A|, |B|) of A = out, B = ref per class into LDS words
+// (class 0, the bulk of a scan, in registers), then one 64-bit integer atomic per non-zero word; a value >= C counts nowhere.
+template <bool TALLY>
+__global__ __launch_bounds__(CC_THREADS) void cc_filter_map_kernel(const int* __restrict__ labels, int vox, int cap,
+                                                                   const unsigned char* __restrict__ keep,
+                                                                   const unsigned char* __restrict__ apply,
+                                                                   const unsigned char* __restrict__ map, long mvs, int C,
+                                                                   unsigned char* __restrict__ out,
+                                                                   const unsigned char* __restrict__ ref,
+                                                                   unsigned long long* __restrict__ tallies) {
+  __shared__ unsigned part[TALLY ? 3 * DUA_BLEND_MAX_CLASSES : 1];
+  __shared__ int red[TALLY ? CC_WAVES : 1][3];
+  const int v = blockIdx.y;
+  const int* lab = labels + (size_t)v * (size_t)vox;
+  const unsigned char* kp = keep + (size_t)v * cap;
+  if constexpr (TALLY) {
+    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) part[i] = 0;
+    __syncthreads();
+  }
+  int z[3] = {0, 0, 0};                                          // class 0: |A & B|, |A|, |B|
+#pragma unroll
+  for (int j = 0; j < CC_PER_THREAD; ++j) {
+    const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
+    if (p >= vox) continue;
+    const int val = map[(size_t)v * mvs + (size_t)p];
+    int o = val;
+    if (val >= 1 && val < C && (!apply || apply[val] != 0)) {
+      const int l = lab[p];
+      if (!(l >= 1 && l <= cap && kp[l - 1] != 0)) o = 0;
+    }
+    out[(size_t)v * (size_t)vox + (size_t)p] = (unsigned char)o;
+    if constexpr (TALLY) {
+      const int r = ref[(size_t)v * (size_t)vox + (size_t)p];
+      if (o == 0) ++z[1];
+      else if (o < C) atomicAdd(&part[3 * o + 1], 1u);
+      if (r == 0) {
+        ++z[2];
+        z[0] += o == 0;
+      } else if (r < C) {
+        atomicAdd(&part[3 * r + 2], 1u);
+        if (r == o) atomicAdd(&part[3 * r], 1u);
+      }
+    }
+  }
+  if constexpr (TALLY) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int t = cc_wave_sum(z[i]);
+      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = t;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) {
+      unsigned long long t = part[i];
+      if (i < 3)
+        for (int k = 0; k < CC_WAVES; ++k) t += (unsigned long long)red[k][i];
+      if (t) atomicAdd(&tallies[i], t);
+    }
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
 static long cc_align256(long x) { return (x + 255) & ~255L; }
@@ -346,6 +463,7 @@ static bool cc_mask_dtype_ok(int t) { return t == DUA_F32 || t == DUA_U8; }
 struct CcScratch {
   long pvs, nb;                      // parent elements per volume, scan blocks per volume
   long parent, blocksum, keep, total;
+  long cls, total_map;               // the label-map form: the class table behind the keep table
 };
 
 static CcScratch cc_layout(int V, int D, int H, int W, int cap) {
@@ -357,6 +475,8 @@ static CcScratch cc_layout(int V, int D, int H, int W, int cap) {
   L.blocksum = cc_align256(L.parent + (long)V * L.pvs * 4);
   L.keep = cc_align256(L.blocksum + (long)V * L.nb * 4);
   L.total = cc_align256(L.keep + (long)V * cap);
+  L.cls = L.total;
+  L.total_map = cc_align256(L.cls + (long)V * cap);
   return L;
 }
 
@@ -386,7 +506,8 @@ int dua_cc_label(int V, int D, int H, int W, const void* mask, int mask_dtype, l
   const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
   const int is_f32 = mask_dtype == DUA_F32;
   hipLaunchKernelGGL(dua::cc_init_kernel, gvox, threads, 0, s, mask, is_f32, mask_vstride, select, (int)vox, W, parent, L.pvs);
-  hipLaunchKernelGGL(dua::cc_merge_kernel, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity);
+  hipLaunchKernelGGL(dua::cc_merge_kernel<false>, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity,
+                     (const unsigned char*)nullptr, 0L);
   hipLaunchKernelGGL(dua::cc_flatten_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb);
   hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
   hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
@@ -442,10 +563,71 @@ int dua_cc_filter(int V, int D, int H, int W, const int* labels, const int* coun
     const hipError_t e = hipMemsetAsync(tallies, 0, sizeof(unsigned long long) * 3 * C, s);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(dua::cc_select_kernel, dim3((unsigned)((cap + dua::CC_THREADS - 1) / dua::CC_THREADS), V),
-                     dim3(dua::CC_THREADS), 0, s, sizes, counts, cap, k, min_size, keep);
+  hipLaunchKernelGGL(dua::cc_select_kernel<false>, dim3((unsigned)((cap + dua::CC_THREADS - 1) / dua::CC_THREADS), V),
+                     dim3(dua::CC_THREADS), 0, s, sizes, counts, cap, k, min_size, keep, (const unsigned char*)nullptr);
   hipLaunchKernelGGL(dua::cc_filter_kernel, dim3((unsigned)L.nb, V), dim3(dua::CC_THREADS), 0, s, labels, (int)vox, cap, keep,
                      apply, mask, mask_dtype == DUA_F32, mask_vstride, out, reference, kind, reference ? C : 1, tallies);
+  return (int)hipGetLastError();
+}
+
+long dua_cc_map_scratch_bytes(int V, int D, int H, int W, int cap) {
+  if (!dua::cc_extents_ok(V, D, H, W) || cap < 1 || cap > DUA_CC_MAX_CAP) return DUA_ERR_ARG;
+  return dua::cc_layout(V, D, H, W, cap).total_map;
+}
+
+int dua_cc_label_map(int V, int D, int H, int W, const unsigned char* map, long map_vstride, int C, int connectivity, int* labels,
+                     int* counts, void* workspace, long workspace_bytes, void* stream) {
+  if (!dua::cc_extents_ok(V, D, H, W) || !map || !labels || !counts || !workspace || connectivity < 1 || connectivity > 3 ||
+      C < 1 || C > DUA_BLEND_MAX_CLASSES)
+    return DUA_ERR_ARG;
+  const long vox = (long)D * H * W;
+  const dua::CcScratch L = dua::cc_layout(V, D, H, W, 1);         // the labelling part of the layout does not depend on cap
+  if (map_vstride < vox || workspace_bytes < L.keep || ((size_t)workspace & 255) != 0 || ((size_t)labels & 3) != 0 ||
+      ((size_t)counts & 3) != 0)
+    return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  int* parent = (int*)((unsigned char*)workspace + L.parent);
+  int* blocksum = (int*)((unsigned char*)workspace + L.blocksum);
+  const dim3 threads(dua::CC_THREADS);
+  const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
+  hipLaunchKernelGGL(dua::cc_init_map_kernel, gvox, threads, 0, s, map, map_vstride, C, (int)vox, W, parent, L.pvs);
+  hipLaunchKernelGGL(dua::cc_merge_kernel<true>, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity, map, map_vstride);
+  hipLaunchKernelGGL(dua::cc_flatten_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb);
+  hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
+  hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
+  hipLaunchKernelGGL(dua::cc_propagate_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, labels);
+  return (int)hipGetLastError();
+}
+
+int dua_cc_filter_map(int V, int D, int H, int W, const unsigned char* map, long map_vstride, int C, const int* labels,
+                      const int* counts, const int* sizes, int cap, int k, int min_size, const unsigned char* apply,
+                      unsigned char* out, const unsigned char* reference, unsigned long long* tallies, void* workspace,
+                      long workspace_bytes, void* stream) {
+  if (!dua::cc_extents_ok(V, D, H, W) || !map || !labels || !counts || !sizes || !out || !workspace || cap < 1 ||
+      cap > DUA_CC_MAX_CAP || k < 0 || C < 1 || C > DUA_BLEND_MAX_CLASSES || ((size_t)labels & 3) != 0 ||
+      ((size_t)counts & 3) != 0 || ((size_t)sizes & 3) != 0)
+    return DUA_ERR_ARG;
+  const long vox = (long)D * H * W;
+  if (map_vstride < vox || (reference != nullptr) != (tallies != nullptr) || ((size_t)tallies & 7) != 0) return DUA_ERR_ARG;
+  const dua::CcScratch L = dua::cc_layout(V, D, H, W, cap);
+  if (workspace_bytes < L.total_map || ((size_t)workspace & 255) != 0) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* keep = (unsigned char*)workspace + L.keep;
+  unsigned char* cls = (unsigned char*)workspace + L.cls;
+  if (tallies) {
+    const hipError_t e = hipMemsetAsync(tallies, 0, sizeof(unsigned long long) * 3 * C, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const dim3 threads(dua::CC_THREADS), gscan((unsigned)L.nb, V);
+  hipLaunchKernelGGL(dua::cc_class_kernel, gscan, threads, 0, s, labels, map, map_vstride, (int)vox, W, cap, cls);
+  hipLaunchKernelGGL(dua::cc_select_kernel<true>, dim3((unsigned)((cap + dua::CC_THREADS - 1) / dua::CC_THREADS), V), threads, 0,
+                     s, sizes, counts, cap, k, min_size, keep, (const unsigned char*)cls);
+  if (tallies)
+    hipLaunchKernelGGL(dua::cc_filter_map_kernel<true>, gscan, threads, 0, s, labels, (int)vox, cap, keep, apply, map, map_vstride,
+                       C, out, reference, tallies);
+  else
+    hipLaunchKernelGGL(dua::cc_filter_map_kernel<false>, gscan, threads, 0, s, labels, (int)vox, cap, keep, apply, map,
+                       map_vstride, C, out, reference, tallies);
   return (int)hipGetLastError();
 }
 

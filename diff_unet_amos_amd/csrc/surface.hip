@@ -44,10 +44,10 @@ __device__ __forceinline__ bool fg_at(const unsigned char* p, size_t i) { return
 
 // border(X) at a foreground voxel: on a face of the volume (a face neighbour lies outside, border_value 0), or some neighbour
 // of the footprint (offsets with at most `conn` non-zero components) is background
-template <typename T>
-__device__ __forceinline__ bool is_border(const T* __restrict__ x, size_t p, int d, int h, int w, int D, int H, int W, int conn) {
+// `fg(offset)` says whether the voxel `offset` elements away is foreground; sd / sh are the element strides of a step along D / H
+template <typename F>
+__device__ __forceinline__ bool is_border_of(F fg, int d, int h, int w, int D, int H, int W, ptrdiff_t sd, ptrdiff_t sh, int conn) {
   if (d == 0 || h == 0 || w == 0 || d == D - 1 || h == H - 1 || w == W - 1) return true;
-  const size_t HW = (size_t)H * W;
 #pragma unroll
   for (int dz = -1; dz <= 1; ++dz)
 #pragma unroll
@@ -56,15 +56,35 @@ __device__ __forceinline__ bool is_border(const T* __restrict__ x, size_t p, int
       for (int dx = -1; dx <= 1; ++dx) {
         const int nnz = (dz != 0) + (dy != 0) + (dx != 0);
         if (nnz == 0 || nnz > conn) continue;
-        if (!fg_at(x, p + (ptrdiff_t)dz * (ptrdiff_t)HW + (ptrdiff_t)dy * W + dx)) return true;
+        if (!fg((ptrdiff_t)dz * sd + (ptrdiff_t)dy * sh + dx)) return true;
       }
   return false;
+}
+
+template <typename T>
+__device__ __forceinline__ bool is_border(const T* __restrict__ x, size_t p, int d, int h, int w, int D, int H, int W, int conn) {
+  return is_border_of([&](ptrdiff_t off) { return fg_at(x, p + off); }, d, h, w, D, H, W, (ptrdiff_t)H * W, (ptrdiff_t)W, conn);
 }
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+
+// the five per-thread counts of a masks block into counts[0..5): shuffles across the wave, LDS across the block, one 64-bit
+// integer atomic per non-zero counter
+__device__ __forceinline__ void masks_block_counts(int na, int nb, int ntp, int nba, int nbb, unsigned long long* __restrict__ counts) {
+  __shared__ int red[SURF_THREADS / 64][5];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  na = wave_sum(na); nb = wave_sum(nb); ntp = wave_sum(ntp); nba = wave_sum(nba); nbb = wave_sum(nbb);
+  if (lane == 0) { red[wv][0] = na; red[wv][1] = nb; red[wv][2] = ntp; red[wv][3] = nba; red[wv][4] = nbb; }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    long long t = 0;
+    for (int k = 0; k < SURF_THREADS / 64; ++k) t += red[k][threadIdx.x];
+    if (t) atomicAdd(&counts[threadIdx.x], (unsigned long long)t);
+  }
 }
 
 // grid (blocks over [0, svs), V).  surf: [V][svs] bytes, the bytes in [vox, svs) written 0.  counts: [V][5], pre-zeroed.
@@ -92,15 +112,91 @@ __global__ __launch_bounds__(SURF_THREADS) void surface_masks_kernel(const TA* _
     }
     surf[(size_t)v * svs + p] = s;
   }
-  __shared__ int red[SURF_THREADS / 64][5];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  na = wave_sum(na); nb = wave_sum(nb); ntp = wave_sum(ntp); nba = wave_sum(nba); nbb = wave_sum(nbb);
-  if (lane == 0) { red[wv][0] = na; red[wv][1] = nb; red[wv][2] = ntp; red[wv][3] = nba; red[wv][4] = nbb; }
+  masks_block_counts(na, nb, ntp, nba, nbb, counts + (size_t)v * 5);
+}
+
+// The label-map form, one (map pair, class) per launch: the mask of the test is (a == cls), that of the reference (b == cls), read
+// from the two maps [..][H][W] themselves, and the pass covers the box of extents (Db, Hb, Wb) at origin (od, oh, ow) only.  The
+// box is the class's bounding box in both maps grown by one voxel per side and clamped to the volume, so a foreground voxel on
+// a face of the box lies on a face of the volume: the face rule of is_border_of on the box is that of the full volume, and an
+// inner voxel's neighbours lie in the box.  surf: [svs] bytes on the box grid [Db][Hb][Wb]; counts: [5], pre-zeroed.
+__global__ __launch_bounds__(SURF_THREADS) void surface_map_masks_kernel(const unsigned char* __restrict__ a,
+                                                                         const unsigned char* __restrict__ b, int cls, int H, int W,
+                                                                         int od, int oh, int ow, int Db, int Hb, int Wb, int conn,
+                                                                         unsigned char* __restrict__ surf, long svs,
+                                                                         unsigned long long* __restrict__ counts) {
+  const long vox = (long)Db * Hb * Wb;
+  const ptrdiff_t sd = (ptrdiff_t)H * W, sh = (ptrdiff_t)W;
+  int na = 0, nb = 0, ntp = 0, nba = 0, nbb = 0;
+  for (int j = 0; j < SURF_PER_THREAD; ++j) {
+    const long p = (long)blockIdx.x * SURF_BLOCK_VOX + (long)j * SURF_THREADS + threadIdx.x;
+    if (p >= svs) break;
+    unsigned char s = 0;
+    if (p < vox) {
+      const int w = (int)(p % Wb), h = (int)((p / Wb) % Hb), d = (int)(p / ((long)Wb * Hb));
+      const size_t q = (size_t)(od + d) * (size_t)sd + (size_t)(oh + h) * (size_t)sh + (size_t)(ow + w);
+      const bool fa = a[q] == cls, fb = b[q] == cls;
+      const bool ba = fa && is_border_of([&](ptrdiff_t off) { return a[q + off] == cls; }, d, h, w, Db, Hb, Wb, sd, sh, conn);
+      const bool bb = fb && is_border_of([&](ptrdiff_t off) { return b[q + off] == cls; }, d, h, w, Db, Hb, Wb, sd, sh, conn);
+      na += fa; nb += fb; ntp += fa && fb; nba += ba; nbb += bb;
+      s = (unsigned char)(ba | (bb << 1));
+    }
+    surf[p] = s;
+  }
+  masks_block_counts(na, nb, ntp, nba, nbb, counts);
+}
+
+// The bounding boxes of every value below C in a pair of label maps: boxes[n][c] = (d0, h0, w0, d1, h1, w1), half-open, of
+// (a[n] == c) | (b[n] == c); pre-set to (INT_MAX x 3, 0 x 3), which is what an absent class keeps.  grid (blocks, N).  A wave takes
+// 64 consecutive voxels of ONE row at a time (d and h are wave-uniform), finds the distinct values among its lanes and one
+// lane per value folds the run's extent into the block's LDS table; the block then folds its table into boxes.  Integer min /
+// max only: the result does not depend on any order.
+constexpr int BOX_ITER = 16;                            // wave tiles per wave
+__global__ void surface_box_init_kernel(int n, int* __restrict__ boxes) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) boxes[i] = i % 6 < 3 ? 0x7fffffff : 0;
+}
+
+__global__ __launch_bounds__(SURF_THREADS) void surface_boxes_kernel(const unsigned char* __restrict__ a, long a_vs,
+                                                                     const unsigned char* __restrict__ b, long b_vs, int D, int H,
+                                                                     int W, int C, int* __restrict__ boxes) {
+  __shared__ int lo[DUA_BLEND_MAX_CLASSES * 3], hi[DUA_BLEND_MAX_CLASSES * 3];
+  for (int i = threadIdx.x; i < 3 * C; i += SURF_THREADS) { lo[i] = 0x7fffffff; hi[i] = 0; }
   __syncthreads();
-  if (threadIdx.x < 5) {
-    long long t = 0;
-    for (int k = 0; k < SURF_THREADS / 64; ++k) t += red[k][threadIdx.x];
-    if (t) atomicAdd(&counts[(size_t)v * 5 + threadIdx.x], (unsigned long long)t);
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tpr = (W + 63) / 64;                        // wave tiles per row
+  const long tiles = (long)D * H * tpr;
+  const unsigned char* maps[2] = {a + (size_t)n * a_vs, b + (size_t)n * b_vs};
+  for (int j = 0; j < BOX_ITER; ++j) {
+    const long t = ((long)blockIdx.x * BOX_ITER + j) * (SURF_THREADS / 64) + wave;
+    if (t >= tiles) break;                              // wave-uniform
+    const long row = t / tpr;
+    const int w0 = (int)(t - row * tpr) * 64, w = w0 + lane;
+    const int h = (int)(row % H), d = (int)(row / H);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int val = w < W ? maps[m][(size_t)row * W + w] : 255;
+      const bool valid = val < C;
+      unsigned long long todo = __ballot(valid);        // wave-uniform: every lane runs the same iterations
+      while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int ll = __shfl(val, leader, 64);
+        const unsigned long long same = __ballot(valid && val == ll);
+        if (lane == leader) {
+          atomicMin(&lo[3 * ll + 0], d); atomicMin(&lo[3 * ll + 1], h); atomicMin(&lo[3 * ll + 2], w0 + __ffsll((long long)same) - 1);
+          atomicMax(&hi[3 * ll + 0], d + 1); atomicMax(&hi[3 * ll + 1], h + 1);
+          atomicMax(&hi[3 * ll + 2], w0 + 64 - __clzll((long long)same));
+        }
+        todo &= ~same;                                  // `same` holds the leader's bit
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * C; i += SURF_THREADS) {
+    if (hi[i] == 0) continue;
+    int* row = boxes + ((size_t)n * C + i / 3) * 6;
+    atomicMin(row + i % 3, lo[i]);
+    atomicMax(row + 3 + i % 3, hi[i]);
   }
 }
 
@@ -623,6 +719,42 @@ static int dice_launch(int V, long vox, const unsigned char* surf, long svs, con
 
 }  // namespace dua
 
+// Everything behind the surface bytes (workspace + L.surf, on the grid [V][D][H][W]) and counts: transform, select, finish and,
+// with tol, the surface Dice.  full_vox: the voxels of the volume the masks live in -- tn and the "mask is full" rule count
+// against it; it is D H W unless the grid is a box of a larger volume (dua_surface_map_report).
+static int surface_table_tail(int V, int D, int H, int W, long full_vox, double sd, double sh, double sw, int nan_for_nonexisting,
+                              unsigned long long* counts, double* out, unsigned char* ws, const dua::SurfaceScratch& L, int classes,
+                              int T, const dua::SurfaceTolerances* tol, unsigned long long* within, double* nsd, hipStream_t s) {
+  const long vox = (long)D * H * W, svs = dua::align256(vox);
+  unsigned char* surf = ws + L.surf;
+  double* dist = (double*)(ws + L.dist);
+  double* partial = (double*)(ws + L.partial);
+  unsigned long long* maxbits = (unsigned long long*)(ws + L.maxbits);
+  unsigned* hist = (unsigned*)(ws + L.hist);
+  unsigned long long* sel = (unsigned long long*)(ws + L.sel);
+  unsigned long long* nextmin = (unsigned long long*)(ws + L.nextmin);
+  hipError_t e = hipMemsetAsync(maxbits, 0, (size_t)2 * V * 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, (size_t)V * 256 * 4, s);
+  if (e == hipSuccess) e = hipMemsetAsync(nextmin, 0xFF, (size_t)V * 8, s);
+  if (e != hipSuccess) return (int)e;
+  // direction 0: seeds border(B) (bit 1), read at border(A) (bit 0); direction 1 the other way round
+  const int rc = dua::edt_launch(V, D, H, W, surf, svs, 2, 1, 2, sd, sh, sw, dist, surf, svs, partial, maxbits, false, 0.0, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(dua::select_init_kernel, dim3((V + 255) / 256), dim3(256), 0, s, V, counts, sel);
+  const dim3 sgrid((unsigned)((svs / 16 + dua::SURF_THREADS * dua::SEL_GROUPS - 1) / (dua::SURF_THREADS * dua::SEL_GROUPS)), V);
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    hipLaunchKernelGGL(dua::select_pass_kernel<0>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, shift, sel, hist,
+                       nextmin);
+    hipLaunchKernelGGL(dua::select_step_kernel, dim3(V), dim3(256), 0, s, shift, sel, hist);
+  }
+  hipLaunchKernelGGL(dua::select_pass_kernel<1>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, 0, sel, hist, nextmin);
+  const int wc = dua::cols_wc(D, W, true);
+  hipLaunchKernelGGL(dua::surface_finish_kernel, dim3(V), dim3(256), 0, s, V, full_vox, counts, partial, H * ((W + wc - 1) / wc),
+                     maxbits, sel, nextmin, nan_for_nonexisting, out);
+  if (tol) return dua::dice_launch(V, vox, surf, svs, dist, classes, T, *tol, counts, nan_for_nonexisting, within, nsd, s);
+  return (int)hipGetLastError();
+}
+
 // the distance table; with tol, the surface Dice outputs too, counted on the same dist buffer (dua_surface_report)
 static int surface_table(int V, int D, int H, int W, const void* test, int test_dtype, long test_vstride, const void* reference,
                          int reference_dtype, long reference_vstride, int connectivity, double sd, double sh, double sw,
@@ -639,36 +771,11 @@ static int surface_table(int V, int D, int H, int W, const void* test, int test_
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   unsigned char* surf = ws + L.surf;
-  double* dist = (double*)(ws + L.dist);
-  double* partial = (double*)(ws + L.partial);
-  unsigned long long* maxbits = (unsigned long long*)(ws + L.maxbits);
-  unsigned* hist = (unsigned*)(ws + L.hist);
-  unsigned long long* sel = (unsigned long long*)(ws + L.sel);
-  unsigned long long* nextmin = (unsigned long long*)(ws + L.nextmin);
   const long svs = dua::align256(vox);
   int rc = dua::masks_launch(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride,
                              connectivity, surf, svs, counts, s);
   if (rc) return rc;
-  hipError_t e = hipMemsetAsync(maxbits, 0, (size_t)2 * V * 8, s);
-  if (e == hipSuccess) e = hipMemsetAsync(hist, 0, (size_t)V * 256 * 4, s);
-  if (e == hipSuccess) e = hipMemsetAsync(nextmin, 0xFF, (size_t)V * 8, s);
-  if (e != hipSuccess) return (int)e;
-  // direction 0: seeds border(B) (bit 1), read at border(A) (bit 0); direction 1 the other way round
-  rc = dua::edt_launch(V, D, H, W, surf, svs, 2, 1, 2, sd, sh, sw, dist, surf, svs, partial, maxbits, false, 0.0, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(dua::select_init_kernel, dim3((V + 255) / 256), dim3(256), 0, s, V, counts, sel);
-  const dim3 sgrid((unsigned)((svs / 16 + dua::SURF_THREADS * dua::SEL_GROUPS - 1) / (dua::SURF_THREADS * dua::SEL_GROUPS)), V);
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    hipLaunchKernelGGL(dua::select_pass_kernel<0>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, shift, sel, hist,
-                       nextmin);
-    hipLaunchKernelGGL(dua::select_step_kernel, dim3(V), dim3(256), 0, s, shift, sel, hist);
-  }
-  hipLaunchKernelGGL(dua::select_pass_kernel<1>, sgrid, dim3(dua::SURF_THREADS), 0, s, surf, svs, dist, vox, 0, sel, hist, nextmin);
-  const int wc = dua::cols_wc(D, W, true);
-  hipLaunchKernelGGL(dua::surface_finish_kernel, dim3(V), dim3(256), 0, s, V, vox, counts, partial, H * ((W + wc - 1) / wc),
-                     maxbits, sel, nextmin, nan_for_nonexisting, out);
-  if (tol) return dua::dice_launch(V, vox, surf, svs, dist, classes, T, *tol, counts, nan_for_nonexisting, within, nsd, s);
-  return (int)hipGetLastError();
+  return surface_table_tail(V, D, H, W, vox, sd, sh, sw, nan_for_nonexisting, counts, out, ws, L, classes, T, tol, within, nsd, s);
 }
 
 
@@ -765,6 +872,107 @@ int dua_surface_report(int V, int D, int H, int W, const void* test, int test_dt
   return surface_table(V, D, H, W, test, test_dtype, test_vstride, reference, reference_dtype, reference_vstride, connectivity,
                        sd, sh, sw, nan_for_nonexisting, counts, out, workspace, workspace_bytes, classes, T, &tol, within, nsd,
                        stream);
+}
+
+// ---- the report of two label maps, per class, inside the class's box ---------------------------------------------------------
+
+// a row of the box table, grown by one voxel per side and clamped: origin and extents.  false: the class is absent (d1 == 0).
+// A row that is neither absent nor a non-empty box inside the volume is refused by the callers.
+static bool map_box_ok(const int* b, int D, int H, int W) {
+  if (b[3] == 0) return true;
+  return b[0] >= 0 && b[0] < b[3] && b[3] <= D && b[1] >= 0 && b[1] < b[4] && b[4] <= H && b[2] >= 0 && b[2] < b[5] && b[5] <= W;
+}
+
+static bool map_box_grow(const int* b, int D, int H, int W, int o[3], int n[3]) {
+  if (b[3] == 0) return false;
+  const int ext[3] = {D, H, W};
+  for (int i = 0; i < 3; ++i) {
+    o[i] = b[i] > 0 ? b[i] - 1 : 0;
+    const int hi = b[3 + i] < ext[i] ? b[3 + i] + 1 : ext[i];
+    n[i] = hi - o[i];
+  }
+  return true;
+}
+
+long dua_surface_map_scratch_bytes(int D, int H, int W, int rows, const int* boxes) {
+  if (!dua::extents_ok(1, D, H, W) || rows < 1 || rows > 65535 || !boxes) return DUA_ERR_ARG;
+  long largest = 0;                                    // the rows run one after the other on one stream and share one region
+  for (int r = 0; r < rows; ++r) {
+    int o[3], n[3];
+    if (!map_box_ok(boxes + 6 * r, D, H, W)) return DUA_ERR_ARG;
+    if (map_box_grow(boxes + 6 * r, D, H, W, o, n)) {
+      const long need = dua::scratch_layout(1, n[0], n[1], n[2]).total;
+      if (need > largest) largest = need;
+    }
+  }
+  return largest;
+}
+
+int dua_surface_map_boxes(int N, int D, int H, int W, const unsigned char* test, long test_vstride, const unsigned char* reference,
+                          long reference_vstride, int C, int* boxes, void* stream) {
+  const long vox = (long)D * H * W;
+  if (!dua::extents_ok(N, D, H, W) || !test || !reference || !boxes || C < 1 || C > DUA_BLEND_MAX_CLASSES ||
+      (long)N * C > 65535 || test_vstride < vox || reference_vstride < vox || ((size_t)boxes & 3) != 0)
+    return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int n = N * C * 6;
+  hipLaunchKernelGGL(dua::surface_box_init_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, boxes);
+  const long tiles = (long)D * H * ((W + 63) / 64), per_block = (long)dua::BOX_ITER * (dua::SURF_THREADS / 64);
+  hipLaunchKernelGGL(dua::surface_boxes_kernel, dim3((unsigned)((tiles + per_block - 1) / per_block), N), dim3(dua::SURF_THREADS),
+                     0, s, test, test_vstride, reference, reference_vstride, D, H, W, C, boxes);
+  return (int)hipGetLastError();
+}
+
+int dua_surface_map_report(int N, int D, int H, int W, const unsigned char* test, long test_vstride,
+                           const unsigned char* reference, long reference_vstride, int K, const int* class_ids, const int* boxes,
+                           int connectivity, double sd, double sh, double sw, int T, const double* tolerances,
+                           int nan_for_nonexisting, unsigned long long* counts, double* out, unsigned long long* within,
+                           double* nsd, void* workspace, long workspace_bytes, void* stream) {
+  const long vox = (long)D * H * W;
+  dua::SurfaceTolerances all;
+  double cap2 = 0.0;
+  if (!dua::extents_ok(N, D, H, W) || !test || !reference || !class_ids || !boxes || !counts || !out || !within || !nsd ||
+      K < 1 || (long)N * K > 65535 || connectivity < 1 || connectivity > 3 || test_vstride < vox || reference_vstride < vox ||
+      !dua::spacing_ok(sd) || !dua::spacing_ok(sh) || !dua::spacing_ok(sw) || !dua::tolerances_ok(K, K, T, tolerances, all, cap2))
+    return DUA_ERR_ARG;
+  for (int k = 0; k < K; ++k)
+    if (class_ids[k] < 0 || class_ids[k] > 255) return DUA_ERR_ARG;
+  const long need = dua_surface_map_scratch_bytes(D, H, W, N * K, boxes);
+  if (need < 0 || workspace_bytes < need || (need > 0 && (!workspace || ((size_t)workspace & 255) != 0))) return DUA_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  for (int r = 0; r < N * K; ++r) {
+    const int n = r / K, k = r % K;
+    unsigned long long* counts_r = counts + (size_t)r * 5;
+    double* out_r = out + (size_t)r * DUA_SURFACE_FIELDS;
+    unsigned long long* within_r = within + (size_t)r * T * 2;
+    double* nsd_r = nsd + (size_t)r * T;
+    hipError_t e = hipMemsetAsync(counts_r, 0, 5 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return (int)e;
+    int o[3], b[3];
+    if (!map_box_grow(boxes + 6 * r, D, H, W, o, b)) {
+      // absent from both maps: the rows a pair of empty masks gets, without a border pass or a transform
+      e = hipMemsetAsync(within_r, 0, (size_t)T * 2 * sizeof(unsigned long long), s);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(dua::surface_finish_kernel, dim3(1), dim3(256), 0, s, 1, vox, counts_r, (const double*)nullptr, 0,
+                         (const unsigned long long*)nullptr, (const unsigned long long*)nullptr,
+                         (const unsigned long long*)nullptr, nan_for_nonexisting, out_r);
+      hipLaunchKernelGGL(dua::surface_dice_finish_kernel, dim3((T + 255) / 256), dim3(256), 0, s, 1, T, counts_r, within_r,
+                         nan_for_nonexisting, nsd_r);
+      continue;
+    }
+    const dua::SurfaceScratch L = dua::scratch_layout(1, b[0], b[1], b[2]);
+    const long svs = dua::align256((long)b[0] * b[1] * b[2]);
+    hipLaunchKernelGGL(dua::surface_map_masks_kernel, dim3((unsigned)((svs + dua::SURF_BLOCK_VOX - 1) / dua::SURF_BLOCK_VOX)),
+                       dim3(dua::SURF_THREADS), 0, s, test + (size_t)n * test_vstride, reference + (size_t)n * reference_vstride,
+                       class_ids[k], H, W, o[0], o[1], o[2], b[0], b[1], b[2], connectivity, ws + L.surf, svs, counts_r);
+    dua::SurfaceTolerances tol;
+    for (int i = 0; i < DUA_SURFACE_MAX_TOLERANCE_ENTRIES; ++i) tol.t2[i] = i < T ? all.t2[(size_t)k * T + i] : -1.0;
+    const int rc = surface_table_tail(1, b[0], b[1], b[2], vox, sd, sh, sw, nan_for_nonexisting, counts_r, out_r, ws, L, 1, T, &tol,
+                                      within_r, nsd_r, s);
+    if (rc) return rc;
+  }
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -466,7 +466,7 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
 
 def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
                  distributed: bool = False, group=None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125,
-                 min_prob: float = 0.0):
+                 min_prob: float = 0.0, postprocess: dict = None, surface: dict = None):
     """The deliverable of one case: (label map uint8 on the grid of the SCAN, Dice fp64 [C] against ``label`` or None).  ``case``:
     a ``prepare.PreparedCase`` -- the streamed blend runs on ``case.image[None, None]`` and one pass
     (dua_blend_finish_labelmap) turns the sum volume into the label map: per voxel of the scan the class probabilities
@@ -475,10 +475,22 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     [1, 1, D, H, W] instead: it is its own grid (identity tables, every weight 0), and the result is the arg-max of
     sigmoid(blend) on it.  ``label``: the raw uint8 label map of the scan, [*scan] on the case's device; class c = channel c, a
     value >= C counts nowhere.  The other arguments as ``evaluate_volume``.  Argument errors are raised before any predictor
-    call."""
+    call.
+
+    ``postprocess``: None, or a dict of ``postprocess.filter_label_map`` keywords (SEGMENT_POSTPROCESS_KEYS): the label map is
+    filtered as it is, on the scan's grid (one union-find for all classes, no one-hot tensor); the map returned is the filtered
+    one and the Dice is that of the filtered map, from the filter pass's tallies.  ``surface``: None, or a dict with a
+    ``tolerance`` and optionally ``connectivity``, ``nan_for_nonexisting``, ``classes`` (default 1 .. C - 1) and
+    ``voxel_spacing`` (default ``case.source_spacing``, the scan's own spacing, or 1 for a plain tensor); it needs ``label``, and
+    the result is then (map, dice, report) with report = ``metrics.label_map_surface_report`` of the returned map against
+    ``label`` (one host read of the box table).  With neither, nothing new is launched."""
     from . import ops
     from .prepare import PreparedCase
     mirror_flips(mirror_axes)
+    if postprocess is not None:
+        _segment_postprocess_kwargs(postprocess)
+    if surface is not None:
+        _segment_surface_kwargs(surface, label)
     min_prob = float(min_prob)
     if not 0.0 <= min_prob <= 1.0:                       # NaN fails both comparisons
         raise ValueError(f"segment_case: min_prob lies in [0, 1], got {min_prob}")
@@ -517,9 +529,85 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
-        out, tallies = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
-                                                 None if label is None else label.contiguous())
-    return out, ops.dice_from_tallies(tallies) if tallies is not None else None
+        if postprocess is None:
+            out, tallies = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
+                                                     None if label is None else label.contiguous())
+        else:
+            from .postprocess import filter_label_map
+            out, _ = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob, None)
+            out, tallies = filter_label_map(out, int(acc.shape[-4]), reference=label, **postprocess)
+    dice = ops.dice_from_tallies(tallies) if tallies is not None else None
+    if surface is None:
+        return out, dice
+    from . import metrics
+    kw = dict(surface)
+    classes = kw.pop("classes", None)
+    if classes is None:
+        classes = range(1, int(acc.shape[-4]))
+    if kw.get("voxel_spacing") is None:
+        kw["voxel_spacing"] = case.source_spacing if isinstance(case, PreparedCase) else None
+    return out, dice, metrics.label_map_surface_report(out, label, classes, kw.pop("tolerance"), **kw)
+
+
+SEGMENT_POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "classes", "cap")
+SEGMENT_SURFACE_KEYS = ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting", "classes")
+
+
+def _segment_postprocess_kwargs(postprocess):
+    """Refuse a ``postprocess`` argument of ``segment_case`` that is not a dict of ``filter_label_map`` keywords with values that
+    function takes, before any predictor call."""
+    from . import postprocess as pp
+    if not isinstance(postprocess, dict) or any(k not in SEGMENT_POSTPROCESS_KEYS for k in postprocess):
+        raise ValueError(f"postprocess: None or a dict with keys among {SEGMENT_POSTPROCESS_KEYS}, got {postprocess!r}")
+    pp._connectivity(postprocess.get("connectivity", 1))
+    pp._count(postprocess.get("num_components", 1), "num_components")
+    pp._count(postprocess.get("min_size", 0), "min_size")
+    pp._cap(postprocess.get("cap"))
+    classes = postprocess.get("classes")
+    if classes is not None and (isinstance(classes, (str, bytes)) or not hasattr(classes, "__iter__") or
+                                any(isinstance(c, bool) or not isinstance(c, int) or c < 1 for c in classes)):
+        raise ValueError(f"postprocess: classes is None or integers >= 1, got {classes!r}")
+
+
+def _segment_surface_kwargs(surface, label):
+    """Refuse a ``surface`` argument of ``segment_case`` that is not a dict of SEGMENT_SURFACE_KEYS with a tolerance, or that
+    comes without a label, before any predictor call."""
+    if not isinstance(surface, dict) or any(k not in SEGMENT_SURFACE_KEYS for k in surface) or "tolerance" not in surface:
+        raise ValueError(f"surface: None or a dict with a 'tolerance' and keys among {SEGMENT_SURFACE_KEYS}, got {surface!r}")
+    if label is None:
+        raise ValueError("surface: the surface metrics compare the label map with label; label is None")
+    if surface.get("connectivity", 1) not in (1, 2, 3) or isinstance(surface.get("connectivity", 1), bool):
+        raise ValueError(f"surface: connectivity must be 1, 2 or 3, got {surface.get('connectivity')!r}")
+    from . import _native as nv
+    from . import metrics, ops
+    classes = surface.get("classes")
+    if classes is not None:
+        if isinstance(classes, (str, bytes)) or not hasattr(classes, "__iter__"):
+            raise ValueError(f"surface: classes is None or a non-empty sequence of class ids, got {classes!r}")
+        classes = list(classes)
+        if not classes or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < nv.BLEND_MAX_CLASSES for c in classes):
+            raise ValueError(f"surface: classes is None or a non-empty sequence of integers in 0..{nv.BLEND_MAX_CLASSES - 1}, got "
+                             f"{classes!r}")
+    # the tolerance against the classes when they are given; against its own length otherwise (the default classes are
+    # 1 .. C - 1, known only once the predictor has run: values, T and the table's limits are still checked here)
+    tolerance = surface["tolerance"]
+    if hasattr(tolerance, "tolist"):
+        tolerance = tolerance.tolist()
+    try:
+        if classes is not None:
+            metrics._tolerance_rows(tolerance, len(classes))
+        elif isinstance(tolerance, (int, float)) and not isinstance(tolerance, bool):
+            metrics._tolerance_rows(tolerance, 1)
+        else:
+            metrics._tolerance_rows(tolerance, len(list(tolerance)))
+        spacing = ops._spacing3(surface.get("voxel_spacing"))
+    except TypeError as e:
+        raise ValueError(f"surface: {e}") from None
+    except ValueError as e:
+        raise ValueError(e.args[0] if str(e).startswith(("tolerance", "voxel_spacing")) else
+                         f"surface: tolerance and voxel_spacing hold numbers ({e})") from None
+    if not all(0.0 < x < float("inf") for x in spacing):
+        raise ValueError(f"surface: voxel_spacing must be finite and > 0, got {surface.get('voxel_spacing')!r}")
 
 
 SURFACE_KEYS = ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting", "distances")

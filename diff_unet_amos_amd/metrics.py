@@ -175,3 +175,85 @@ def normalized_surface_dice(test, reference, tolerance, voxel_spacing=None, conn
     t = surface_dice_table(test[None, None], reference[None, None], float(tolerance), voxel_spacing, connectivity,
                            nan_for_nonexisting)
     return float(t["nsd"][0, 0, 0])
+
+
+# ---- two label maps, per class, inside the class's box (include/dua_hip.h "surface report of two label maps") --------------------
+
+def label_map_workspace_bytes(shape, boxes):
+    """Workspace bytes of ``label_map_surface_report`` per class: ``boxes`` are host rows [N][K][6] (d0, h0, w0, d1, h1, w1),
+    half-open, d1 == 0 for a class in neither map; the result is a list of K ints, entry k the bytes class k needs -- the
+    distance table's workspace on its largest box over the N map pairs, grown by one voxel per side and clamped to ``shape``.
+    The (pair, class) rows of a call run one after the other and share one region, so a call needs ``max`` of the list.  Host
+    arithmetic (dua_surface_map_scratch_bytes): no device is needed."""
+    K = len(boxes[0])
+    return [ops.surface_map_workspace_bytes(shape, [pair[k] for pair in boxes]) for k in range(K)]
+
+
+def class_groups(needs, max_workspace_bytes=None):
+    """The groups the classes 0 .. K - 1 are processed in under ``max_workspace_bytes`` (``needs``: bytes per class).  The classes
+    of a group share one region sized to its largest class, so as soon as every class fits, ONE group does: the limit requires
+    no more.  A class that alone exceeds the limit is refused (ValueError)."""
+    if max_workspace_bytes is not None:
+        if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
+            raise ValueError(f"max_workspace_bytes must be None or an integer >= 1, got {max_workspace_bytes!r}")
+        for k, need in enumerate(needs):
+            if need > max_workspace_bytes:
+                raise ValueError(f"max_workspace_bytes={max_workspace_bytes}: class index {k} alone needs {need} bytes")
+    return [list(range(len(needs)))]
+
+
+def _label_map_pair(test_map, reference_map):
+    for t, name in ((test_map, "test_map"), (reference_map, "reference_map")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on the MI355X")
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name}: a uint8 label map of class ids, not {t.dtype}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: surface distances run on an MI355X (device 'cuda'); there is no CPU path in this package")
+    if test_map.dim() not in (3, 4) or 0 in test_map.shape or tuple(test_map.shape) != tuple(reference_map.shape):
+        raise ValueError(f"test_map and reference_map: two label maps [D, H, W] or [N, D, H, W] of one shape, got "
+                         f"{tuple(test_map.shape)} and {tuple(reference_map.shape)}")
+    if test_map.dim() == 3:
+        return test_map[None], reference_map[None]
+    return test_map, reference_map
+
+
+def label_map_surface_report(test_map, reference_map, classes, tolerance, voxel_spacing=None, connectivity=1,
+                             nan_for_nonexisting=True, boxes=None, max_workspace_bytes=None):
+    """``surface_report`` of two uint8 device label maps ([D, H, W] or [N, D, H, W]) for the class ids in ``classes`` (K of them,
+    each in 0..63), with the mask of class c read as (map == c) from the maps themselves -- no one-hot tensor -- and each class
+    worked on inside its bounding box in both maps, grown by one voxel.  Returns the keys of ``surface_report``: fp64 / int64
+    [N, K], and [N, K, T] for ``nsd`` / ``within_test`` / ``within_reference``.  Every integer count, hd, hd95, nsd and the
+    within counts are bit-identical to ``surface_report`` on the expansion over the full extent; asd / assd sum the same fp64
+    terms in another block order.  ``tolerance``: a scalar, K values or a [K, T] table, as ``surface_dice_table``.
+
+    HOST SYNCHRONISATION: the box table int32 [N, K, 6] is computed on the device and read to the host once per call, to size
+    the launches and the workspace; that is the only one.  ``boxes`` (what an earlier call's maps gave, an int32 tensor or
+    nested rows [N][K][6], (d0, h0, w0, d1, h1, w1) half-open, d1 == 0 for a class in neither map) avoids it.
+    ``max_workspace_bytes``: a limit on the workspace of the call (``max(label_map_workspace_bytes(...))``: the classes run
+    one after the other in one region sized to the largest box, so one group of classes always suffices, see ``class_groups``);
+    a class whose box alone needs more is refused with a ValueError before anything is launched."""
+    a, b = _label_map_pair(test_map, reference_map)
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1, 2 or 3, got {connectivity!r}")
+    ids = [int(c) for c in classes]
+    if not ids or any(c < 0 or c >= nv.BLEND_MAX_CLASSES for c in ids):
+        raise ValueError(f"classes: at least one class id in 0..{nv.BLEND_MAX_CLASSES - 1}, got {list(classes)!r}")
+    N, K = a.shape[0], len(ids)
+    rows = _tolerance_rows(tolerance, K)
+    T = len(rows[0])
+    if boxes is None:
+        table = ops.surface_map_boxes(a, b, max(ids) + 1)[:, ids]
+        boxes = table.cpu().tolist()                                  # the one host read of this function
+    else:
+        boxes = boxes.tolist() if hasattr(boxes, "tolist") else [[list(r) for r in pair] for pair in boxes]
+        if len(boxes) != N or any(len(pair) != K or any(len(r) != 6 for r in pair) for pair in boxes):
+            raise ValueError(f"boxes: [{N}][{K}][6] rows (d0, h0, w0, d1, h1, w1), one per (map pair, class)")
+    class_groups(label_map_workspace_bytes(a.shape[1:], boxes), max_workspace_bytes)        # one group, or a refusal
+    counts, table, within, nsd = ops.surface_map_report(a, b, ids, [r for pair in boxes for r in pair], rows, voxel_spacing,
+                                                        connectivity, nan_for_nonexisting)
+    table = table.view(N, K, -1)
+    col = {name: i for i, name in enumerate(nv.SURFACE_FIELDS)}
+    out = {k: table[:, :, col[k]] for k in TABLE_KEYS}
+    out.update(_dice_dict(counts, within, nsd, N, K))
+    return out

@@ -1883,6 +1883,131 @@ def cc_filter(labels, counts, sizes, k=1, min_size=0, apply=None, mask=None, ref
     return out, tallies
 
 
+def _label_maps(t, name):
+    """A uint8 device tensor [N, D, H, W] of class ids, contiguous, as (tensor, N, D, H, W)."""
+    assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4, f"{name}: a uint8 device tensor [N, D, H, W] of class ids"
+    t = t.contiguous()
+    return (t, *t.shape)
+
+
+def _cc_map_workspace(V, D, H, W, cap, device):
+    need = int(nv.lib().dua_cc_map_scratch_bytes(V, D, H, W, int(cap)))
+    if need < 0:
+        raise ValueError(f"connected components: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1) "
+                         f"or cap={cap} (1..{nv.CC_MAX_CAP})")
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
+def cc_label_map(label_map, num_classes, connectivity=1):
+    """dua_cc_label_map for every map of label_map (uint8 [N, D, H, W]): (labels int32 [N, D, H, W], counts int32 [N]); the
+    components of all classes 1 .. num_classes - 1 numbered together by their first voxel, two voxels connected only when they
+    carry the same value.  No host synchronisation."""
+    m, V, D, H, W = _label_maps(label_map, "label_map")
+    ws, need = _cc_map_workspace(V, D, H, W, 1, m.device)
+    labels = torch.empty((V, D, H, W), dtype=torch.int32, device=m.device)
+    counts = torch.empty((V,), dtype=torch.int32, device=m.device)
+    with torch.cuda.device(m.device):
+        nv.check(nv.lib().dua_cc_label_map(V, D, H, W, nv.ptr(m), D * H * W, int(num_classes), int(connectivity), nv.ptr(labels),
+                                           nv.ptr(counts), nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_label_map")
+    return labels, counts
+
+
+def cc_filter_map(label_map, num_classes, labels, counts, sizes, k=1, min_size=0, apply=None, reference=None):
+    """dua_cc_filter_map: (filtered map uint8 [N, D, H, W], tallies int64 [num_classes, 3] or None).  ``labels`` / ``counts`` as
+    ``cc_label_map`` returns them, ``sizes`` as ``cc_sizes``; per class the ``k`` largest components are kept (0: no limit),
+    none below ``min_size`` voxels.  ``apply``: uint8 [num_classes] device flags, a class with 0 is passed through.
+    ``reference``: a uint8 label map like ``label_map``; with it, the tallies of ``blend_finish`` for the filtered map."""
+    m, V, D, H, W = _label_maps(label_map, "label_map")
+    dev, Cn = m.device, int(num_classes)
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (V, D, H, W) and \
+        labels.device == dev, f"labels: contiguous int32 [{V}, {D}, {H}, {W}] on the map's device"
+    _i32c(counts, "counts")
+    _i32c(sizes, "sizes")
+    assert tuple(counts.shape) == (V,) and sizes.dim() == 2 and sizes.shape[0] == V and counts.device == dev and \
+        sizes.device == dev, f"counts int32 [{V}] and sizes int32 [{V}, cap] on the map's device"
+    cap = int(sizes.shape[1])
+    apply = _cc_flags(apply, Cn, "apply", dev)
+    ref = None
+    if reference is not None:
+        ref, *rshape = _label_maps(reference, "reference")
+        assert tuple(rshape) == (V, D, H, W) and ref.device == dev, "reference: a label map like label_map, on its device"
+    ws, need = _cc_map_workspace(V, D, H, W, cap, dev)
+    out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_cc_filter_map(V, D, H, W, nv.ptr(m), D * H * W, Cn, nv.ptr(labels), nv.ptr(counts), nv.ptr(sizes),
+                                            cap, int(k), int(min_size), nv.ptr(apply), nv.ptr(out), nv.ptr(ref), nv.ptr(tallies),
+                                            nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_filter_map")
+    return out, tallies
+
+
+# ---- evaluation: surface report of two label maps (csrc/surface.hip) --------------------------------------------------------------
+
+def surface_map_boxes(test_map, reference_map, num_classes):
+    """dua_surface_map_boxes: int32 [N, num_classes, 6] device table, row (n, c) = (d0, h0, w0, d1, h1, w1), half-open, the
+    bounding box of (test_map[n] == c) | (reference_map[n] == c); d1 == 0 where class c is in neither.  No host synchronisation."""
+    a, N, D, H, W = _label_maps(test_map, "test_map")
+    b, *bshape = _label_maps(reference_map, "reference_map")
+    assert tuple(bshape) == (N, D, H, W) and b.device == a.device, "test_map and reference_map: one shape, one device"
+    boxes = torch.empty((N, int(num_classes), 6), dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        nv.check(nv.lib().dua_surface_map_boxes(N, D, H, W, nv.ptr(a), D * H * W, nv.ptr(b), D * H * W, int(num_classes),
+                                                nv.ptr(boxes), nv.stream_ptr()), "dua_surface_map_boxes")
+    return boxes
+
+
+def _host_boxes(boxes):
+    """A host box table (a list of rows of six ints) as a ctypes int array."""
+    import ctypes as C
+    flat = [int(x) for row in boxes for x in row]
+    assert flat and len(flat) % 6 == 0, "boxes: rows of (d0, h0, w0, d1, h1, w1)"
+    return (C.c_int * len(flat))(*flat), len(flat) // 6
+
+
+def surface_map_workspace_bytes(shape, boxes):
+    """dua_surface_map_scratch_bytes: the workspace ``surface_map_report`` needs for the rows of ``boxes`` (host rows of six ints)
+    in a volume of extents ``shape``: per row that is not absent, the workspace of the distance table on the box grown by one
+    voxel per side and clamped.  Host arithmetic; no device is touched."""
+    D, H, W = (int(x) for x in shape)
+    arr, rows = _host_boxes(boxes)
+    need = int(nv.lib().dua_surface_map_scratch_bytes(D, H, W, rows, arr))
+    if need < 0:
+        raise ValueError(f"surface report of label maps: unsupported extents {(D, H, W)} or a box outside them in {boxes!r}")
+    return need
+
+
+def surface_map_report(test_map, reference_map, classes, boxes, tolerances, voxel_spacing=None, connectivity=1,
+                       nan_for_nonexisting=True):
+    """dua_surface_map_report: ``surface_report`` of the masks (test_map == c, reference_map == c) for c in ``classes``, each inside
+    its box: (counts int64 [N K, 5], table fp64 [N K, len(nv.SURFACE_FIELDS)], within int64 [N K, T, 2], nsd fp64 [N K, T]), row
+    n K + k for classes[k].  ``boxes``: HOST rows [N K][6]; ``tolerances``: a host [K][T] table.  No host synchronisation."""
+    import ctypes as C
+    a, N, D, H, W = _label_maps(test_map, "test_map")
+    b, *bshape = _label_maps(reference_map, "reference_map")
+    assert tuple(bshape) == (N, D, H, W) and b.device == a.device, "test_map and reference_map: one shape, one device"
+    ids = [int(c) for c in classes]
+    K = len(ids)
+    arr, rows = _host_boxes(boxes)
+    assert rows == N * K, f"boxes: {N * K} rows, one per (map pair, class), got {rows}"
+    sd, sh, sw = _spacing3(voxel_spacing)
+    tol, tol_classes, T = _tolerance_table(tolerances)
+    assert tol_classes == K, f"tolerances: one row per class ({K}), got {tol_classes}"
+    need = surface_map_workspace_bytes((D, H, W), boxes)
+    dev = a.device
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    counts = torch.empty((N * K, 5), dtype=torch.int64, device=dev)
+    out = torch.empty((N * K, len(nv.SURFACE_FIELDS)), dtype=torch.float64, device=dev)
+    within = torch.empty((N * K, T, 2), dtype=torch.int64, device=dev)
+    nsd = torch.empty((N * K, T), dtype=torch.float64, device=dev)
+    vox = D * H * W
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_surface_map_report(N, D, H, W, nv.ptr(a), vox, nv.ptr(b), vox, K, (C.c_int * K)(*ids), arr,
+                                                 int(connectivity), sd, sh, sw, T, tol, int(bool(nan_for_nonexisting)),
+                                                 nv.ptr(counts), nv.ptr(out), nv.ptr(within), nv.ptr(nsd), nv.ptr(ws), need,
+                                                 nv.stream_ptr()), "dua_surface_map_report")
+    return counts, out, within, nsd
+
+
 # ---- training input: augmented batches from device-resident volumes (csrc/augment.hip; utils.py:143-160, engine.py:157-165) ----
 
 def _i32c(t, name):

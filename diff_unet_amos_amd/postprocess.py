@@ -162,3 +162,86 @@ def keep_largest_components(mask, connectivity=1, num_components=1, min_size=0, 
 def remove_small_components(mask, min_size, connectivity=1, channels=None, cap=None):
     """``keep_largest_components`` without a limit on the number: every component of at least ``min_size`` voxels stays."""
     return filter_components(mask, connectivity, 0, min_size, channels, cap)[0]
+
+
+# ---- a label map as it is: one union-find for all classes (include/dua_hip.h "Components of a label map") ------------------------
+#
+# ``segment_case`` returns one uint8 label map on the grid of the scan.  The functions below label and filter it without the
+# [C, *scan] one-hot tensor: a voxel with value c in 1 .. num_classes - 1 is foreground of class c, 0 and values >= num_classes
+# are background to the labelling and pass through the filter, and two adjacent foreground voxels are connected only when they
+# carry the same value.  Per class c the components are those of scipy.ndimage.label(label_map == c, structure), in scipy's
+# order; all classes are numbered together by their first voxel.  The keep-largest rule applies per class.
+
+def _device_label_map(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a torch tensor on the MI355X")
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{name}: a uint8 label map of class ids, not {t.dtype}")
+    if t.dim() not in (3, 4) or 0 in t.shape:
+        raise ValueError(f"{name}: a non-empty label map [D, H, W] or [N, D, H, W], got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+    return t if t.dim() == 4 else t[None]
+
+
+def _num_classes(num_classes):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= nv.BLEND_MAX_CLASSES:
+        raise ValueError(f"num_classes must be an integer in 1..{nv.BLEND_MAX_CLASSES}, got {num_classes!r}")
+    return num_classes
+
+
+def _class_list(classes, num_classes):
+    """The sorted list of ``classes`` (None: all), checked against 1 .. num_classes - 1."""
+    if classes is None:
+        return None
+    chosen = sorted({int(c) for c in classes})
+    if any(c < 1 or c >= num_classes for c in chosen):
+        raise ValueError(f"classes must lie in 1..{num_classes - 1}, got {list(classes)!r}")
+    return chosen
+
+
+def label_map_components(label_map, num_classes, connectivity=1):
+    """(labels int32 shaped like ``label_map``, count int32 [N] or a 0-d tensor) of a uint8 device label map [D, H, W] or
+    [N, D, H, W]: the components of the classes 1 .. num_classes - 1, numbered 1, 2, ... together by their first voxel in raster
+    order.  For every class c, the labels on (label_map == c) are those of scipy.ndimage.label(label_map == c, structure) in the
+    same order; the class of a label is the map's value on it."""
+    Cn, conn = _num_classes(num_classes), _connectivity(connectivity)
+    m = _device_label_map(label_map, "label_map")
+    labels, counts = ops.cc_label_map(m, Cn, conn)
+    return labels.view(label_map.shape), counts.view(label_map.shape[:-3])
+
+
+def filter_label_map(label_map, num_classes, connectivity=1, num_components=1, min_size=0, classes=None, cap=None, reference=None):
+    """(filtered uint8 label map shaped like ``label_map``, tallies int64 [num_classes, 3] or None).  A component of class c stays
+    when it is among the ``num_components`` largest components OF CLASS c (ties to the component whose first voxel comes first;
+    0 = no limit) and has at least ``min_size`` voxels; the voxels of a dropped component become 0.  ``classes``: the classes that
+    are filtered (None: 1 .. num_classes - 1), the others pass through, as do 0 and values >= num_classes.  ``cap``: the size
+    table's entries per map, over all classes together (the overflow rule of the module).  ``reference``: a uint8 label map
+    like ``label_map``; with it the same pass writes the Dice tallies (|A & B|, |A|, |B|) per class of the filtered map, which
+    ``ops.dice_from_tallies`` turns into Dice."""
+    Cn, conn = _num_classes(num_classes), _connectivity(connectivity)
+    k, min_size, cap = _count(num_components, "num_components"), _count(min_size, "min_size"), _cap(cap)
+    chosen = _class_list(classes, Cn)
+    m = _device_label_map(label_map, "label_map")
+    ref = None
+    if reference is not None:
+        if not isinstance(reference, torch.Tensor) or not reference.is_cuda:
+            raise RuntimeError("reference: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+        if reference.dtype != torch.uint8 or tuple(reference.shape) != tuple(label_map.shape):
+            raise ValueError(f"reference: a uint8 label map {tuple(label_map.shape)}, got {reference.dtype} {tuple(reference.shape)}")
+        ref = reference.view(m.shape)
+    flags = None
+    if chosen is not None:
+        flags = torch.zeros((1, Cn), dtype=torch.uint8, device=m.device)  # filled on the device: a capture holds no host copy
+        for c in chosen:
+            flags[:, c] = 1
+        flags = flags.view(-1)
+    lab, counts = ops.cc_label_map(m, Cn, conn)
+    sizes = ops.cc_sizes(lab, cap)
+    out, tallies = ops.cc_filter_map(m, Cn, lab, counts, sizes, k, min_size, apply=flags, reference=ref)
+    return out.view(label_map.shape), tallies
+
+
+def keep_largest_in_label_map(label_map, num_classes, connectivity=1, num_components=1, min_size=0, classes=None, cap=None):
+    """``filter_label_map`` without a reference: the filtered uint8 label map alone."""
+    return filter_label_map(label_map, num_classes, connectivity, num_components, min_size, classes, cap)[0]

@@ -197,6 +197,17 @@ class PreparedCase:
         g = self.geometry
         return {"lo": g.lo, "weight": g.weight, "nearest": g.nearest}
 
+    @property
+    def source_spacing(self):
+        """The voxel spacing of the scan per SOURCE axis (the unit of the affine, millimetres for AMOS), as the surface metrics
+        take it for a label map on the scan's grid: ``geometry.s_in`` is per prepared axis, ``geometry.perm[j]`` the source
+        axis behind prepared axis j.  Host arithmetic only."""
+        g = self.geometry
+        s = [0.0, 0.0, 0.0]
+        for j, p in enumerate(g.perm):
+            s[p] = float(g.s_in[j])
+        return tuple(s)
+
     def linear_tables(self):
         """``linear_restore_tables`` of this case on its device, as ``ops.blend_finish_labelmap`` takes them: (three int32 lo
         vectors, three fp32 weight vectors, the prepared axis of each source axis); uploaded once."""

@@ -999,6 +999,76 @@ int dua_cc_filter(int V, int D, int H, int W, const int* labels, const int* coun
                   unsigned char* out, const void* reference, int reference_dtype, int label_map, int C,
                   unsigned long long* tallies, void* workspace, long workspace_bytes, void* stream);
 
+/* Components of a label map.  The same labelling and filter for V = N uint8 maps [D][H][W] of class ids and a class count
+ * C <= DUA_BLEND_MAX_CLASSES, without a one-hot expansion; map v starts map_vstride bytes after map v - 1.
+ *   Foreground.  A voxel with value c in 1..C-1 is foreground of class c.  Value 0 and values >= C are background to the
+ *     labelling.
+ *   Adjacency.  Two adjacent foreground voxels are connected iff they carry the SAME value; adjacent means
+ *     generate_binary_structure(3, k) as above.  Every component therefore has one class, the value at its root.
+ *   Labels.  One union-find over the map serves all classes: the components of all classes are numbered 1, 2, ... together,
+ *     by their first voxel in raster order; counts[v] is their number over all classes.  For every class c the set of
+ *     components of class c is exactly that of scipy.ndimage.label(map == c, structure), and the joint numbering restricted to
+ *     class c keeps scipy's order (the r-th label of class c, in increasing order, is scipy's label r).
+ *   Sizes.  dua_cc_sizes on those labels, unchanged, with the overflow rule above against cap.
+ *   Filter.  With n = min(counts[v], cap), label l in 1..n of class c is kept when
+ *       (k == 0 or its position among the labels OF CLASS c in np.argsort(-sizes, kind="stable") is below k)
+ *       and  sizes[v][l - 1] >= min_size.
+ *     apply (uint8 [C], may be NULL = all): a class with apply[c] == 0 is passed through.  A voxel of out keeps its value when
+ *     its component is kept, when its class is passed through, or when its value is 0 or >= C; otherwise it becomes 0.  Labels
+ *     above cap are never kept.
+ * Integer-only, exact, identical between runs, enqueue-only and capturable, like the entry points above. */
+/* Bytes of workspace dua_cc_label_map and dua_cc_filter_map take: dua_cc_scratch_bytes plus V cap bytes (the class of every
+ * label). */
+long dua_cc_map_scratch_bytes(int V, int D, int H, int W, int cap);
+/* labels (int32 [V][D H W], WRITTEN) and counts (int32 [V], WRITTEN) of map, as stated above.  workspace: at least
+ * dua_cc_map_scratch_bytes(V, D, H, W, cap) bytes for any cap, 256-byte aligned. */
+int dua_cc_label_map(int V, int D, int H, int W, const unsigned char* map, long map_vstride, int C, int connectivity, int* labels,
+                     int* counts, void* workspace, long workspace_bytes, void* stream);
+/* out (uint8 [V][D H W], WRITTEN) = the filtered map, from map and the labels, counts and sizes the calls above left (same
+ * cap).  reference (uint8 [V][D H W], a label map) and tallies are given together or not at all: tallies (64-bit unsigned
+ * [C][3], WRITTEN, the call zeroes it first) = |A & B|, |A|, |B| per class over batch and space, A = (out == c),
+ * B = (reference == c), in the layout of dua_blend_finish; a value >= C counts nowhere. */
+int dua_cc_filter_map(int V, int D, int H, int W, const unsigned char* map, long map_vstride, int C, const int* labels,
+                      const int* counts, const int* sizes, int cap, int k, int min_size, const unsigned char* apply,
+                      unsigned char* out, const unsigned char* reference, unsigned long long* tallies, void* workspace,
+                      long workspace_bytes, void* stream);
+
+/* ---- evaluation: surface report of two label maps ----------------------------------------------------------------------------
+ * dua_surface_report for N pairs of uint8 label maps [D][H][W] (test, reference) and K classes, without a one-hot expansion:
+ * row n K + k of every output is the row dua_surface_report gives for the pair of masks (test[n] == class_ids[k],
+ * reference[n] == class_ids[k]).  Each (pair, class) is worked on inside its box only:
+ *   box      = the bounding box of (test == c) | (reference == c), as a row (d0, h0, w0, d1, h1, w1), half-open; d1 == 0 says the
+ *              class is absent from both maps (dua_surface_map_boxes then leaves d0 = h0 = w0 = INT_MAX, h1 = w1 = 0);
+ *   grid     = the box grown by one voxel per side and clamped to the volume.  A foreground voxel on a face of that grid is on a
+ *              face of the volume, so the borders are those of the full volume (border_value 0: a voxel on a face of the
+ *              volume is always a border voxel).  All seeds and all queries of the transform lie in the grid, so every squared
+ *              distance is the minimum of the same fp64 sums as in the full volume: the same bits;
+ *   outputs  : every integer count, hd, hd95 (and its two order statistics), within and nsd are bit-identical to
+ *              dua_surface_report on the expansion; tn counts against the full D H W; asd / assd sum the same fp64 terms in
+ *              another block order;
+ *   absent   : a class absent from both maps gets the rows of two empty masks (the nan_for_nonexisting rule), with no border
+ *              pass and no transform.
+ * The box table lives on the HOST for dua_surface_map_report: it sizes the launches and the workspace.  Reading the table
+ * dua_surface_map_boxes wrote back to the host is the one synchronisation of this path, and it is the caller's; a caller who
+ * knows the boxes passes them and synchronises nowhere.  A row of boxes that is neither absent nor a non-empty box inside the
+ * volume: DUA_ERR_ARG.  A box that does not contain its class gives the metrics of the class clipped to the grid.  tolerances:
+ * a HOST array fp64 [K][T], limits as above; class_ids: HOST int [K], values 0..255.  N K <= 65535. */
+/* boxes (int32 [N][C][6], WRITTEN) of every value 0..C-1, C <= DUA_BLEND_MAX_CLASSES; integer min / max atomics, enqueue-only. */
+int dua_surface_map_boxes(int N, int D, int H, int W, const unsigned char* test, long test_vstride, const unsigned char* reference,
+                          long reference_vstride, int C, int* boxes, void* stream);
+/* Bytes of workspace dua_surface_map_report needs for `rows` rows of a HOST box table: the LARGEST over the rows that are not
+ * absent of dua_surface_scratch_bytes(1, grid extents) -- the rows run one after the other on the stream and share one
+ * region.  Host arithmetic only. */
+long dua_surface_map_scratch_bytes(int D, int H, int W, int rows, const int* boxes);
+/* counts (int64 [N K][5]), out (fp64 [N K][DUA_SURFACE_FIELDS]), within (uint64 [N K][T][2]), nsd (fp64 [N K][T]): all WRITTEN.
+ * boxes: HOST int32 [N K][6], row n K + k for class_ids[k] in pair n.  workspace: at least
+ * dua_surface_map_scratch_bytes(D, H, W, N K, boxes) bytes, 256-byte aligned (may be NULL when that is 0). */
+int dua_surface_map_report(int N, int D, int H, int W, const unsigned char* test, long test_vstride,
+                           const unsigned char* reference, long reference_vstride, int K, const int* class_ids, const int* boxes,
+                           int connectivity, double sd, double sh, double sw, int T, const double* tolerances,
+                           int nan_for_nonexisting, unsigned long long* counts, double* out, unsigned long long* within,
+                           double* nsd, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- training input: augmented batches from device-resident volumes ------------------------------------------------
  * The random tail of the reference's training transforms (utils.py:143-160: RandCropByPosNegLabeld, three RandFlipd,
  * RandRotate90d, RandScaleIntensityd, RandShiftIntensityd) and the one-hot expansion of Engine.convert_labels
