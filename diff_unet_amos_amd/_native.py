@@ -338,6 +338,11 @@ _SIGS = {
     "dua_cc_label_map": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_int, _P, _P, _P, C.c_long, _P]),
     "dua_cc_filter_map": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                     _P, C.c_long, _P]),
+    "dua_fill_holes_scratch_bytes": (C.c_long, [C.c_int] * 5),
+    "dua_fill_holes_mask": (C.c_int, [C.c_int] * 4 + [_P, C.c_int, C.c_long, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                      _P, C.c_long, _P]),
+    "dua_fill_holes_map": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, C.c_int, C.c_int, C.c_ulonglong, _P, _P, _P, _P, _P, C.c_long,
+                                     _P]),
     "dua_surface_map_boxes": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, _P, C.c_long, C.c_int, _P, _P]),
     "dua_surface_map_scratch_bytes": (C.c_long, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
     "dua_surface_map_report": (C.c_int, [C.c_int] * 4 + [_P, C.c_long, _P, C.c_long, C.c_int, C.POINTER(C.c_int),

@@ -17,68 +17,11 @@
 //   filter  : per volume the k largest labels (ties to the smaller label) and / or those of at least min_size voxels are kept;
 //             one pass writes the uint8 mask and, with a reference, the three Dice counts per class.
 // Integer work throughout: results are exact and do not depend on the order in which workgroups run.
-#include "common.hpp"
-#include "../../include/dua_hip.h"
+// The find / union, the run start of the inits and the merge and flatten launches are shared with fill_holes.hip through
+// components.hpp.
+#include "components.hpp"
 
 namespace dua {
-
-constexpr int CC_THREADS = 256;
-constexpr int CC_PER_THREAD = 4;
-constexpr int CC_SCAN_BLOCK = CC_THREADS * CC_PER_THREAD;      // voxels per block of the numbering scan (and of sizes / filter)
-constexpr int CC_WAVES = CC_THREADS / 64;
-constexpr int CC_BG = -1;                                      // parent of a background voxel
-enum : int { CC_REF_NONE = 0, CC_REF_ONEHOT_F32, CC_REF_ONEHOT_U8, CC_REF_MAP };
-
-__device__ __forceinline__ bool cc_fg(const void* m, int is_f32, size_t i) {
-  return is_f32 ? reinterpret_cast<const float*>(m)[i] != 0.f : reinterpret_cast<const unsigned char*>(m)[i] != 0;
-}
-
-__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int cc_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// THE INVARIANT of every loop below: parent[i] <= i for every foreground voxel, at all times, and a slot only ever decreases
-// (init writes the start of the voxel's run, merge writes with atomicMin a root smaller than the slot's index, flatten writes
-// the root).  So the chain i, parent[i], parent[parent[i]], ... strictly decreases until it meets a slot with parent[i] == i:
-// find terminates, whatever other threads store meanwhile (a value read late is an older, larger ancestor of the same set).
-__device__ __forceinline__ int cc_find(const int* parent, int i) {
-  int p = cc_load(parent + i);
-  while (p != i) {                    // p < i
-    i = p;
-    p = cc_load(parent + i);
-  }
-  return i;
-}
-
-// Lock-free union.  hi > lo are the two roots found; atomicMin writes lo into hi's slot and returns what the slot held.
-//   old == hi : the slot was still a root when written -- hi's set now hangs below lo, done.
-//   old <  hi : another thread had linked hi below old first.  The slot now holds min(old, lo), so hi stays attached to one of
-//               them and the link that remains to be made is old ~ lo: repeat with their roots.
-// Both new roots are < hi (find(old) <= old < hi, find(lo) <= lo < hi), so max(a, b) strictly decreases from one iteration to
-// the next and the loop ends, at the latest with both roots equal.
-__device__ __forceinline__ void cc_union(int* parent, int a, int b) {
-  a = cc_find(parent, a);
-  b = cc_find(parent, b);
-  while (a != b) {
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    const int old = __hip_atomic_fetch_min(parent + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == hi) break;
-    a = cc_find(parent, old);
-    b = cc_find(parent, lo);
-  }
-}
-
-// the parent the init writes: the first voxel of the lane's run inside its wave (`starts` has a bit per run start), CC_BG for
-// background
-__device__ __forceinline__ int cc_run_parent(bool fg, unsigned long long starts, int lane, long p) {
-  if (!fg) return CC_BG;
-  const unsigned long long below = starts & (~0ull >> (63 - lane));         // bits 0 .. lane: never empty for a foreground lane
-  return (int)p - (lane - (63 - __clzll((long long)below)));
-}
 
 // grid (ceil(vox / 256), V).  A wave holds 64 consecutive voxels: every lane takes part in the ballots.  A volume with
 // select[v] == 0 is all background to everything that follows.
@@ -451,14 +394,15 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_map_kernel(const int* __
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
-static long cc_align256(long x) { return (x + 255) & ~255L; }
-
-static bool cc_extents_ok(int V, int D, int H, int W) {
-  if (V < 1 || V > 65535 || D < 1 || H < 1 || W < 1) return false;
-  return (long)D * H <= 0x7fffffffL / W && (long)D * H * W < 0x7fffffffL;       // linear indices are int32
+void cc_launch_merge(hipStream_t s, int V, int D, int H, int W, int connectivity, int* parent, long pvs) {
+  const long vox = (long)D * H * W;
+  hipLaunchKernelGGL(cc_merge_kernel<false>, dim3((unsigned)((vox + CC_THREADS - 1) / CC_THREADS), V), dim3(CC_THREADS), 0, s,
+                     parent, pvs, D, H, W, connectivity, (const unsigned char*)nullptr, 0L);
 }
 
-static bool cc_mask_dtype_ok(int t) { return t == DUA_F32 || t == DUA_U8; }
+void cc_launch_flatten(hipStream_t s, int V, long vox, int* parent, long pvs, int* blocksum, long nb) {
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3((unsigned)nb, V), dim3(CC_THREADS), 0, s, parent, pvs, (int)vox, blocksum, (int)nb);
+}
 
 struct CcScratch {
   long pvs, nb;                      // parent elements per volume, scan blocks per volume
@@ -506,9 +450,8 @@ int dua_cc_label(int V, int D, int H, int W, const void* mask, int mask_dtype, l
   const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
   const int is_f32 = mask_dtype == DUA_F32;
   hipLaunchKernelGGL(dua::cc_init_kernel, gvox, threads, 0, s, mask, is_f32, mask_vstride, select, (int)vox, W, parent, L.pvs);
-  hipLaunchKernelGGL(dua::cc_merge_kernel<false>, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity,
-                     (const unsigned char*)nullptr, 0L);
-  hipLaunchKernelGGL(dua::cc_flatten_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb);
+  dua::cc_launch_merge(s, V, D, H, W, connectivity, parent, L.pvs);
+  dua::cc_launch_flatten(s, V, vox, parent, L.pvs, blocksum, L.nb);
   hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
   hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
   hipLaunchKernelGGL(dua::cc_propagate_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, labels);
@@ -592,7 +535,7 @@ int dua_cc_label_map(int V, int D, int H, int W, const unsigned char* map, long 
   const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
   hipLaunchKernelGGL(dua::cc_init_map_kernel, gvox, threads, 0, s, map, map_vstride, C, (int)vox, W, parent, L.pvs);
   hipLaunchKernelGGL(dua::cc_merge_kernel<true>, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity, map, map_vstride);
-  hipLaunchKernelGGL(dua::cc_flatten_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb);
+  dua::cc_launch_flatten(s, V, vox, parent, L.pvs, blocksum, L.nb);
   hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
   hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
   hipLaunchKernelGGL(dua::cc_propagate_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, labels);

@@ -418,7 +418,7 @@ def streamed_sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_s
 
 def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1,
                     overlap: float = 0.25, distributed: bool = False, group=None, postprocess: dict = None,
-                    surface: dict = None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125):
+                    surface: dict = None, mirror_axes=None, fill_holes: dict = None, mode: str = "constant", sigma_scale=0.125):
     """Engine.infer (engine.py:167-182) and the Dice of the result (metric.py:37-49) in the streamed form: (mask uint8
     [B, C, D, H, W] = sigmoid(blend) > 0.5, dice fp64 [C] or None without ``labels``).  The normalised fp32 volume is never
     written: one pass over the sum volume divides, crops, binarises and counts.  ``labels``: one-hot [B, C, D, H, W] (non-zero =
@@ -435,11 +435,17 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     ``metrics.surface_report`` (the distance table too) with ``distances=True``.
     ``mirror_axes``: mirror test-time augmentation as in ``streamed_sliding_window_inference`` (F predictor calls per window
     batch, the same all-reduce).  ``postprocess``, ``surface`` and Step-Uncertainty Fusion compose with it without change:
-    they run after the finish pass, or inside the predictor."""
+    they run after the finish pass, or inside the predictor.
+    ``fill_holes``: None, or a dict with keys among ("connectivity", "channels"): ``postprocess.fill_holes`` on the mask, AFTER
+    ``postprocess`` when both are given (keep-largest first, then fill).  The mask, the Dice and the ``surface`` report are then
+    those of the filled mask, the Dice from the fill pass's tallies.  None changes no launch of the paths above."""
     from . import ops
     mirror_flips(mirror_axes)                              # refuse bad axes before any predictor call
     if surface is not None:
         _surface_kwargs(surface, labels)
+    if fill_holes is not None:
+        from . import postprocess as pp
+        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_KEYS, "channels")
     _need_device(image, "evaluate_volume")
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
@@ -449,7 +455,13 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
-        if postprocess is not None:
+        if fill_holes is not None:
+            _, mask, _ = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True)
+            if postprocess is not None:
+                mask = pp.filter_components(mask, **postprocess)[0]
+            mask, _, *tallies = pp.fill_holes(mask, labels=labels, **fill_holes)
+            tallies = tallies[0] if tallies else None
+        elif postprocess is not None:
             from .postprocess import filter_components
             _, mask, _ = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True)
             mask, tallies = filter_components(mask, labels=labels, **postprocess)
@@ -466,7 +478,7 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
 
 def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
                  distributed: bool = False, group=None, mirror_axes=None, mode: str = "constant", sigma_scale=0.125,
-                 min_prob: float = 0.0, postprocess: dict = None, surface: dict = None):
+                 min_prob: float = 0.0, postprocess: dict = None, surface: dict = None, fill_holes: dict = None):
     """The deliverable of one case: (label map uint8 on the grid of the SCAN, Dice fp64 [C] against ``label`` or None).  ``case``:
     a ``prepare.PreparedCase`` -- the streamed blend runs on ``case.image[None, None]`` and one pass
     (dua_blend_finish_labelmap) turns the sum volume into the label map: per voxel of the scan the class probabilities
@@ -483,12 +495,20 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     ``tolerance`` and optionally ``connectivity``, ``nan_for_nonexisting``, ``classes`` (default 1 .. C - 1) and
     ``voxel_spacing`` (default ``case.source_spacing``, the scan's own spacing, or 1 for a plain tensor); it needs ``label``, and
     the result is then (map, dice, report) with report = ``metrics.label_map_surface_report`` of the returned map against
-    ``label`` (one host read of the box table).  With neither, nothing new is launched."""
+    ``label`` (one host read of the box table).  With neither, nothing new is launched.
+
+    ``fill_holes``: None, or a dict with keys among ("connectivity", "classes"): ``postprocess.fill_holes_in_label_map`` on the
+    label map, on the scan's grid, AFTER ``postprocess`` when both are given (keep-largest first, then fill).  The map, the Dice
+    and the ``surface`` report are then those of the filled map, the Dice from the fill pass's tallies.  None changes no launch
+    of the paths above."""
     from . import ops
     from .prepare import PreparedCase
     mirror_flips(mirror_axes)
     if postprocess is not None:
         _segment_postprocess_kwargs(postprocess)
+    if fill_holes is not None:
+        from . import postprocess as pp
+        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_MAP_KEYS, "classes")
     if surface is not None:
         _segment_surface_kwargs(surface, label)
     min_prob = float(min_prob)
@@ -529,7 +549,13 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
-        if postprocess is None:
+        if fill_holes is not None:
+            out, _ = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob, None)
+            if postprocess is not None:
+                out = pp.filter_label_map(out, int(acc.shape[-4]), **postprocess)[0]
+            out, _, *tallies = pp.fill_holes_in_label_map(out, int(acc.shape[-4]), reference=label, **fill_holes)
+            tallies = tallies[0] if tallies else None
+        elif postprocess is None:
             out, tallies = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
                                                      None if label is None else label.contiguous())
         else:
@@ -657,7 +683,7 @@ def dice_per_class(outputs: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int = 1, overlap: float = 0.25,
           distributed: bool = False, group=None, streaming: bool = False, postprocess: dict = None, mirror_axes=None,
-          mode: str = "constant", sigma_scale=0.125) -> torch.Tensor:
+          fill_holes: dict = None, mode: str = "constant", sigma_scale=0.125) -> torch.Tensor:
     """Engine.infer (engine.py:167-182): sliding-window DDIM sampling -> sigmoid -> > 0.5.  ``streaming``: the same through
     ``evaluate_volume`` (no list of window outputs, no fp32 normalised volume).  ``mode``, ``sigma_scale``: the blend's
     importance map, as ``sliding_window_inference``.  ``postprocess``: None, or a dict of
@@ -665,13 +691,18 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     Step-Uncertainty Fusion is the model's switch (``DiffUNet(..., uncer_step=R)``), not an argument of this function.
     ``mirror_axes``: mirror test-time augmentation, as ``sliding_window_inference``; ``postprocess`` and Step-Uncertainty
     Fusion compose with it without change.  The all-gather form (``distributed=True, streaming=False``) does not take it --
-    its gathered bytes would grow F-fold -- and raises ValueError: use ``streaming=True``, whose all-reduce does not grow."""
+    its gathered bytes would grow F-fold -- and raises ValueError: use ``streaming=True``, whose all-reduce does not grow.
+    ``fill_holes``: None, or a dict with keys among ("connectivity", "channels"): ``postprocess.fill_holes`` on the binarised
+    volume, after ``postprocess`` when both are given."""
     if postprocess is not None:
         _postprocess_kwargs(postprocess)
+    if fill_holes is not None:
+        from . import postprocess as pp
+        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_KEYS, "channels")
     augmented = len(mirror_flips(mirror_axes)) > 1
     if streaming:
         return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess,
-                               mirror_axes=mirror_axes, mode=mode, sigma_scale=sigma_scale)[0].float()
+                               mirror_axes=mirror_axes, mode=mode, sigma_scale=sigma_scale, fill_holes=fill_holes)[0].float()
     if distributed and augmented:
         raise ValueError("mirror_axes: the all-gather form would gather F times the window outputs; pass streaming=True "
                          "(one all-reduce of the same size) for mirror test-time augmentation across ranks")
@@ -679,6 +710,11 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     kw = dict(group=group) if distributed else dict(mirror_axes=mirror_axes)
     with torch.no_grad():
         out = fn(image, roi_size, sw_batch_size, model, overlap, mode=mode, sigma_scale=sigma_scale, pred_type="ddim_sample", **kw)
+    if fill_holes is not None:
+        mask = binarise(out)
+        if postprocess is not None:
+            mask = pp.keep_largest_components(mask, **postprocess)
+        return pp.fill_holes(mask, **fill_holes)[0].float()
     if postprocess is not None:
         from .postprocess import keep_largest_components
         return keep_largest_components(binarise(out), **postprocess).float()

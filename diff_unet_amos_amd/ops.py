@@ -1807,6 +1807,27 @@ def _cc_flags(flags, V, name, device):
     return flags
 
 
+def _cc_reference(reference, classes, label_map, V, D, H, W, dev):
+    """The reference of a tallying pass over V volumes [D, H, W] as (tensor or None, dtype code, label-map flag, classes): one-hot
+    [V, D, H, W] (fp32, uint8 or bool) or, with ``label_map``, a uint8 label map [V / classes, D, H, W]."""
+    if reference is None:
+        return None, 0, 0, 1
+    Cn = int(classes)
+    assert reference.is_cuda and reference.device == dev, "reference: on the device of the volumes"
+    assert Cn >= 1 and V % Cn == 0, f"classes must divide the {V} volumes"
+    ref = reference.view(torch.uint8) if reference.dtype == torch.bool else reference
+    ref = ref.contiguous()
+    if label_map:
+        if ref.dtype != torch.uint8:
+            raise TypeError(f"reference: a label map is uint8, not {ref.dtype}")
+        assert ref.numel() == (V // Cn) * D * H * W, f"label map: {V // Cn} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
+        return ref, nv.U8, 1, Cn
+    if ref.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"reference: one-hot labels are float32, uint8 or bool, not {ref.dtype}")
+    assert ref.numel() == V * D * H * W, f"one-hot reference: {V} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
+    return ref, nv.F32 if ref.dtype == torch.float32 else nv.U8, 0, Cn
+
+
 def cc_label(mask, connectivity=1, select=None):
     """dua_cc_label for every volume of mask ([..., D, H, W]; fp32, uint8 or bool): (labels int32 [V, D, H, W], counts int32 [V]),
     the labels of scipy.ndimage.label per volume.  ``select``: uint8 [V] device flags, a volume with 0 is not labelled (labels 0,
@@ -1856,23 +1877,7 @@ def cc_filter(labels, counts, sizes, k=1, min_size=0, apply=None, mask=None, ref
         m, mcode, Vm, *ext = _surface_mask(mask, "mask")
         assert (Vm, *ext) == (V, D, H, W) and m.device == dev, "mask: the volumes the labels were made from"
     assert apply is None or m is not None, "apply: volumes passed through are copied from mask"
-    ref, rcode, is_map, Cn = None, 0, 0, 1
-    if reference is not None:
-        Cn = int(classes)
-        assert reference.is_cuda and reference.device == dev, "reference: on the labels' device"
-        assert Cn >= 1 and V % Cn == 0, f"classes must divide the {V} volumes"
-        ref = reference.view(torch.uint8) if reference.dtype == torch.bool else reference
-        ref = ref.contiguous()
-        if label_map:
-            if ref.dtype != torch.uint8:
-                raise TypeError(f"reference: a label map is uint8, not {ref.dtype}")
-            assert ref.numel() == (V // Cn) * D * H * W, f"label map: {V // Cn} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
-            rcode, is_map = nv.U8, 1
-        else:
-            if ref.dtype not in (torch.float32, torch.uint8):
-                raise TypeError(f"reference: one-hot labels are float32, uint8 or bool, not {ref.dtype}")
-            assert ref.numel() == V * D * H * W, f"one-hot reference: {V} volumes [{D}, {H}, {W}], got {tuple(ref.shape)}"
-            rcode = nv.F32 if ref.dtype == torch.float32 else nv.U8
+    ref, rcode, is_map, Cn = _cc_reference(reference, classes, label_map, V, D, H, W, dev)
     ws, need = _cc_workspace(V, D, H, W, cap, dev)
     out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
@@ -1939,6 +1944,62 @@ def cc_filter_map(label_map, num_classes, labels, counts, sizes, k=1, min_size=0
                                             cap, int(k), int(min_size), nv.ptr(apply), nv.ptr(out), nv.ptr(ref), nv.ptr(tallies),
                                             nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_filter_map")
     return out, tallies
+
+
+# ---- evaluation: fill holes (csrc/fill_holes.hip) --------------------------------------------------------------------------------
+
+def _fill_holes_workspace(V, D, H, W, label_map, device):
+    need = int(nv.lib().dua_fill_holes_scratch_bytes(V, D, H, W, int(label_map)))
+    if need < 0:
+        raise ValueError(f"fill holes: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1)")
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
+def fill_holes_mask(mask, connectivity=1, select=None, reference=None, classes=1, label_map=False):
+    """dua_fill_holes_mask for every volume of mask ([..., D, H, W]; fp32, uint8 or bool): (out [V, D, H, W] of the mask's dtype
+    -- the mask with the voxels of every enclosed hole set to 1 --, filled int64 [V], tallies int64 [classes, 3] or None).
+    ``select``: uint8 [V] device flags, a volume with 0 is copied through.  ``reference`` / ``classes`` / ``label_map``: as
+    ``cc_filter``.  No host synchronisation."""
+    m, code, V, D, H, W = _surface_mask(mask, "mask")
+    dev = m.device
+    select = _cc_flags(select, V, "select", dev)
+    ref, rcode, is_map, Cn = _cc_reference(reference, classes, label_map, V, D, H, W, dev)
+    ws, need = _fill_holes_workspace(V, D, H, W, False, dev)
+    out = torch.empty((V, D, H, W), dtype=m.dtype, device=dev)
+    filled = torch.empty((V,), dtype=torch.int64, device=dev)
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_fill_holes_mask(V, D, H, W, nv.ptr(m), code, D * H * W, int(connectivity), nv.ptr(select), nv.ptr(out),
+                                              nv.ptr(filled), nv.ptr(ref), rcode, is_map, Cn, nv.ptr(tallies), nv.ptr(ws), need,
+                                              nv.stream_ptr()), "dua_fill_holes_mask")
+    return out, filled, tallies
+
+
+def fill_holes_map(label_map, num_classes, connectivity=1, classes=None, reference=None):
+    """dua_fill_holes_map for every map of label_map (uint8 [N, D, H, W]): (filled map uint8 [N, D, H, W], filled int64
+    [num_classes] -- the voxels that became class c, over the N maps --, tallies int64 [num_classes, 3] or None).  ``classes``:
+    the classes that may fill, integers in 1 .. num_classes - 1 (None: all of them).  ``reference``: a uint8 label map like
+    ``label_map``; with it, the tallies of ``blend_finish`` for the filled map.  No host synchronisation."""
+    m, V, D, H, W = _label_maps(label_map, "label_map")
+    dev, Cn = m.device, int(num_classes)
+    chosen = range(1, Cn) if classes is None else classes
+    class_mask = 0
+    for c in chosen:
+        assert 1 <= int(c) < Cn, f"classes lie in 1..{Cn - 1}, got {c!r}"
+        class_mask |= 1 << int(c)
+    ref = None
+    if reference is not None:
+        ref, *rshape = _label_maps(reference, "reference")
+        assert tuple(rshape) == (V, D, H, W) and ref.device == dev, "reference: a label map like label_map, on its device"
+    ws, need = _fill_holes_workspace(V, D, H, W, True, dev)
+    out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
+    filled = torch.empty((Cn,), dtype=torch.int64, device=dev)
+    tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
+    with torch.cuda.device(dev):
+        nv.check(nv.lib().dua_fill_holes_map(V, D, H, W, nv.ptr(m), D * H * W, Cn, int(connectivity), class_mask, nv.ptr(out),
+                                             nv.ptr(filled), nv.ptr(ref), nv.ptr(tallies), nv.ptr(ws), need, nv.stream_ptr()),
+                 "dua_fill_holes_map")
+    return out, filled, tallies
 
 
 # ---- evaluation: surface report of two label maps (csrc/surface.hip) --------------------------------------------------------------

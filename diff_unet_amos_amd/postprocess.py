@@ -89,6 +89,28 @@ def _channel_flags(mask, chosen):
     return flags.view(-1)
 
 
+def _reference_labels(mask, labels):
+    """``labels`` of a tallying call on ``mask`` as (reference or None, classes, is a label map): one-hot like ``mask``
+    [B, C, D, H, W] (fp32, uint8 or bool; other dtypes are compared with 0) or a uint8 label map [B, D, H, W]."""
+    if labels is None:
+        return None, 1, False
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise RuntimeError("labels: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
+    if mask.dim() != 5:
+        raise ValueError(f"with labels, mask is [B, C, D, H, W]; got {tuple(mask.shape)}")
+    Cn = mask.shape[1]
+    if tuple(labels.shape) == tuple(mask.shape):
+        ref, is_map = labels if labels.dtype in (torch.float32, torch.uint8, torch.bool) else labels != 0, False
+    elif tuple(labels.shape) == (mask.shape[0], *mask.shape[2:]) and labels.dtype == torch.uint8:
+        ref, is_map = labels, True
+    else:
+        raise ValueError(f"labels: one-hot {tuple(mask.shape)} or a uint8 label map {(mask.shape[0], *mask.shape[2:])}, got "
+                         f"{labels.dtype} {tuple(labels.shape)}")
+    if Cn > nv.BLEND_MAX_CLASSES:
+        raise ValueError(f"at most {nv.BLEND_MAX_CLASSES} classes, got {Cn}")
+    return ref, Cn, is_map
+
+
 def label_components(mask, connectivity=1):
     """(labels int32 shaped like ``mask``, count int32 shaped like ``mask.shape[:-3]``) of a [..., D, H, W] device mask (fp32,
     uint8 or bool; other dtypes are compared with 0 first).  Per volume, labels equals
@@ -128,22 +150,7 @@ def filter_components(mask, connectivity=1, num_components=1, min_size=0, channe
     chosen = _channels(mask, channels)
     mask = _device_mask(mask, "mask")
     flags = _channel_flags(mask, chosen)
-    ref, Cn, is_map = None, 1, False
-    if labels is not None:
-        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-            raise RuntimeError("labels: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
-        if mask.dim() != 5:
-            raise ValueError(f"with labels, mask is [B, C, D, H, W]; got {tuple(mask.shape)}")
-        Cn = mask.shape[1]
-        if tuple(labels.shape) == tuple(mask.shape):
-            ref = labels if labels.dtype in (torch.float32, torch.uint8, torch.bool) else labels != 0
-        elif tuple(labels.shape) == (mask.shape[0], *mask.shape[2:]) and labels.dtype == torch.uint8:
-            ref, is_map = labels, True
-        else:
-            raise ValueError(f"labels: one-hot {tuple(mask.shape)} or a uint8 label map {(mask.shape[0], *mask.shape[2:])}, got "
-                             f"{labels.dtype} {tuple(labels.shape)}")
-        if Cn > nv.BLEND_MAX_CLASSES:
-            raise ValueError(f"at most {nv.BLEND_MAX_CLASSES} classes, got {Cn}")
+    ref, Cn, is_map = _reference_labels(mask, labels)
     lab, counts = ops.cc_label(mask, conn, select=flags)
     sizes = ops.cc_sizes(lab, cap)
     out, tallies = ops.cc_filter(lab, counts, sizes, k, min_size, apply=flags, mask=mask if flags is not None else None,
@@ -245,3 +252,74 @@ def filter_label_map(label_map, num_classes, connectivity=1, num_components=1, m
 def keep_largest_in_label_map(label_map, num_classes, connectivity=1, num_components=1, min_size=0, classes=None, cap=None):
     """``filter_label_map`` without a reference: the filtered uint8 label map alone."""
     return filter_label_map(label_map, num_classes, connectivity, num_components, min_size, classes, cap)[0]
+
+
+# ---- filling of enclosed holes (include/dua_hip.h "evaluation: fill holes", csrc/fill_holes.hip) ---------------------------------
+#
+# The step that follows keep-largest in most organ pipelines: a pocket of background inside a solid organ costs Dice and adds
+# a false inner surface to every surface metric.  The union-find of the components runs on the BACKGROUND voxels here;
+# ``connectivity`` is scipy's generate_binary_structure(3, connectivity) and governs both how background voxels join and which
+# voxels count as neighbours of a background component (1, the default, is ``binary_fill_holes``' default).
+
+def fill_holes(mask, connectivity=1, channels=None, labels=None):
+    """(filled mask of the input's dtype and shape, filled int64 ``mask.shape[:-3]`` -- the voxels filled per volume --) and,
+    when ``labels`` is given, the Dice tallies int64 [C, 3] of the result as a third entry.  Per volume [D, H, W] a hole is a
+    component of (mask == 0) with no voxel on a face of the volume; its voxels become 1, everything else is returned as it
+    came, so (result != 0) equals scipy.ndimage.binary_fill_holes(volume, generate_binary_structure(3, connectivity)).
+    ``channels``: the class channels (axis -4) that are filled, the others are copied through (None: all).  ``labels``: as
+    ``filter_components`` takes them, with ``mask`` [B, C, D, H, W]."""
+    conn = _connectivity(connectivity)
+    chosen = _channels(mask, channels)
+    dtype = mask.dtype if isinstance(mask, torch.Tensor) else None
+    mask = _device_mask(mask, "mask")
+    flags = _channel_flags(mask, chosen)
+    ref, Cn, is_map = _reference_labels(mask, labels)
+    out, filled, tallies = ops.fill_holes_mask(mask, conn, select=flags, reference=ref, classes=Cn, label_map=is_map)
+    out = out.view(mask.shape)
+    if mask.dtype == torch.bool:
+        out = out.view(torch.bool)
+    if out.dtype != dtype:
+        out = out.to(dtype)                                     # a dtype that was compared with 0 on the way in
+    filled = filled.view(mask.shape[:-3])
+    return (out, filled) if labels is None else (out, filled, tallies)
+
+
+def fill_holes_in_label_map(label_map, num_classes, connectivity=1, classes=None, reference=None):
+    """(filled uint8 label map shaped like ``label_map``, filled int64 [num_classes] -- the voxels that became class c --) and,
+    when ``reference`` (a uint8 label map like ``label_map``) is given, the Dice tallies int64 [num_classes, 3] of the result as a
+    third entry.  A component of (label_map == 0) is filled with class c when it touches no face of the volume, every voxel
+    adjacent to it carries the same value c, 1 <= c < num_classes and c is among ``classes`` (None: 1 .. num_classes - 1).  A
+    component bordered by two values, by a value >= num_classes or by a class that is not selected stays 0; non-zero voxels never
+    change.  All classes are decided on the input map in one pass, so the result does not depend on an order of the classes.
+    For a map with one class it is ``binary_fill_holes(label_map == c)``; unlike ``binary_fill_holes`` run class by class it
+    does not fill a pocket that holds an island of another class."""
+    Cn, conn = _num_classes(num_classes), _connectivity(connectivity)
+    chosen = _class_list(classes, Cn)
+    m = _device_label_map(label_map, "label_map")
+    ref = None
+    if reference is not None:
+        if not isinstance(reference, torch.Tensor) or not reference.is_cuda:
+            raise RuntimeError("reference: fill_holes runs on an MI355X (device 'cuda'); there is no CPU path in this package")
+        if reference.dtype != torch.uint8 or tuple(reference.shape) != tuple(label_map.shape):
+            raise ValueError(f"reference: a uint8 label map {tuple(label_map.shape)}, got {reference.dtype} {tuple(reference.shape)}")
+        ref = reference.view(m.shape)
+    out, filled, tallies = ops.fill_holes_map(m, Cn, conn, classes=chosen, reference=ref)
+    out = out.view(label_map.shape)
+    return (out, filled) if reference is None else (out, filled, tallies)
+
+
+FILL_HOLES_KEYS = ("connectivity", "channels")                  # of evaluate_volume's and infer's ``fill_holes=`` (mask form)
+FILL_HOLES_MAP_KEYS = ("connectivity", "classes")               # of segment_case's ``fill_holes=`` (map form)
+
+
+def _fill_holes_kwargs(fill_holes, keys, selection):
+    """Refuse a ``fill_holes=`` argument that is not a dict with keys among ``keys`` and values the fill functions take, before
+    any device work.  ``selection``: the key that holds a list of non-negative integers (channels or classes)."""
+    if not isinstance(fill_holes, dict) or any(k not in keys for k in fill_holes):
+        raise ValueError(f"fill_holes: None or a dict with keys among {keys}, got {fill_holes!r}")
+    _connectivity(fill_holes.get("connectivity", 1))
+    chosen = fill_holes.get(selection)
+    low = 1 if selection == "classes" else 0
+    if chosen is not None and (isinstance(chosen, (str, bytes)) or not hasattr(chosen, "__iter__") or
+                               any(isinstance(c, bool) or not isinstance(c, int) or c < low for c in chosen)):
+        raise ValueError(f"fill_holes: {selection} is None or integers >= {low}, got {chosen!r}")

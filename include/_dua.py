@@ -109,6 +109,19 @@ _L.dua_adamw_step_ex.restype = C.c_int
 _L.dua_adamw_step_ex.argtypes = ([C.POINTER(AdamWList), C.c_float, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3 +
                                  [C.c_int, C.c_void_p, C.POINTER(AdamWEma), C.c_float, C.c_void_p])
 
+# filling of enclosed holes after keep-largest: dua_fill_holes_mask is scipy.ndimage.binary_fill_holes per (sample, class)
+# volume; dua_fill_holes_map fills a background component of a uint8 label map that touches no face and is bordered by one
+# selectable class (class_mask: bit c = class c may fill) with that class.  Both write the filled voxel counts and, with a
+# reference, the Dice tallies; the workspace comes from dua_fill_holes_scratch_bytes.  The contract is in dua_hip.h
+_L.dua_fill_holes_scratch_bytes.restype = C.c_long
+_L.dua_fill_holes_scratch_bytes.argtypes = [C.c_int] * 5
+_L.dua_fill_holes_mask.restype = C.c_int
+_L.dua_fill_holes_mask.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_long, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 +
+                                   [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p])
+_L.dua_fill_holes_map.restype = C.c_int
+_L.dua_fill_holes_map.argtypes = ([C.c_int] * 4 + [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 5 +
+                                  [C.c_long, C.c_void_p])
+
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream

@@ -1033,6 +1033,57 @@ int dua_cc_filter_map(int V, int D, int H, int W, const unsigned char* map, long
                       unsigned char* out, const unsigned char* reference, unsigned long long* tallies, void* workspace,
                       long workspace_bytes, void* stream);
 
+/* ---- evaluation: fill holes --------------------------------------------------------------------------------------------------
+ * Filling of enclosed holes, the morphological step after keep-largest: scipy.ndimage.binary_fill_holes for V = N * C binary
+ * volumes (the mask form), and its label-map form for V = N uint8 maps of class ids, without a one-hot expansion.  Conventions,
+ * limits and argument checks as for the connected components above: connectivity k in 1..3 is generate_binary_structure(3, k),
+ * and it governs BOTH how background voxels join and which voxels count as neighbours of a component.  All arithmetic is
+ * integer (the union-find of the components on the background voxels, byte flags, 64-bit atomicOr, integer atomic adds): every
+ * output is exact and identical between runs; every entry point only enqueues on `stream`, so the chain can be captured.
+ *
+ * Mask form, per volume m [D][H][W]:
+ *   A hole is a k-connected component of {m == 0} with no voxel on any of the six faces of the volume.
+ *   out = m, with every hole voxel set to 1 (out has the mask's dtype; a foreground value is copied as it is).
+ *   (out != 0) equals scipy.ndimage.binary_fill_holes(m, structure=generate_binary_structure(3, k)).
+ *   select (uint8 [V], may be NULL = all): a volume with select[v] == 0 is copied through, nothing of it is filled.
+ *   filled (64-bit unsigned [V], WRITTEN, zeroed first): the voxels filled per volume.
+ *   reference / tallies, given together or not at all: tallies (64-bit unsigned [C][3], WRITTEN, zeroed first) = |A & B|, |A|,
+ *   |B| per class c = v mod C, A = (out != 0), B = reference, in the layouts dua_cc_filter takes (label_map == 0: one-hot
+ *   [V][D H W], DUA_F32 or DUA_U8; label_map != 0: DUA_U8 [V / C][D H W] of class ids); C divides V, C <= DUA_BLEND_MAX_CLASSES
+ *   (C is ignored without a reference).
+ *
+ * Map form, per map [D][H][W] with a class count C <= 64:
+ *   A hole is a k-connected component Hc of {map == 0} that
+ *     - touches no face of the volume,
+ *     - has every voxel that is k-adjacent to a voxel of Hc and not in Hc carry the SAME value c, and
+ *     - 1 <= c < C and bit c of class_mask is set (class_mask: bits among 1 .. C - 1, anything else is DUA_ERR_ARG).
+ *   Such a hole is filled with c.  A background component stays 0 when it is bordered by two different values, by a value >= C
+ *   or by a class that is not selected.  Non-zero voxels are never changed; values >= C pass through.  The rule is order-free:
+ *   all classes are decided on the input map, in one pass.  For a map with one non-zero value c it coincides with
+ *   binary_fill_holes(map == c).  It DIFFERS from binary_fill_holes run per class in one place, on purpose: a pocket of class c
+ *   that contains an island of another class is bordered by two values and is not filled.
+ *   filled (64-bit unsigned [C], WRITTEN, zeroed first): the voxels filled per class, over the V maps.
+ *   reference (uint8 [V][D H W], a label map) / tallies ([C][3]): as dua_cc_filter_map, for the filled map.
+ *
+ * Per root of a background component the passes keep one border flag (a byte) and, in the map form, one 64-bit set of
+ * neighbour values: bit c for a selectable class c; bit 0 -- which no neighbour of a 0-component can claim -- for "a value >= C
+ * or a class that is not selected".  A component is filled when it has no border flag and its set is exactly one bit >= 1. */
+/* Bytes of workspace for this batch (DUA_ERR_ARG for bad extents): per voxel one int32 (the parents) and one byte (the border
+ * flags), one int32 per 1024 voxels, and with label_map != 0 one 64-bit word per voxel (the neighbour sets). */
+long dua_fill_holes_scratch_bytes(int V, int D, int H, int W, int label_map);
+/* out ([V][D H W] of the mask's dtype, WRITTEN) and filled of mask, as stated above.  workspace: at least
+ * dua_fill_holes_scratch_bytes(V, D, H, W, 0) bytes, 256-byte aligned. */
+int dua_fill_holes_mask(int V, int D, int H, int W, const void* mask, int mask_dtype, long mask_vstride, int connectivity,
+                        const unsigned char* select, void* out, unsigned long long* filled, const void* reference,
+                        int reference_dtype, int label_map, int C, unsigned long long* tallies, void* workspace,
+                        long workspace_bytes, void* stream);
+/* out (uint8 [V][D H W], WRITTEN) and filled of map, as stated above.  workspace: at least
+ * dua_fill_holes_scratch_bytes(V, D, H, W, 1) bytes, 256-byte aligned. */
+int dua_fill_holes_map(int V, int D, int H, int W, const unsigned char* map, long map_vstride, int C, int connectivity,
+                       unsigned long long class_mask, unsigned char* out, unsigned long long* filled,
+                       const unsigned char* reference, unsigned long long* tallies, void* workspace, long workspace_bytes,
+                       void* stream);
+
 /* ---- evaluation: surface report of two label maps ----------------------------------------------------------------------------
  * dua_surface_report for N pairs of uint8 label maps [D][H][W] (test, reference) and K classes, without a one-hot expansion:
  * row n K + k of every output is the row dua_surface_report gives for the pair of masks (test[n] == class_ids[k],
