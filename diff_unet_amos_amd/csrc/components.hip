@@ -17,8 +17,8 @@
 //   filter  : per volume the k largest labels (ties to the smaller label) and / or those of at least min_size voxels are kept;
 //             one pass writes the uint8 mask and, with a reference, the three Dice counts per class.
 // Integer work throughout: results are exact and do not depend on the order in which workgroups run.
-// The find / union, the run start of the inits and the merge and flatten launches are shared with fill_holes.hip through
-// components.hpp.
+// The find / union, the run start of the inits, the Dice tallies of the filter passes, the check of the reference, the head of
+// the workspace layout and the merge and flatten launches are shared with fill_holes.hip through components.hpp.
 #include "components.hpp"
 
 namespace dua {
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const int* __rest
   const unsigned char* kp = keep + (size_t)v * cap;
   const bool on = !apply || apply[v] != 0;
   const int c = v % C, b = v / C;
-  int nab = 0, na = 0, nr = 0;
+  int n[3] = {0, 0, 0};                                          // |A & B|, |A|, |B|
 #pragma unroll
   for (int j = 0; j < CC_PER_THREAD; ++j) {
     const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
@@ -293,23 +293,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_kernel(const int* __rest
       a = cc_fg(mask, mask_f32, (size_t)v * mvs + (size_t)p);
     }
     out[(size_t)v * (size_t)vox + (size_t)p] = a ? 1 : 0;
-    if (ref_kind != CC_REF_NONE) {
-      bool r;
-      if (ref_kind == CC_REF_MAP) r = reinterpret_cast<const unsigned char*>(ref)[(size_t)b * (size_t)vox + (size_t)p] == c;
-      else r = cc_fg(ref, ref_kind == CC_REF_ONEHOT_F32, (size_t)v * (size_t)vox + (size_t)p);
-      nab += a && r; na += a; nr += r;
-    }
+    if (ref_kind != CC_REF_NONE) cc_onehot_add(n, a, cc_ref_fg(ref, ref_kind, v, b, c, vox, p));
   }
   if (ref_kind == CC_REF_NONE) return;                           // kernel-uniform
   __shared__ int red[CC_WAVES][3];
-  nab = cc_wave_sum(nab); na = cc_wave_sum(na); nr = cc_wave_sum(nr);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = nab; red[threadIdx.x >> 6][1] = na; red[threadIdx.x >> 6][2] = nr; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long t = 0;
-    for (int k = 0; k < CC_WAVES; ++k) t += (unsigned long long)red[k][threadIdx.x];
-    if (t) atomicAdd(&tallies[(size_t)c * 3 + threadIdx.x], t);
-  }
+  cc_onehot_flush(cc_block_totals<3>(n, red, 0), c, tallies);
 }
 
 // ---- the label-map form of the filter ------------------------------------------------------------------------------------
@@ -332,8 +320,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_class_kernel(const int* __restr
 }
 
 // grid (nb, V): out[v][p] = map[v][p] where the value is 0 or >= C, where its class is passed through (apply[value] == 0) or
-// where the voxel's component is kept; 0 otherwise.  TALLY: (|A & B|, |A|, |B|) of A = out, B = ref per class into LDS words
-// (class 0, the bulk of a scan, in registers), then one 64-bit integer atomic per non-zero word; a value >= C counts nowhere.
+// where the voxel's component is kept; 0 otherwise.  TALLY: (|A & B|, |A|, |B|) of A = out, B = ref per class (CcMapTally).
 template <bool TALLY>
 __global__ __launch_bounds__(CC_THREADS) void cc_filter_map_kernel(const int* __restrict__ labels, int vox, int cap,
                                                                    const unsigned char* __restrict__ keep,
@@ -347,11 +334,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_map_kernel(const int* __
   const int v = blockIdx.y;
   const int* lab = labels + (size_t)v * (size_t)vox;
   const unsigned char* kp = keep + (size_t)v * cap;
+  CcMapTally tally{part, red};
   if constexpr (TALLY) {
-    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) part[i] = 0;
+    tally.zero(C);
     __syncthreads();
   }
-  int z[3] = {0, 0, 0};                                          // class 0: |A & B|, |A|, |B|
 #pragma unroll
   for (int j = 0; j < CC_PER_THREAD; ++j) {
     const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
@@ -363,32 +350,12 @@ __global__ __launch_bounds__(CC_THREADS) void cc_filter_map_kernel(const int* __
       if (!(l >= 1 && l <= cap && kp[l - 1] != 0)) o = 0;
     }
     out[(size_t)v * (size_t)vox + (size_t)p] = (unsigned char)o;
-    if constexpr (TALLY) {
-      const int r = ref[(size_t)v * (size_t)vox + (size_t)p];
-      if (o == 0) ++z[1];
-      else if (o < C) atomicAdd(&part[3 * o + 1], 1u);
-      if (r == 0) {
-        ++z[2];
-        z[0] += o == 0;
-      } else if (r < C) {
-        atomicAdd(&part[3 * r + 2], 1u);
-        if (r == o) atomicAdd(&part[3 * r], 1u);
-      }
-    }
+    if constexpr (TALLY) tally.add(o, ref[(size_t)v * (size_t)vox + (size_t)p], C);
   }
   if constexpr (TALLY) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int t = cc_wave_sum(z[i]);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = t;
-    }
+    tally.reduce();
     __syncthreads();
-    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) {
-      unsigned long long t = part[i];
-      if (i < 3)
-        for (int k = 0; k < CC_WAVES; ++k) t += (unsigned long long)red[k][i];
-      if (t) atomicAdd(&tallies[i], t);
-    }
+    tally.flush(C, tallies);
   }
 }
 
@@ -404,20 +371,25 @@ void cc_launch_flatten(hipStream_t s, int V, long vox, int* parent, long pvs, in
   hipLaunchKernelGGL(cc_flatten_kernel, dim3((unsigned)nb, V), dim3(CC_THREADS), 0, s, parent, pvs, (int)vox, blocksum, (int)nb);
 }
 
-struct CcScratch {
-  long pvs, nb;                      // parent elements per volume, scan blocks per volume
-  long parent, blocksum, keep, total;
+// the numbering both label entry points run on the parents an init and a merge left: flatten, scan of the block counts, rank,
+// propagate
+static void cc_launch_number(hipStream_t s, int V, long vox, int* parent, long pvs, int* blocksum, long nb, int* counts,
+                             int* labels) {
+  const dim3 threads(CC_THREADS), gscan((unsigned)nb, V);
+  cc_launch_flatten(s, V, vox, parent, pvs, blocksum, nb);
+  hipLaunchKernelGGL(cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)nb, counts);
+  hipLaunchKernelGGL(cc_rank_kernel, gscan, threads, 0, s, parent, pvs, (int)vox, blocksum, (int)nb, labels);
+  hipLaunchKernelGGL(cc_propagate_kernel, gscan, threads, 0, s, parent, pvs, (int)vox, labels);
+}
+
+struct CcScratch : CcPrefix {
+  long keep, total;
   long cls, total_map;               // the label-map form: the class table behind the keep table
 };
 
 static CcScratch cc_layout(int V, int D, int H, int W, int cap) {
-  CcScratch L;
-  const long vox = (long)D * H * W;
-  L.pvs = (vox + 63) & ~63L;
-  L.nb = (vox + CC_SCAN_BLOCK - 1) / CC_SCAN_BLOCK;
-  L.parent = 0;
-  L.blocksum = cc_align256(L.parent + (long)V * L.pvs * 4);
-  L.keep = cc_align256(L.blocksum + (long)V * L.nb * 4);
+  CcScratch L{cc_layout_prefix(V, D, H, W)};
+  L.keep = L.end;
   L.total = cc_align256(L.keep + (long)V * cap);
   L.cls = L.total;
   L.total_map = cc_align256(L.cls + (long)V * cap);
@@ -446,15 +418,11 @@ int dua_cc_label(int V, int D, int H, int W, const void* mask, int mask_dtype, l
   hipStream_t s = (hipStream_t)stream;
   int* parent = (int*)((unsigned char*)workspace + L.parent);
   int* blocksum = (int*)((unsigned char*)workspace + L.blocksum);
-  const dim3 threads(dua::CC_THREADS);
-  const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
+  const dim3 threads(dua::CC_THREADS), gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V);
   const int is_f32 = mask_dtype == DUA_F32;
   hipLaunchKernelGGL(dua::cc_init_kernel, gvox, threads, 0, s, mask, is_f32, mask_vstride, select, (int)vox, W, parent, L.pvs);
   dua::cc_launch_merge(s, V, D, H, W, connectivity, parent, L.pvs);
-  dua::cc_launch_flatten(s, V, vox, parent, L.pvs, blocksum, L.nb);
-  hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
-  hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
-  hipLaunchKernelGGL(dua::cc_propagate_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, labels);
+  dua::cc_launch_number(s, V, vox, parent, L.pvs, blocksum, L.nb, counts, labels);
   return (int)hipGetLastError();
 }
 
@@ -482,22 +450,8 @@ int dua_cc_filter(int V, int D, int H, int W, const int* labels, const int* coun
   if (apply && !mask) return DUA_ERR_ARG;                        // a volume passed through is copied from its mask
   if (mask && (!dua::cc_mask_dtype_ok(mask_dtype) || mask_vstride < vox || (mask_dtype == DUA_F32 && ((size_t)mask & 3) != 0)))
     return DUA_ERR_ARG;
-  if ((reference != nullptr) != (tallies != nullptr)) return DUA_ERR_ARG;
-  int kind = dua::CC_REF_NONE;
-  if (reference) {
-    if (C < 1 || C > DUA_BLEND_MAX_CLASSES || V % C != 0 || ((size_t)tallies & 7) != 0) return DUA_ERR_ARG;
-    if (label_map) {
-      if (reference_dtype != DUA_U8) return DUA_ERR_ARG;
-      kind = dua::CC_REF_MAP;
-    } else if (reference_dtype == DUA_F32) {
-      if (((size_t)reference & 3) != 0) return DUA_ERR_ARG;
-      kind = dua::CC_REF_ONEHOT_F32;
-    } else if (reference_dtype == DUA_U8) {
-      kind = dua::CC_REF_ONEHOT_U8;
-    } else {
-      return DUA_ERR_ARG;
-    }
-  }
+  int kind;
+  if (dua::cc_reference_kind(reference, reference_dtype, label_map, C, V, tallies, &kind) != 0) return DUA_ERR_ARG;
   const dua::CcScratch L = dua::cc_layout(V, D, H, W, cap);
   if (workspace_bytes < L.total || ((size_t)workspace & 255) != 0) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -531,14 +485,10 @@ int dua_cc_label_map(int V, int D, int H, int W, const unsigned char* map, long 
   hipStream_t s = (hipStream_t)stream;
   int* parent = (int*)((unsigned char*)workspace + L.parent);
   int* blocksum = (int*)((unsigned char*)workspace + L.blocksum);
-  const dim3 threads(dua::CC_THREADS);
-  const dim3 gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V), gscan((unsigned)L.nb, V);
+  const dim3 threads(dua::CC_THREADS), gvox((unsigned)((vox + dua::CC_THREADS - 1) / dua::CC_THREADS), V);
   hipLaunchKernelGGL(dua::cc_init_map_kernel, gvox, threads, 0, s, map, map_vstride, C, (int)vox, W, parent, L.pvs);
   hipLaunchKernelGGL(dua::cc_merge_kernel<true>, gvox, threads, 0, s, parent, L.pvs, D, H, W, connectivity, map, map_vstride);
-  dua::cc_launch_flatten(s, V, vox, parent, L.pvs, blocksum, L.nb);
-  hipLaunchKernelGGL(dua::cc_scan_blocks_kernel, dim3(V), threads, 0, s, blocksum, (int)L.nb, counts);
-  hipLaunchKernelGGL(dua::cc_rank_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, blocksum, (int)L.nb, labels);
-  hipLaunchKernelGGL(dua::cc_propagate_kernel, gscan, threads, 0, s, parent, L.pvs, (int)vox, labels);
+  dua::cc_launch_number(s, V, vox, parent, L.pvs, blocksum, L.nb, counts, labels);
   return (int)hipGetLastError();
 }
 

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(CC_THREADS) void fh_fill_mask_kernel(const int* __r
   const T* m = reinterpret_cast<const T*>(mask) + (size_t)v * mvs;
   T* o = reinterpret_cast<T*>(out) + (size_t)v * (size_t)vox;
   const int c = v % C, b = v / C;
-  int nf = 0, nab = 0, na = 0, nr = 0;
+  int n[4] = {0, 0, 0, 0};                                       // |A & B|, |A|, |B|, filled
 #pragma unroll
   for (int j = 0; j < CC_PER_THREAD; ++j) {
     const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
@@ -176,33 +176,16 @@ __global__ __launch_bounds__(CC_THREADS) void fh_fill_mask_kernel(const int* __r
     T val = m[p];                                                // x >= 0 says val == 0
     if (x >= 0 && border[x] == 0) {
       val = (T)1;
-      ++nf;
+      ++n[3];
     }
     o[p] = val;
-    if (ref_kind != CC_REF_NONE) {
-      const bool a = val != (T)0;
-      bool r;
-      if (ref_kind == CC_REF_MAP) r = reinterpret_cast<const unsigned char*>(ref)[(size_t)b * (size_t)vox + (size_t)p] == c;
-      else r = cc_fg(ref, ref_kind == CC_REF_ONEHOT_F32, (size_t)v * (size_t)vox + (size_t)p);
-      nab += a && r; na += a; nr += r;
-    }
+    if (ref_kind != CC_REF_NONE) cc_onehot_add(n, val != (T)0, cc_ref_fg(ref, ref_kind, v, b, c, vox, p));
   }
   __shared__ int red[CC_WAVES][4];
-  nf = cc_wave_sum(nf);
-  if (ref_kind != CC_REF_NONE) { nab = cc_wave_sum(nab); na = cc_wave_sum(na); nr = cc_wave_sum(nr); }    // kernel-uniform
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6][0] = nab; red[threadIdx.x >> 6][1] = na; red[threadIdx.x >> 6][2] = nr; red[threadIdx.x >> 6][3] = nf;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    unsigned long long t = 0;
-    for (int k = 0; k < CC_WAVES; ++k) t += (unsigned long long)red[k][threadIdx.x];
-    if (threadIdx.x == 3) {
-      if (t) atomicAdd(&filled[v], t);
-    } else if (ref_kind != CC_REF_NONE && t) {
-      atomicAdd(&tallies[(size_t)c * 3 + threadIdx.x], t);
-    }
-  }
+  const bool tally = ref_kind != CC_REF_NONE;                    // kernel-uniform; without it the three counts are 0 everywhere
+  const unsigned long long t = cc_block_totals<4>(n, red, tally ? 0 : 3);
+  if (threadIdx.x == 3 && t) atomicAdd(&filled[v], t);
+  if (tally) cc_onehot_flush(t, c, tallies);
 }
 
 // grid (nb, V): the map form's fill.  out[v][p] = map[v][p] unless the value is 0, the root of p has no border flag and its
@@ -224,11 +207,10 @@ __global__ __launch_bounds__(CC_THREADS) void fh_fill_map_kernel(const int* __re
   const int* parent = parent_all + (size_t)v * pvs;
   const unsigned char* border = border_all + (size_t)v * pvs;
   const unsigned long long* set = set_all + (size_t)v * pvs;
+  CcMapTally tally{part, red};
   for (int i = threadIdx.x; i < C; i += CC_THREADS) fpart[i] = 0;
-  if constexpr (TALLY)
-    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) part[i] = 0;
+  if constexpr (TALLY) tally.zero(C);
   __syncthreads();
-  int z[3] = {0, 0, 0};                                          // class 0: |A & B|, |A|, |B|
 #pragma unroll
   for (int j = 0; j < CC_PER_THREAD; ++j) {
     const long p = (long)blockIdx.x * CC_SCAN_BLOCK + j * CC_THREADS + threadIdx.x;
@@ -245,55 +227,25 @@ __global__ __launch_bounds__(CC_THREADS) void fh_fill_map_kernel(const int* __re
       }
     }
     out[(size_t)v * (size_t)vox + (size_t)p] = (unsigned char)o;
-    if constexpr (TALLY) {
-      const int r = ref[(size_t)v * (size_t)vox + (size_t)p];
-      if (o == 0) ++z[1];
-      else if (o < C) atomicAdd(&part[3 * o + 1], 1u);
-      if (r == 0) {
-        ++z[2];
-        z[0] += o == 0;
-      } else if (r < C) {
-        atomicAdd(&part[3 * r + 2], 1u);
-        if (r == o) atomicAdd(&part[3 * r], 1u);
-      }
-    }
+    if constexpr (TALLY) tally.add(o, ref[(size_t)v * (size_t)vox + (size_t)p], C);
   }
-  if constexpr (TALLY) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int t = cc_wave_sum(z[i]);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i] = t;
-    }
-  }
+  if constexpr (TALLY) tally.reduce();
   __syncthreads();
   for (int i = threadIdx.x; i < C; i += CC_THREADS)
     if (fpart[i]) atomicAdd(&filled[i], (unsigned long long)fpart[i]);
-  if constexpr (TALLY) {
-    for (int i = threadIdx.x; i < 3 * C; i += CC_THREADS) {
-      unsigned long long t = part[i];
-      if (i < 3)
-        for (int k = 0; k < CC_WAVES; ++k) t += (unsigned long long)red[k][i];
-      if (t) atomicAdd(&tallies[i], t);
-    }
-  }
+  if constexpr (TALLY) tally.flush(C, tallies);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
-struct FhScratch {
-  long pvs, nb;                      // parent elements per volume, scan blocks per volume
-  long parent, blocksum, border, total_mask;
+struct FhScratch : CcPrefix {
+  long border, total_mask;
   long set, total_map;               // the map form: one 64-bit neighbour set per voxel index, behind the border flags
 };
 
 static FhScratch fh_layout(int V, int D, int H, int W) {
-  FhScratch L;
-  const long vox = (long)D * H * W;
-  L.pvs = (vox + 63) & ~63L;
-  L.nb = (vox + CC_SCAN_BLOCK - 1) / CC_SCAN_BLOCK;
-  L.parent = 0;
-  L.blocksum = cc_align256(L.parent + (long)V * L.pvs * 4);
-  L.border = cc_align256(L.blocksum + (long)V * L.nb * 4);
+  FhScratch L{cc_layout_prefix(V, D, H, W)};
+  L.border = L.end;
   L.total_mask = cc_align256(L.border + (long)V * L.pvs);
   L.set = L.total_mask;
   L.total_map = cc_align256(L.set + (long)V * L.pvs * 8);
@@ -332,22 +284,8 @@ int dua_fill_holes_mask(int V, int D, int H, int W, const void* mask, int mask_d
   const long vox = (long)D * H * W;
   const bool f32 = mask_dtype == DUA_F32;
   if (mask_vstride < vox || ((size_t)filled & 7) != 0 || (f32 && ((((size_t)mask) | ((size_t)out)) & 3) != 0)) return DUA_ERR_ARG;
-  if ((reference != nullptr) != (tallies != nullptr)) return DUA_ERR_ARG;
-  int kind = dua::CC_REF_NONE;
-  if (reference) {
-    if (C < 1 || C > DUA_BLEND_MAX_CLASSES || V % C != 0 || ((size_t)tallies & 7) != 0) return DUA_ERR_ARG;
-    if (label_map) {
-      if (reference_dtype != DUA_U8) return DUA_ERR_ARG;
-      kind = dua::CC_REF_MAP;
-    } else if (reference_dtype == DUA_F32) {
-      if (((size_t)reference & 3) != 0) return DUA_ERR_ARG;
-      kind = dua::CC_REF_ONEHOT_F32;
-    } else if (reference_dtype == DUA_U8) {
-      kind = dua::CC_REF_ONEHOT_U8;
-    } else {
-      return DUA_ERR_ARG;
-    }
-  }
+  int kind;
+  if (dua::cc_reference_kind(reference, reference_dtype, label_map, C, V, tallies, &kind) != 0) return DUA_ERR_ARG;
   const dua::FhScratch L = dua::fh_layout(V, D, H, W);
   if (workspace_bytes < L.total_mask || ((size_t)workspace & 255) != 0) return DUA_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;

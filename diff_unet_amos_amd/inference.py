@@ -42,6 +42,9 @@ from typing import Callable, Sequence
 import torch
 import torch.nn.functional as F
 
+from . import postprocess as pp
+from .postprocess import POSTPROCESS_KEYS, SEGMENT_POSTPROCESS_KEYS  # noqa: F401  (the stage dicts' keys, kept under this name)
+
 
 def _scan_interval(image_size, roi_size, overlap):
     out = []
@@ -444,29 +447,18 @@ def evaluate_volume(model, image: torch.Tensor, labels: torch.Tensor = None, roi
     if surface is not None:
         _surface_kwargs(surface, labels)
     if fill_holes is not None:
-        from . import postprocess as pp
-        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_KEYS, "channels")
+        pp.check_stage_kwargs("fill_holes", "mask", fill_holes)
     _need_device(image, "evaluate_volume")
     if postprocess is not None:
-        _postprocess_kwargs(postprocess)
+        pp.check_stage_kwargs("postprocess", "mask", postprocess)
     if distributed and group is None:
         import torch.distributed as dist
         group = dist.group.WORLD
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
-        if fill_holes is not None:
-            _, mask, _ = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True)
-            if postprocess is not None:
-                mask = pp.filter_components(mask, **postprocess)[0]
-            mask, _, *tallies = pp.fill_holes(mask, labels=labels, **fill_holes)
-            tallies = tallies[0] if tallies else None
-        elif postprocess is not None:
-            from .postprocess import filter_components
-            _, mask, _ = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True)
-            mask, tallies = filter_components(mask, labels=labels, **postprocess)
-        else:
-            _, mask, tallies = ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=labels)
+        mask, tallies = _run_stages(lambda ref: ops.blend_finish(acc, divisor, crop_lo, spatial, want_mask=True, labels=ref)[1:],
+                                    _stages(postprocess, fill_holes, pp.filter_components, pp.fill_holes, "labels"), labels)
     dice = ops.dice_from_tallies(tallies) if tallies is not None else None
     if surface is None:
         return mask, dice
@@ -505,10 +497,9 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     from .prepare import PreparedCase
     mirror_flips(mirror_axes)
     if postprocess is not None:
-        _segment_postprocess_kwargs(postprocess)
+        pp.check_stage_kwargs("postprocess", "map", postprocess)
     if fill_holes is not None:
-        from . import postprocess as pp
-        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_MAP_KEYS, "classes")
+        pp.check_stage_kwargs("fill_holes", "map", fill_holes)
     if surface is not None:
         _segment_surface_kwargs(surface, label)
     min_prob = float(min_prob)
@@ -549,19 +540,10 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     with torch.no_grad():
         acc, divisor, crop_lo, spatial = _streamed_sum(image, roi_size, sw_batch_size, model, overlap, group if distributed else None,
                                                        None, None, dict(pred_type="ddim_sample"), mode, sigma_scale, mirror_axes)
-        if fill_holes is not None:
-            out, _ = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob, None)
-            if postprocess is not None:
-                out = pp.filter_label_map(out, int(acc.shape[-4]), **postprocess)[0]
-            out, _, *tallies = pp.fill_holes_in_label_map(out, int(acc.shape[-4]), reference=label, **fill_holes)
-            tallies = tallies[0] if tallies else None
-        elif postprocess is None:
-            out, tallies = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
-                                                     None if label is None else label.contiguous())
-        else:
-            from .postprocess import filter_label_map
-            out, _ = ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob, None)
-            out, tallies = filter_label_map(out, int(acc.shape[-4]), reference=label, **postprocess)
+        out, tallies = _run_stages(
+            lambda ref: ops.blend_finish_labelmap(acc, divisor, crop_lo, spatial, tables, source_shape, min_prob,
+                                                  None if ref is None else ref.contiguous()),
+            _stages(postprocess, fill_holes, pp.filter_label_map, pp.fill_holes_in_label_map, "reference", int(acc.shape[-4])), label)
     dice = ops.dice_from_tallies(tallies) if tallies is not None else None
     if surface is None:
         return out, dice
@@ -575,24 +557,33 @@ def segment_case(model, case, label: torch.Tensor = None, roi_size=(96, 96, 96),
     return out, dice, metrics.label_map_surface_report(out, label, classes, kw.pop("tolerance"), **kw)
 
 
-SEGMENT_POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "classes", "cap")
+def _run_stages(first, stages, reference):
+    """The chain behind ``postprocess=`` and ``fill_holes=``: ``first(ref)``, then every ``stage(result, ref)`` in order, each
+    returning (result, tallies or None).  The LAST call that runs gets ``reference`` and so produces the tallies; every call
+    before it gets None and tallies nothing.  Returns (the last result, its tallies).  Without stages this is ``first(reference)``
+    and nothing else."""
+    result, tallies = first(reference if not stages else None)
+    for i, stage in enumerate(stages):
+        result, tallies = stage(result, reference if i == len(stages) - 1 else None)
+    return result, tallies
+
+
+def _stages(postprocess, fill_holes, filter_fn, fill_fn, reference_key, *args):
+    """The stages of ``_run_stages`` for the two dicts, each present when its dict is: ``filter_fn(result, *args, **postprocess)``,
+    then ``fill_fn(result, *args, **fill_holes)`` (keep-largest first, then fill).  ``reference_key``: the keyword under which
+    the two functions take the reference."""
+    stages = []
+    if postprocess is not None:
+        stages.append(lambda result, ref: filter_fn(result, *args, **{reference_key: ref}, **postprocess))
+    if fill_holes is not None:
+        def fill(result, ref):
+            out, _, *tallies = fill_fn(result, *args, **{reference_key: ref}, **fill_holes)
+            return out, tallies[0] if tallies else None
+        stages.append(fill)
+    return stages
+
+
 SEGMENT_SURFACE_KEYS = ("tolerance", "voxel_spacing", "connectivity", "nan_for_nonexisting", "classes")
-
-
-def _segment_postprocess_kwargs(postprocess):
-    """Refuse a ``postprocess`` argument of ``segment_case`` that is not a dict of ``filter_label_map`` keywords with values that
-    function takes, before any predictor call."""
-    from . import postprocess as pp
-    if not isinstance(postprocess, dict) or any(k not in SEGMENT_POSTPROCESS_KEYS for k in postprocess):
-        raise ValueError(f"postprocess: None or a dict with keys among {SEGMENT_POSTPROCESS_KEYS}, got {postprocess!r}")
-    pp._connectivity(postprocess.get("connectivity", 1))
-    pp._count(postprocess.get("num_components", 1), "num_components")
-    pp._count(postprocess.get("min_size", 0), "min_size")
-    pp._cap(postprocess.get("cap"))
-    classes = postprocess.get("classes")
-    if classes is not None and (isinstance(classes, (str, bytes)) or not hasattr(classes, "__iter__") or
-                                any(isinstance(c, bool) or not isinstance(c, int) or c < 1 for c in classes)):
-        raise ValueError(f"postprocess: classes is None or integers >= 1, got {classes!r}")
 
 
 def _segment_surface_kwargs(surface, label):
@@ -657,15 +648,6 @@ def _one_hot_labels(labels, channels):
     return labels
 
 
-POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "channels", "cap")
-
-
-def _postprocess_kwargs(postprocess):
-    """Refuse a ``postprocess`` argument that is not a dict of ``keep_largest_components`` keywords, before any predictor call."""
-    if not isinstance(postprocess, dict) or any(k not in POSTPROCESS_KEYS for k in postprocess):
-        raise ValueError(f"postprocess: None or a dict with keys among {POSTPROCESS_KEYS}, got {postprocess!r}")
-
-
 def binarise(outputs: torch.Tensor) -> torch.Tensor:
     """engine.py:179-180."""
     return (torch.sigmoid(outputs) > 0.5).float()
@@ -695,10 +677,9 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     ``fill_holes``: None, or a dict with keys among ("connectivity", "channels"): ``postprocess.fill_holes`` on the binarised
     volume, after ``postprocess`` when both are given."""
     if postprocess is not None:
-        _postprocess_kwargs(postprocess)
+        pp.check_stage_kwargs("postprocess", "mask", postprocess)
     if fill_holes is not None:
-        from . import postprocess as pp
-        pp._fill_holes_kwargs(fill_holes, pp.FILL_HOLES_KEYS, "channels")
+        pp.check_stage_kwargs("fill_holes", "mask", fill_holes)
     augmented = len(mirror_flips(mirror_axes)) > 1
     if streaming:
         return evaluate_volume(model, image, None, roi_size, sw_batch_size, overlap, distributed, group, postprocess,
@@ -710,12 +691,5 @@ def infer(model, image: torch.Tensor, roi_size=(96, 96, 96), sw_batch_size: int 
     kw = dict(group=group) if distributed else dict(mirror_axes=mirror_axes)
     with torch.no_grad():
         out = fn(image, roi_size, sw_batch_size, model, overlap, mode=mode, sigma_scale=sigma_scale, pred_type="ddim_sample", **kw)
-    if fill_holes is not None:
-        mask = binarise(out)
-        if postprocess is not None:
-            mask = pp.keep_largest_components(mask, **postprocess)
-        return pp.fill_holes(mask, **fill_holes)[0].float()
-    if postprocess is not None:
-        from .postprocess import keep_largest_components
-        return keep_largest_components(binarise(out), **postprocess).float()
-    return binarise(out)
+    return _run_stages(lambda ref: (binarise(out), None),
+                       _stages(postprocess, fill_holes, pp.filter_components, pp.fill_holes, "labels"), None)[0].float()

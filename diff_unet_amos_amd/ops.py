@@ -1791,11 +1791,13 @@ def surface_report(test, reference, tolerances, voxel_spacing=None, connectivity
 
 # ---- evaluation: connected components (csrc/components.hip) -------------------------------------------------------------------
 
-def _cc_workspace(V, D, H, W, cap, device):
-    need = int(nv.lib().dua_cc_scratch_bytes(V, D, H, W, int(cap)))
+def _cc_scratch(size_fn, noun, V, D, H, W, last, device, last_is_cap=True):
+    """(workspace, bytes) as ``size_fn`` (one of the dua_*_scratch_bytes functions of components.hip and fill_holes.hip) sizes
+    it; ``last`` is its fifth argument, a cap or a label-map flag.  ``noun`` opens the message of a refusal."""
+    need = int(size_fn(V, D, H, W, int(last)))
     if need < 0:
-        raise ValueError(f"connected components: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1) "
-                         f"or cap={cap} (1..{nv.CC_MAX_CAP})")
+        raise ValueError(f"{noun}: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1)" +
+                         (f" or cap={last} (1..{nv.CC_MAX_CAP})" if last_is_cap else ""))
     return torch.empty(need, dtype=torch.uint8, device=device), need
 
 
@@ -1828,19 +1830,35 @@ def _cc_reference(reference, classes, label_map, V, D, H, W, dev):
     return ref, nv.F32 if ref.dtype == torch.float32 else nv.U8, 0, Cn
 
 
+def _label_map_reference(reference, V, D, H, W, dev):
+    """The reference of a map-form tallying pass: None, or a label map like the V maps [D, H, W] on ``dev``."""
+    if reference is None:
+        return None
+    ref, *rshape = _label_maps(reference, "reference")
+    assert tuple(rshape) == (V, D, H, W) and ref.device == dev, "reference: a label map like label_map, on its device"
+    return ref
+
+
+def _cc_number(entry, size_fn, dev, V, D, H, W, *args):
+    """The allocation and the launch behind ``cc_label`` and ``cc_label_map``: (labels int32 [V, D, H, W], counts int32 [V]) of
+    the entry point named ``entry``, whose arguments between the extents and ``labels`` are ``args``."""
+    L = nv.lib()
+    ws, need = _cc_scratch(getattr(L, size_fn), "connected components", V, D, H, W, 1, dev)
+    labels = torch.empty((V, D, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty((V,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nv.check(getattr(L, entry)(V, D, H, W, *args, nv.ptr(labels), nv.ptr(counts), nv.ptr(ws), need, nv.stream_ptr()), entry)
+    return labels, counts
+
+
 def cc_label(mask, connectivity=1, select=None):
     """dua_cc_label for every volume of mask ([..., D, H, W]; fp32, uint8 or bool): (labels int32 [V, D, H, W], counts int32 [V]),
     the labels of scipy.ndimage.label per volume.  ``select``: uint8 [V] device flags, a volume with 0 is not labelled (labels 0,
     count 0).  No host synchronisation."""
     m, code, V, D, H, W = _surface_mask(mask, "mask")
     select = _cc_flags(select, V, "select", m.device)
-    ws, need = _cc_workspace(V, D, H, W, 1, m.device)
-    labels = torch.empty((V, D, H, W), dtype=torch.int32, device=m.device)
-    counts = torch.empty((V,), dtype=torch.int32, device=m.device)
-    with torch.cuda.device(m.device):
-        nv.check(nv.lib().dua_cc_label(V, D, H, W, nv.ptr(m), code, D * H * W, int(connectivity), nv.ptr(select), nv.ptr(labels),
-                                       nv.ptr(counts), nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_label")
-    return labels, counts
+    return _cc_number("dua_cc_label", "dua_cc_scratch_bytes", m.device, V, D, H, W, nv.ptr(m), code, D * H * W, int(connectivity),
+                      nv.ptr(select))
 
 
 def cc_sizes(labels, cap):
@@ -1878,7 +1896,7 @@ def cc_filter(labels, counts, sizes, k=1, min_size=0, apply=None, mask=None, ref
         assert (Vm, *ext) == (V, D, H, W) and m.device == dev, "mask: the volumes the labels were made from"
     assert apply is None or m is not None, "apply: volumes passed through are copied from mask"
     ref, rcode, is_map, Cn = _cc_reference(reference, classes, label_map, V, D, H, W, dev)
-    ws, need = _cc_workspace(V, D, H, W, cap, dev)
+    ws, need = _cc_scratch(nv.lib().dua_cc_scratch_bytes, "connected components", V, D, H, W, cap, dev)
     out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
     with torch.cuda.device(dev):
@@ -1895,26 +1913,13 @@ def _label_maps(t, name):
     return (t, *t.shape)
 
 
-def _cc_map_workspace(V, D, H, W, cap, device):
-    need = int(nv.lib().dua_cc_map_scratch_bytes(V, D, H, W, int(cap)))
-    if need < 0:
-        raise ValueError(f"connected components: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1) "
-                         f"or cap={cap} (1..{nv.CC_MAX_CAP})")
-    return torch.empty(need, dtype=torch.uint8, device=device), need
-
-
 def cc_label_map(label_map, num_classes, connectivity=1):
     """dua_cc_label_map for every map of label_map (uint8 [N, D, H, W]): (labels int32 [N, D, H, W], counts int32 [N]); the
     components of all classes 1 .. num_classes - 1 numbered together by their first voxel, two voxels connected only when they
     carry the same value.  No host synchronisation."""
     m, V, D, H, W = _label_maps(label_map, "label_map")
-    ws, need = _cc_map_workspace(V, D, H, W, 1, m.device)
-    labels = torch.empty((V, D, H, W), dtype=torch.int32, device=m.device)
-    counts = torch.empty((V,), dtype=torch.int32, device=m.device)
-    with torch.cuda.device(m.device):
-        nv.check(nv.lib().dua_cc_label_map(V, D, H, W, nv.ptr(m), D * H * W, int(num_classes), int(connectivity), nv.ptr(labels),
-                                           nv.ptr(counts), nv.ptr(ws), need, nv.stream_ptr()), "dua_cc_label_map")
-    return labels, counts
+    return _cc_number("dua_cc_label_map", "dua_cc_map_scratch_bytes", m.device, V, D, H, W, nv.ptr(m), D * H * W, int(num_classes),
+                      int(connectivity))
 
 
 def cc_filter_map(label_map, num_classes, labels, counts, sizes, k=1, min_size=0, apply=None, reference=None):
@@ -1932,11 +1937,8 @@ def cc_filter_map(label_map, num_classes, labels, counts, sizes, k=1, min_size=0
         sizes.device == dev, f"counts int32 [{V}] and sizes int32 [{V}, cap] on the map's device"
     cap = int(sizes.shape[1])
     apply = _cc_flags(apply, Cn, "apply", dev)
-    ref = None
-    if reference is not None:
-        ref, *rshape = _label_maps(reference, "reference")
-        assert tuple(rshape) == (V, D, H, W) and ref.device == dev, "reference: a label map like label_map, on its device"
-    ws, need = _cc_map_workspace(V, D, H, W, cap, dev)
+    ref = _label_map_reference(reference, V, D, H, W, dev)
+    ws, need = _cc_scratch(nv.lib().dua_cc_map_scratch_bytes, "connected components", V, D, H, W, cap, dev)
     out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
     with torch.cuda.device(dev):
@@ -1948,13 +1950,6 @@ def cc_filter_map(label_map, num_classes, labels, counts, sizes, k=1, min_size=0
 
 # ---- evaluation: fill holes (csrc/fill_holes.hip) --------------------------------------------------------------------------------
 
-def _fill_holes_workspace(V, D, H, W, label_map, device):
-    need = int(nv.lib().dua_fill_holes_scratch_bytes(V, D, H, W, int(label_map)))
-    if need < 0:
-        raise ValueError(f"fill holes: unsupported extents V={V}, D={D}, H={H}, W={W} (V <= 65535, D H W < 2^31 - 1)")
-    return torch.empty(need, dtype=torch.uint8, device=device), need
-
-
 def fill_holes_mask(mask, connectivity=1, select=None, reference=None, classes=1, label_map=False):
     """dua_fill_holes_mask for every volume of mask ([..., D, H, W]; fp32, uint8 or bool): (out [V, D, H, W] of the mask's dtype
     -- the mask with the voxels of every enclosed hole set to 1 --, filled int64 [V], tallies int64 [classes, 3] or None).
@@ -1964,7 +1959,7 @@ def fill_holes_mask(mask, connectivity=1, select=None, reference=None, classes=1
     dev = m.device
     select = _cc_flags(select, V, "select", dev)
     ref, rcode, is_map, Cn = _cc_reference(reference, classes, label_map, V, D, H, W, dev)
-    ws, need = _fill_holes_workspace(V, D, H, W, False, dev)
+    ws, need = _cc_scratch(nv.lib().dua_fill_holes_scratch_bytes, "fill holes", V, D, H, W, False, dev, last_is_cap=False)
     out = torch.empty((V, D, H, W), dtype=m.dtype, device=dev)
     filled = torch.empty((V,), dtype=torch.int64, device=dev)
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None
@@ -1987,11 +1982,8 @@ def fill_holes_map(label_map, num_classes, connectivity=1, classes=None, referen
     for c in chosen:
         assert 1 <= int(c) < Cn, f"classes lie in 1..{Cn - 1}, got {c!r}"
         class_mask |= 1 << int(c)
-    ref = None
-    if reference is not None:
-        ref, *rshape = _label_maps(reference, "reference")
-        assert tuple(rshape) == (V, D, H, W) and ref.device == dev, "reference: a label map like label_map, on its device"
-    ws, need = _fill_holes_workspace(V, D, H, W, True, dev)
+    ref = _label_map_reference(reference, V, D, H, W, dev)
+    ws, need = _cc_scratch(nv.lib().dua_fill_holes_scratch_bytes, "fill holes", V, D, H, W, True, dev, last_is_cap=False)
     out = torch.empty((V, D, H, W), dtype=torch.uint8, device=dev)
     filled = torch.empty((Cn,), dtype=torch.int64, device=dev)
     tallies = torch.empty((Cn, 3), dtype=torch.int64, device=dev) if ref is not None else None

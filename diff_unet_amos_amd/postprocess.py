@@ -20,6 +20,8 @@ can be captured into a graph.  There is no CPU path.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _native as nv
@@ -76,17 +78,27 @@ def _channels(mask, channels):
     return chosen
 
 
-def _channel_flags(mask, chosen):
-    """uint8 [V] device flags of the volumes whose channel is in ``chosen``, or None for all; filled on the device, so a graph
-    capture holds no copy from the host."""
+def _selection_flags(chosen, shape, device):
+    """uint8 device flags, one per volume of a [..., C, D, H, W] tensor of ``shape``: 1 where the volume's channel (or, for the
+    one row of a label map, the class) is in ``chosen``; None for all.  Filled on the device, so a graph capture holds no copy
+    from the host."""
     if chosen is None:
         return None
-    Cn = mask.shape[-4]
-    flags = torch.zeros((mask.numel() // (Cn * mask.shape[-3] * mask.shape[-2] * mask.shape[-1]), Cn), dtype=torch.uint8,
-                        device=mask.device)
+    flags = torch.zeros((math.prod(shape[:-4]), shape[-4]), dtype=torch.uint8, device=device)
     for c in chosen:
         flags[:, c] = 1
     return flags.view(-1)
+
+
+def _reference_map(reference, label_map, m, runs):
+    """``reference`` of a map-form tallying call as a tensor shaped like ``m`` (``label_map`` with a leading axis), or None."""
+    if reference is None:
+        return None
+    if not isinstance(reference, torch.Tensor) or not reference.is_cuda:
+        raise RuntimeError(f"reference: {runs} on an MI355X (device 'cuda'); there is no CPU path in this package")
+    if reference.dtype != torch.uint8 or tuple(reference.shape) != tuple(label_map.shape):
+        raise ValueError(f"reference: a uint8 label map {tuple(label_map.shape)}, got {reference.dtype} {tuple(reference.shape)}")
+    return reference.view(m.shape)
 
 
 def _reference_labels(mask, labels):
@@ -149,7 +161,7 @@ def filter_components(mask, connectivity=1, num_components=1, min_size=0, channe
         _cap(cap)
     chosen = _channels(mask, channels)
     mask = _device_mask(mask, "mask")
-    flags = _channel_flags(mask, chosen)
+    flags = _selection_flags(chosen, mask.shape, mask.device)
     ref, Cn, is_map = _reference_labels(mask, labels)
     lab, counts = ops.cc_label(mask, conn, select=flags)
     sizes = ops.cc_sizes(lab, cap)
@@ -230,19 +242,8 @@ def filter_label_map(label_map, num_classes, connectivity=1, num_components=1, m
     k, min_size, cap = _count(num_components, "num_components"), _count(min_size, "min_size"), _cap(cap)
     chosen = _class_list(classes, Cn)
     m = _device_label_map(label_map, "label_map")
-    ref = None
-    if reference is not None:
-        if not isinstance(reference, torch.Tensor) or not reference.is_cuda:
-            raise RuntimeError("reference: connected components run on an MI355X (device 'cuda'); there is no CPU path in this package")
-        if reference.dtype != torch.uint8 or tuple(reference.shape) != tuple(label_map.shape):
-            raise ValueError(f"reference: a uint8 label map {tuple(label_map.shape)}, got {reference.dtype} {tuple(reference.shape)}")
-        ref = reference.view(m.shape)
-    flags = None
-    if chosen is not None:
-        flags = torch.zeros((1, Cn), dtype=torch.uint8, device=m.device)  # filled on the device: a capture holds no host copy
-        for c in chosen:
-            flags[:, c] = 1
-        flags = flags.view(-1)
+    ref = _reference_map(reference, label_map, m, "connected components run")
+    flags = _selection_flags(chosen, (Cn, *m.shape[1:]), m.device)
     lab, counts = ops.cc_label_map(m, Cn, conn)
     sizes = ops.cc_sizes(lab, cap)
     out, tallies = ops.cc_filter_map(m, Cn, lab, counts, sizes, k, min_size, apply=flags, reference=ref)
@@ -272,7 +273,7 @@ def fill_holes(mask, connectivity=1, channels=None, labels=None):
     chosen = _channels(mask, channels)
     dtype = mask.dtype if isinstance(mask, torch.Tensor) else None
     mask = _device_mask(mask, "mask")
-    flags = _channel_flags(mask, chosen)
+    flags = _selection_flags(chosen, mask.shape, mask.device)
     ref, Cn, is_map = _reference_labels(mask, labels)
     out, filled, tallies = ops.fill_holes_mask(mask, conn, select=flags, reference=ref, classes=Cn, label_map=is_map)
     out = out.view(mask.shape)
@@ -296,30 +297,42 @@ def fill_holes_in_label_map(label_map, num_classes, connectivity=1, classes=None
     Cn, conn = _num_classes(num_classes), _connectivity(connectivity)
     chosen = _class_list(classes, Cn)
     m = _device_label_map(label_map, "label_map")
-    ref = None
-    if reference is not None:
-        if not isinstance(reference, torch.Tensor) or not reference.is_cuda:
-            raise RuntimeError("reference: fill_holes runs on an MI355X (device 'cuda'); there is no CPU path in this package")
-        if reference.dtype != torch.uint8 or tuple(reference.shape) != tuple(label_map.shape):
-            raise ValueError(f"reference: a uint8 label map {tuple(label_map.shape)}, got {reference.dtype} {tuple(reference.shape)}")
-        ref = reference.view(m.shape)
+    ref = _reference_map(reference, label_map, m, "fill_holes runs")
     out, filled, tallies = ops.fill_holes_map(m, Cn, conn, classes=chosen, reference=ref)
     out = out.view(label_map.shape)
     return (out, filled) if reference is None else (out, filled, tallies)
 
 
-FILL_HOLES_KEYS = ("connectivity", "channels")                  # of evaluate_volume's and infer's ``fill_holes=`` (mask form)
-FILL_HOLES_MAP_KEYS = ("connectivity", "classes")               # of segment_case's ``fill_holes=`` (map form)
+# ---- the stage dicts of inference.py: ``postprocess=`` and ``fill_holes=`` of evaluate_volume / infer (the mask form) and of
+# segment_case (the map form) -----------------------------------------------------------------------------------------------------
+
+POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "channels", "cap")            # filter_components
+SEGMENT_POSTPROCESS_KEYS = ("connectivity", "num_components", "min_size", "classes", "cap")    # filter_label_map
+FILL_HOLES_KEYS = ("connectivity", "channels")                                                  # fill_holes
+FILL_HOLES_MAP_KEYS = ("connectivity", "classes")                                               # fill_holes_in_label_map
+
+_STAGE_KEYS = {("postprocess", "mask"): POSTPROCESS_KEYS, ("postprocess", "map"): SEGMENT_POSTPROCESS_KEYS,
+               ("fill_holes", "mask"): FILL_HOLES_KEYS, ("fill_holes", "map"): FILL_HOLES_MAP_KEYS}
+_STAGE_VALUES = {"connectivity": _connectivity, "num_components": lambda v: _count(v, "num_components"),
+                 "min_size": lambda v: _count(v, "min_size"), "cap": _cap}
+# the key that holds a list of integers and their lower bound.  The channels of the mask-form ``postprocess=`` are not listed:
+# filter_components takes whatever int() takes and checks the range against the mask's channel axis, which no one knows here.
+_STAGE_SELECTION = {("postprocess", "map"): ("classes", 1), ("fill_holes", "mask"): ("channels", 0),
+                    ("fill_holes", "map"): ("classes", 1)}
 
 
-def _fill_holes_kwargs(fill_holes, keys, selection):
-    """Refuse a ``fill_holes=`` argument that is not a dict with keys among ``keys`` and values the fill functions take, before
-    any device work.  ``selection``: the key that holds a list of non-negative integers (channels or classes)."""
-    if not isinstance(fill_holes, dict) or any(k not in keys for k in fill_holes):
-        raise ValueError(f"fill_holes: None or a dict with keys among {keys}, got {fill_holes!r}")
-    _connectivity(fill_holes.get("connectivity", 1))
-    chosen = fill_holes.get(selection)
-    low = 1 if selection == "classes" else 0
+def check_stage_kwargs(stage, form, value):
+    """Refuse the ``stage`` ("postprocess" or "fill_holes") argument of an inference function in the ``form`` "mask" or "map"
+    unless it is a dict with keys among the stage's key tuple and values the stage's function takes, with that function's own
+    message -- before any predictor call and any device work."""
+    keys = _STAGE_KEYS[stage, form]
+    if not isinstance(value, dict) or any(k not in keys for k in value):
+        raise ValueError(f"{stage}: None or a dict with keys among {keys}, got {value!r}")
+    for key, check in _STAGE_VALUES.items():
+        if key in value:
+            check(value[key])
+    selection, low = _STAGE_SELECTION.get((stage, form), (None, 0))
+    chosen = value.get(selection)
     if chosen is not None and (isinstance(chosen, (str, bytes)) or not hasattr(chosen, "__iter__") or
                                any(isinstance(c, bool) or not isinstance(c, int) or c < low for c in chosen)):
-        raise ValueError(f"fill_holes: {selection} is None or integers >= {low}, got {chosen!r}")
+        raise ValueError(f"{stage}: {selection} is None or integers >= {low}, got {chosen!r}")

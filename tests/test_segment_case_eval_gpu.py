@@ -88,6 +88,58 @@ def test_postprocess_and_surface_equal_the_steps_composed_by_hand(run):
     assert no_label[1] is None and _same(no_label[0], want_map)
 
 
+# The native entry points each call makes after its last dua_blend_accumulate*, in order, as recorded before the stage chain of
+# inference.py was written once (_run_stages): the chain must make exactly these calls.  With a label or without, the names are
+# the same -- the reference is an argument of the last call, not a call of its own.
+# (KW is the gaussian mode: its divisor, dua_blend_weight_sum, is made after the windows and before the finish pass.)
+SEGMENT_CASE_CALLS = {
+    "neither": ["dua_blend_weight_sum", "dua_blend_finish_labelmap"],
+    "postprocess": ["dua_blend_weight_sum", "dua_blend_finish_labelmap", "dua_cc_label_map", "dua_cc_sizes", "dua_cc_filter_map"],
+    "fill_holes": ["dua_blend_weight_sum", "dua_blend_finish_labelmap", "dua_fill_holes_map"],
+    "both": ["dua_blend_weight_sum", "dua_blend_finish_labelmap", "dua_cc_label_map", "dua_cc_sizes", "dua_cc_filter_map",
+             "dua_fill_holes_map"],
+}
+EVALUATE_VOLUME_CALLS = {
+    "neither": ["dua_blend_weight_sum", "dua_blend_finish_weighted"],
+    "postprocess": ["dua_blend_weight_sum", "dua_blend_finish_weighted", "dua_cc_label", "dua_cc_sizes", "dua_cc_filter"],
+    "fill_holes": ["dua_blend_weight_sum", "dua_blend_finish_weighted", "dua_fill_holes_mask"],
+    "both": ["dua_blend_weight_sum", "dua_blend_finish_weighted", "dua_cc_label", "dua_cc_sizes", "dua_cc_filter",
+             "dua_fill_holes_mask"],
+}
+
+
+def _calls_after_the_last_accumulate(monkeypatch, fn):
+    from diff_unet_amos_amd import _native as nv
+    names, real = [], nv.check
+
+    def check(rc, what):
+        names.append(what)
+        return real(rc, what)
+
+    with monkeypatch.context() as m:
+        m.setattr(nv, "check", check)
+        fn()
+    last = max(i for i, name in enumerate(names) if name.startswith("dua_blend_accumulate"))
+    return names[last + 1:]
+
+
+@pytest.mark.parametrize("stages", ["neither", "postprocess", "fill_holes", "both"])
+def test_the_native_calls_after_the_blend_are_the_recorded_ones(run, monkeypatch, stages):
+    case, pred, label = run["case"], run["pred"], run["label"]
+    has_pp, has_fill = stages in ("postprocess", "both"), stages in ("fill_holes", "both")
+    vol = case.image[None, None]
+    onehot_map = (torch.arange(vol[0, 0].numel(), device=DEV) % CHANNELS).to(torch.uint8).view(1, *vol.shape[2:])
+    for lab, ref in ((label, onehot_map), (None, None)):
+        kw = dict(postprocess=dict(connectivity=2, num_components=1, min_size=2, classes=(1, 2)) if has_pp else None,
+                  fill_holes=dict(connectivity=1, classes=(1, 2)) if has_fill else None)
+        got = _calls_after_the_last_accumulate(monkeypatch, lambda: inference.segment_case(pred, case, lab, ROI, 2, 0.25, **kw, **KW))
+        assert got == SEGMENT_CASE_CALLS[stages], ("segment_case", lab is not None)
+        kw = dict(postprocess=dict(connectivity=2, num_components=1, min_size=2, channels=(1, 2)) if has_pp else None,
+                  fill_holes=dict(connectivity=1, channels=(1, 2)) if has_fill else None)
+        got = _calls_after_the_last_accumulate(monkeypatch, lambda: inference.evaluate_volume(pred, vol, ref, ROI, 2, 0.25, **kw, **KW))
+        assert got == EVALUATE_VOLUME_CALLS[stages], ("evaluate_volume", ref is not None)
+
+
 def test_a_plain_tensor_uses_unit_spacing(run):
     case, pred = run["case"], run["pred"]
     vol = case.image[None, None]
