@@ -56,10 +56,10 @@ class DeconvForm(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kernel", "tile_voxels", "grid_x", "grid_y", "grid_z", "lds_bytes", "lds_limit")]
 
 
-# dua_conv3_form.kernel (DUA_CONV3_*) and dua_deconv_form.kernel (DUA_DECONV_*)
-(CONV3_FIRST, CONV3_TAP0, CONV3_TAP1, CONV3_WIDE, CONV3_WIDE_BWD, CONV3_WIDE_PT, CONV3_V2_4, CONV3_V2_4_HALF, CONV3_V2_4_KD,
+# dua_conv3_form.kernel (DUA_CONV3_*) and dua_deconv_form.kernel (DUA_DECONV_*); _RETIRED_*: a value no form answers any more
+(CONV3_FIRST, CONV3_TAP0, CONV3_TAP1, CONV3_WIDE, CONV3_WIDE_BWD, _RETIRED_CONV3_5, CONV3_V2_4, CONV3_V2_4_HALF, CONV3_V2_4_KD,
  CONV3_V2_2, CONV3_V2_2_KD) = range(11)
-DECONV_ONE_TAP, DECONV_KSPLIT, DECONV_ALLTAPS_128, DECONV_ALLTAPS_256 = range(4)
+DECONV_ONE_TAP, DECONV_KSPLIT, DECONV_ALLTAPS_128, _RETIRED_DECONV_3 = range(4)
 
 
 class UpConvDesc(C.Structure):

@@ -27,7 +27,7 @@ struct Conv3Args {
 };
 
 // conv3d_wide.hip: the 8-accumulator form (8x8x8 tiles) for fp16 layers with >= 1024 tiles of 4x8x8; D, H, W multiples of 8,
-// Cin a multiple of 16.  `a` and `f` as conv3_form decided them: DUA_CONV3_WIDE (shipped), _WIDE_BWD or _WIDE_PT (A/B only).
-int launch_conv3_wide(Conv3Args a, const Conv3Form& f, hipStream_t s);
+// Cin a multiple of 16.  `a` and `f` as conv3_form decided them: DUA_CONV3_WIDE or _WIDE_BWD.
+int launch_conv3_wide(const Conv3Args& a, const Conv3Form& f, hipStream_t s);
 
 }  // namespace dua

@@ -89,7 +89,7 @@ constexpr int conv3_lds_limit(int kernel) {
   switch (kernel) {
     case DUA_CONV3_FIRST: return FIRST_LDS + PARTIAL_LDS_PAD;
     case DUA_CONV3_TAP0: case DUA_CONV3_TAP1: return TAP_LDS + PARTIAL_LDS_PAD;
-    case DUA_CONV3_WIDE: case DUA_CONV3_WIDE_BWD: case DUA_CONV3_WIDE_PT: return WIDE_LDS_LIMIT;
+    case DUA_CONV3_WIDE: case DUA_CONV3_WIDE_BWD: return WIDE_LDS_LIMIT;
     case DUA_CONV3_V2_4: case DUA_CONV3_V2_4_HALF: return c3v2::LDS_MAIN + XF_LDS_MAX + PARTIAL_LDS_PAD;
     case DUA_CONV3_V2_2: return c3v2::LDS_MAIN + XF_LDS_MAX;
     default: return LDS_CU;                                                   // the kd-plane forms
@@ -115,8 +115,6 @@ constexpr int deconv_lds_limit(int kernel, int elem_bytes) {
 // The only place that knows the hand-set values (include/dua_hip.h lists them); everything else reads the flags.
 struct Conv3Policy {
   bool wide = false;            // the wide-tile form where the layer qualifies
-  bool wide_persistent = false; // ... with persistent workgroups (A/B only)
-  int stagger = 0;              // ... whose odd-slot workgroup of a CU starts this many sleeps late
   bool kd_plane = false;        // kd planes by LDS-DMA for the launches that cannot put two workgroups on every CU
   bool automatic = false;       // split-K and 2x8x8 tiles by the size of the layer
   int split_target = 0;         // split-K: workgroups aimed at
@@ -141,23 +139,20 @@ inline int decode_conv3_policy(int policy, Conv3Policy* out) {
     case 3: p.td2 = true; break;
     case 6: automatic(false); break;
     case 7: automatic(true); break;
-    case 9: p.stagger = 2; [[fallthrough]];
-    case 8: automatic(true); p.wide = p.wide_persistent = true; break;
     default: return DUA_ERR_ARG;
   }
   *out = p;
   return 0;
 }
 
-// dua_deconv_k2s2_fwd: 0, or 6 = the A/B forms
+// dua_deconv_k2s2_fwd: 0, or 6 = no k-split kernel
 struct DeconvPolicy {
   bool ksplit = true;           // Cin chunks split over the waves where the layer qualifies
-  bool tiles_256 = false;       // 256-voxel all-taps tiles where they fit
 };
 inline int decode_deconv_policy(int policy, DeconvPolicy* out) {
   switch (policy) {
     case 0: *out = DeconvPolicy{}; return 0;
-    case 6: *out = DeconvPolicy{false, true}; return 0;
+    case 6: *out = DeconvPolicy{false}; return 0;
     default: return DUA_ERR_ARG;
   }
 }
@@ -179,7 +174,6 @@ struct Conv3Form : dua_conv3_form {
   int nchunks, ntiles, tiles_h, tiles_w, nct, cout_pad;    // geometry the kernels take (Conv3Args)
   int tap_ch;                                              // packed index of the tap channel, or -1
   int items;                                               // first-layer kernel: (sample, tile) items its workgroups walk
-  int stagger;                                             // persistent wide form
   int fin_G, fin_VL, fin_ITER;                             // finish launch: channel groups per pass, voxel lanes, voxels per lane
   unsigned fin_grid_x, fin_grid_y;
 };
@@ -191,7 +185,7 @@ inline long conv3_split_bytes(const dua_conv3_desc* d, int ks, int cout_pad) {
   return ks > 1 ? (long)ks * d->N * d->D * d->H * d->W * cout_pad * 4 : 0;
 }
 
-// cus: compute units of the device (first-layer and persistent wide grids; <= 0 is an error for those two only).
+// cus: compute units of the device (the first-layer kernel's grid; <= 0 is an error for that form only).
 inline int conv3_form(const dua_conv3_desc* d, const Conv3Policy& p, bool fused, bool backward_sums, long workspace_bytes, int cus,
                       Conv3Form* f) {
   using namespace c3;
@@ -221,13 +215,12 @@ inline int conv3_form(const dua_conv3_desc* d, const Conv3Policy& p, bool fused,
     f->kernel = f->tap_ch == 16 ? (p.first ? DUA_CONV3_FIRST : DUA_CONV3_TAP1) : DUA_CONV3_TAP0;
   } else if (half && p.wide && !d->background && base >= 1024 && d->D % 8 == 0 && d->H % 8 == 0 && d->W % 8 == 0 && d->Cin % 16 == 0 &&
              d->Cin <= (fused ? 256 : 384) && vox * d->Cin_stride < 0x7fffffffL) {
-    // fp16 layers with tiles to spare (96^3).  The persistent forms (accumulators held by name; staggered start) measured
-    // 1.5-2.5 % SLOWER than one tile per workgroup (profiles/r5_conv_wide_persistent_named_acc_ab.txt): kept for that A/B only
-    f->kernel = p.wide_persistent ? DUA_CONV3_WIDE_PT : backward_sums ? DUA_CONV3_WIDE_BWD : DUA_CONV3_WIDE;
+    // fp16 layers with tiles to spare (96^3): one 8x8x8 tile per workgroup
+    f->kernel = backward_sums ? DUA_CONV3_WIDE_BWD : DUA_CONV3_WIDE;
   } else {
     f->kernel = DUA_CONV3_V2_4;                                        // refined below
   }
-  const bool is_wide = f->kernel >= DUA_CONV3_WIDE && f->kernel <= DUA_CONV3_WIDE_PT;
+  const bool is_wide = f->kernel == DUA_CONV3_WIDE || f->kernel == DUA_CONV3_WIDE_BWD;
   // 16-channel-blocked buffers: read by the wide-tile form only, written by it and by the first-layer kernel only
   if ((in_blk && !is_wide) || (out_blk && !is_wide && f->kernel != DUA_CONV3_FIRST)) return DUA_ERR_ARG;
   if ((in_blk && (d->Cin_off % 16 || d->Cin_stride % 16)) || (out_blk && (d->Cout_off % 16 || d->Cout_stride % 16))) return DUA_ERR_ARG;
@@ -253,15 +246,6 @@ inline int conv3_form(const dua_conv3_desc* d, const Conv3Policy& p, bool fused,
     f->grid_x = f->ntiles;
     f->lds_bytes = c3w::LDS_FIXED + (fused ? xf_lds(d->Cin) : 0) + (backward_sums ? WIDE_BWD_LDS : 0);
     if (f->lds_bytes > WIDE_LDS_LIMIT) return DUA_ERR_ARG;
-    if (f->kernel == DUA_CONV3_WIDE_PT) {
-      // two workgroups per CU over the whole launch, shared by the (cout tile, sample) pairs; each walks its tiles with stride grid.x
-      if (cus <= 0) return DUA_ERR_ARG;
-      const int pairs = f->nct * d->N;
-      int gx = (2 * cus + pairs - 1) / pairs;
-      gx = (gx + 7) & ~7;                                          // whole XCD rounds: tile t and t + grid.x stay on one XCD
-      f->grid_x = std::min(gx, f->ntiles);
-      f->stagger = p.stagger;
-    }
   } else {
     if (p.automatic) {
       int ks, ups;
@@ -312,7 +296,7 @@ inline int conv3_form(const dua_conv3_desc* d, bool fused, bool backward_sums, l
 
 // dua_conv3d_k3_workspace: the split of the SLAB policy for the plain channels-last launch of d's shape.  Its target rounds up
 // where the kd-plane targets round down, and ksplit grows with the workgroups aimed at, so this is never smaller than what any
-// policy a plan runs with (0, 6, 7, 8, 9) splits into: a workspace of this size enables the split under each of them
+// policy a plan runs with (0, 6, 7) splits into: a workspace of this size enables the split under each of them
 // (tests/test_conv3_form.py holds the inequality).
 inline long conv3_workspace_bytes(const dua_conv3_desc* d) {
   Conv3Policy slab;
@@ -327,7 +311,7 @@ inline long conv3_workspace_bytes(const dua_conv3_desc* d) {
 // dua_conv3d_k3_kernel_kind of a form: 0 = conv3d_k3_v2_kernel in any instantiation, 1 = first-layer, 2 = wide-tile
 inline int conv3_kind_of(const Conv3Form& f) {
   if (f.kernel == DUA_CONV3_FIRST) return 1;
-  return f.kernel >= DUA_CONV3_WIDE && f.kernel <= DUA_CONV3_WIDE_PT ? 2 : 0;
+  return f.kernel == DUA_CONV3_WIDE || f.kernel == DUA_CONV3_WIDE_BWD ? 2 : 0;
 }
 
 // ---- the form of a transposed-convolution launch ----------------------------------------------------------------------------
@@ -352,11 +336,9 @@ inline int deconv_form(const dua_conv3_desc* d, bool fused, int Do, int Ho, int 
   f->grid_y = 8 * f->nct; f->grid_z = d->N;                         // one tap per workgroup, unless all taps below
   if (vox >= 256L * 128 && f->nchunks <= 4) {
     // enough tiles to fill the chip with one workgroup per 8 taps.  128-voxel tiles: two workgroups per CU up to 64 input
-    // channels (70 KB each), one's pixel-shuffle stores under the other's loads; the 256-voxel form (one workgroup per CU)
-    // stays for A/B where it fits
-    const bool big = p.tiles_256 && deconv_alltaps_lds(256, f->nchunks, eb) + xf <= LDS_CU;
-    f->kernel = big ? DUA_DECONV_ALLTAPS_256 : DUA_DECONV_ALLTAPS_128;
-    f->tile_voxels = big ? 256 : 128;
+    // channels (70 KB each), one's pixel-shuffle stores under the other's loads
+    f->kernel = DUA_DECONV_ALLTAPS_128;
+    f->tile_voxels = 128;
     f->lds_bytes = deconv_alltaps_lds(f->tile_voxels, f->nchunks, eb) + xf;
     f->grid_y = f->nct;
   } else if (f->nchunks >= 8 && f->nchunks <= 4 * dcs::MC && p.ksplit) {   // Cin >= 256: waves split the Cin chunks

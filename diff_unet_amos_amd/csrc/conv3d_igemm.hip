@@ -918,7 +918,7 @@ static int launch_conv3(const dua_conv3_desc* d, const void* x, const void* w, c
     case DUA_CONV3_FIRST: if constexpr (F16) hipLaunchKernelGGL(conv3d_k3_first_kernel, grid, block, lds, s, a, f.items); break;
     case DUA_CONV3_TAP0: if constexpr (F16) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 0>), grid, block, lds, s, a); break;
     case DUA_CONV3_TAP1: if constexpr (F16) hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 1>), grid, block, lds, s, a); break;
-    case DUA_CONV3_WIDE: case DUA_CONV3_WIDE_BWD: case DUA_CONV3_WIDE_PT: return launch_conv3_wide(a, f, s);
+    case DUA_CONV3_WIDE: case DUA_CONV3_WIDE_BWD: return launch_conv3_wide(a, f, s);
     case DUA_CONV3_V2_4: hipLaunchKernelGGL(conv3d_k3_v2_kernel<T>, grid, block, lds, s, a); break;
     case DUA_CONV3_V2_4_HALF: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, true>), grid, block, lds, s, a); break;
     case DUA_CONV3_V2_4_KD: hipLaunchKernelGGL((conv3d_k3_v2_kernel<T, 4, 2, false, true>), grid, block, lds, s, a); break;

@@ -308,10 +308,10 @@ __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a
 // weights of the next pair are prefetched while this pair multiplies, and a pair ends with one pixel-shuffle store of both
 // taps -- outputs 2w and 2w + 1 lie next to each other, so a store instruction writes whole runs (in the 16-channel-block
 // layout: 512 contiguous bytes per block) where one tap alone writes every other 32- or 64-byte piece.
-template <typename T, int MBLK>
+template <typename T>
 __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) {
   using namespace dc;
-  constexpr int TM = 64 * MBLK * 2, WR = 32 * MBLK;          // voxels per workgroup / per wave (MBLK 32-row MFMA blocks each)
+  constexpr int TM = 128, WR = 32;                          // voxels per workgroup / per wave (one 32-row MFMA block)
   using Frag = typename Elem<T>::Frag;
   constexpr int EPG = Elem<T>::EPG;
   constexpr int CK = KG * EPG;
@@ -414,25 +414,20 @@ __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) 
   // wait for those stores to be acknowledged by memory.
   load_pair(1);
   for (int tp = 0; tp < 4; ++tp) {
-    f32x16 acc[2][MBLK][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int tk = 0; tk < 2; ++tk) {
 #pragma unroll
-      for (int m = 0; m < MBLK; ++m)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[tk][m][0][i] = bq0; acc[tk][m][1][i] = bq1; }
+      for (int i = 0; i < 16; ++i) { acc[tk][0][i] = bq0; acc[tk][1][i] = bq1; }
       const char* wb = wlds + ((tp & 1) * 2 + tk) * wtap;
       for (int ch = 0; ch < a.nchunks; ++ch) {
 #pragma unroll
         for (int ks = 0; ks < KG / 2; ++ks) {
           const Frag b0 = *(const Frag*)(wb + ch * W_BYTES + ((2 * ks + hh) * BN + r) * 16);
           const Frag b1 = *(const Frag*)(wb + ch * W_BYTES + ((2 * ks + hh) * BN + 32 + r) * 16);
-#pragma unroll
-          for (int m = 0; m < MBLK; ++m) {
-            const Frag am = *(const Frag*)(alds + (wave * WR + m * 32 + r) * VSA + ch * 64 + (2 * ks + hh) * 16);
-            mma32(acc[tk][m][0], am, b0);
-            mma32(acc[tk][m][1], am, b1);
-          }
+          const Frag am = *(const Frag*)(alds + (wave * WR + r) * VSA + ch * 64 + (2 * ks + hh) * 16);
+          mma32(acc[tk][0], am, b0);
+          mma32(acc[tk][1], am, b1);
         }
       }
     }
@@ -444,10 +439,8 @@ __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) 
 #pragma unroll
       for (int tk = 0; tk < 2; ++tk)
 #pragma unroll
-        for (int m = 0; m < MBLK; ++m)
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            *(T*)(ot + (2 * (m * 32 + acc_row(i, hh)) + tk) * RB + r * (int)sizeof(T)) = (T)acc[tk][m][q][i];
+        for (int i = 0; i < 16; ++i)
+          *(T*)(ot + (2 * acc_row(i, hh) + tk) * RB + r * (int)sizeof(T)) = (T)acc[tk][q][i];
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int it = 0; it < NST; ++it) {
@@ -670,10 +663,8 @@ static inline int deconv_res_lds(int nchunks, int nsk) {
 
 // dynamic-LDS limits (raised once per device by ensure_prepared(), common.hpp): deconv_lds_limit(), which the forms report
 static const LdsAttr kDeconvLdsAttrs[] = {
-    {(const void*)deconv_k2s2_alltaps_kernel<f16, 2>, deconv_lds_limit(DUA_DECONV_ALLTAPS_256, 2)},
-    {(const void*)deconv_k2s2_alltaps_kernel<f16, 1>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 2)},
-    {(const void*)deconv_k2s2_alltaps_kernel<float, 2>, deconv_lds_limit(DUA_DECONV_ALLTAPS_256, 4)},
-    {(const void*)deconv_k2s2_alltaps_kernel<float, 1>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 4)},
+    {(const void*)deconv_k2s2_alltaps_kernel<f16>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 2)},
+    {(const void*)deconv_k2s2_alltaps_kernel<float>, deconv_lds_limit(DUA_DECONV_ALLTAPS_128, 4)},
     {(const void*)deconv_k2s2_ksplit_kernel<f16>, deconv_lds_limit(DUA_DECONV_KSPLIT, 2)},
     {(const void*)deconv_k2s2_ksplit_kernel<float>, deconv_lds_limit(DUA_DECONV_KSPLIT, 4)},
     {(const void*)deconv_k2s2_kernel<f16>, deconv_lds_limit(DUA_DECONV_ONE_TAP, 2)},
@@ -704,8 +695,7 @@ static int launch_deconv(const dua_conv3_desc* d, const void* x, const void* w, 
   switch (f.kernel) {
     case DUA_DECONV_ONE_TAP: hipLaunchKernelGGL(deconv_k2s2_kernel<T>, grid, block, f.lds_bytes, s, a); break;
     case DUA_DECONV_KSPLIT: hipLaunchKernelGGL(deconv_k2s2_ksplit_kernel<T>, grid, block, f.lds_bytes, s, a); break;
-    case DUA_DECONV_ALLTAPS_128: hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 1>), grid, block, f.lds_bytes, s, a); break;
-    case DUA_DECONV_ALLTAPS_256: hipLaunchKernelGGL((deconv_k2s2_alltaps_kernel<T, 2>), grid, block, f.lds_bytes, s, a); break;
+    case DUA_DECONV_ALLTAPS_128: hipLaunchKernelGGL(deconv_k2s2_alltaps_kernel<T>, grid, block, f.lds_bytes, s, a); break;
     default: return DUA_ERR_ARG;
   }
   return (int)hipGetLastError();

@@ -404,8 +404,8 @@ def conv3_workspace_bytes(dtype, N, D, H, W, cin, cout):
 # tests and the A/B tools set these to reach forms the automatic choice would not take for their shapes; the library itself keeps
 # no option state.
 # conv3d_k3: 2 = 4x8x8 tiles, split-K with the wider target (up to 256 base workgroups) when a workspace is given; 3 = 2x8x8 tiles
-# (slab form); 6 / 7 = automatic without the kd-plane / the wide-tile form; 8 / 9 = persistent wide form.  deconv_k2s2: 6.
-CONV_POLICY = 0          # conv3d_k3 / deconv_k2s2: 0, 2, 3, 6, 7, 8, 9 (| _native.POLICY_NO_FINISH)
+# (slab form); 6 / 7 = automatic without the kd-plane / the wide-tile form.  deconv_k2s2: 6 = no k-split kernel.
+CONV_POLICY = 0          # conv3d_k3 / deconv_k2s2: 0, 2, 3, 6, 7 (| _native.POLICY_NO_FINISH)
 WGRAD_POLICY = 0         # conv3d_k3_wgrad: bit field, see include/dua_hip.h
 
 KIND_V2, KIND_FIRST, KIND_WIDE = 0, 1, 2          # dua_conv3d_k3_kernel_kind

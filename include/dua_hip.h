@@ -78,11 +78,11 @@ typedef struct {
                                       give it) and same-process A/B timing; results are the same.  dua_conv3d_k3_fwd: low byte
                                       2 = 4x8x8 tiles, split-K with the wider target (up to 256 base workgroups) when a workspace
                                       is given, 3 = 2x8x8 tiles (slab form), 6 = automatic without the
-                                      kd-plane / LDS-DMA form of the small layers, 7 = automatic without the wide-tile form, 8 / 9 = the wide-tile
-                                      form with persistent workgroups (9: staggered start; both measured slower, kept for A/B);
+                                      kd-plane / LDS-DMA form of the small layers, 7 = automatic without the wide-tile form
+                                      (8 and 9, the wide-tile form with persistent workgroups, are retired and rejected);
                                       bit 8 (DUA_POLICY_NO_FINISH) = skip the split-K finish kernel (timing the main kernel alone:
                                       outputs are then NOT valid).  dua_deconv_k2s2_fwd: 6 = the one-tap-per-workgroup kernel
-                                      for every shape that has it, 256-voxel all-taps tiles.  dua_conv3d_k3_wgrad: bit 0 = plain
+                                      instead of the k-split kernel.  dua_conv3d_k3_wgrad: bit 0 = plain
                                       block order, bits 1-4 = workgroups per CU over the launch, bit 5 / 6 = the 6-wave forms,
                                       bit 7 = tiles through registers, bit 8 = the first form (a workgroup per kd plane of taps)
                                       instead of the fetch-once form (fp16).  A per-call field: the library keeps no mutable option
@@ -106,15 +106,15 @@ int dua_deconv_k2s2_kernel_kind(const dua_conv3_desc* d);
 /* The whole launch form of a call, decided by the one host function the launchers themselves run (csrc/conv3_form.hpp): which
  * kernel instantiation, its grid and dynamic LDS, and the split.  Both kernel_kind queries above are projections of it.
  * fused = the call will pass a producer descriptor with statistics; workspace_bytes = what the call will pass (0 = none);
- * cus = compute units to decide for, 0 = the current device (cus > 0 answers without touching the GPU; only the persistent
- * forms' grids depend on it).  Returns 0 or DUA_ERR_ARG for a call the launcher rejects. */
+ * cus = compute units to decide for, 0 = the current device (cus > 0 answers without touching the GPU; only the first-layer
+ * kernel's grid depends on it).  Returns 0 or DUA_ERR_ARG for a call the launcher rejects. */
 enum {
   DUA_CONV3_FIRST = 0,       /* conv3d_k3_first_kernel: resident weights, persistent workgroups */
   DUA_CONV3_TAP0 = 1,        /* conv3d_k3_v2_kernel<f16, 4, 0>: the lone tap channel */
   DUA_CONV3_TAP1 = 2,        /* conv3d_k3_v2_kernel<f16, 4, 1>: 16 channels + the tap channel */
   DUA_CONV3_WIDE = 3,        /* conv3d_k3_wide_kernel */
   DUA_CONV3_WIDE_BWD = 4,    /* conv3d_k3_wide_bwd_kernel (dua_conv3d_k3_dgrad_reduce) */
-  DUA_CONV3_WIDE_PT = 5,     /* conv3d_k3_wide_pt_kernel: persistent workgroups */
+  /* 5: retired (the wide-tile form with persistent workgroups); never answered */
   DUA_CONV3_V2_4 = 6,        /* conv3d_k3_v2_kernel<T, 4>: 4x8x8 tiles, slab form */
   DUA_CONV3_V2_4_HALF = 7,   /* ... <f16, 4, 2, true>: half-empty last Cin chunk */
   DUA_CONV3_V2_4_KD = 8,     /* ... <T, 4, 2, false, true>: kd-plane form (split-K launches) */
@@ -131,15 +131,15 @@ typedef struct {
   int lds_limit;             /* the dynamic-LDS limit dua_prepare() registers for that kernel */
   long workspace_needed;     /* bytes the split this policy wants for d needs (0: it wants none); the launch splits when
                                 workspace_bytes covers it.  Never more than dua_conv3d_k3_workspace(d) under the policies plans
-                                run with (0, 6, 7, 8, 9). */
+                                run with (0, 6, 7). */
 } dua_conv3_form;
 int dua_conv3d_k3_form(const dua_conv3_desc* d, int fused, long workspace_bytes, int cus, dua_conv3_form* out);
 
 enum {
   DUA_DECONV_ONE_TAP = 0,    /* deconv_k2s2_kernel: 256 voxels x one tap per workgroup */
   DUA_DECONV_KSPLIT = 1,     /* deconv_k2s2_ksplit_kernel: Cin chunks split over the waves */
-  DUA_DECONV_ALLTAPS_128 = 2, /* deconv_k2s2_alltaps_kernel<T, 1>: 128-voxel tiles */
-  DUA_DECONV_ALLTAPS_256 = 3 /* deconv_k2s2_alltaps_kernel<T, 2>: 256-voxel tiles (policy 6) */
+  DUA_DECONV_ALLTAPS_128 = 2 /* deconv_k2s2_alltaps_kernel<T>: 128-voxel tiles */
+  /* 3: retired (256-voxel all-taps tiles); never answered */
 };
 typedef struct {
   int kernel;                /* DUA_DECONV_* */

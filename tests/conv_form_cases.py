@@ -7,8 +7,8 @@ FEATURES = (64, 64, 128, 256, 512, 64)
 CLASSES = 16
 F32, F16 = 0, 1                           # DUA_F32, DUA_F16
 IN_BLOCKED, OUT_BLOCKED = 1, 2
-POLICIES = (0, 2, 3, 6, 7, 8, 9)
-PLAN_POLICIES = (0, 6, 7, 8, 9)           # what plans run with (ops.CONV_POLICY of a whole-loop A/B)
+POLICIES = (0, 2, 3, 6, 7)
+PLAN_POLICIES = (0, 6, 7)                 # what plans run with (ops.CONV_POLICY of a whole-loop A/B)
 FIELDS = ("dtype", "N", "D", "H", "W", "Cin", "Cin_stride", "Cin_off", "Cout", "Cout_stride", "Cout_off", "tap_channel_plus1",
           "background", "layout", "policy")
 

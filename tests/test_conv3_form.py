@@ -35,7 +35,7 @@ def _dform(nv, d, fused=0, dims=(0, 0, 0)):
 
 def _kind(nv, f):
     """dua_conv3d_k3_kernel_kind as a projection of the form"""
-    return 1 if f.kernel == nv.CONV3_FIRST else 2 if f.kernel in (nv.CONV3_WIDE, nv.CONV3_WIDE_BWD, nv.CONV3_WIDE_PT) else 0
+    return 1 if f.kernel == nv.CONV3_FIRST else 2 if f.kernel in (nv.CONV3_WIDE, nv.CONV3_WIDE_BWD) else 0
 
 
 def _workspace(nv, d):
@@ -109,7 +109,7 @@ def test_tile_depth_and_kd_plane_regimes(nv):
     assert (f.kernel, f.tile_depth, f.ksplit) == (nv.CONV3_V2_2, 2, 1)
     assert f.grid_x * f.grid_y * f.grid_z == 384
     assert kernel("16x16x32 48->48", 0).kernel == nv.CONV3_V2_4_HALF
-    for policy, want in ((0, nv.CONV3_WIDE), (8, nv.CONV3_WIDE_PT), (9, nv.CONV3_WIDE_PT), (7, nv.CONV3_V2_4)):
+    for policy, want in ((0, nv.CONV3_WIDE), (7, nv.CONV3_V2_4)):
         f = kernel("64^3 64->64", policy)
         assert f.kernel == want and f.tile_depth == (4 if policy == 7 else 8), policy
     assert kernel("tap 16 + 1", 0).kernel == nv.CONV3_FIRST
@@ -154,7 +154,7 @@ def test_unknown_policies_are_rejected_by_the_query_and_the_launcher(nv):
     L = nv.lib()
     one = C.c_void_p(16)
     base = K.desc(K.F16, 1, (8, 8, 8), 16, 64)
-    for policy in (5, 10, 1, 4, 255, 512, 1 << 16, 2 | 1024):
+    for policy in (5, 8, 9, 10, 1, 4, 255, 512, 1 << 16, 2 | 1024):         # 8, 9: the retired persistent wide forms
         d = K.with_fields(base, policy=policy)
         assert _form(nv, d)[0] == nv.ERR_ARG, policy
         desc = nv.Conv3Desc(*d)
@@ -194,7 +194,7 @@ def test_rejections(nv):
     # backward sums ride on the shipped wide form only
     sup = L.dua_conv3d_k3_dgrad_reduce_supported
     assert sup(C.byref(nv.Conv3Desc(*wide))) == 1
-    for d in (small, K.with_fields(wide, policy=7), K.with_fields(wide, policy=8), K.with_fields(wide, dtype=K.F32),
+    for d in (small, K.with_fields(wide, policy=7), K.with_fields(wide, dtype=K.F32),
               K.with_fields(wide, layout=K.IN_BLOCKED), K.with_fields(wide, background=1)):
         assert sup(C.byref(nv.Conv3Desc(*d))) == 0, d
     # the transposed convolution: never reads blocks, writes them from the all-taps kernel only
@@ -208,10 +208,10 @@ def test_rejections(nv):
 
 
 def test_deconv_forms(nv):
-    """all-taps tiles of 128 voxels (256 under policy 6 where they fit), Cin chunks over the waves from 256 channels, one tap
-    per workgroup otherwise; grids and LDS within the registered limits"""
+    """all-taps tiles of 128 voxels under both policies, Cin chunks over the waves from 256 channels (not under policy 6), one
+    tap per workgroup otherwise; grids and LDS within the registered limits"""
     cases = [(K.desc(K.F16, 1, (48, 48, 48), 64, 64), 0, nv.DECONV_ALLTAPS_128, (864, 1, 1)),
-             (K.desc(K.F16, 1, (48, 48, 48), 64, 64), 6, nv.DECONV_ALLTAPS_256, (432, 1, 1)),
+             (K.desc(K.F16, 1, (48, 48, 48), 64, 64), 6, nv.DECONV_ALLTAPS_128, (864, 1, 1)),
              (K.desc(K.F16, 2, (12, 12, 12), 256, 128), 0, nv.DECONV_KSPLIT, (27, 16, 2)),
              (K.desc(K.F16, 2, (12, 12, 12), 256, 128), 6, nv.DECONV_ONE_TAP, (7, 16, 2)),
              (K.desc(K.F32, 1, (8, 8, 8), 512, 256), 0, nv.DECONV_ONE_TAP, (2, 32, 1)),

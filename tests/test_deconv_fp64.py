@@ -1,5 +1,5 @@
-"""dua_deconv_k2s2_fwd / dua_deconv_k2s2_pad_fwd in each of their four forms -- one tap per workgroup, k-split, all taps with 128-
-and 256-voxel tiles -- against an fp64 reference on the operands the kernel read, per element, within the bound derived from the
+"""dua_deconv_k2s2_fwd / dua_deconv_k2s2_pad_fwd in each of their three forms -- one tap per workgroup, k-split, all taps (128-voxel
+tiles) -- against an fp64 reference on the operands the kernel read, per element, within the bound derived from the
 form's arithmetic (tests/fp64ref.py: deconv_fwd_chain, bound; the CPU controls are in test_deconv_materialize_fp64ref.py).  fp16
 and fp32, with and without a fused producer transform (per-sample statistics rows and additive term, N = 2), with and without
 replicate-pad planes, channels-last and 16-channel-block output, channel slices inside wider buffers.  Every case asserts the form it
@@ -18,10 +18,10 @@ import fp64ref as R
 pytestmark = pytest.mark.gpu
 
 F16, F32 = torch.float16, torch.float32
-ONE_TAP, KSPLIT, ALL128, ALL256 = range(4)                 # dua_deconv_form.kernel
-FORM = {ONE_TAP: "one_tap", KSPLIT: "ksplit", ALL128: "alltaps", ALL256: "alltaps"}
-KIND = {ONE_TAP: 0, KSPLIT: 1, ALL128: 2, ALL256: 2}       # dua_deconv_k2s2_kernel_kind
-NAME = {ONE_TAP: "one-tap", KSPLIT: "k-split", ALL128: "all-taps 128", ALL256: "all-taps 256"}
+ONE_TAP, KSPLIT, ALL128 = range(3)                         # dua_deconv_form.kernel
+FORM = {ONE_TAP: "one_tap", KSPLIT: "ksplit", ALL128: "alltaps"}
+KIND = {ONE_TAP: 0, KSPLIT: 1, ALL128: 2}                  # dua_deconv_k2s2_kernel_kind
+NAME = {ONE_TAP: "one-tap", KSPLIT: "k-split", ALL128: "all-taps 128"}
 CIN_OFF, COUT_OFF, SENTINEL = 8, 16, 9.0
 
 
@@ -32,7 +32,7 @@ def _ops():
 
 @pytest.fixture
 def deconv_policy(request):
-    """ops.CONV_POLICY for one case (6 = the 256-voxel all-taps tiles where they fit), restored afterwards."""
+    """ops.CONV_POLICY for one case, restored afterwards."""
     ops = _ops()
     ops.CONV_POLICY = request.param
     yield request.param
@@ -46,7 +46,7 @@ def _case(kernel, dtype, N, cin, cout, dims, fused=False, pad=(0, 0, 0), blocked
         tag += f" pad{''.join(map(str, pad))}"
     if blocked:
         tag += " blocked"
-    return pytest.param(6 if kernel == ALL256 else 0, kernel, dtype, N, cin, cout, dims, fused, pad, blocked, id=tag.replace(" ", "-"))
+    return pytest.param(0, kernel, dtype, N, cin, cout, dims, fused, pad, blocked, id=tag.replace(" ", "-"))
 
 
 def _both(kernel, dtype, cin, cout, dims, N=1):
@@ -74,13 +74,6 @@ CASES += [_case(KSPLIT, F16, 2, 272, 72, (2, 3, 3), fused=True, pad=p) for p in 
 CASES += [_case(KSPLIT, F32, 2, 136, 64, (3, 4, 5), fused=True, pad=p) for p in PADS]
 # all taps: 4 chunks, the limit (fp16 128 channels; fp32 64 channels is the 64 -> 64 case above)
 CASES += _both(ALL128, F16, 128, 32, (32, 32, 32))
-# all taps, 256-voxel tiles (policy 6): the two all-taps shapes again in fp16; fp32 fits that form's LDS up to 32 input channels
-CASES += _both(ALL256, F16, 64, 64, (32, 32, 32)) + _both(ALL256, F16, 40, 72, (30, 34, 36))
-CASES += _both(ALL256, F32, 32, 64, (32, 32, 32)) + _both(ALL256, F32, 24, 72, (30, 34, 36))
-CASES += [_case(ALL256, F16, 2, 40, 72, (30, 34, 36), fused=True, pad=p) for p in PADS]
-CASES += [_case(ALL256, F32, 2, 24, 72, (30, 34, 36), fused=True, pad=(1, 1, 1))]
-CASES += [_case(ALL256, F16, 1, 64, 64, (32, 32, 32), blocked=True), _case(ALL256, F16, 2, 40, 72, (30, 34, 36), fused=True, blocked=True),
-          _case(ALL256, F32, 2, 24, 72, (30, 34, 36), fused=True, blocked=True)]
 
 
 def _producer(x, cin, dtype, g):
@@ -168,10 +161,9 @@ def test_deconv_forward_within_fp64_bound(deconv_policy, kernel, dtype, N, cin, 
 
 def test_every_form_appears_in_both_types_fused_padded_and_blocked():
     seen = {(p.values[1], p.values[2], p.values[7], any(p.values[8]), p.values[9]) for p in CASES}
-    for k in (ONE_TAP, KSPLIT, ALL128, ALL256):
+    for k in (ONE_TAP, KSPLIT, ALL128):
         for dt in (F16, F32):
             assert (k, dt, False, False, False) in seen and (k, dt, True, False, False) in seen, (k, dt)
             assert (k, dt, True, True, False) in seen, (k, dt)
-    for k in (ALL128, ALL256):
-        for dt in (F16, F32):
-            assert any(s[0] == k and s[1] == dt and s[4] for s in seen), (k, dt)
+    for dt in (F16, F32):
+        assert any(s[0] == ALL128 and s[1] == dt and s[4] for s in seen), dt

@@ -57,7 +57,7 @@ SCALE = 2.0 ** 22
 CASES = {"even-64": dict(N=1, dims=(64, 64, 64), t=(417,), fold_min_tiles=1, seed=11),
          "odd-b2": dict(N=2, dims=(33, 35, 40), t=(37, 811), fold_min_tiles=None, seed=12)}
 NEAR_CAP, NEAR_MIN_ROW = 1e-4, 10 ** 4
-DECONV_FORM = {0: "one_tap", 1: "ksplit", 2: "alltaps", 3: "alltaps"}
+DECONV_FORM = {0: "one_tap", 1: "ksplit", 2: "alltaps"}
 
 
 def _net(seed):

@@ -8,7 +8,7 @@ the ordered lists of (kernel name with template arguments, grid, workgroup size,
   python3 tools/conv_form_trace.py compare <dirA> <dirB> [summary file]
 
 Cases (tests/conv_form_cases.py): every convolution descriptor of the pinned plans and the kernel-test regimes up to 64^3
-x policy {0, 2, 3, 6, 7, 8, 9} x fused x workspace {none, what the form asks for, far more} x background, the 96^3 first-layer
+x policy {0, 2, 3, 6, 7} x fused x workspace {none, what the form asks for, far more} x background, the 96^3 first-layer
 and wide launches once each, the backward-sums launch of every descriptor that has one, and the plans' transposed convolutions
 x policy {0, 6} x fused.  Workspace sizes always come from THIS tree's form query, so both builds are handed the same calls;
 `lib:<path>` only replaces the library whose launchers run (as in tools/bench_conv.py).  `run` also prints one line per call
