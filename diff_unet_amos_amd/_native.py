@@ -305,6 +305,13 @@ _SIGS = {
                                             _P]),
     "dua_seg_loss_terms_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P] + [C.c_int] * 6 +
                                 [_P, C.c_int, _P]),
+    "dua_seg_loss_boundary_scratch_bytes": (C.c_long, [C.c_int, C.c_int, C.c_long]),
+    "dua_seg_loss_boundary_reduce": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P, _P, _P, C.c_long,
+                                               _P]),
+    "dua_seg_loss_boundary_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P, C.c_float, C.c_float,
+                                             C.c_float, _P, _P, _P, C.c_int, _P]),
+    "dua_seg_loss_terms_boundary_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P] +
+                                         [C.c_int] * 6 + [_P, _P, _P, C.c_int, _P]),
     "dua_temb_train_fwd": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(TembBlocks), _P, _P, _P]),
     "dua_temb_train_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(TembBlocks), _P, _P, _P, _P, _P, _P, _P, _P]),
     "dua_grads_nonfinite": (C.c_int, [C.POINTER(AdamWList), _P, _P]),
@@ -382,6 +389,8 @@ _SIGS = {
     "dua_blend_finish_labelmap": (C.c_int, [_P] + [C.c_int] * 4 + [_P] * 4 + [C.c_int] * 9 + [_P] * 6 + [C.c_int] * 3 + [C.c_float] +
                                   [_P] * 4),
     "dua_suf_accumulate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "dua_sdf_scratch_bytes": (C.c_long, [C.c_int] * 5),
+    "dua_sdf_maps": (C.c_int, [C.c_int] * 5 + [_P, C.c_float, _P, _P, _P, C.c_long, _P]),
 }
 
 _lib = None

@@ -87,12 +87,42 @@ __global__ __launch_bounds__(256) void seg_loss_reduce_kernel(const T* __restric
   }
 }
 
-template <typename T>
+// The voxel loop of the gradient kernel.  WITH_B: the boundary term's part (include/dua_hip.h, dua_seg_loss_boundary_*) rides in
+// the same pass, gb * ((phi * s (1 - s)) * a_bnd) with phi fp32 [N][C][V] like the labels and a_bnd = (float)(1 / M), added in
+// fp32 to g * [named terms] before the ONE rounding to T -- the arithmetic of lt_grad_rows<.., true> in seg_loss_terms.hip.
+template <typename T, bool WITH_B>
+__device__ __forceinline__ void seg_loss_grad_rows(const T* __restrict__ p, int p_stride, const float* __restrict__ y, int C,
+                                                   long V, int n, const float* k0, const float* k1, float g, float a_mse,
+                                                   float a_bce, T* __restrict__ dp, int dp_stride,
+                                                   const float* __restrict__ phi, float gb, float a_bnd) {
+  for (long v = blockIdx.x * 256L + threadIdx.x; v < V; v += (long)gridDim.x * 256) {
+    const T* pr = p + ((long)n * V + v) * p_stride;
+    T* dr = dp + ((long)n * V + v) * dp_stride;
+    for (int c = 0; c < C; ++c) {
+      const float pv = (float)pr[c];
+      const float yv = y[((long)n * C + c) * V + v];
+      const float s = 1.f / (1.f + __expf(-pv));
+      const float ds = s * (1.f - s), d = s - yv;
+      if constexpr (WITH_B)
+        dr[c] = (T)(g * (a_mse * d * ds + a_bce * d + (k0[c] * yv + k1[c]) * ds) +
+                    gb * (phi[((long)n * C + c) * V + v] * ds * a_bnd));
+      else
+        dr[c] = (T)(g * (a_mse * d * ds + a_bce * d + (k0[c] * yv + k1[c]) * ds));
+    }
+  }
+}
+
+// BND: the form dua_seg_loss_boundary_grad launches, gb = *bscale.  gb == 0 (a schedule that starts at alpha = 0) runs the loop
+// without the term and does not read phi: there the compiler rounds g * (..) straight to fp16 (v_fma_mixlo_f16), and alpha = 0
+// must give the bits of the step without a boundary weight.  BND = false is the kernel as it was.
+template <typename T, bool BND = false>
 __global__ __launch_bounds__(256) void seg_loss_grad_kernel(const T* __restrict__ p, int p_stride,
                                                             const float* __restrict__ y, int C, long V,
                                                             const double* __restrict__ sums, int N,
                                                             const float* __restrict__ gscale, float w_mse, float w_bce,
-                                                            float w_dice, T* __restrict__ dp, int dp_stride) {
+                                                            float w_dice, T* __restrict__ dp, int dp_stride,
+                                                            const float* __restrict__ phi = nullptr,
+                                                            const float* __restrict__ bscale = nullptr, float a_bnd = 0.f) {
   __shared__ float k0[LOSS_MAXC], k1[LOSS_MAXC];     // dice' = k0 * y + k1
   const int n = blockIdx.y;
   const float g = gscale ? *gscale : 1.f;
@@ -105,17 +135,14 @@ __global__ __launch_bounds__(256) void seg_loss_grad_kernel(const T* __restrict_
     k1[threadIdx.x] = (float)(Ie / (De * De)) * invNC;
   }
   __syncthreads();
-  for (long v = blockIdx.x * 256L + threadIdx.x; v < V; v += (long)gridDim.x * 256) {
-    const T* pr = p + ((long)n * V + v) * p_stride;
-    T* dr = dp + ((long)n * V + v) * dp_stride;
-    for (int c = 0; c < C; ++c) {
-      const float pv = (float)pr[c];
-      const float yv = y[((long)n * C + c) * V + v];
-      const float s = 1.f / (1.f + __expf(-pv));
-      const float ds = s * (1.f - s), d = s - yv;
-      dr[c] = (T)(g * (a_mse * d * ds + a_bce * d + (k0[c] * yv + k1[c]) * ds));
+  if constexpr (BND) {
+    const float gb = *bscale;
+    if (gb != 0.f) {                                 // uniform
+      seg_loss_grad_rows<T, true>(p, p_stride, y, C, V, n, k0, k1, g, a_mse, a_bce, dp, dp_stride, phi, gb, a_bnd);
+      return;
     }
   }
+  seg_loss_grad_rows<T, false>(p, p_stride, y, C, V, n, k0, k1, g, a_mse, a_bce, dp, dp_stride, nullptr, 0.f, 0.f);
 }
 
 }  // namespace dua
@@ -137,6 +164,26 @@ int dua_seg_loss_reduce(int dtype, int N, int C, long voxels, const void* logits
   return (int)hipGetLastError();
 }
 
+int dua_seg_loss_boundary_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                               const double* sums, const float* gscale, float w_mse, float w_bce, float w_dice, const float* phi,
+                               const float* bscale, void* dlogits, int dlogits_stride, void* stream) {
+  if (!logits || !labels || !sums || !phi || !bscale || !dlogits || N <= 0 || N > 65535 || C <= 0 || C > dua::LOSS_MAXC ||
+      voxels <= 0 || logits_stride < C || dlogits_stride < C) return DUA_ERR_ARG;
+  long b = (voxels + 255) / 256;
+  dim3 grid((unsigned)(b > 4096 ? 4096 : b), N);
+  const float a_bnd = (float)(1.0 / ((double)N * (double)C * (double)voxels));
+  if (dtype == DUA_F16)
+    hipLaunchKernelGGL((dua::seg_loss_grad_kernel<dua::f16, true>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const dua::f16*)logits, logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice,
+                       (dua::f16*)dlogits, dlogits_stride, phi, bscale, a_bnd);
+  else if (dtype == DUA_F32)
+    hipLaunchKernelGGL((dua::seg_loss_grad_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)logits,
+                       logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice, (float*)dlogits, dlogits_stride,
+                       phi, bscale, a_bnd);
+  else return DUA_ERR_ARG;
+  return (int)hipGetLastError();
+}
+
 int dua_seg_loss_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
                       const double* sums, const float* gscale, float w_mse, float w_bce, float w_dice, void* dlogits,
                       int dlogits_stride, void* stream) {
@@ -146,10 +193,12 @@ int dua_seg_loss_grad(int dtype, int N, int C, long voxels, const void* logits, 
   dim3 grid((unsigned)(b > 4096 ? 4096 : b), N);
   if (dtype == DUA_F16)
     hipLaunchKernelGGL(dua::seg_loss_grad_kernel<dua::f16>, grid, dim3(256), 0, (hipStream_t)stream, (const dua::f16*)logits,
-                       logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice, (dua::f16*)dlogits, dlogits_stride);
+                       logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice, (dua::f16*)dlogits, dlogits_stride,
+                       (const float*)nullptr, (const float*)nullptr, 0.f);
   else if (dtype == DUA_F32)
     hipLaunchKernelGGL(dua::seg_loss_grad_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)logits,
-                       logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice, (float*)dlogits, dlogits_stride);
+                       logits_stride, labels, C, voxels, sums, N, gscale, w_mse, w_bce, w_dice, (float*)dlogits, dlogits_stride,
+                       (const float*)nullptr, (const float*)nullptr, 0.f);
   else return DUA_ERR_ARG;
   return (int)hipGetLastError();
 }

@@ -243,22 +243,14 @@ __global__ __launch_bounds__(64) void seg_loss_terms_finish_kernel(int N, int C,
   dcomb[0] = (float)dc;
 }
 
-template <typename T, int NG>
-__global__ __launch_bounds__(256) void seg_loss_terms_grad_kernel(const T* __restrict__ p, int p_stride,
-                                                                  const float* __restrict__ y, int C, long V,
-                                                                  const float* __restrict__ consts,
-                                                                  const float* __restrict__ gscale, float a_mse, float a_bce,
-                                                                  float a_ce, int use_mse, int use_bce, int use_k, int use_ce,
-                                                                  T* __restrict__ dp, int dp_stride, int vec_in, int vec_out) {
-  __shared__ float k0[LT_MAXC], k1[LT_MAXC];
-  const int n = blockIdx.y;
-  const float gs = gscale ? *gscale : 1.f;
-  if (threadIdx.x < LT_MAXC) {
-    const bool have = use_k && threadIdx.x < C;
-    k0[threadIdx.x] = have ? consts[((long)n * C + threadIdx.x) * 2] : 0.f;
-    k1[threadIdx.x] = have ? consts[((long)n * C + threadIdx.x) * 2 + 1] : 0.f;
-  }
-  __syncthreads();
+// The voxel loop of the gradient kernel.  WITH_B: the boundary term's part rides in the same pass, gb * phi * s (1 - s) * a_bnd
+// (phi fp32 [N][C][V] like the labels), added in fp32 to gs * [named terms] before the ONE rounding to T.
+template <typename T, int NG, bool WITH_B>
+__device__ __forceinline__ void lt_grad_rows(const T* __restrict__ p, int p_stride, const float* __restrict__ y, int C, long V,
+                                             int n, const float* k0, const float* k1, float gs, float a_mse, float a_bce,
+                                             float a_ce, int use_mse, int use_bce, int use_k, int use_ce, T* __restrict__ dp,
+                                             int dp_stride, int vec_in, int vec_out, const float* __restrict__ phi, float gb,
+                                             float a_bnd) {
   for (long v = blockIdx.x * 256L + threadIdx.x; v < V; v += (long)gridDim.x * 256) {
     const T* pr = p + ((long)n * V + v) * p_stride;
     const float* yr = y + (long)n * C * V + v;
@@ -294,6 +286,8 @@ __global__ __launch_bounds__(256) void seg_loss_terms_grad_kernel(const T* __res
       const int c0 = 8 * g;
       if (c0 < C) {
         float o[8];
+        [[maybe_unused]] float fv[8];
+        if constexpr (WITH_B) lt_labels8(phi + ((long)n * C + c0) * V + v, V, min(8, C - c0), fv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float x = pv[g][e], t = yv[g][e];
@@ -305,6 +299,7 @@ __global__ __launch_bounds__(256) void seg_loss_terms_grad_kernel(const T* __res
           if (use_k) acc += (k0[c0 + e] * t + k1[c0 + e]) * ds;          // k0, k1 hold LT_MAXC entries, 0 past C
           if (use_ce) acc += a_ce * (rl * __expf(x - m) - t);
           o[e] = gs * acc;
+          if constexpr (WITH_B) o[e] += gb * (fv[e] * ds * a_bnd);
         }
         if constexpr (sizeof(T) == 2) {
           if (vec_out) {
@@ -320,6 +315,85 @@ __global__ __launch_bounds__(256) void seg_loss_terms_grad_kernel(const T* __res
       }
     }
   }
+}
+
+// BND: the form dua_seg_loss_terms_boundary_grad launches, gb = *bscale.  gb == 0 (a schedule that starts at alpha = 0) runs the
+// loop without the term and does not read phi: there the compiler may round gs * acc straight to fp16 (v_fma_mixlo_f16, which it
+// does for one element of eight), and alpha = 0 must give the bits of the step without a boundary weight.  BND = false is the
+// kernel as it was.
+template <typename T, int NG, bool BND = false>
+__global__ __launch_bounds__(256) void seg_loss_terms_grad_kernel(const T* __restrict__ p, int p_stride,
+                                                                  const float* __restrict__ y, int C, long V,
+                                                                  const float* __restrict__ consts,
+                                                                  const float* __restrict__ gscale, float a_mse, float a_bce,
+                                                                  float a_ce, int use_mse, int use_bce, int use_k, int use_ce,
+                                                                  T* __restrict__ dp, int dp_stride, int vec_in, int vec_out,
+                                                                  const float* __restrict__ phi = nullptr,
+                                                                  const float* __restrict__ bscale = nullptr, float a_bnd = 0.f) {
+  __shared__ float k0[LT_MAXC], k1[LT_MAXC];
+  const int n = blockIdx.y;
+  const float gs = gscale ? *gscale : 1.f;
+  if (threadIdx.x < LT_MAXC) {
+    const bool have = use_k && threadIdx.x < C;
+    k0[threadIdx.x] = have ? consts[((long)n * C + threadIdx.x) * 2] : 0.f;
+    k1[threadIdx.x] = have ? consts[((long)n * C + threadIdx.x) * 2 + 1] : 0.f;
+  }
+  __syncthreads();
+  if constexpr (BND) {
+    const float gb = *bscale;
+    if (gb != 0.f) {                                       // uniform
+      lt_grad_rows<T, NG, true>(p, p_stride, y, C, V, n, k0, k1, gs, a_mse, a_bce, a_ce, use_mse, use_bce, use_k, use_ce, dp,
+                                dp_stride, vec_in, vec_out, phi, gb, a_bnd);
+      return;
+    }
+  }
+  lt_grad_rows<T, NG, false>(p, p_stride, y, C, V, n, k0, k1, gs, a_mse, a_bce, a_ce, use_mse, use_bce, use_k, use_ce, dp,
+                             dp_stride, vec_in, vec_out, nullptr, 0.f, 0.f);
+}
+
+// The boundary term's sum, sum_{c,v} sigmoid(p) phi, as a pass of its own (the named reduce above keeps its code): a thread owns
+// a voxel and walks its row like the reduce does, adds s * phi in fp32, and the workgroup WRITES one fp64 partial.
+// partials: fp64 [N][gridDim.x].
+template <typename T>
+__global__ __launch_bounds__(256) void seg_loss_boundary_reduce_kernel(const T* __restrict__ p, int p_stride,
+                                                                       const float* __restrict__ phi, int C, long V,
+                                                                       double* __restrict__ partials, int vec) {
+  __shared__ float red[4];
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float acc = 0.f;
+  for (long v = blockIdx.x * 256L + threadIdx.x; v < V; v += (long)gridDim.x * 256) {
+    const T* pr = p + ((long)n * V + v) * p_stride;
+    const float* fr = phi + (long)n * C * V + v;
+    for (int c0 = 0; c0 < C; c0 += 8) {
+      const int nch = min(8, C - c0);
+      float pv[8], fv[8];
+      lt_load8(pr + c0, vec != 0, nch, pv);
+      lt_labels8(fr + (long)c0 * V, V, nch, fv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc += (1.f / (1.f + __expf(-pv[e]))) * fv[e];
+    }
+  }
+  acc = lt_wave_sum(acc);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[(long)n * gridDim.x + blockIdx.x] = (((double)red[0] + (double)red[1]) + (double)red[2]) + (double)red[3];
+}
+
+// One wave: lane j adds the partials j, j + 64, .. in that order, then the xor tree -- a fixed order.  B = sum / (N C V);
+// bterm[0] = B and loss[0] (holding L_named, as dua_seg_loss_terms_finish left it) becomes L_named + alpha B, formed in fp64
+// and rounded once.  alpha = 0 leaves loss[0] as it is, whatever B is.
+__global__ __launch_bounds__(64) void seg_loss_boundary_finish_kernel(const double* __restrict__ partials, long rows, double M,
+                                                                      const float* __restrict__ alpha, float* loss,
+                                                                      float* __restrict__ bterm) {
+  double acc = 0.0;
+  for (long r = threadIdx.x; r < rows; r += 64) acc += partials[r];
+  acc = lt_wave_sum(acc);
+  if (threadIdx.x != 0) return;
+  const double B = acc / M;
+  const float a = alpha[0];
+  bterm[0] = (float)B;
+  if (a != 0.f) loss[0] = (float)((double)loss[0] + (double)a * B);      // 0 * (an inf or NaN B) would turn L_named into NaN
 }
 
 inline bool lt_dims_ok(int N, int C, long voxels) {
@@ -380,9 +454,14 @@ int dua_seg_loss_terms_finish(int N, int C, long voxels, int use_mse, int use_bc
   return (int)hipGetLastError();
 }
 
-int dua_seg_loss_terms_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
-                            const float* consts, const float* gscale, int use_mse, int use_bce, int use_dice, int use_ce,
-                            int use_dice_ce, int use_gdice, void* dlogits, int dlogits_stride, void* stream) {
+}  // extern "C"
+
+// dua_seg_loss_terms_grad (phi == NULL: a term must be selected) and dua_seg_loss_terms_boundary_grad (phi, bscale: the named part may
+// be empty)
+static int lt_grad_launch(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                          const float* consts, const float* gscale, int use_mse, int use_bce, int use_dice, int use_ce,
+                          int use_dice_ce, int use_gdice, const float* phi, const float* bscale, void* dlogits,
+                          int dlogits_stride, void* stream) {
   const int flags[6] = {use_mse, use_bce, use_dice, use_ce, use_dice_ce, use_gdice};
   int any = 0;
   for (int f : flags) {
@@ -390,24 +469,75 @@ int dua_seg_loss_terms_grad(int dtype, int N, int C, long voxels, const void* lo
     any |= f;
   }
   const int use_k = use_dice || use_dice_ce || use_gdice, nce = use_ce + use_dice_ce;
-  if (!logits || !labels || !dlogits || !dua::lt_dims_ok(N, C, voxels) || logits_stride < C || dlogits_stride < C || !any ||
-      (use_k && !consts) || (dtype != DUA_F16 && dtype != DUA_F32))
+  if (!logits || !labels || !dlogits || !dua::lt_dims_ok(N, C, voxels) || logits_stride < C || dlogits_stride < C ||
+      (!any && !phi) || (use_k && !consts) || (dtype != DUA_F16 && dtype != DUA_F32))
     return DUA_ERR_ARG;
   const double M = (double)N * (double)C * (double)voxels;
   const float a_mse = (float)(2.0 / M), a_bce = (float)(1.0 / M), a_ce = (float)((double)nce / ((double)N * (double)voxels));
+  const float a_bnd = (float)(1.0 / M);
   long b = (voxels + 255) / 256;
   const dim3 grid((unsigned)(b > dua::LT_GRAD_BLOCKS ? dua::LT_GRAD_BLOCKS : b), N);
   const int f16v = dtype == DUA_F16 && C % 8 == 0;
   const int vec_in = f16v && logits_stride % 8 == 0 && ((size_t)logits & 15) == 0;
   const int vec_out = f16v && dlogits_stride % 8 == 0 && ((size_t)dlogits & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
-#define LT_GRAD(T, NG)                                                                                                        \
-  hipLaunchKernelGGL((dua::seg_loss_terms_grad_kernel<T, NG>), grid, dim3(256), 0, s, (const T*)logits, logits_stride, labels, C, \
-                     voxels, consts, gscale, a_mse, a_bce, a_ce, use_mse, use_bce, use_k, nce != 0, (T*)dlogits,                  \
-                     dlogits_stride, vec_in, vec_out)
+#define LT_GRAD(T, NG)                                                                                                          \
+  do {                                                                                                                          \
+    if (phi)                                                                                                                    \
+      hipLaunchKernelGGL((dua::seg_loss_terms_grad_kernel<T, NG, true>), grid, dim3(256), 0, s, (const T*)logits, logits_stride, \
+                         labels, C, voxels, consts, gscale, a_mse, a_bce, a_ce, use_mse, use_bce, use_k, nce != 0, (T*)dlogits, \
+                         dlogits_stride, vec_in, vec_out, phi, bscale, a_bnd);                                                  \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((dua::seg_loss_terms_grad_kernel<T, NG>), grid, dim3(256), 0, s, (const T*)logits, logits_stride,      \
+                         labels, C, voxels, consts, gscale, a_mse, a_bce, a_ce, use_mse, use_bce, use_k, nce != 0, (T*)dlogits, \
+                         dlogits_stride, vec_in, vec_out, (const float*)nullptr, (const float*)nullptr, 0.f);                   \
+  } while (0)
   if (dtype == DUA_F16) LT_BY_GROUPS(LT_GRAD, dua::f16); else LT_BY_GROUPS(LT_GRAD, float);
 #undef LT_GRAD
   return (int)hipGetLastError();
+}
+
+extern "C" {
+
+int dua_seg_loss_terms_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                            const float* consts, const float* gscale, int use_mse, int use_bce, int use_dice, int use_ce,
+                            int use_dice_ce, int use_gdice, void* dlogits, int dlogits_stride, void* stream) {
+  return lt_grad_launch(dtype, N, C, voxels, logits, logits_stride, labels, consts, gscale, use_mse, use_bce, use_dice, use_ce,
+                        use_dice_ce, use_gdice, nullptr, nullptr, dlogits, dlogits_stride, stream);
+}
+
+long dua_seg_loss_boundary_scratch_bytes(int N, int C, long voxels) {
+  if (!dua::lt_dims_ok(N, C, voxels)) return DUA_ERR_ARG;
+  return (long)N * dua::lt_reduce_blocks(voxels) * (long)sizeof(double);
+}
+
+int dua_seg_loss_boundary_reduce(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* phi,
+                                 const float* alpha, float* loss, float* bterm, void* scratch, long scratch_bytes,
+                                 void* stream) {
+  if (!logits || !phi || !alpha || !loss || !bterm || !scratch || !dua::lt_dims_ok(N, C, voxels) || logits_stride < C ||
+      (dtype != DUA_F16 && dtype != DUA_F32) || scratch_bytes < dua_seg_loss_boundary_scratch_bytes(N, C, voxels))
+    return DUA_ERR_ARG;
+  const int G = (int)dua::lt_reduce_blocks(voxels);
+  const int vec = dtype == DUA_F16 && C % 8 == 0 && logits_stride % 8 == 0 && ((size_t)logits & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == DUA_F16)
+    hipLaunchKernelGGL(dua::seg_loss_boundary_reduce_kernel<dua::f16>, dim3(G, N), dim3(256), 0, s, (const dua::f16*)logits,
+                       logits_stride, phi, C, voxels, (double*)scratch, vec);
+  else
+    hipLaunchKernelGGL(dua::seg_loss_boundary_reduce_kernel<float>, dim3(G, N), dim3(256), 0, s, (const float*)logits,
+                       logits_stride, phi, C, voxels, (double*)scratch, vec);
+  hipLaunchKernelGGL(dua::seg_loss_boundary_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)scratch, (long)N * G,
+                     (double)N * (double)C * (double)voxels, alpha, loss, bterm);
+  return (int)hipGetLastError();
+}
+
+int dua_seg_loss_terms_boundary_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride,
+                                     const float* labels, const float* consts, const float* gscale, int use_mse, int use_bce,
+                                     int use_dice, int use_ce, int use_dice_ce, int use_gdice, const float* phi,
+                                     const float* bscale, void* dlogits, int dlogits_stride, void* stream) {
+  if (!phi || !bscale) return DUA_ERR_ARG;
+  return lt_grad_launch(dtype, N, C, voxels, logits, logits_stride, labels, consts, gscale, use_mse, use_bce, use_dice, use_ce,
+                        use_dice_ce, use_gdice, phi, bscale, dlogits, dlogits_stride, stream);
 }
 
 #undef LT_BY_GROUPS

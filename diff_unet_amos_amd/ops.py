@@ -811,6 +811,87 @@ def seg_loss_grad(logits, labels, sums, gscale, names=LOSS_NAMES):
     return out
 
 
+def signed_distance_maps(labels, threshold=0.5, out=None, d2=None, scratch=None):
+    """Signed distance maps of a label batch for the boundary term (include/dua_hip.h, dua_sdf_maps; csrc/sdf.hip).
+    labels: fp32 [N, C, D, H, W] on the device, contiguous (one-hot, all-zero at a voxel, or soft).  Per volume (n, c) the mask is
+    ``labels > threshold`` (strict); returns ``phi`` fp32 [N, C, D, H, W]: sqrt(d2) outside the mask, 1 - sqrt(d2) inside, d2 the
+    exact squared Euclidean distance in voxels to the nearest voxel of the other set inside the patch, and 0 for a whole volume
+    whose mask is empty or full.  ``d2``: an int32 tensor of the labels' shape that receives the integer d2 (0 where phi is forced
+    to 0), or None.  ``out``: where to write phi; it MAY be ``labels`` itself (the labels are consumed by the first pass), and may
+    not overlap ``d2``.  ``scratch``: an int32 tensor of labels.numel() elements to reuse, else one torch.empty per call (it
+    needs no zeroing, so it does not come out of the ZeroArena).  1 <= D, H, W <= 512, N C <= 65535.  Exact, the same bits on
+    every run, no host read (capturable)."""
+    assert labels.is_cuda and labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 5
+    N, Cc, D, H, W = labels.shape
+    nbytes = int(nv.lib().dua_sdf_scratch_bytes(N, Cc, D, H, W))
+    assert nbytes > 0, "signed_distance_maps: extents 1..512, N C <= 65535"
+    phi = torch.empty_like(labels) if out is None else out
+    assert phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == labels.shape
+    if d2 is not None:
+        assert d2.is_cuda and d2.dtype == torch.int32 and d2.is_contiguous() and d2.shape == labels.shape
+        nb = labels.numel() * 4                      # d2, phi and labels are contiguous and of this many bytes each
+        assert all(abs(d2.data_ptr() - t.data_ptr()) >= nb for t in (phi, labels)), "d2 may overlap nothing"
+    if scratch is None:
+        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
+    assert scratch.is_cuda and scratch.dtype == torch.int32 and scratch.is_contiguous() and scratch.numel() * 4 >= nbytes
+    for t in (labels, phi, d2):
+        assert t is None or not (t.data_ptr() < scratch.data_ptr() + scratch.numel() * 4 and
+                                 scratch.data_ptr() < t.data_ptr() + t.numel() * 4), "scratch may overlap nothing"
+    assert phi.data_ptr() == labels.data_ptr() or abs(phi.data_ptr() - labels.data_ptr()) >= labels.numel() * 4, \
+        "out is the labels tensor itself or does not overlap it"
+    nv.check(nv.lib().dua_sdf_maps(N, Cc, D, H, W, nv.ptr(labels), float(threshold), nv.ptr(phi), nv.ptr(d2), nv.ptr(scratch),
+                                   scratch.numel() * 4, nv.stream_ptr()), "dua_sdf_maps")
+    return phi
+
+
+def _boundary_check(logits, labels, phi, scalar):
+    assert phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == labels.shape
+    assert scalar.is_cuda and scalar.dtype == torch.float32 and scalar.numel() == 1
+
+
+def seg_loss_boundary_reduce(logits, labels, names, combine, phi, alpha, bterm=None):
+    """seg_loss_reduce with the boundary term: L = L_named + alpha B, B = mean over (n, c, v) of sigmoid(logits) phi (``phi``:
+    signed_distance_maps(labels); ``alpha``: 0-dim fp32 DEVICE tensor, so a schedule changes it under a captured graph).  alpha
+    multiplies outside the combine.  The named part is seg_loss_reduce itself (the same kernels for the same names), then one
+    pass over logits and phi and a one-wave tail.  ``bterm``: a 0-dim fp32 device tensor that receives B, else a new one.
+    Returns (L, sums, dcomb, B)."""
+    L, sums, dcomb = seg_loss_reduce(logits, labels, names, combine)
+    N, Cc = labels.shape[:2]
+    V = labels.shape[2] * labels.shape[3] * labels.shape[4]
+    _boundary_check(logits, labels, phi, alpha)
+    B = torch.empty((), dtype=torch.float32, device=logits.device) if bterm is None else bterm
+    _boundary_check(logits, labels, phi, B)
+    nbytes = int(nv.lib().dua_seg_loss_boundary_scratch_bytes(N, Cc, V))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    nv.check(nv.lib().dua_seg_loss_boundary_reduce(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1],
+                                                   nv.ptr(phi), nv.ptr(alpha), nv.ptr(L), nv.ptr(B), nv.ptr(scratch), nbytes,
+                                                   nv.stream_ptr()), "dua_seg_loss_boundary_reduce")
+    return L, sums, dcomb, B
+
+
+def seg_loss_boundary_grad(logits, labels, sums, gscale, names, phi, bscale):
+    """dlogits = gscale * [named terms] + bscale * phi s (1 - s) / (N C V) in ONE pass: the sum is formed in fp32 and rounded once
+    to the logits' dtype, by the gradient kernel seg_loss_grad takes for ``names``.  ``sums``: seg_loss_boundary_reduce's; ``gscale`` = upstream x dcomb (0-dim device tensor or None = 1),
+    ``bscale`` = upstream x alpha (0-dim fp32 device tensor)."""
+    N, Cc = labels.shape[:2]
+    V = labels.shape[2] * labels.shape[3] * labels.shape[4]
+    out = zeros(tuple(logits.shape), logits.dtype, logits.device) if logits.shape[-1] > Cc else torch.empty_like(logits)
+    g = gscale.detach().float().reshape(1).contiguous() if gscale is not None else None
+    b = bscale.detach().float().reshape(1).contiguous()
+    _boundary_check(logits, labels, phi, b)
+    if any(n_ in EXT_LOSS_NAMES for n_ in names):
+        nv.check(nv.lib().dua_seg_loss_terms_boundary_grad(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1],
+                                                           nv.ptr(labels), nv.ptr(_terms_consts(sums, N, Cc)), nv.ptr(g),
+                                                           *_terms_use(names), nv.ptr(phi), nv.ptr(b), nv.ptr(out), out.shape[-1],
+                                                           nv.stream_ptr()), "dua_seg_loss_terms_boundary_grad")
+        return out
+    w = [1.0 if n_ in names else 0.0 for n_ in LOSS_NAMES]
+    nv.check(nv.lib().dua_seg_loss_boundary_grad(nv.dt_code(logits.dtype), N, Cc, V, nv.ptr(logits), logits.shape[-1],
+                                                 nv.ptr(labels), nv.ptr(sums), nv.ptr(g), w[0], w[1], w[2], nv.ptr(phi), nv.ptr(b),
+                                                 nv.ptr(out), out.shape[-1], nv.stream_ptr()), "dua_seg_loss_boundary_grad")
+    return out
+
+
 def materialize(raw, Cc, norm, out, out_off, emb=None, pooled=None, out_blocked=False):
     _cl_check(raw, "raw"); _cl_check(out, "out")
     N, D, H, W, rs = raw.shape

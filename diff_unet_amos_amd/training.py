@@ -396,18 +396,30 @@ class _SegLoss(torch.autograd.Function):
     derivative of the combine (1/count under "mean", 1/(1 + total) under "log")."""
 
     @staticmethod
-    def forward(ctx, logits, labels, names=("mse", "bce", "dice"), combine="sum"):
+    def forward(ctx, logits, labels, names=("mse", "bce", "dice"), combine="sum", boundary=None):
         from . import ops
-        L, sums, dcomb = ops.seg_loss_reduce(logits, labels, names, combine)
-        ctx.save_for_backward(logits, labels, sums, dcomb)
-        ctx.names = names
+        ctx.names, ctx.boundary = names, boundary is not None
+        if boundary is None:
+            L, sums, dcomb = ops.seg_loss_reduce(logits, labels, names, combine)
+            ctx.save_for_backward(logits, labels, sums, dcomb)
+            return L
+        # the boundary term (include/dua_hip.h, dua_seg_loss_boundary_*): L = L_named + alpha B with ``boundary`` = (phi, alpha)
+        # -- ops.signed_distance_maps(labels) and a 0-dim fp32 device tensor -- or (phi, alpha, bterm), bterm a 0-dim fp32
+        # device tensor that receives B.  alpha stays outside the combine: dcomb scales the named part of the gradient only.
+        phi, alpha = boundary[0], boundary[1]
+        L, sums, dcomb, _ = ops.seg_loss_boundary_reduce(logits, labels, names, combine, phi, alpha,
+                                                         boundary[2] if len(boundary) > 2 else None)
+        ctx.save_for_backward(logits, labels, sums, dcomb, phi, alpha)
         return L
 
     @staticmethod
     def backward(ctx, g):
         from . import ops
+        if ctx.boundary:
+            logits, labels, sums, dcomb, phi, alpha = ctx.saved_tensors
+            return ops.seg_loss_boundary_grad(logits, labels, sums, g * dcomb, ctx.names, phi, g * alpha), None, None, None, None
         logits, labels, sums, dcomb = ctx.saved_tensors
-        return ops.seg_loss_grad(logits, labels, sums, g * dcomb, ctx.names), None, None, None
+        return ops.seg_loss_grad(logits, labels, sums, g * dcomb, ctx.names), None, None, None, None
 
 
 def native_conv_denoise(net, image, x, step, dtype=torch.float16):
@@ -619,11 +631,16 @@ class NativeConvTrainer:
     (``self.ema``, parallel to ``self.params``; guided_diffusion/train_util.py:86-89, 216-218), updated only on steps that are
     taken.  On the library's optimizer both ride in the step's own launches (ops.grad_norm takes the place of the overflow
     check, ops.adamw_step clips and averages), so a captured step replays them; ``fused_optimizer=False`` runs them in torch
-    operators.  Both default to None: the step is then launch for launch what it was."""
+    operators.  Both default to None: the step is then launch for launch what it was.
+    ``boundary_weight``: alpha of L = L_named + alpha B, the boundary term of Kervadec et al. on signed distance maps of the
+    step's labels (mask: ``labels > boundary_threshold``), computed on the device inside the step -- and inside the captured
+    graph; include/dua_hip.h, dua_sdf_maps and dua_seg_loss_boundary_*.  alpha lives in a device scalar:
+    ``set_boundary_weight(a)`` changes it between steps (the authors raise it on a schedule) without a recapture, and
+    ``boundary_term()`` is the last step's B.  None (the default): no new buffer, no new launch."""
 
     def __init__(self, net, lr=2e-4, weight_decay=1e-4, losses="mse,bce,dice", loss_combine="sum",
                  dtype=torch.float16, init_scale=2.0 ** 12, overlap=True, graph=False, fused_optimizer=True,
-                 wgrad_overlap=True, max_grad_norm=None, ema_rate=None):
+                 wgrad_overlap=True, max_grad_norm=None, ema_rate=None, boundary_weight=None, boundary_threshold=0.5):
         import torch.distributed as dist
         self.net, self.dtype = net, dtype
         self.lr, self.weight_decay, self.init_scale = lr, weight_decay, init_scale
@@ -647,6 +664,12 @@ class NativeConvTrainer:
             raise ValueError(f"max_grad_norm must be positive (inf: measure only), got {max_grad_norm}")
         if ema_rate is not None and not 0.0 <= float(ema_rate) < 1.0:
             raise ValueError(f"ema_rate must be in [0, 1), got {ema_rate}")
+        self._bnd = None
+        if boundary_weight is not None:
+            dev = self.params[0].device
+            self._bnd = dict(alpha=torch.full((), self._boundary_alpha(boundary_weight), dtype=torch.float32, device=dev),
+                             term=torch.zeros((), dtype=torch.float32, device=dev), threshold=float(boundary_threshold),
+                             phi=None, scratch=None)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.ema_rate = None if ema_rate is None else float(ema_rate)
         self._param_names = [k for k, p in net.named_parameters() if p.requires_grad]
@@ -683,6 +706,42 @@ class NativeConvTrainer:
         # scratch buffers of ops exist before the capture and do not land in the graph's private memory pool)
         self.capture_stream = torch.cuda.Stream(device=dev) if (graph and dev.type == "cuda") else None
 
+    @staticmethod
+    def _boundary_alpha(a):
+        import math
+        a = float(a)
+        if not (math.isfinite(a) and a >= 0.0):
+            raise ValueError(f"boundary_weight must be finite and >= 0, got {a}")
+        return a
+
+    def set_boundary_weight(self, a):
+        """alpha of L = L_named + alpha B from the next step on: written into the device scalar the (captured) step reads."""
+        if self._bnd is None:
+            raise RuntimeError("set_boundary_weight() needs a trainer built with boundary_weight")
+        self._bnd["alpha"].fill_(self._boundary_alpha(a))
+
+    def boundary_term(self):
+        """The last step's B = mean of sigmoid(logits) phi, a 0-dim device tensor (no host read)."""
+        if self._bnd is None:
+            raise RuntimeError("boundary_term() needs a trainer built with boundary_weight")
+        return self._bnd["term"]
+
+    def _boundary_buffers(self, labels):
+        b = self._bnd
+        if b is not None and (b["phi"] is None or b["phi"].shape != labels.shape):
+            b["phi"] = torch.empty(tuple(labels.shape), dtype=torch.float32, device=labels.device)
+            b["scratch"] = torch.empty(labels.numel(), dtype=torch.int32, device=labels.device)
+
+    def _boundary(self, labels):
+        """(phi, alpha, bterm) for _SegLoss, phi from this step's labels; None without a boundary weight."""
+        if self._bnd is None:
+            return None
+        from . import ops
+        self._boundary_buffers(labels)
+        b = self._bnd
+        ops.signed_distance_maps(labels, b["threshold"], out=b["phi"], scratch=b["scratch"])
+        return b["phi"], b["alpha"], b["term"]
+
     def _allreduce(self):
         if not self.distributed or self.overlap:          # the DDP reducer already averaged them during backward
             return
@@ -700,7 +759,8 @@ class NativeConvTrainer:
             x_t = ops.q_sample_affine(g["labels"], 2.0, -1.0, g["noise"], g["qtab"], g["t"])      # q_sample(label * 2 - 1, t, noise)
             self.optimizer.zero_grad(set_to_none=True)
             with torch.enable_grad():
-                loss = _SegLoss.apply(self.module(g["images"], x_t, g["t"]), g["labels"], self.loss_names, self.loss_combine)
+                loss = _SegLoss.apply(self.module(g["images"], x_t, g["t"]), g["labels"], self.loss_names, self.loss_combine,
+                                      self._boundary(g["labels"]))
                 with _wgrad_side(self.wgrad_stream):
                     (loss * g["scale"]).backward()
         return loss.detach()
@@ -747,6 +807,7 @@ class NativeConvTrainer:
                        scale=torch.full((), self.init_scale if self.dtype == torch.float16 else 1.0, device=dev),
                        growth=torch.zeros((), dtype=torch.int32, device=dev), found_inf=torch.zeros((), device=dev),
                        found_flag=torch.zeros((), device=dev))
+        self._boundary_buffers(self._g["labels"])          # the maps and their scratch: allocated before the capture
         saved = [p.detach().clone() for p in self.params]
         # ... and the optimizer state as it is NOW: a checkpoint loaded before the first step (load_checkpoint ->
         # optimizer.load_state_dict) must survive the warm-up updates below
@@ -855,8 +916,8 @@ class NativeConvTrainer:
         if self.arena is not None:
             self.arena.reset()
         with (self.arena if self.arena is not None else contextlib.nullcontext()), torch.enable_grad():
-            loss = _SegLoss.apply(self.module(images, x_t, t), labels.float().contiguous(), self.loss_names,
-                                  self.loss_combine)
+            y = labels.float().contiguous()
+            loss = _SegLoss.apply(self.module(images, x_t, t), y, self.loss_names, self.loss_combine, self._boundary(y))
             amp = self._amp_state() if (self.dtype == torch.float16 and self.native_opt) else None
             with _wgrad_side(self.wgrad_stream):
                 (loss * (amp["scale"] if amp is not None else self.scale)).backward()

@@ -403,6 +403,42 @@ int dua_seg_loss_terms_grad(int dtype, int N, int C, long voxels, const void* lo
                             const float* consts, const float* gscale, int use_mse, int use_bce, int use_dice, int use_ce,
                             int use_dice_ce, int use_gdice, void* dlogits, int dlogits_stride, void* stream);
 
+/* The boundary term (Kervadec et al., "Boundary loss for highly unbalanced segmentation") beside the named terms of the fused
+ * loss (csrc/seg_loss.hip, csrc/seg_loss_terms.hip).  It is a weight of its own, not a name: the authors use it as L_region + alpha L_boundary.
+ *
+ *   B = 1/(N C V) sum_{n,c,v} sigmoid(p) phi          phi: fp32 [N][C][V] like the labels, of dua_sdf_maps; B may be negative
+ *   L = L_named + alpha B                             L_named: the combined loss of the selected names, as above
+ *   dlogits = gs [named terms] + gb phi s (1 - s) / (N C V)
+ * alpha multiplies OUTSIDE the combine: "mean" and "log" keep their meaning and dcomb does not touch the boundary part.
+ * gs = *gscale is upstream x dcomb as above, gb = *bscale is upstream x alpha; both are device scalars, so a schedule changes
+ * alpha between replays of one captured graph.  The named part runs exactly as without the term -- dua_seg_loss_reduce /
+ * _finish[_mn] for a name set within mse / bce / dice / multi_neighbor, dua_seg_loss_terms_reduce / _finish otherwise -- so
+ * L_named, dcomb and, at alpha = 0, L and every gradient element have the bits of the step without a boundary weight.
+ *
+ * dua_seg_loss_boundary_scratch_bytes: N * min(512, ceil(voxels / 256)) doubles (one partial per workgroup), or DUA_ERR_ARG.
+ * dua_seg_loss_boundary_reduce: a pass of its own over logits and phi (the named reduces keep their code and bits): a thread
+ *   adds s phi in fp32, each workgroup WRITES one fp64 partial, a one-wave launch adds them in workgroup order (same inputs,
+ *   same bits, no floating-point atomics), writes bterm[0] = B and replaces loss[0] -- holding L_named, as the finish entry
+ *   left it -- by L_named + *alpha B, formed in fp64 from the fp64 B and rounded once.  *alpha = 0
+ *   leaves loss[0] as it is by a branch, also where B is inf or NaN.  alpha, loss, bterm: DEVICE fp32.
+ * dua_seg_loss_boundary_grad, dua_seg_loss_terms_boundary_grad: dua_seg_loss_grad / dua_seg_loss_terms_grad with the boundary
+ *   part added in the SAME pass: per element  g_s acc + g_b ((phi (s (1 - s))) (float)(1 / (N C V)))  in fp32, rounded ONCE to
+ *   the logits' dtype; acc and g_s acc are the named kernel's own operations, so *bscale = 0 gives the values of the entry
+ *   without the term, whichever family the name set takes (a name set within mse / bce / dice / multi_neighbor: the first).
+ *   Channels past C are not written.  The terms form accepts use_* all 0.
+ * DUA_ERR_ARG: a NULL operand (phi, alpha / bscale, loss, bterm, scratch included), C > 64, N > 65535, stride < C,
+ *   scratch_bytes too small, and whatever the entry without the term refuses other than "no term selected". */
+long dua_seg_loss_boundary_scratch_bytes(int N, int C, long voxels);
+int dua_seg_loss_boundary_reduce(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* phi,
+                                 const float* alpha, float* loss, float* bterm, void* scratch, long scratch_bytes, void* stream);
+int dua_seg_loss_boundary_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride, const float* labels,
+                               const double* sums, const float* gscale, float w_mse, float w_bce, float w_dice, const float* phi,
+                               const float* bscale, void* dlogits, int dlogits_stride, void* stream);
+int dua_seg_loss_terms_boundary_grad(int dtype, int N, int C, long voxels, const void* logits, int logits_stride,
+                                     const float* labels, const float* consts, const float* gscale, int use_mse, int use_bce,
+                                     int use_dice, int use_ce, int use_dice_ce, int use_gdice, const float* phi,
+                                     const float* bscale, void* dlogits, int dlogits_stride, void* stream);
+
 /* Timestep embedding under training (models/diffusion/utils.py:5-54, denoiser.py:51-52,65): for sample n
  *   e = [sin | cos](t[n] * freqs), z1 = W0 e + b0, h1 = swish(z1), z2 = W1 h1 + b1, s = swish(z2), add_b = Wp_b s + bp_b
  * for every TwoConv block b (its temb_proj).  ``add`` / ``dadd`` are BLOCK-MAJOR: block b's [N][cout_b] rows are contiguous
@@ -1710,6 +1746,37 @@ int dua_blend_finish_labelmap(const float* sum, int C, int Dp, int Hp, int Wp, c
 #define DUA_SUF_MAX_RUNS 16
 int dua_suf_accumulate(int G, int R, int C, long voxels, const float* logits, const float* step_coef, int nsteps,
                        const int* step_word, int step, int* err_word, float* acc, void* stream);
+
+/* Signed distance maps of a label batch, for the boundary term of the fused loss (csrc/sdf.hip).
+ *
+ * labels: fp32 NCDHW [N][C][D][H][W], what the loss takes: one-hot, all-zero at a voxel, or soft (label smoothing).
+ * Sets:   for volume (n, c), pos = { v : y > threshold } (STRICT; 0.5 on one-hot labels is .bool()), neg = the rest.
+ * d2(v):  the squared Euclidean distance in voxels (unit spacing: an integer) from v to the nearest voxel of the OTHER set,
+ *         taken inside the patch -- scipy's distance_transform_edt of the mask for v in pos, of its complement for v in neg.
+ * phi:    fp32 [N][C][D][H][W], in fp32 IEEE operations (the build has no fast-math, -ffp-contract=off, and fp32 sqrt is
+ *         correctly rounded):
+ *           v in neg:  phi = sqrtf((float)d2)
+ *           v in pos:  phi = 1.0f - sqrtf((float)d2)
+ *         and phi = 0 for the WHOLE volume where the other set is empty: a class absent from the patch, or one that fills it
+ *         (an all-background crop does that to class 0, where the transform of an empty complement has no meaning).
+ *         Against Kervadec's fp64 form edt(neg) neg - (edt(pos) - 1) pos that is within 2^-23 max(1, sqrt(d2)) per voxel: one
+ *         correctly rounded square root, one rounded subtraction.
+ * d2_out: int32 [N][C][D][H][W] or NULL: the integer d2, 0 where phi is forced to 0.
+ * Limits: 1 <= D, H, W <= 512 (d2 < 2^24 converts to fp32 exactly), N C <= 65535.
+ *
+ * Three separable passes (W, H, D) over ONE signed 32-bit word per voxel -- the sign is the membership, the magnitude the
+ * partial squared distance to the other set, 2^30 = none yet; a voxel's partial distance to its own set is always 0 -- so both
+ * transforms cost one read and one write per pass.  Lines are staged in LDS and searched outward until k^2 >= best; a line
+ * never leaves its volume.  Integer minima only: exact, the same bits on every run, no atomics, no host read (capturable).
+ * Traffic: 6 words per voxel (labels in, word out; word in, word out; word in, phi out), +1 with d2_out.
+ * labels are consumed by the first pass, so phi MAY be the labels buffer itself; d2_out and scratch may alias nothing.
+ *
+ * dua_sdf_scratch_bytes: N C D H W int32 words, or DUA_ERR_ARG.  The scratch needs no zeroing.
+ * Invalid arguments (an extent outside the limits, a NULL labels / phi / scratch, a NaN threshold, scratch_bytes too small):
+ * DUA_ERR_ARG, before the device is touched. */
+long dua_sdf_scratch_bytes(int N, int C, int D, int H, int W);
+int dua_sdf_maps(int N, int C, int D, int H, int W, const float* labels, float threshold, float* phi, int* d2_out, void* scratch,
+                 long scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }
