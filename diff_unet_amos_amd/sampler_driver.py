@@ -157,7 +157,7 @@ class SamplerDriver:
         return self.suf_logits, self.suf_acc[R], self.tables[tkey]
 
     def sample_loop(self, diffusion, kind, noise=None, step_noise=None, eta=0.0, use_graph=True, seed=None, want_sum=None,
-                    snapshots=None, fuse_runs=None, step_logits=None):
+                    snapshots=None, fuse_runs=None, step_logits=None, first_step=0):
         """T reverse steps (T = diffusion.num_timesteps) starting from ``noise`` (x_T, NCDHW) or a fresh draw: the loop bodies
         of p_sample_loop_progressive / ddim_sample_loop_progressive (gaussian_diffusion.py:487-535, 667-716), one captured HIP
         graph replayed per step.  ``step_noise``: optional list of per-step NCDHW draws (parity runs; eager mode); otherwise the
@@ -171,9 +171,17 @@ class SamplerDriver:
         (dua_suf_accumulate, include/dua_hip.h has the formula) in the same captured graph; no plain sum is kept, and the
         result carries ``fused_pred_xstart`` (NCDHW [N / R, C, ...]).  R = 1 is not the plain sum: the steps are still weighted.
         ``step_logits``: optional list; with ``fuse_runs`` (eager mode) a copy of every step's logits is appended to it.
+        ``first_step`` = s: ``noise`` is the state after s steps and the loop runs steps s .. T - 1 only (the tail of a long
+        process); ``step_noise`` then has T - s entries, entry j belonging to step s + j, and ``snapshots`` keys stay absolute
+        step counts.  The in-kernel noise is keyed by (seed, step), so resuming from a snapshot repeats the full run's bits.
         Returns dict(sample, sum_pred_xstart (None without the sum))."""
         fuse = None
+        first_step = int(first_step)
+        if not 0 <= first_step < diffusion.num_timesteps:
+            raise ValueError(f"first_step={first_step}: the process has steps 0 <= k < {diffusion.num_timesteps}")
         if fuse_runs is not None:
+            if first_step:
+                raise NotImplementedError("fuse_runs: the fused sum runs over all steps, first_step must be 0")
             R = int(fuse_runs)
             if kind != "ddim":
                 raise NotImplementedError("fuse_runs: Step-Uncertainty Fusion is defined for the DDIM loop only")
@@ -194,11 +202,13 @@ class SamplerDriver:
         assert tuple(noise.shape) == shape
         x_T = noise.detach().float().contiguous()
         self._reset(x_T)
+        if first_step:
+            self.counter.fill_(first_step)
         mode = nv.MODE_DDPM if kind == "ddpm" else nv.MODE_DDIM
         coef_table, row_of_step = self._step_tables(diffusion, kind, eta)
         self.new_seed(seed)
         if step_noise is not None:
-            assert len(step_noise) == T
+            assert len(step_noise) == T - first_step
         if step_noise is not None or snapshots or step_logits is not None:
             use_graph = False
         if fuse is not None:
@@ -207,21 +217,23 @@ class SamplerDriver:
 
         def run(plan, first, last):
             for k in range(first, last):
-                eps = None if step_noise is None else step_noise[k].detach().to(self.dev).float().contiguous()
+                eps = None if step_noise is None else step_noise[k - first_step].detach().to(self.dev).float().contiguous()
                 plan._one_step(mode, row_of_step, coef_table, eps, want_sum)
                 if snapshots and (k + 1) in snapshots:
                     snapshots[k + 1] = ops.from_channels_last(plan.x_state, self.C)
 
-        finish = self._finish_count(kind, T)
+        finish = min(self._finish_count(kind, T), T - first_step)
         if not use_graph:
-            run(self, 0, T - finish)
+            run(self, first_step, T - finish)
         else:
             gkey = (diffusion, kind, float(eta), want_sum)
             g = self.graphs.get(gkey)
             if g is None:
                 g = self.graphs[gkey] = self._capture(lambda: self._one_step(mode, row_of_step, coef_table, None, want_sum))
                 self._reset(x_T)                    # the warm-up step advanced the state
-            for _ in range(T - finish):
+                if first_step:
+                    self.counter.fill_(first_step)
+            for _ in range(T - finish - first_step):
                 g.replay()
         if finish:
             self._finish(T - finish, T, run)

@@ -130,6 +130,47 @@ def test_finishing_steps(diffusion, x_T):
     assert p.names() == ["reset"] + ["step"] * (T - 2) + ["finish"] and p.log[-1] == ("finish", T - 2, T)
 
 
+def test_first_step_runs_the_tail_of_the_process(diffusion, x_T, monkeypatch):
+    """first_step = s: the counter word starts at s (again behind the capture's warm-up), steps s .. T - 1 run, entry j of
+    step_noise belongs to step s + j, snapshot keys stay absolute, and the finishing steps keep their place."""
+    draws = [torch.full((1, 2, 2, 2, 2), float(k)) for k in range(T - 2)]
+    p = StubPlan()
+    monkeypatch.setattr("diff_unet_amos_amd.ops.from_channels_last", lambda src, c: ("state after", p.names().count("step")))
+    snaps = {3: None, T: None}
+    p.sample_loop(diffusion, "ddpm", noise=x_T, step_noise=draws, snapshots=snaps, seed=1, first_step=2)
+    assert p.names() == ["reset"] + ["step"] * (T - 2) and int(p.counter.item()) == 2       # the stub's steps do not advance it
+    assert [float(e[4].flatten()[0]) for e in p.log if e[0] == "step"] == [0.0, 1.0, 2.0]
+    assert snaps == {3: ("state after", 1), T: ("state after", T - 2)}
+    with pytest.raises(AssertionError):
+        StubPlan().sample_loop(diffusion, "ddpm", noise=x_T, step_noise=draws + draws[:1], seed=1, first_step=2)
+    p = StubPlan()
+    p.counter.fill_(99)                                                                      # as a warm-up step would leave it
+    p.sample_loop(diffusion, "ddpm", noise=x_T, seed=1, first_step=2)
+    assert p.names() == ["reset", "capture", "reset"] + ["replay"] * (T - 2) and int(p.counter.item()) == 2
+    p = StubPlan(finish=2)
+    p.sample_loop(diffusion, "ddpm", noise=x_T, seed=1, first_step=1)
+    assert p.names() == ["reset", "capture", "reset"] + ["replay"] * (T - 3) + ["finish"] and p.log[-1] == ("finish", T - 2, T)
+    p = StubPlan(finish=2)                                                                   # a start inside the finishing steps
+    p.sample_loop(diffusion, "ddpm", noise=x_T, seed=1, first_step=T - 1, use_graph=False)
+    assert p.names() == ["reset", "finish"] and p.log[-1] == ("finish", T - 1, T)
+    p = StubPlan()                                                                           # the default leaves the word alone
+    p.counter.fill_(99)
+    p.sample_loop(diffusion, "ddpm", noise=x_T, seed=1, use_graph=False)
+    assert int(p.counter.item()) == 99
+
+
+def test_first_step_argument_errors(diffusion, x_T):
+    for bad in (-1, T, T + 3):
+        p = StubPlan()
+        with pytest.raises(ValueError, match=rf"first_step={bad}: the process has steps 0 <= k < {T}"):
+            p.sample_loop(diffusion, "ddpm", noise=x_T, seed=1, first_step=bad)
+        assert p.names() == []
+    p = StubPlan()
+    with pytest.raises(NotImplementedError, match="fuse_runs"):
+        p.sample_loop(diffusion, "ddim", noise=x_T, seed=1, fuse_runs=1, first_step=1)
+    assert p.names() == []
+
+
 def test_seed_draws(diffusion, x_T):
     p = StubPlan()
     torch.manual_seed(123)
