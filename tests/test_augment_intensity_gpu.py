@@ -162,6 +162,14 @@ PRODUCER = dict(roi=(16, 16, 16), pos=2, neg=1, flip_prob=0.3, rot90_prob=0.4, m
 INTENSITY = dict(noise_prob=0.6, blur_prob=0.6, brightness_prob=0.6, contrast_prob=0.6, gamma_prob=0.7, gamma_invert_prob=0.5)
 
 
+def _expect(ref_vols, vid, counter, roi, class_ids):
+    """(images, labels, intensity rows, (fp64 images, bound)) of producer call ``counter`` with PRODUCER and INTENSITY."""
+    ints, floats = ref.draw(ref_vols, vid, counter, seed=8, **PRODUCER)
+    images, labels = ref.apply(ref_vols, ints, floats, roi, class_ids)
+    rows = iref.draw_rows(len(vid), counter, SEED, **INTENSITY)
+    return images.numpy(), labels.numpy(), rows, iref.reference(images.numpy(), rows, SEED)
+
+
 @gpu
 def test_next_with_intensity_captured_in_a_graph_gives_the_restatements_batches_replay_by_replay():
     aug = _aug()
@@ -177,10 +185,7 @@ def test_next_with_intensity_captured_in_a_graph_gives_the_restatements_batches_
     assert plain.intensity is None and plain.intensity_rows is None
 
     def expect(counter):
-        ints, floats = ref.draw(ref_vols, vid, counter, seed=8, **PRODUCER)
-        images, labels = ref.apply(ref_vols, ints, floats, roi, class_ids)
-        rows = iref.draw_rows(len(vid), counter, SEED, **INTENSITY)
-        return images.numpy(), labels.numpy(), rows, iref.reference(images.numpy(), rows, SEED)
+        return _expect(ref_vols, vid, counter, roi, class_ids)
 
     first = prod.next(ids)                                   # an eager call first: the capture starts at counter 1
     today = plain.next(ids)

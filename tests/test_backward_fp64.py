@@ -306,6 +306,25 @@ def test_dgrad_reduce_within_fp64_bound(cin):
 
 
 # ---- head and max-pool backward ---------------------------------------------------------------------------------------------------
+def _check_head_bwd(u, dl, w, du, dW, db, mfma):
+    """du, dW, db of ops.head_bwd against fp64 on the operands it read; ``mfma``: the launch took the MFMA path (fp16 weights)."""
+    dtype = u.dtype
+    C, K = u.shape[-1], dl.shape[-1]
+    V = u.numel() // C
+    c_du, c_w = R.head_bwd_chains(V, dtype, mfma=mfma)
+    ud, dld = u.double().reshape(V, C), dl.double().reshape(V, K)
+    wq = (w.half() if mfma else w).double()                  # the MFMA path multiplies fp16 weights
+    ref_du = dld @ wq
+    b_du = R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, dtype)
+    r1 = R.check(du.reshape(V, C), ref_du, b_du)
+    ref_w, ab_w = dld.t() @ ud, dld.abs().t() @ ud.abs()
+    r2 = R.check(dW, ref_w, R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32)
+    ref_b, ab_b = dld.sum(0), dld.abs().sum(0)
+    r3 = R.check(db, ref_b, R.U32 * c_w * ab_b * (1 + R.U32) + R.FLOOR32)
+    print(f"head bwd {dtype}: du {r1}; dW {r2}; db {r3}")
+    assert max(r1.ratio, r2.ratio, r3.ratio) <= 1.0, (r1, r2, r3)
+
+
 @pytest.mark.parametrize("dtype", [F16, F32])
 def test_head_backward_within_fp64_bound(dtype):
     """96^3, batch 2, C = 64, K = 16: fp16 takes the MFMA path and head_reduce_kernel, fp32 the plain kernel and the same reduce."""
@@ -316,19 +335,7 @@ def test_head_backward_within_fp64_bound(dtype):
     w = _randn((K, C), 43, F32, scale=0.2)
     du, dW, db = ops.head_bwd(dl, u, w)
     torch.cuda.synchronize()
-    V = N * S ** 3
-    c_du, c_w = R.head_bwd_chains(V, dtype, mfma=dtype == F16)
-    ud, dld = u.double().reshape(V, C), dl.double().reshape(V, K)
-    wq = (w.half() if dtype == F16 else w).double()          # the MFMA path multiplies fp16 weights
-    ref_du = dld @ wq
-    b_du = R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, dtype)
-    r1 = R.check(du.reshape(V, C), ref_du, b_du)
-    ref_w, ab_w = dld.t() @ ud, dld.abs().t() @ ud.abs()
-    r2 = R.check(dW, ref_w, R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32)
-    ref_b, ab_b = dld.sum(0), dld.abs().sum(0)
-    r3 = R.check(db, ref_b, R.U32 * c_w * ab_b * (1 + R.U32) + R.FLOOR32)
-    print(f"head bwd {dtype}: du {r1}; dW {r2}; db {r3}")
-    assert max(r1.ratio, r2.ratio, r3.ratio) <= 1.0, (r1, r2, r3)
+    _check_head_bwd(u, dl, w, du, dW, db, mfma=dtype == F16)
 
 
 @pytest.mark.parametrize("dtype", [F16, F32])
@@ -371,16 +378,27 @@ def test_deconv_backward_within_fp64_bound(dims, fine, cin, cout, cskip):
     """deconv_k2s2_bwd, batch 2, fp16: dy read in place from the upsampled half of the concat gradient; the padded form where the
     fine level is one plane longer than 2x the coarse one (its folded dy operand is summed and rounded once: an emulated input,
     covered by the RSS term as the forward's fused transforms are)."""
-    ops, nv = _ops(), _nv()
-    N, dt = 2, F16
+    ops = _ops()
+    x, dcat, w = _deconv_bwd_operands(dims, fine, cin, cout, cskip)
+    dx, dw = ops.deconv_k2s2_bwd(x, cin, 8, dcat, cout, cskip, w)
+    torch.cuda.synchronize()
+    _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw)
+
+
+def _deconv_bwd_operands(dims, fine, cin, cout, cskip, N=2, dt=F16):
+    """(x with 8 channels in front, the concat gradient whose upsampled half is dy, w) of one DECONV_LEVELS entry."""
     D, H, W = dims
-    padded = tuple(fine) != (2 * D, 2 * H, 2 * W)
     seed = sum(dims) + cin
     x = _randn((N, D, H, W, cin + 8), seed, dt)
     dcat = _randn((N, *fine, cskip + cout), seed + 1, dt)
     w = _randn((cin, cout, 2, 2, 2), seed + 2, F32, scale=cin ** -0.5)
-    dx, dw = ops.deconv_k2s2_bwd(x, cin, 8, dcat, cout, cskip, w)
-    torch.cuda.synchronize()
+    return x, dcat, w
+
+
+def _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw, N=2, dt=F16):
+    nv = _nv()
+    D, H, W = dims
+    padded = tuple(fine) != (2 * D, 2 * H, 2 * W)
     c_dx, c_dw, P = R.deconv_bwd_chains(N, D, H, W, cin, cout, dt)
     d = nv.Conv3Desc(nv.dt_code(dt), N, D, H, W, cin, cin + 8, 8, cout, cskip + cout, cskip)
     combos = -(-cin // 64) * -(-cout // 64)

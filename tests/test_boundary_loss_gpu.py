@@ -40,6 +40,30 @@ def _seg_loss(logits, labels, names, combine, boundary):
     return L.detach(), saved[2], saved[3], x.grad
 
 
+def _check_results(config, c, names, combine, alpha, bterm, L, buf, dcomb, grad, mn):
+    """B, L, dcomb and every gradient element of one _seg_loss call with the boundary term against the fp64 references."""
+    shape, dtype, pad = config
+    logits, labels, phi, r = c["logits"], c["labels"], c["phi"], c["r"]
+    N, C = shape[:2]
+    V = labels[0, 0].numel()
+    wB, bB = BR.term_ref(r)
+    three = BR.three_term(names)                           # the kernel family: the one these names take without the term
+    assert buf.numel() == (N * C * 4 + 2 if three else N * C * 5 + 3)
+    sums = buf if three else buf[:N * C * 4 + 3]
+    wLn, wdc = BR.named_finish_ref(sums, N, C, V, names, combine, mn)
+    wL, bL = BR.loss_ref(wLn, alpha, r)
+    gs, gb = float(torch.tensor(SCALE, dtype=F32, device=DEV) * dcomb), float(torch.tensor(SCALE, dtype=F32, device=DEV) * alpha)
+    gr = BR.grad_ref(logits, labels, buf, gs, names, phi, gb)
+    got, padding = LT.grad_rows(grad, C)
+    res = dict(B=abs(float(bterm) - float(wB)) / float(bB), L=abs(float(L) - float(wL)) / float(bL),
+               dcomb=LT.check(dcomb.cpu().reshape(1), wdc.reshape(1), LT.finish_bound(wdc).reshape(1)).ratio,
+               grad=BR.check(got, gr["ref"], BR.grad_bound(gr, dtype)).ratio, pad=LT.check_padding(padding).ratio)
+    print(f"{shape} {str(dtype)[6:]} pad {pad} {'+'.join(names)}/{combine}: B {float(bterm):.9g} (fp64 {float(wB):.9g}), "
+          f"L {float(L):.9g} (fp64 {float(wL):.9g}); |err| / bound: " + ", ".join(f"{k} {v:.3g}" for k, v in res.items()))
+    for k, v in res.items():
+        assert v <= 1.0, (names, combine, k, v)
+
+
 @pytest.mark.parametrize("config", CONFIGS, ids=[f"{'x'.join(map(str, s))}-{str(d)[6:]}-pad{p}" for s, d, p in CONFIGS])
 def test_value_and_gradient_within_the_bounds(config):
     from diff_unet_amos_amd import ops
@@ -50,27 +74,12 @@ def test_value_and_gradient_within_the_bounds(config):
     V = labels[0, 0].numel()
     alpha = torch.tensor(BR.ALPHA, dtype=F32, device=DEV)
     zero = torch.zeros((), dtype=F32, device=DEV)
-    wB, bB = BR.term_ref(r)
     for names in BR.NAME_SETS:
         mn = ops.multi_neighbor_partials(logits, labels).cpu() if "multi_neighbor" in names else None
         for combine in BR.COMBINES:
             bterm = torch.full((), float("nan"), dtype=F32, device=DEV)
             L, buf, dcomb, grad = _seg_loss(logits, labels, names, combine, (phi, alpha, bterm))
-            three = BR.three_term(names)                           # the kernel family: the one these names take without the term
-            assert buf.numel() == (N * C * 4 + 2 if three else N * C * 5 + 3)
-            sums = buf if three else buf[:N * C * 4 + 3]
-            wLn, wdc = BR.named_finish_ref(sums, N, C, V, names, combine, mn)
-            wL, bL = BR.loss_ref(wLn, alpha, r)
-            gs, gb = float(torch.tensor(SCALE, dtype=F32, device=DEV) * dcomb), float(torch.tensor(SCALE, dtype=F32, device=DEV) * alpha)
-            gr = BR.grad_ref(logits, labels, buf, gs, names, phi, gb)
-            got, padding = LT.grad_rows(grad, C)
-            res = dict(B=abs(float(bterm) - float(wB)) / float(bB), L=abs(float(L) - float(wL)) / float(bL),
-                       dcomb=LT.check(dcomb.cpu().reshape(1), wdc.reshape(1), LT.finish_bound(wdc).reshape(1)).ratio,
-                       grad=BR.check(got, gr["ref"], BR.grad_bound(gr, dtype)).ratio, pad=LT.check_padding(padding).ratio)
-            print(f"{shape} {str(dtype)[6:]} pad {pad} {'+'.join(names)}/{combine}: B {float(bterm):.9g} (fp64 {float(wB):.9g}), "
-                  f"L {float(L):.9g} (fp64 {float(wL):.9g}); |err| / bound: " + ", ".join(f"{k} {v:.3g}" for k, v in res.items()))
-            for k, v in res.items():
-                assert v <= 1.0, (names, combine, k, v)
+            _check_results(config, c, names, combine, alpha, bterm, L, buf, dcomb, grad, mn)
             # alpha = 0: the value and every gradient element of the path without the term
             L0, _, _, grad0 = _seg_loss(logits, labels, names, combine, (phi, zero))
             Ln, _, _, gradn = _seg_loss(logits, labels, names, combine, None)

@@ -108,6 +108,16 @@ def _fp64_bound_check(got, act, w, b, dtype, emulated=False, split_parts=0, seed
     return r
 
 
+def _conv3_operands(shape):
+    """(generator, x or raw NCDHW, w, b) of a (N, Cin, Cout, D, H, W) convolution case; the generator goes on to the producer."""
+    N, Cin, Cout, D, H, W = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    x = torch.randn(N, Cin, D, H, W, generator=g)
+    w = torch.randn(Cout, Cin, 3, 3, 3, generator=g) / (27 * Cin) ** 0.5
+    b = torch.randn(Cout, generator=g)
+    return g, x, w, b
+
+
 @pytest.fixture
 def conv_variant(request):
     """Force one of the conv3d_k3 launch shapes (0: automatic policy with split-K / 2x8x8 tiles where they pay,
@@ -140,10 +150,7 @@ def conv_variant(request):
 def test_conv3_raw_and_stats(dtype, shape, conv_variant):
     ops = _ops()
     N, Cin, Cout, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    x = torch.randn(N, Cin, D, H, W, generator=g)
-    w = torch.randn(Cout, Cin, 3, 3, 3, generator=g) / (27 * Cin) ** 0.5
-    b = torch.randn(Cout, generator=g)
+    g, x, w, b = _conv3_operands(shape)
     xq, wq = x.to(dtype).float(), w.to(dtype).float()          # operands as the kernel sees them
     ref = F.conv3d(xq, wq, b, padding=1)
 
@@ -266,10 +273,7 @@ def test_conv3_split_k(dtype, shape, conv_variant):
     summed by the finish kernel, which also adds the bias and takes the InstanceNorm sums."""
     ops = _ops()
     N, Cin, Cout, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    raw = torch.randn(N, Cin, D, H, W, generator=g)
-    w = torch.randn(Cout, Cin, 3, 3, 3, generator=g) / (27 * Cin) ** 0.5
-    b = torch.randn(Cout, generator=g)
+    g, raw, w, b = _conv3_operands(shape)
     norm, act = _producer(raw, dtype, g, add=torch.randn(N, Cin, generator=g))
     ref = F.conv3d(act.to(dtype).float(), w.to(dtype).float(), b, padding=1)
     nbytes = ops.conv3_workspace_bytes(dtype, N, D, H, W, Cin, Cout)
@@ -320,15 +324,8 @@ def test_conv3_fused_input_transform_and_channel_slices(dtype, conv_variant):
     assert float((ybuf[..., :8].float() + 5).abs().max()) == 0 and float((ybuf[..., 48:].float() + 5).abs().max()) == 0
 
 
-@pytest.mark.parametrize("classes,shape,cout", [(16, (1, 16, 24, 8), 64), (16, (2, 10, 9, 13), 64), (0, (1, 8, 16, 16), 64),
-                                                (16, (1, 40, 72, 72), 64),      # 810 tiles: persistent workgroups take two
-                                                (16, (3, 12, 20, 16), 8), (16, (1, 9, 17, 8), 96)])
-def test_conv3_single_channel_tap_form(classes, shape, cout):
-    """First layers: the lone image channel behind 16 (denoiser) or 0 (encoder) ordinary channels contracted as two
-    k-steps over its 27 taps; against torch conv3d on the fp16-rounded operands and against the ordinary form.  With 16
-    channels the default is the resident-weight kernel (persistent workgroups); conv_variant 6 keeps the slab pipeline."""
-    ops = _ops()
-    from diff_unet_amos_amd import _native as nv
+def _tap_operands(classes, shape, cout):
+    """(x NCDHW in the reference's channel order [image | x_t], w, b, channel map, x packed [x_t | image | pad] on the device)."""
     N, D, H, W = shape
     cin_src, cin_p = classes + 1, classes + 8
     g = torch.Generator().manual_seed(classes + D)
@@ -339,6 +336,21 @@ def test_conv3_single_channel_tap_form(classes, shape, cout):
     xp = torch.zeros(N, D, H, W, cin_p, dtype=torch.float16, device="cuda")
     xp[..., :classes] = x[:, 1:].permute(0, 2, 3, 4, 1).half()
     xp[..., classes] = x[:, 0].half()
+    return x, w, b, perm, xp
+
+
+@pytest.mark.parametrize("classes,shape,cout", [(16, (1, 16, 24, 8), 64), (16, (2, 10, 9, 13), 64), (0, (1, 8, 16, 16), 64),
+                                                (16, (1, 40, 72, 72), 64),      # 810 tiles: persistent workgroups take two
+                                                (16, (3, 12, 20, 16), 8), (16, (1, 9, 17, 8), 96)])
+def test_conv3_single_channel_tap_form(classes, shape, cout):
+    """First layers: the lone image channel behind 16 (denoiser) or 0 (encoder) ordinary channels contracted as two
+    k-steps over its 27 taps; against torch conv3d on the fp16-rounded operands and against the ordinary form.  With 16
+    channels the default is the resident-weight kernel (persistent workgroups); conv_variant 6 keeps the slab pipeline."""
+    ops = _ops()
+    from diff_unet_amos_amd import _native as nv
+    N, D, H, W = shape
+    cin_p = classes + 8
+    x, w, b, perm, xp = _tap_operands(classes, shape, cout)
     outs = []
     try:
         for tap, variant in ((None, 0), (classes, 0), (classes, 6)):
@@ -376,20 +388,27 @@ def test_conv3_single_channel_tap_form(classes, shape, cout):
         assert torch.equal(ycl, y_plain)
 
 
+def _permuted_operands(dtype, C=5):
+    """(image, x_t, w, b, the [x_t | image | 0-pad] buffer on the device, channel map) of the first denoiser layer's case."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(3)
+    image = torch.rand(1, 1, 8, 8, 8, generator=g); xt = torch.randn(1, C, 8, 8, 8, generator=g)
+    w = torch.randn(16, C + 1, 3, 3, 3, generator=g) * 0.1
+    b = torch.randn(16, generator=g)
+    buf = torch.zeros((1, 8, 8, 8, 8), dtype=dtype, device="cuda")
+    ops.to_channels_last(xt.cuda(), buf, 0, C)
+    bufv = buf.view(-1, 8); bufv[:, C] = image.cuda().view(-1).to(dtype)
+    perm = list(range(1, C + 1)) + [0]
+    return image, xt, w, b, buf, perm
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 def test_conv3_permuted_padded_input_channels(dtype):
     """First denoiser layer: torch.cat([image, x_t]) (denoiser.py:298) stored as [x_t | image | 0-pad]."""
     ops = _ops()
     C = 5
-    g = torch.Generator().manual_seed(3)
-    image = torch.rand(1, 1, 8, 8, 8, generator=g); xt = torch.randn(1, C, 8, 8, 8, generator=g)
-    w = torch.randn(16, C + 1, 3, 3, 3, generator=g) * 0.1
-    b = torch.randn(16, generator=g)
+    image, xt, w, b, buf, perm = _permuted_operands(dtype, C)
     ref = F.conv3d(torch.cat([image, xt], 1).to(dtype).float(), w.to(dtype).float(), b, padding=1)
-    buf = torch.zeros((1, 8, 8, 8, 8), dtype=dtype, device="cuda")
-    ops.to_channels_last(xt.cuda(), buf, 0, C)
-    bufv = buf.view(-1, 8); bufv[:, C] = image.cuda().view(-1).to(dtype)
-    perm = list(range(1, C + 1)) + [0]
     wp, bp = ops.pack_conv3_weights(w.cuda(), b.cuda(), dtype, cin_packed=8, perm=perm + [-1] * (8 - len(perm)))
     y = torch.zeros((1, 8, 8, 8, 16), dtype=dtype, device="cuda")
     ops.conv3d_k3(buf, 8, 0, wp, bp, 16, y, 0, ops.stats_buffer(1, 16, "cuda"))
@@ -472,6 +491,16 @@ def test_deconv_k2s2_into_a_blocked_buffer(fused):
         ops.deconv_k2s2(small, 64, 0, wp, bp, Cout, torch.zeros(1, 8, 8, 8, 128, dtype=dtype, device="cuda"), 64, out_blocked=True)
 
 
+def _deconv_operands(shape):
+    """(generator, raw NCDHW, w, b) of a (N, Cin, Cout, D, H, W) transposed-convolution case."""
+    N, Cin, Cout, D, H, W = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    raw = torch.randn(N, Cin, D, H, W, generator=g)
+    w = torch.randn(Cin, Cout, 2, 2, 2, generator=g) / Cin ** 0.5
+    b = torch.randn(Cout, generator=g)
+    return g, raw, w, b
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("shape", [(1, 64, 32, 3, 3, 3), (2, 40, 72, 2, 4, 6), (1, 16, 16, 6, 6, 6),
                                    (1, 64, 64, 32, 32, 32), (1, 40, 72, 30, 34, 36),      # these two: all-taps kernel
@@ -482,10 +511,7 @@ def test_deconv_k2s2_into_a_blocked_buffer(fused):
 def test_deconv_k2s2(dtype, shape, fused):
     ops = _ops()
     N, Cin, Cout, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    raw = torch.randn(N, Cin, D, H, W, generator=g)
-    w = torch.randn(Cin, Cout, 2, 2, 2, generator=g) / Cin ** 0.5
-    b = torch.randn(Cout, generator=g)
+    g, raw, w, b = _deconv_operands(shape)
     xin = raw.to(dtype).float()
     norm = None
     if fused:
@@ -837,12 +863,8 @@ def test_conv3_wgrad_permuted_input_channels():
     assert (dw.double() - want).abs().max().item() <= 2e-5 * want.abs().max().item()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
-@pytest.mark.parametrize("shape", [(2, 8, 8, 8, 64), (1, 6, 10, 4, 24), (2, 4, 4, 4, 136), (1, 2, 2, 2, 512)])
-def test_instnorm_lrelu_backward_matches_autograd(dtype, shape):
-    """conv stats -> materialize (+ per-(n,c) add) forward, then the reduce/apply backward pair against torch autograd
-    of instance_norm -> leaky_relu -> + add on the same raw tensor."""
+def _instnorm_bwd_operands(dtype, shape):
+    """(raw, gamma, beta, add, dA, forward statistics, ops.Norm) of a (N, D, H, W, C) InstanceNorm + LeakyReLU backward case."""
     ops = _ops()
     N, D, H, W, Cc = shape
     dev = torch.device("cuda:0")
@@ -852,10 +874,23 @@ def test_instnorm_lrelu_backward_matches_autograd(dtype, shape):
     beta = torch.randn(Cc, generator=g, device=dev) * 0.2
     add = torch.randn(N, Cc, generator=g, device=dev)
     dA = torch.randn(N, D, H, W, Cc, generator=g, device=dev).to(dtype)
-    V = D * H * W
     rd = raw.double()
     stats = ops.stats_encode(torch.stack([rd.sum((1, 2, 3)), (rd * rd).sum((1, 2, 3))], -1))
-    norm = ops.Norm(stats, gamma, beta, V, add=add, add_stride=Cc)
+    norm = ops.Norm(stats, gamma, beta, D * H * W, add=add, add_stride=Cc)
+    return raw, gamma, beta, add, dA, stats, norm
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("shape", [(2, 8, 8, 8, 64), (1, 6, 10, 4, 24), (2, 4, 4, 4, 136), (1, 2, 2, 2, 512)])
+def test_instnorm_lrelu_backward_matches_autograd(dtype, shape):
+    """conv stats -> materialize (+ per-(n,c) add) forward, then the reduce/apply backward pair against torch autograd
+    of instance_norm -> leaky_relu -> + add on the same raw tensor."""
+    ops = _ops()
+    N, D, H, W, Cc = shape
+    V = D * H * W
+    raw, gamma, beta, add, dA, stats, norm = _instnorm_bwd_operands(dtype, shape)
+    rd = raw.double()
     act = torch.empty_like(raw)
     ops.materialize(raw, Cc, norm, act, 0)
     dY = torch.empty_like(raw)
@@ -962,12 +997,8 @@ def test_maxpool_backward_add_matches_torch(dtype):
     assert (out0.double() - a.grad.permute(0, 2, 3, 4, 1)).abs().max().item() <= tol
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
-@pytest.mark.parametrize("shape", [(2, 8, 8, 8, 64, 16), (1, 3, 5, 7, 8, 2), (2, 6, 4, 10, 32, 13), (1, 5, 7, 9, 64, 16),
-                                   (2, 4, 4, 5, 64, 11), (1, 16, 24, 20, 64, 16)])
-def test_head_forward_backward_match_torch(dtype, shape):
-    ops = _ops()
+def _head_operands(dtype, shape):
+    """(u, w, b, dlogits) of a (N, D, H, W, C, K) head case."""
     N, D, H, W, Cc, K = shape
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(sum(shape))
@@ -975,6 +1006,16 @@ def test_head_forward_backward_match_torch(dtype, shape):
     w = torch.randn(K, Cc, generator=g, device=dev) * 0.2
     b = torch.randn(K, generator=g, device=dev)
     dl = torch.randn(N, D, H, W, K, generator=g, device=dev).to(dtype)
+    return u, w, b, dl
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("shape", [(2, 8, 8, 8, 64, 16), (1, 3, 5, 7, 8, 2), (2, 6, 4, 10, 32, 13), (1, 5, 7, 9, 64, 16),
+                                   (2, 4, 4, 5, 64, 11), (1, 16, 24, 20, 64, 16)])
+def test_head_forward_backward_match_torch(dtype, shape):
+    ops = _ops()
+    u, w, b, dl = _head_operands(dtype, shape)
     out = ops.head_fwd(u, w, b)
     du, dW, db = ops.head_bwd(dl, u, w)
     ud, wd, bd = u.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)

@@ -44,10 +44,15 @@ def _seg_loss(logits, labels, names, combine, scale):
 def _check_case(logits, labels, names=ALL6, combine="sum", scale=SCALE, what="", r=None, mn=None):
     """sums against reduce_ref, L / dcomb / constants against finish_ref of the device sums, every gradient element against
     grad_ref of the device sums, padding channels zero."""
+    return _check_results(logits, labels, _seg_loss(logits, labels, names, combine, scale), names, combine, what, r, mn)
+
+
+def _check_results(logits, labels, results, names=ALL6, combine="sum", what="", r=None, mn=None):
+    """``_check_case`` on the results of a ``_seg_loss`` call made elsewhere."""
     from diff_unet_amos_amd import ops
     N, C = labels.shape[:2]
     V = labels[0, 0].numel()
-    L, buf, dcomb, g, grad = _seg_loss(logits, labels, names, combine, scale)
+    L, buf, dcomb, g, grad = results
     assert buf.numel() == N * C * 5 + 3                    # the seg_loss_terms path: sums, then the constants
     sums, consts = buf[:N * C * 4 + 3], ops._terms_consts(buf, N, C).view(N, C, 2)
     if r is None:

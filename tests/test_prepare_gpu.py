@@ -147,15 +147,21 @@ def test_tie_table_on_the_device():
 
 # ---- restore ----
 
-@pytest.mark.parametrize("perm,signs,pixdim,one_to_one", [
-    ((0, 1, 2), (1, 1, 1), (0.7, 0.7, 0.7), True), ((2, 0, 1), (-1, 1, -1), (0.78, 0.78, 0.78), True),
-    ((1, 2, 0), (1, -1, -1), PIXDIM, False), ((2, 1, 0), (-1, -1, 1), (3.0, 0.5, 6.0), False)])
-def test_restore(perm, signs, pixdim, one_to_one):
+def _restore_operands():
+    """A 13 x 10 x 7 scan whose foreground box is not the whole volume, and its label map."""
     image, label = _case(seed=11)
     image[:2] = -1000
     image[:, 9] = -1000
     image[:, :, 0] = -1000
     image[2, 0, 1] = image[12, 8, 6] = 70
+    return image, label
+
+
+@pytest.mark.parametrize("perm,signs,pixdim,one_to_one", [
+    ((0, 1, 2), (1, 1, 1), (0.7, 0.7, 0.7), True), ((2, 0, 1), (-1, 1, -1), (0.78, 0.78, 0.78), True),
+    ((1, 2, 0), (1, -1, -1), PIXDIM, False), ((2, 1, 0), (-1, -1, 1), (3.0, 0.5, 6.0), False)])
+def test_restore(perm, signs, pixdim, one_to_one):
+    image, label = _restore_operands()
     affine = R.signed_permutation_affine(perm, signs, SPACING)
     case, ref = _check_case(image, label, affine, pixdim, what=f"restore {perm} {signs} {pixdim}")
     got = case.restore(case.label)

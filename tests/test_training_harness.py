@@ -229,6 +229,11 @@ def test_native_conv_training_path_matches_oracle_autograd(dtype):
     got = native_conv_denoise(net, image.to(dev), x_t.to(dev), t.to(dev), dtype)
     scale = 4096.0 if dtype == torch.float16 else 1.0
     (crit(got, labels.to(dev)) * scale).backward()
+    _check_native_step(ref, net, got, want, dtype, scale)
+
+
+def _check_native_step(ref, net, got, want, dtype, scale):
+    """Forward logits and every parameter gradient of ``net`` (gradients scaled by ``scale``) against the oracle ``ref``."""
     ftol = 2e-4 if dtype == torch.float32 else 3e-2
     assert (got.detach().cpu() - want.detach()).abs().max().item() < ftol
     gp = dict(net.named_parameters())

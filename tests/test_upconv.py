@@ -143,6 +143,28 @@ def test_packer_writes_the_composed_weights_in_streaming_order(shape):
     assert torch.allclose(btab.cpu().double(), want_b, rtol=1e-5, atol=1e-5)
 
 
+def _upconv_operands(shape, with_act=False):
+    """(x_e NCDHW, raw coarse tensor NCDHW, wc, bc, wd, bd, the coarse tensor's producer descriptor, the channels-last skip and
+    coarse buffers on the device [, the reference activation of the coarse tensor]) of one test_upconv_matches_deconv_cat_conv case."""
+    ops = _ops()
+    dt = torch.float16
+    N, Cs, Cu, Cmid, Cout, D, H, W, soff, sstride, uoff, ustride, ooff, ostride = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    xs = torch.randn(N, Cs, D, H, W, generator=g)
+    raw_u = torch.randn(N, Cu, D // 2, H // 2, W // 2, generator=g) * 1.5 + 0.25
+    wc = torch.randn(Cout, Cs + Cmid, 3, 3, 3, generator=g) / (27 * (Cs + Cmid)) ** 0.5
+    bc = torch.randn(Cout, generator=g)
+    wd = torch.randn(Cu, Cmid, 2, 2, 2, generator=g) / Cu ** 0.5
+    bd = torch.randn(Cmid, generator=g)
+    from test_kernels_gpu import _producer
+    norm, act = _producer(raw_u, dt, g, add=torch.randn(N, Cu, generator=g))
+    xbuf = torch.full((N, D, H, W, sstride), 3.0, dtype=dt, device="cuda")
+    ops.to_channels_last(xs.cuda(), xbuf, soff, Cs)
+    ubuf = torch.full((N, D // 2, H // 2, W // 2, ustride), 2.0, dtype=dt, device="cuda")
+    ops.to_channels_last(raw_u.cuda(), ubuf, uoff, Cu)
+    return (xs, raw_u, wc, bc, wd, bd, norm, xbuf, ubuf) + ((act,) if with_act else ())
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", [(False, False), (True, True)])
 @pytest.mark.parametrize("shape", [
@@ -158,23 +180,11 @@ def test_upconv_matches_deconv_cat_conv(shape, layout):
     in_blk, out_blk = layout
     if in_blk and (soff % 16 or sstride % 16 or ooff % 16 or ostride % 16):
         pytest.skip("blocked buffers need 16-channel offsets")
-    g = torch.Generator().manual_seed(sum(shape))
-    xs = torch.randn(N, Cs, D, H, W, generator=g)
-    raw_u = torch.randn(N, Cu, D // 2, H // 2, W // 2, generator=g) * 1.5 + 0.25
-    wc = torch.randn(Cout, Cs + Cmid, 3, 3, 3, generator=g) / (27 * (Cs + Cmid)) ** 0.5
-    bc = torch.randn(Cout, generator=g)
-    wd = torch.randn(Cu, Cmid, 2, 2, 2, generator=g) / Cu ** 0.5
-    bd = torch.randn(Cmid, generator=g)
-    from test_kernels_gpu import _producer
-    norm, act = _producer(raw_u, dt, g, add=torch.randn(N, Cu, generator=g))
+    xs, raw_u, wc, bc, wd, bd, norm, xbuf, ubuf, act = _upconv_operands(shape, with_act=True)
     up = F.conv_transpose3d(act.to(dt).float(), wd, bd, stride=2)
     ref = F.conv3d(torch.cat([xs.to(dt).float(), up], 1), wc, bc, padding=1)
-    xbuf = torch.full((N, D, H, W, sstride), 3.0, dtype=dt, device="cuda")
-    ops.to_channels_last(xs.cuda(), xbuf, soff, Cs)
     if in_blk:
         xbuf = ops.to_blocked(xbuf)
-    ubuf = torch.full((N, D // 2, H // 2, W // 2, ustride), 2.0, dtype=dt, device="cuda")
-    ops.to_channels_last(raw_u.cuda(), ubuf, uoff, Cu)
     ybuf = torch.full((N, D, H, W, ostride), -5.0, dtype=dt, device="cuda")
     w_skip, wu, btab = ops.pack_upconv_weights(wc.cuda(), bc.cuda(), wd.cuda(), bd.cuda(), Cs)
     stats = ops.stats_buffer(N, Cout, "cuda")
@@ -261,17 +271,9 @@ def test_deconv_res_matches_deconv_cat_pointwise(shape):
     dt = torch.float16
     N, Cs, Cu, Cmid, Cout, D, H, W = shape            # D, H, W: COARSE extents
     cu_packed = -(-Cu // 64) * 64
-    g = torch.Generator().manual_seed(sum(shape))
-    skip = torch.randn(N, Cs, 2 * D, 2 * H, 2 * W, generator=g)
-    lo = torch.randn(N, Cu, D, H, W, generator=g)
-    w3 = torch.randn(Cout, Cmid + Cs, generator=g) / (Cmid + Cs) ** 0.5
-    wd = torch.randn(Cu, Cmid, 2, 2, 2, generator=g) / Cu ** 0.5
+    skip, lo, w3, wd, cat, lbuf = _deconv_res_operands(shape)
     up = F.conv_transpose3d(lo.to(dt).float(), wd, None, stride=2)
     ref = F.conv3d(torch.cat([up, skip.to(dt).float()], 1), w3[:, :, None, None, None])
-    cat = torch.full((N, 2 * D, 2 * H, 2 * W, Cmid + Cs), 3.0, dtype=dt, device="cuda")     # the upsampled half is never read
-    ops.to_channels_last(skip.cuda(), cat, Cmid, Cs)
-    lbuf = torch.zeros((N, D, H, W, cu_packed), dtype=dt, device="cuda")
-    ops.to_channels_last(lo.cuda(), lbuf, 0, Cu)
     y = torch.full((N, 2 * D, 2 * H, 2 * W, Cout), -5.0, dtype=dt, device="cuda")
     assert ops.deconv_res_supported(dt, N, D, H, W, Cu, cu_packed, Cout, Cout, Cs)
     wp, wsp = ops.pack_deconv_res_weights(w3.cuda(), wd.cuda(), Cs, up_first=True)
@@ -280,10 +282,39 @@ def test_deconv_res_matches_deconv_cat_pointwise(shape):
     got = ops.from_channels_last(y, Cout, 0).cpu()
     err = (got - ref).abs()
     assert torch.allclose(got, ref, **TOL16), (float(err.max()), [int(v) for v in torch.nonzero(err == err.max())[0]])
-    # section-1 check of tests/fp64ref.py: the composed weights W3_up . Wd[child] formed in fp32 and rounded once to fp16 (as
-    # pack_deconv_res_weights does; a one-ulp flip of a weight whose fp32 composition sums in another order is the RSS term),
-    # the skip weights rounded to fp16, per element at the sampled fine-grid voxels
+    _deconv_res_fp64_check(got, skip, lo, w3, wd, shape)
+    st = ops.stats_decode(stats).cpu()[:, :Cout]
+    gd = got.double().flatten(2)
+    assert bool(((st[..., 0] - gd.sum(-1)).abs() <= 1e-3 * gd.abs().sum(-1) + 0.5).all())
+    assert bool(((st[..., 1] - (gd * gd).sum(-1)).abs() <= 2e-3 * (gd * gd).sum(-1) + 0.5).all())
+    assert not ops.deconv_res_supported(dt, N, D, H, W, 192, 192, Cout, Cout, Cs)          # more than 128 coarse channels
+
+
+def _deconv_res_operands(shape):
+    """(skip NCDHW on the fine grid, lo NCDHW, w3, wd, the concat buffer holding the skip half, the padded coarse buffer)."""
+    ops = _ops()
+    dt = torch.float16
+    N, Cs, Cu, Cmid, Cout, D, H, W = shape            # D, H, W: COARSE extents
+    cu_packed = -(-Cu // 64) * 64
+    g = torch.Generator().manual_seed(sum(shape))
+    skip = torch.randn(N, Cs, 2 * D, 2 * H, 2 * W, generator=g)
+    lo = torch.randn(N, Cu, D, H, W, generator=g)
+    w3 = torch.randn(Cout, Cmid + Cs, generator=g) / (Cmid + Cs) ** 0.5
+    wd = torch.randn(Cu, Cmid, 2, 2, 2, generator=g) / Cu ** 0.5
+    cat = torch.full((N, 2 * D, 2 * H, 2 * W, Cmid + Cs), 3.0, dtype=dt, device="cuda")     # the upsampled half is never read
+    ops.to_channels_last(skip.cuda(), cat, Cmid, Cs)
+    lbuf = torch.zeros((N, D, H, W, cu_packed), dtype=dt, device="cuda")
+    ops.to_channels_last(lo.cuda(), lbuf, 0, Cu)
+    return skip, lo, w3, wd, cat, lbuf
+
+
+def _deconv_res_fp64_check(got, skip, lo, w3, wd, shape):
+    """Section-1 check of tests/fp64ref.py: the composed weights W3_up . Wd[child] formed in fp32 and rounded once to fp16 (as
+    pack_deconv_res_weights does; a one-ulp flip of a weight whose fp32 composition sums in another order is the RSS term),
+    the skip weights rounded to fp16, per element at the sampled fine-grid voxels."""
     import fp64ref as R
+    dt = torch.float16
+    N, Cs, Cu, Cmid, Cout, D, H, W = shape
     pts = R.sample_voxels(N, (2 * D, 2 * H, 2 * W), n_random=1000, seed=sum(shape))
     child = (pts[:, 1] & 1) * 4 + (pts[:, 2] & 1) * 2 + (pts[:, 3] & 1)
     lo_q = lo.to(dt).double()[pts[:, 0], :, pts[:, 1] >> 1, pts[:, 2] >> 1, pts[:, 3] >> 1]                    # [P, Cu]
@@ -292,11 +323,7 @@ def test_deconv_res_matches_deconv_cat_pointwise(shape):
     bnd = R.bound(ref64, ab, sq, R.chain_length(Cu + Cs, dt), dt, emulated_in=dt)
     r = R.check(got.double()[pts[:, 0], :, pts[:, 1], pts[:, 2], pts[:, 3]], ref64, bnd, pts)
     assert r.ratio <= 1, r
-    st = ops.stats_decode(stats).cpu()[:, :Cout]
-    gd = got.double().flatten(2)
-    assert bool(((st[..., 0] - gd.sum(-1)).abs() <= 1e-3 * gd.abs().sum(-1) + 0.5).all())
-    assert bool(((st[..., 1] - (gd * gd).sum(-1)).abs() <= 2e-3 * (gd * gd).sum(-1) + 0.5).all())
-    assert not ops.deconv_res_supported(dt, N, D, H, W, 192, 192, Cout, Cout, Cs)          # more than 128 coarse channels
+    return r
 
 
 @pytest.mark.gpu
