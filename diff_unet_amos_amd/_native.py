@@ -227,6 +227,7 @@ _SIGS = {
     "dua_prepared_kernels": (C.c_int, []),
     "dua_mfma_probe": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
     "dua_chain_probe": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P]),
+    "dua_mfma_single": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "dua_deconv_k2s2_fwd": (C.c_int, [C.POINTER(Conv3Desc), _P, _P, _P, C.POINTER(InNorm), _P, _P]),
     "dua_deconv_k2s2_pad_fwd": (C.c_int, [C.POINTER(Conv3Desc), C.c_int, C.c_int, C.c_int, _P, _P, _P, C.POINTER(InNorm), _P, _P]),
     "dua_conv3d_k3_dgrad_reduce_supported": (C.c_int, [C.POINTER(Conv3Desc)]),

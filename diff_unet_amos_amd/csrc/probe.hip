@@ -81,6 +81,35 @@ __global__ __launch_bounds__(256) void chain_probe_kernel(int mode, const float*
   }
 }
 
+// What ONE matrix instruction computes, for tests/test_mfma_model_gpu.py: workgroup t (one wave) loads tile t of A, B and C,
+// issues a single D = C + A . B and stores D.  A: fp16 [tiles][M][K] (row i, then k); B: fp16 [tiles][N][K] (COLUMN j, then k:
+// the same mapping as A, csrc/common.hpp mma32); C, D: fp32 [tiles][M][N].  BIG: 32x32x16, else 16x16x32.
+template <bool BIG>
+__global__ __launch_bounds__(64) void mfma_single_kernel(const f16* A, const f16* B, const float* Cm, float* Dm) {
+  constexpr int MN = BIG ? 32 : 16, K = BIG ? 16 : 32;
+  const int l = threadIdx.x, r = l & (MN - 1), h = l / MN;
+  const size_t t = blockIdx.x;
+  const f16x8 a = *reinterpret_cast<const f16x8*>(A + (t * MN + r) * K + 8 * h);
+  const f16x8 b = *reinterpret_cast<const f16x8*>(B + (t * MN + r) * K + 8 * h);
+  const float* c = Cm + t * MN * MN;
+  float* d = Dm + t * MN * MN;
+  if constexpr (BIG) {                                   // register v of lane (r, h): row (v & 3) + 8 (v >> 2) + 4 h, column r
+    f32x16 acc;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = c[((v & 3) + 8 * (v >> 2) + 4 * h) * 32 + r];
+    mma32(acc, a, b);
+#pragma unroll
+    for (int v = 0; v < 16; ++v) d[((v & 3) + 8 * (v >> 2) + 4 * h) * 32 + r] = acc[v];
+  } else {                                               // register v of lane (r, h): row 4 h + v, column r
+    f32x4 acc;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc[v] = c[(4 * h + v) * 16 + r];
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) d[(4 * h + v) * 16 + r] = acc[v];
+  }
+}
+
 }  // namespace dua
 
 extern "C" int dua_chain_probe(int mode, int workgroups, const float* in, float* out, unsigned long long* words, void* stream) {
@@ -94,5 +123,17 @@ extern "C" int dua_chain_probe(int mode, int workgroups, const float* in, float*
 extern "C" int dua_mfma_probe(int workgroups, int iters, float* sink, unsigned long long* stamps, void* stream) {
   if (workgroups <= 0 || iters <= 0 || !sink) return DUA_ERR_ARG;
   hipLaunchKernelGGL(dua::mfma_probe_kernel, dim3(workgroups), dim3(256), 0, (hipStream_t)stream, iters, sink, stamps);
+  return (int)hipGetLastError();
+}
+
+// One v_mfma_f32_32x32x16_f16 (shape 0) or v_mfma_f32_16x16x32_f16 (shape 1) per tile, one single-wave workgroup per tile.
+extern "C" int dua_mfma_single(int shape, int tiles, const void* A, const void* B, const float* C, float* D, void* stream) {
+  if (shape < 0 || shape > 1 || tiles <= 0 || tiles > 65536 || !A || !B || !C || !D) return DUA_ERR_ARG;
+  if (shape == 0)
+    hipLaunchKernelGGL(dua::mfma_single_kernel<true>, dim3(tiles), dim3(64), 0, (hipStream_t)stream, (const dua::f16*)A,
+                       (const dua::f16*)B, C, D);
+  else
+    hipLaunchKernelGGL(dua::mfma_single_kernel<false>, dim3(tiles), dim3(64), 0, (hipStream_t)stream, (const dua::f16*)A,
+                       (const dua::f16*)B, C, D);
   return (int)hipGetLastError();
 }

@@ -540,6 +540,12 @@ int dua_mfma_probe(int workgroups, int iters, float* sink, unsigned long long* s
  * 3 + a read of the words the previous launch's atomics wrote.  in/out: workgroups * 256 floats; words: 64 x 8 bytes. */
 int dua_chain_probe(int mode, int workgroups, const float* in, float* out, unsigned long long* words, void* stream);
 
+/* Measurement aid (tests/test_mfma_model_gpu.py): what ONE fp16 matrix instruction computes.  One single-wave workgroup per
+ * tile issues a single D = C + A . B: shape 0 = v_mfma_f32_32x32x16_f16 (M = N = 32, K = 16), shape 1 =
+ * v_mfma_f32_16x16x32_f16 (M = N = 16, K = 32).  A: fp16 [tiles][M][K]; B: fp16 [tiles][N][K] (column j of B, then k);
+ * C, D: fp32 [tiles][M][N].  tiles <= 65536. */
+int dua_mfma_single(int shape, int tiles, const void* A, const void* B, const float* C, float* D, void* stream);
+
 /* Packs nn.Conv3d weight fp32[Cout][Cin_src][3][3][3] into the kernel's slab order
  * [cout_tile][chunk][kd][kh*3+kw][k-group][64][16 B].  in_perm (device int32[Cin_packed], may be
  * NULL = identity) gives for each packed input channel its source channel, or -1 for a zero pad

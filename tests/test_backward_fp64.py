@@ -306,8 +306,9 @@ def test_dgrad_reduce_within_fp64_bound(cin):
 
 
 # ---- head and max-pool backward ---------------------------------------------------------------------------------------------------
-def _check_head_bwd(u, dl, w, du, dW, db, mfma):
-    """du, dW, db of ops.head_bwd against fp64 on the operands it read; ``mfma``: the launch took the MFMA path (fp16 weights)."""
+def _check_head_bwd(u, dl, w, du, dW, db, mfma, nominal=False):
+    """du, dW, db of ops.head_bwd against fp64 on the operands it read; ``mfma``: the launch took the MFMA path (fp16 weights);
+    ``nominal``: with the bound's term for subnormal fp16 operands (the three contractions are MFMA ones; db multiplies by ones)."""
     dtype = u.dtype
     C, K = u.shape[-1], dl.shape[-1]
     V = u.numel() // C
@@ -315,12 +316,21 @@ def _check_head_bwd(u, dl, w, du, dW, db, mfma):
     ud, dld = u.double().reshape(V, C), dl.double().reshape(V, K)
     wq = (w.half() if mfma else w).double()                  # the MFMA path multiplies fp16 weights
     ref_du = dld @ wq
-    b_du = R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, dtype)
-    r1 = R.check(du.reshape(V, C), ref_du, b_du)
+    b_du = R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, dtype, nominal=R.nominal_sum(dld, wq) if nominal else None)
     ref_w, ab_w = dld.t() @ ud, dld.abs().t() @ ud.abs()
-    r2 = R.check(dW, ref_w, R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32)
+    b_w = R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32
     ref_b, ab_b = dld.sum(0), dld.abs().sum(0)
-    r3 = R.check(db, ref_b, R.U32 * c_w * ab_b * (1 + R.U32) + R.FLOOR32)
+    b_b = R.U32 * c_w * ab_b * (1 + R.U32) + R.FLOOR32
+    if nominal:
+        assert mfma
+        t_w = R.subnormal_term(R.nominal_sum(dld.t(), ud)) * (1 + R.U32)
+        t_b = R.subnormal_term(R.nominal_sum(dld.t(), torch.ones_like(ud[:, :1]))[:, 0]) * (1 + R.U32)
+        print(f"head bwd: the subnormal term is {_share(R.subnormal_term(R.nominal_sum(dld, wq)), b_du)} of du's bound, "
+              f"{_share(t_w, b_w + t_w)} of dW's, {_share(t_b, b_b + t_b)} of db's")
+        b_w, b_b = b_w + t_w, b_b + t_b
+    r1 = R.check(du.reshape(V, C), ref_du, b_du)
+    r2 = R.check(dW, ref_w, b_w)
+    r3 = R.check(db, ref_b, b_b)
     print(f"head bwd {dtype}: du {r1}; dW {r2}; db {r3}")
     assert max(r1.ratio, r2.ratio, r3.ratio) <= 1.0, (r1, r2, r3)
 
@@ -395,7 +405,8 @@ def _deconv_bwd_operands(dims, fine, cin, cout, cskip, N=2, dt=F16):
     return x, dcat, w
 
 
-def _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw, N=2, dt=F16):
+def _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw, N=2, dt=F16, nominal=False):
+    """``nominal``: with the bound's term for subnormal fp16 operands on both contractions"""
     nv = _nv()
     D, H, W = dims
     padded = tuple(fine) != (2 * D, 2 * H, 2 * W)
@@ -406,12 +417,210 @@ def _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw, N=2, dt=
     dyf = R.deconv_fold_dy(dcat[..., cskip:], D, H, W)
     xs = x[..., 8:8 + cin]
     ref, ab, sq, rw, aw = R.deconv_bwd_ref(xs, dyf, w, dt)
-    r1 = R.check(dx, ref, R.bound(ref, ab, sq, c_dx, dt, emulated_in=dt if padded else None))
+    ndx, ndw = R.deconv_bwd_nominal(xs, dyf, w, padded) if nominal else (None, None)
+    b1 = R.bound(ref, ab, sq, c_dx, dt, emulated_in=dt if padded else None, nominal=ndx)
+    r1 = R.check(dx, ref, b1)
     b2 = R.U32 * c_dw * aw * (1 + R.U32) + R.FLOOR32
     if padded:
         A2 = (dyf * dyf).reshape(N, D, 2, H, 2, W, 2, cout).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(-1, 8 * cout)
         ssq = ((xs.double().reshape(-1, cin) ** 2).t() @ A2).reshape(cin, 2, 2, 2, cout).permute(0, 4, 1, 2, 3).contiguous()
         b2 = b2 + R.C_RSS * R.U16 * ssq.sqrt()
+    if nominal:
+        b2 = b2 + R.subnormal_term(ndw) * (1 + R.U32)
+        print(f"deconv bwd: the subnormal term is {_share(R.subnormal_term(ndx), b1)} of dx's bound, {_share(R.subnormal_term(ndw), b2)} of dw's")
     r2 = R.check(dw, rw, b2)
     print(f"deconv bwd {dims}->{fine} {cin}->{cout} P={P}{' padded' if padded else ''}: dx {r1}; dw {r2}")
     assert r1.ratio <= 1.0 and r2.ratio <= 1.0, (r1, r2)
+
+
+# ---- fp16 operands below the normal range -------------------------------------------------------------------------------------------
+# What a step at the trainer's initial loss scale feeds the backward kernels: gradient operands that straddle 2^-14, lie below it
+# throughout, or are a few subnormal ulps (fp64ref.subnormal_regime), the other operand O(1) as above.  The bounds are the ones
+# above plus fp64ref's term for subnormal operands, derived from the matrix-instruction model that tests/test_mfma_model_gpu.py holds
+# on the instruction; every element is compared, and the floor of half a subnormal ulp in the bound of an fp16 output makes a
+# flushed OUTPUT fail as well.
+def _share(term, bnd):
+    return f"{float((term / bnd).mean()):.2f}"
+
+
+def _gradient(shape, regime, seed):
+    """the gradient operand of a regime on the device; its subnormal share is asserted before anything is launched"""
+    t, want = R.subnormal_regime(shape, regime, seed, DEV)
+    got = R.subnormal_share(t)
+    assert abs(got - want) < 0.02, (regime, got, want)
+    return t
+
+
+GEOS.update({"sub4": (1, 4, 4, 4, 512, 0, 512, 512, 0, 512, 512, False),       # the deepest level of a 64^3 step: the taps route
+             "sub2": (1, 2, 2, 2, 512, 0, 512, 512, 0, 512, 512, False),
+             "subragged": (2, 6, 5, 7, 40, 0, 40, 72, 0, 72, 40, False)})      # the plain route, every tile ragged
+SUB_WGRAD = [("sub4", 0, "full", "fo-taps"), ("sub2", 0, "full", "fo-taps"), ("subragged", 0, "full", "fo-plain"),
+             ("l12", THREE_KD, "full", "3kd-part"), ("l12", THREE_KD, "short", "3kd-atomic")]
+_SUB_CACHE = {}
+
+
+def _sub_wgrad_operands(geo, regime):
+    key = (geo, regime)
+    if key not in _SUB_CACHE:
+        _SUB_CACHE.clear()
+        N, D, H, W, cx, co_x, cin, cy, co_y, cout, cin_src, _ = GEOS[geo]
+        seed = sum(map(ord, geo + regime))
+        x = _randn((N, D, H, W, cx), seed, F16)
+        dy = _gradient((N, D, H, W, cy), regime, seed + 1)
+        dw0 = _randn((cout, cin_src, 3, 3, 3), seed + 2, F32, scale=2.0 ** -20)
+        _SUB_CACHE[key] = (x, dy, dw0) + R.wgrad_ref(x, co_x, cin, dy, co_y, cout, cin_src=cin_src, nominal=True)
+    return _SUB_CACHE[key]
+
+
+@pytest.mark.parametrize("regime", R.SUBNORMAL_REGIMES)
+@pytest.mark.parametrize("geo,policy,ws_mode,route", SUB_WGRAD, ids=[f"{c[0]}-{c[3]}" for c in SUB_WGRAD])
+def test_conv3_wgrad_subnormal_dy_within_fp64_bound(geo, policy, ws_mode, route, regime):
+    ops = _ops()
+    N, D, H, W, cx, co_x, cin, cy, co_y, cout, cin_src, _ = GEOS[geo]
+    x, dy, dw0, ref, ab, nom = _sub_wgrad_operands(geo, regime)
+    form = _form(geo, F16, policy, ws_mode, None)
+    assert form["name"] == route, form
+    assert _wgrad_ws(geo, F16, policy) == form["ws"], "partition mirror drifted from the launcher"
+    ws = torch.empty(max(form["ws"], 16) if ws_mode == "full" else 16, dtype=torch.uint8, device=DEV)
+    assert ws_mode == "full" or form["ws"] > 16
+    dw = dw0.clone()
+    ops.WGRAD_POLICY = policy
+    try:
+        ops.conv3d_k3_wgrad(x, cin, co_x, dy, cout, co_y, dw, workspace=ws)
+    finally:
+        ops.WGRAD_POLICY = 0
+    torch.cuda.synchronize()
+    bnd = R.wgrad_bound(ref, ab, dw0, form["chain"], nominal=nom)
+    res = R.check(dw.double(), dw0.double() + ref, bnd)
+    old = R.check(dw.double(), dw0.double() + ref, R.wgrad_bound(ref, ab, dw0, form["chain"]))
+    print(f"wgrad {geo} {regime} {form['name']} P={form['P']} tiles={form['total']}: {res}; the subnormal term is "
+          f"{_share(R.subnormal_term(nom), bnd)} of the bound (without it: ratio {old.ratio:.3g})")
+    assert res.ratio <= 1.0, res
+
+
+def _dense_conv_check(tag, x, cin, w_ref, bias, y, cout, chain):
+    """every element of a 3x3x3 convolution launch (forward, or the data gradient on flipped, transposed weights) against fp64"""
+    ref, ab, sq, nom = R.conv3_dense_ref(x, cin, R.conv3_weights(w_ref, F16), bias, nominal=True)
+    bnd = R.bound(ref, ab, sq, chain, F16, nominal=nom)
+    res = R.check(y[..., :cout], ref, bnd)
+    sub_out = R.subnormal_share(y[..., :cout])
+    print(f"{tag}: {res}; the subnormal term is {_share(R.subnormal_term(nom), bnd)} of the bound; {sub_out:.2f} of the stored outputs "
+          f"are subnormal")
+    assert res.ratio <= 1.0, res
+
+
+SUB_DGRAD = [(2, 6, 512, 512), (1, 12, 256, 256)]
+
+
+@pytest.mark.parametrize("regime", R.SUBNORMAL_REGIMES)
+@pytest.mark.parametrize("N,S,cin_f,cout_f", SUB_DGRAD, ids=[f"{n}x{s}^3-{a}to{b}" for (n, s, a, b) in SUB_DGRAD])
+def test_conv3_dgrad_subnormal_dy_within_fp64_bound(N, S, cin_f, cout_f, regime):
+    """training._dgrad as in test_conv3_dgrad_launch_within_fp64_bound, dy in the regime, every element of dx"""
+    ops, nv = _ops(), _nv()
+    dy = _gradient((N, S, S, S, cout_f), regime, S + cin_f)
+    w = _randn((cout_f, cin_f, 3, 3, 3), S + cout_f, F32, scale=(27 * cout_f) ** -0.5)
+    wp, bp = ops.pack_conv3_weights_dgrad(w, F16, cout_packed=cout_f)
+    ws = ops.splitk_ws(F16, N, S, S, S, cout_f, cin_f, DEV)
+    d = nv.Conv3Desc(nv.dt_code(F16), N, S, S, S, cout_f, cout_f, 0, cin_f, cin_f, 0, 0, 0, 0, ops.CONV_POLICY)
+    split = ops.conv3_form(d, False, 0 if ws is None else ws.numel() * ws.element_size()).ksplit > 1
+    dx = torch.empty((N, S, S, S, cin_f), dtype=F16, device=DEV)
+    ops.conv3d_k3(dy, cout_f, 0, wp, bp, cin_f, dx, 0, ops.stats_buffer(N, cin_f, DEV), workspace=ws)
+    torch.cuda.synchronize()
+    parts = 3 * -(-cout_f // ops.chunk_elems(F16)) if split else 0
+    _dense_conv_check(f"dgrad {N}x{S}^3 {cout_f}->{cin_f} {regime} split {split}", dy, cout_f,
+                      w.flip(2, 3, 4).transpose(0, 1).contiguous(), None, dx, cin_f, R.chain_length(27 * cout_f, F16, parts))
+
+
+@pytest.mark.parametrize("regime", R.SUBNORMAL_REGIMES)
+def test_dgrad_reduce_subnormal_dy_within_fp64_bound(regime):
+    """conv3d_k3_dgrad_reduce at the smallest shape it supports (262 144 voxels: 1 x 64^3, 64 -> 64), every element of dx"""
+    ops = _ops()
+    N, S, C = 1, 64, 64
+    assert ops.conv3d_k3_dgrad_reduce_supported(F16, N, S, S, S, C, C)
+    assert not any(ops.conv3d_k3_dgrad_reduce_supported(F16, 1, a, b, c, C, C) for a, b, c in ((64, 64, 56), (56, 64, 64), (64, 56, 64)))
+    dy = _gradient((N, S, S, S, C), regime, 61)
+    w = _randn((C, C, 3, 3, 3), 62, F32, scale=(27 * C) ** -0.5)
+    raw, gamma, beta, stats, norm = _norm_case(N, S, C, 63)
+    wp, bp = ops.pack_conv3_weights_dgrad(w, F16, cout_packed=C)
+    dx = torch.empty((N, S, S, S, C), dtype=F16, device=DEV)
+    ops.conv3d_k3_dgrad_reduce(dy, C, wp, bp, C, dx, raw, norm, ops.instnorm_bwd_sums(raw, norm))
+    torch.cuda.synchronize()
+    _dense_conv_check(f"dgrad_reduce 64^3 {regime}", dy, C, w.flip(2, 3, 4).transpose(0, 1).contiguous(), None, dx, C,
+                      R.chain_length(27 * C, F16))
+
+
+SUB_DECONV = [((2, 2, 2), (4, 4, 4), 512, 256, 256), ((5, 4, 6), (11, 8, 13), 128, 64, 64)]      # the second: padded on two axes
+
+
+@pytest.mark.parametrize("regime", R.SUBNORMAL_REGIMES)
+@pytest.mark.parametrize("dims,fine,cin,cout,cskip", SUB_DECONV, ids=["2x2x2-512to256", "5x4x6-padded-128to64"])
+def test_deconv_backward_subnormal_dy_within_fp64_bound(dims, fine, cin, cout, cskip, regime):
+    ops = _ops()
+    x, _, w = _deconv_bwd_operands(dims, fine, cin, cout, cskip)
+    dcat = _gradient((2, *fine, cskip + cout), regime, sum(fine) + cin)
+    dx, dw = ops.deconv_k2s2_bwd(x, cin, 8, dcat, cout, cskip, w)
+    torch.cuda.synchronize()
+    _check_deconv_bwd(dims, fine, cin, cout, cskip, x, dcat, w, dx, dw, nominal=True)
+
+
+def test_head_backward_on_loss_gradients_at_the_initial_scale():
+    """(1, 5, 7, 9) voxels, 64 channels, 16 classes: dlogits = seg_loss_grad at 2^12 x dcomb on logits spread over +-16 whose labels
+    mostly agree with them -- where the sigmoid saturates the gradient underflows into the subnormals, as it does in training."""
+    ops = _ops()
+    N, dims, C, K = 1, (5, 7, 9), 64, 16
+    g = torch.Generator(device=DEV).manual_seed(71)
+    logits = ((torch.rand((N, *dims, K), generator=g, device=DEV) * 32 - 16)).to(F16)
+    flip = torch.rand((N, *dims, K), generator=g, device=DEV) < 0.05
+    labels = ((logits > 0) ^ flip).float().permute(0, 4, 1, 2, 3).contiguous()
+    _, sums, dcomb = ops.seg_loss_reduce(logits, labels)
+    dl = ops.seg_loss_grad(logits, labels, sums, dcomb * 2.0 ** 12)
+    share = R.subnormal_share(dl)
+    print(f"head bwd: {share:.2f} of the loss gradient is subnormal, {float((dl == 0).float().mean()):.2f} zero")
+    assert share > 0.25, share
+    u = _randn((N, *dims, C), 72, F16)
+    w = _randn((K, C), 73, F32, scale=0.2)
+    du, dW, db = ops.head_bwd(dl, u, w)
+    torch.cuda.synchronize()
+    _check_head_bwd(u, dl, w, du, dW, db, mfma=True, nominal=True)
+
+
+def _decayed(shape, seed):
+    w, want = R.subnormal_regime(shape, "decayed", seed, DEV)
+    assert abs(R.subnormal_share(w) - want) < 0.02
+    return w
+
+
+def test_conv3_forward_with_weights_across_the_normal_boundary():
+    """conv3d_k3 fp16, 1 x 8^3, 64 -> 64, weights log-uniform in [2^-20, 2^-8] (what a decayed layer can hold): the packer and the
+    kernel must keep the subnormal half of them"""
+    ops = _ops()
+    N, S, C = 1, 8, 64
+    x = _randn((N, S, S, S, C), 81, F16)
+    w = _decayed((C, C, 3, 3, 3), 82).float()
+    b = _randn((C,), 83, F32, scale=2.0 ** -12)
+    wp, bp = ops.pack_conv3_weights(w, b, F16)
+    y = torch.empty((N, S, S, S, C), dtype=F16, device=DEV)
+    ops.conv3d_k3(x, C, 0, wp, bp, C, y, 0, ops.stats_buffer(N, C, DEV))
+    torch.cuda.synchronize()
+    _dense_conv_check("conv3d_k3 forward, decayed weights", x, C, w, b, y, C, R.chain_length(27 * C, F16))
+
+
+def test_token_gemm_with_weights_across_the_normal_boundary():
+    """token_gemm at the smallest K-split case of test_swin_fp64.TOKGEMM (64 x 520 -> 64, 3 K slices), every row"""
+    ops, nv = _ops(), _nv()
+    M, K, Nn, ks = 64, 520, 64, 3
+    assert int(nv.lib().dua_token_gemm_workspace(M, K, Nn)) > 0          # the K-split form
+    A = _randn((M, K), 91, F16)
+    Wt = _decayed((Nn, K), 92)
+    b = _randn((Nn,), 93, F32, scale=2.0 ** -12)
+    out = torch.empty((M, Nn), dtype=F16, device=DEV)
+    ops.token_gemm(A, Wt, b, "plain", out=out)
+    torch.cuda.synchronize()
+    Ad, Wd = A.double(), Wt.double()
+    ref, ab, sq = R.contract(Ad, Wd.t())
+    ref, ab = ref + b.double()[None], ab + b.double().abs()[None]
+    nom = R.nominal_sum(Ad, Wd.t())
+    bnd = R.bound(ref, ab, sq, R.chain_length(K, F16, ks), F16, nominal=nom)
+    res = R.check(out, ref, bnd)
+    print(f"token_gemm {M}x{K}->{Nn}, decayed weights: {res}; the subnormal term is {_share(R.subnormal_term(nom), bnd)} of the bound")
+    assert res.ratio <= 1.0, res

@@ -21,22 +21,25 @@ ops.conv3d_k3_dgrad_reduce_supported answer and be non-empty.  ``odd-b2``: N = 2
 different scale -- floor pooling, replicate-padded transposed convolutions and their backward, the odd max-pool backward, two sample
 rows in every temb block, per-sample statistics.
 
-The backward is seeded with 2^22, not the 2^12 the harness tests use.  Measured at 2^12 (the figures are records, not thresholds): the
-output gradients of the two deepest levels (4^3, 2^3 voxels) are fp16 SUBNORMALS throughout (mean |dy| 3e-7 and 5e-8), and the
-fetch-once weight gradient of those layers then lands up to 1.07 (even-64, enc.down_4.conv_1) and 2.89 (odd-b2, down_4.conv_1) times its
-bound, 7e-6 of the element.  The kernel alone on random operands, 4^3 x 512 -> 512, max |err| / (2^-24 sum |terms|): 3.2 with dy in the
-normal range, 12.7 with every dy below 2^-14, 95 with dy of a few subnormal ulps -- against a chain of 22.  fp64ref's bounds rest on
-fp16 x fp16 products that are exact in fp32 and summed with one rounding per addition; the matrix instruction does not keep that for
-an operand without a normalised significand, and no existing derivation covers it (its internal alignment width is not documented).
-Every bound here is therefore applied where its premise holds: with the seed at 2^22 the deepest dy are in the normal range
-(the share of subnormal dy operands is printed with every weight-gradient row), nothing overflows (a non-finite value has ratio inf),
-and the bounds are the existing ones, unchanged.  What this leaves unchecked is the accuracy of dW at levels whose dy underflows,
-which is what a step at the trainer's initial loss scale of 2^12 computes: a bound for it needs a term for subnormal operands.
+Two loss scales.  ``test_training_step_wiring_and_every_launch_in_fp64`` seeds the backward with 2^22: the output gradients of every
+level are in fp16's normal range, and the bounds are the ones the per-kernel tests derive, without the term below.
+``test_training_step_at_the_trainers_initial_loss_scale`` seeds it with NativeConvTrainer's own default ``init_scale`` (2^12, read
+from the signature), the regime every fp16 run starts in: the output gradients of the two deepest levels (4^3, 2^3 voxels) are then
+fp16 SUBNORMALS throughout (mean |dy| 3e-7 and 5e-8), and the share of subnormal dy is printed with every weight-gradient, data-
+gradient, transposed-convolution-backward and head-backward row.  fp64ref's accumulation rule alone does not hold there: the fetch-once
+weight gradient of those layers lands up to 1.07 (even-64, enc.down_4.conv_1) and 2.89 (odd-b2, down_4.conv_1) times the old bound,
+because the matrix instruction aligns its products by exponent FIELD and a subnormal operand sits up to 10 bits below its field.
+tests/test_mfma_model_gpu.py measures that on the instruction (24 places below the largest nominal exponent of a step of 8 products
+arrive, the 25th does not) and fp64ref's ``nominal=`` term turns it into a derived part of the bound (fp64ref's module docstring);
+the backward MFMA launches (dgrad, dgrad_reduce, wgrad, deconv_bwd, head_bwd) are held to the bound with that term, every other
+launch to the same bound as at 2^22, and nothing overflows (a non-finite value has ratio inf).
 
 Measured worst |err| / bound per kind (even-64; odd-b2), records: conv .992 .992, fold .755, mat .998 .999, deconv .993 .993, head_fwd
 .987 .990, loss_reduce .352 .570, loss_grad .997 .995, head_bwd .998 .998, pool_bwd .999 .999, norm_bwd .998 .998, dgrad .914 .924,
 dgrad_reduce .910, wgrad .204 .138, deconv_bwd .966 .901, bias_stats .053 .090, bias_sums .993 .969, temb_fwd .404 .430, temb_bwd .998
-.961, to_cl .999 .999; near-kink share at most 1.2e-7 (enc.conv_0.conv_1) and 5.1e-7 (upcat_1.conv_0), zero in every other layer."""
+.961, to_cl .999 .999; near-kink share at most 1.2e-7 (enc.conv_0.conv_1) and 5.1e-7 (upcat_1.conv_0), zero in every other layer.
+At the trainer's scale, the backward kinds: head_bwd .991 .974, pool_bwd .940 .982, norm_bwd .999 .996, dgrad .880 .894, dgrad_reduce
+.867, wgrad .159 .128, deconv_bwd .935 .783, loss_grad .935 .980, temb_bwd .999 .969; subnormal dy per layer 0.3 .. 0.95 (even-64)."""
 import ctypes
 import time
 import zlib
@@ -112,10 +115,11 @@ def _expected_routes(table, N, dims, fold_on):
 
 # ---- per-launch references ------------------------------------------------------------------------------------------------------------------
 class _Ctx:
-    def __init__(self, case, table, net):
+    def __init__(self, case, table, net, nominal=False):
         from diff_unet_amos_amd import _native as nv
         from diff_unet_amos_amd import ops
         self.case, self.table, self.ops, self.nv = case, table, ops, nv
+        self.nominal = nominal             # bounds of the backward MFMA launches with fp64ref's term for subnormal fp16 operands
         self.params = {n: p.detach() for n, p in net.named_parameters()}
         self.prefix = {f"{b.name}.{c}": f"{b.prefix}.{c}" for b in table.blocks for c in ("conv_0", "conv_1")}
         self.rows, self.near, self._pts, self.spent = [], [], {}, {}
@@ -154,9 +158,15 @@ def _stats_ratio(c, y, stats):
     return R.check(torch.stack([words[..., 0], words[..., 1]]), torch.stack([S, Q]), torch.stack([bs, bq]))
 
 
-def _conv_like(c, r, x, y, w, bias, cin, cout, cs_in, cs_out, stats=None):
+def _sub(t):
+    """share of subnormal elements of an fp16 gradient operand, for the printed rows"""
+    return f"dy-subnormal={R.subnormal_share(t):.2f}"
+
+
+def _conv_like(c, r, x, y, w, bias, cin, cout, cs_in, cs_out, stats=None, gradient=False):
     """A 3x3x3 convolution launch (forward, or the data gradient = the forward kernel on flipped, transposed weights): sampled
-    outputs against gather_taps + conv3_ref within R.bound, split-K partials from the launcher's own form."""
+    outputs against gather_taps + conv3_ref within R.bound, split-K partials from the launcher's own form.  ``gradient``: x is a
+    gradient operand (its subnormal share is printed; with c.nominal the bound has the term for subnormal operands)."""
     ops, nv = c.ops, c.nv
     N, D, H, W = r.meta["dims"][:4]
     d = nv.Conv3Desc(nv.dt_code(F16), N, D, H, W, cin, cs_in, r.meta.get("cin_off", 0), cout, cs_out, r.meta.get("cout_off", 0), 0, 0, 0,
@@ -164,11 +174,14 @@ def _conv_like(c, r, x, y, w, bias, cin, cout, cs_in, cs_out, stats=None):
     split = r.kind != "dgrad_reduce" and ops.conv3_form(d, False, r.meta["ws_bytes"]).ksplit > 1
     pts = c.pts(N, (D, H, W))
     A, _ = R.gather_taps(x, pts, 0, cin)
-    ref, ab, sq = _dev_contract(A, R.conv3_weights(w, F16), bias)
+    Wm = R.conv3_weights(w, F16)
+    ref, ab, sq = _dev_contract(A, Wm, bias)
     parts = 3 * -(-cin // ops.chunk_elems(F16)) if split else 0
-    bnd = R.bound(ref, ab, sq, R.chain_length(27 * cin, F16, parts), F16)
+    nom = R.nominal_sum(A.reshape(A.shape[0], -1).cuda(), Wm.cuda()).cpu() if gradient and c.nominal else None
+    bnd = R.bound(ref, ab, sq, R.chain_length(27 * cin, F16, parts), F16, nominal=nom)
     res = R.check(R.gather_points(y, pts, 0, cout), ref, bnd, pts)
-    c.row(r, "split" if split else "", f"{N}x{D}x{H}x{W} {cin}->{cout}", len(pts), res)
+    what = " ".join((["split"] if split else []) + ([_sub(x[..., :cin])] if gradient else []))
+    c.row(r, what, f"{N}x{D}x{H}x{W} {cin}->{cout}", len(pts), res)
     if stats is not None:
         c.row(r, "stats", f"{N}x{cout}", N * cout * 2, _stats_ratio(c, y, stats))
 
@@ -189,7 +202,8 @@ def chk_dgrad(c, r):
     cin, cout = r.meta["cin"], r.meta["cout"]
     assert tuple(wd.shape[:2]) == (cout, cin), (wd.shape, cin, cout)
     r.meta.setdefault("ws_bytes", 0)
-    _conv_like(c, r, r.ins["dy"].t, r.outs["dx"].t, wd, torch.zeros(cout), cin, cout, r.meta.get("cs_in", cin), r.meta.get("cs_out", cout))
+    _conv_like(c, r, r.ins["dy"].t, r.outs["dx"].t, wd, torch.zeros(cout), cin, cout, r.meta.get("cs_in", cin), r.meta.get("cs_out", cout),
+               gradient=True)
 
 
 def chk_fold(c, r):
@@ -321,10 +335,16 @@ def chk_head_bwd(c, r):
     ud, dld = u.double().reshape(V, C), dl.double().reshape(V, K)
     wq = w.half().double()                                 # the MFMA path multiplies fp16 weights
     ref_du = dld @ wq
-    c.row(r, "du", f"{V}x{K}->{C}", V * C, R.check(r.outs["du"].t.reshape(V, C), ref_du, R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, F16)))
+    t_du = t_w = t_b = None
+    if c.nominal:                                          # three MFMA contractions over dlogits (db multiplies by ones)
+        t_du = R.nominal_sum(dld, wq)
+        t_w = R.subnormal_term(R.nominal_sum(dld.t(), ud)) * (1 + R.U32)
+        t_b = R.subnormal_term(R.nominal_sum(dld.t(), torch.ones_like(ud[:, :1]))[:, 0]) * (1 + R.U32)
+    c.row(r, f"du {_sub(dl)}", f"{V}x{K}->{C}", V * C,
+          R.check(r.outs["du"].t.reshape(V, C), ref_du, R.bound(ref_du, dld.abs() @ wq.abs(), None, c_du, F16, nominal=t_du)))
     ref_w, ab_w = dld.t() @ ud, dld.abs().t() @ ud.abs()
-    c.row(r, "dW", f"{K}x{C}", K * C, R.check(r.outs["dW"].t, ref_w, R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32))
-    c.row(r, "db", f"{K}", K, R.check(r.outs["db"].t, dld.sum(0), R.U32 * c_w * dld.abs().sum(0) * (1 + R.U32) + R.FLOOR32))
+    c.row(r, "dW", f"{K}x{C}", K * C, R.check(r.outs["dW"].t, ref_w, R.U32 * c_w * ab_w * (1 + R.U32) + R.FLOOR32 + (0.0 if t_w is None else t_w)))
+    c.row(r, "db", f"{K}", K, R.check(r.outs["db"].t, dld.sum(0), R.U32 * c_w * dld.abs().sum(0) * (1 + R.U32) + R.FLOOR32 + (0.0 if t_b is None else t_b)))
 
 
 def chk_pool_bwd(c, r):
@@ -380,16 +400,18 @@ def chk_wgrad(c, r):
     dw, dw0 = r.outs["dw"].t, m["dw0"]
     assert not m["perm"] and not bool(dw0.any())
     cin_src = dw.shape[1]
-    ref, ab = R.wgrad_ref(r.ins["x"].t, 0, cin, r.ins["dy"].t, 0, cout, cin_src=cin_src)
+    ref, ab, *nom = R.wgrad_ref(r.ins["x"].t, 0, cin, r.ins["dy"].t, 0, cout, cin_src=cin_src, nominal=c.nominal)
     P, combos, total = R.wgrad_fo_partitions(N, D, H, W, cin, cout, 0)
     route = R.wgrad_fo_route(combos, None)
     d = nv.Conv3Desc(nv.dt_code(F16), N, D, H, W, cin, m["cs_in"], 0, cout, m["cs_out"], 0, 0, 0, 0, c.ops.WGRAD_POLICY)
     ws = int(nv.lib().dua_conv3d_k3_wgrad_workspace(ctypes.byref(d)))
     assert ws == P * combos * 27 * 2048 * 4, f"{r.label}: partition mirror drifted from the launcher: {ws} vs P={P} combos={combos}"
-    res = R.check(dw.double(), dw0.double() + ref, R.wgrad_bound(ref, ab, dw0, R.wgrad_fo_chain(P, total, route)))
+    bnd = R.wgrad_bound(ref, ab, dw0, R.wgrad_fo_chain(P, total, route), nominal=nom[0] if nom else None)
+    res = R.check(dw.double(), dw0.double() + ref, bnd)
     dy = r.ins["dy"].t
     sub = float(((dy != 0) & (dy.abs() < 2.0 ** -14)).float().mean())
-    c.row(r, f"fo-{route} P={P} dy-subnormal={sub:.2f}", f"{N}x{D}x{H}x{W} {cin}({cin_src})->{cout}", dw.numel(), res)
+    term = f" sub-term={float((R.subnormal_term(nom[0]) / bnd).mean()):.2f}" if nom else ""       # its mean share of the bound
+    c.row(r, f"fo-{route} P={P} dy-subnormal={sub:.2f}{term}", f"{N}x{D}x{H}x{W} {cin}({cin_src})->{cout}", dw.numel(), res)
 
 
 def chk_deconv_bwd(c, r):
@@ -407,8 +429,12 @@ def chk_deconv_bwd(c, r):
     dyf = R.deconv_fold_dy(dy, D, H, W)
     ref, ab, sq, rw, aw = R.deconv_bwd_ref(xs, dyf, w, F16)
     shape = f"{N}x{D}x{H}x{W} {cin}<-{cout}{' padded' if padded else ''}"
-    c.row(r, "dx", shape, ref.numel(), R.check(r.outs["dx"].t, ref, R.bound(ref, ab, sq, c_dx, F16, emulated_in=F16 if padded else None)))
+    ndx, ndw = R.deconv_bwd_nominal(xs, dyf, w, padded) if c.nominal else (None, None)
+    c.row(r, f"dx {_sub(dy)}", shape, ref.numel(),
+          R.check(r.outs["dx"].t, ref, R.bound(ref, ab, sq, c_dx, F16, emulated_in=F16 if padded else None, nominal=ndx)))
     b2 = R.U32 * c_dw * aw * (1 + R.U32) + R.FLOOR32
+    if c.nominal:
+        b2 = b2 + R.subnormal_term(ndw) * (1 + R.U32)
     if padded:        # the folded dy operand is summed and rounded once: an emulated input, covered by the RSS term
         A2 = (dyf * dyf).reshape(N, D, 2, H, 2, W, 2, cout).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(-1, 8 * cout)
         ssq = ((xs.double().reshape(-1, cin) ** 2).t() @ A2).reshape(cin, 2, 2, 2, cout).permute(0, 4, 1, 2, 3).contiguous()
@@ -478,6 +504,23 @@ WIRED_ONLY = {"pack_batch", "pack", "pack_deconv", "pack_fold", "external"}
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_training_step_wiring_and_every_launch_in_fp64(case, monkeypatch):
+    _step_in_fp64(case, monkeypatch, SCALE, nominal=False)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_training_step_at_the_trainers_initial_loss_scale(case, monkeypatch):
+    """The same step, wiring and per-launch checks with the backward seeded at NativeConvTrainer's own default ``init_scale``: the
+    gradient operands of the deep levels are fp16 subnormals, and the backward MFMA launches are held to their bounds with
+    fp64ref's term for such operands."""
+    import inspect
+
+    from diff_unet_amos_amd.training import NativeConvTrainer
+    scale = inspect.signature(NativeConvTrainer.__init__).parameters["init_scale"].default
+    assert isinstance(scale, float) and 1.0 < scale < SCALE
+    _step_in_fp64(case, monkeypatch, scale, nominal=True)
+
+
+def _step_in_fp64(case, monkeypatch, scale, nominal):
     from diff_unet_amos_amd import _native as nv
     from diff_unet_amos_amd import ops
     from diff_unet_amos_amd.training import _SegLoss, native_logits_cl
@@ -495,7 +538,7 @@ def test_training_step_wiring_and_every_launch_in_fp64(case, monkeypatch):
         tr.begin(image=image, x_t=x_t, t=t, labels=labels)
         logits = native_logits_cl(net, image, x_t, t, F16)
         loss = _SegLoss.apply(logits, labels)
-        (loss * SCALE).backward()
+        (loss * scale).backward()
     torch.cuda.synchronize()
     trace = tr.trace
     grads = {n: p.grad for n, p in net.named_parameters()}
@@ -505,7 +548,7 @@ def test_training_step_wiring_and_every_launch_in_fp64(case, monkeypatch):
     by = {r.label: r for r in trace}
     folded = {r.label.split(".")[0] for r in trace if r.kind == "fold"}
     reduced = {r.label.split(".conv_1/")[0] for r in trace if r.kind == "dgrad_reduce"}
-    print(f"\n[{case}] {len(trace) - 2} launches recorded in {t_step:.1f} s; folded {sorted(folded)} (queries: {sorted(fold)}); "
+    print(f"\n[{case}] backward seeded with {scale:g}; {len(trace) - 2} launches recorded in {t_step:.1f} s; folded {sorted(folded)} (queries: {sorted(fold)}); "
           f"reduce along {sorted(reduced)} (queries: {sorted(reduce)})")
     assert folded == fold and reduced == reduce, (folded, fold, reduced, reduce)
     if case == "even-64":
@@ -520,7 +563,7 @@ def test_training_step_wiring_and_every_launch_in_fp64(case, monkeypatch):
     assert not findings, findings
     assert tied == len(grads) == len(table.grads)
     # ---- (b) every launch against fp64 ------------------------------------------------------------------------------------------------
-    c = _Ctx(case, table, net)
+    c = _Ctx(case, table, net, nominal)
     errors = []
     for r in trace:
         if r.kind in WIRED_ONLY:
@@ -534,10 +577,10 @@ def test_training_step_wiring_and_every_launch_in_fp64(case, monkeypatch):
         r.ins, r.outs = {}, {}            # the clones of this launch are done with
     torch.cuda.synchronize()
     # ---- (d) the table ------------------------------------------------------------------------------------------------------------------
-    print(f"  {'launch':<44} {'kind':<13} {'shape':<40} {'points':>9} {'err/bound':>10}  worst at")
+    print(f"  {'launch':<60} {'kind':<13} {'shape':<40} {'points':>9} {'err/bound':>10}  worst at")
     worst = {}
     for row in c.rows:
-        print(f"  {row['label']:<44} {row['kind']:<13} {row['shape']:<40} {row['n']:>9} {row['ratio']:>10.4f}  {row['res'].where}")
+        print(f"  {row['label']:<60} {row['kind']:<13} {row['shape']:<40} {row['n']:>9} {row['ratio']:>10.4f}  {row['res'].where}")
         worst[row["kind"]] = max(worst.get(row["kind"], 0.0), row["ratio"])
     print(f"  [{case}] worst |err| / bound per kind: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
     # ---- (c) near-kink share ---------------------------------------------------------------------------------------------------------------
