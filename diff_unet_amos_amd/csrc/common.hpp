@@ -34,6 +34,7 @@ typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 enum : int { DT_F32 = 0, DT_F16 = 1 };
 
@@ -119,6 +120,32 @@ __device__ __forceinline__ void lds_dma_16(const void* src_lane, unsigned lds_ds
 // sendmsg) -- saving it costs the weight-gradient kernel 1-4 %.
 __device__ __forceinline__ void lds_dma_16_m0_unsaved(const void* src_lane, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src_lane), "s"(__builtin_amdgcn_readfirstlane(lds_dst)) : "memory");
+}
+
+// ---- Cache policy of the hand-off stores ("cache policy") ----
+// What a launch writes for the NEXT launch goes out write-through (sc1): the kernel boundary then has no dirty L2 lines to
+// write back on the critical path.  sc1 drops the line from the writer's L2 -- the reader is another launch, on any XCD.  A
+// policy bit changes where a line is kept, never a value.  16-byte stores only (a narrower sc1 store is one fabric write
+// each), and never nt on a hand-off (nt is not write-through).  -DDUA_CACHE_PARTS=0 (tools/build_diag.sh cp0
+// -DDUA_CACHE_PARTS=0) builds the library with plain stores: the same-box A/B partner, and the partner of
+// tests/test_cache_policy_gpu.py; the library keeps no option state.  Bits 2 (nt on once-per-step streams) and 4 (nt on the
+// split-K weight streams) were built, measured slower and taken out again: DESIGN section 5.
+#ifndef DUA_CACHE_PARTS
+#define DUA_CACHE_PARTS 1
+#endif
+constexpr bool CACHE_HANDOFF_WT = (DUA_CACHE_PARTS & 1) != 0;
+
+// No builtin stores 16 bytes with sc1 through a plain pointer, so it is one asm statement: hipcc does not count it (nothing
+// here waits for a store; its own counted waits only become stricter) and does not know when the statement has read its data
+// registers -- the trailing s_nop 1 is the wait state a following overwrite of them needs.
+template <typename V>
+__device__ __forceinline__ void store16_handoff(void* p, const V& v) {
+  static_assert(sizeof(V) == 16, "16-byte fragments only");
+  if constexpr (CACHE_HANDOFF_WT) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(__builtin_bit_cast(u32x4_t, v)) : "memory");
+  } else {
+    *(V*)p = v;
+  }
 }
 
 // Input transform applied while a consumer stages its operand: the producer stored the raw
@@ -340,7 +367,6 @@ __device__ __forceinline__ void xform_prep(float* sc, float* sh, float* ad, floa
 
 // one 16-byte fragment (four registers of two fp16 each); the four instructions of a register are issued a register apart, so
 // that no v_fma_mixhi follows the v_fma_mixlo it merges with back to back (hipcc pads that pair with s_nop)
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4_t xform_frag_mix(u32x4_t x, const float* a, const float* b, const float* an, const float* bn) {
   u32x4_t p, n, r;
 #pragma unroll

@@ -397,8 +397,8 @@ __global__ __launch_bounds__(256, BIG ? 1 : 2) void conv3d_k3_v2_kernel(Conv3Arg
           const int v = it * 8 + (lane >> 3), cg = lane & 7;
           const int gh = h0 + hbase + (v >> 3), gw = w0 + (v & 7);
           if (gh < a.H && gw < a.W)
-            *(f32x4*)(pout + (((long)gdz * a.H + gh) * a.W + gw) * a.cout_pad + q * 32 + cg * 4) =
-                *(const f32x4*)(otf + v * OSF + cg * 16);
+            store16_handoff(pout + (((long)gdz * a.H + gh) * a.W + gw) * a.cout_pad + q * 32 + cg * 4,
+                            *(const f32x4*)(otf + v * OSF + cg * 16));
         }
       }
       if (q == 0) __syncthreads();
@@ -467,8 +467,8 @@ __global__ __launch_bounds__(256, BIG ? 1 : 2) void conv3d_k3_v2_kernel(Conv3Arg
         const int v = it * VPI + lane / GPV, cg = lane % GPV;
         const int gh = h0 + hbase + (v >> 3), gw = w0 + (v & 7);
         if ((full || (gh < a.H && gw < a.W)) && ct * BN + q * 32 + cg * EPG < a.Cout)
-          *(Frag*)(yout + (((long)gd * a.H + gh) * a.W + gw) * a.Cout_stride + q * 32 + cg * EPG) =
-              *(const Frag*)(ot + v * OS + cg * 16);
+          store16_handoff(yout + (((long)gd * a.H + gh) * a.W + gw) * a.Cout_stride + q * 32 + cg * EPG,
+                          *(const Frag*)(ot + v * OS + cg * 16));
       }
     }
     if (q == 0) __syncthreads();               // staging tile is reused by the second half
@@ -722,8 +722,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_k3_first_kernel(Conv3Args a, in
           const int v = it * 8 + (lane >> 3), cg = lane & 7;
           const int gh = h0 + 4 * m + (v >> 3), gw = w0 + (v & 7);
           if ((full || (gh < a.H && gw < a.W)) && ct * BN + cg * 8 < a.Cout)
-            *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
-                *(const f16x8*)(ot + v * 128 + cg * 16);
+            store16_handoff(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox),
+                            *(const f16x8*)(ot + v * 128 + cg * 16));
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

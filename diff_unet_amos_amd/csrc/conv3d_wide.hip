@@ -114,8 +114,8 @@ __device__ __forceinline__ void wide_store_rows(const Conv3Args& a, f16* yout, c
     const int v = it * 8 + (lane >> 3), cg = lane & 7;
     const int gh = h0 + (v >> 3), gw = w0 + (v & 7);
     if (ct * BN + cg * 8 < a.Cout)
-      *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
-          *(const f16x8*)(ot + v * 128 + cg * 16);
+      store16_handoff(yout + chan_off(a.out_blk, ((long)gd * a.H + gh) * a.W + gw, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox),
+                      *(const f16x8*)(ot + v * 128 + cg * 16));
   }
   wide_wave_sync();
 }

@@ -149,8 +149,8 @@ __global__ __launch_bounds__(256) void deconv_k2s2_kernel(DeconvArgs a) {
       const int h = (int)(t % a.H), d = (int)(t / a.H);
       const long ov = ((long)(2 * d + ti) * H2 + (2 * h + tj)) * W2 + (2 * w + tk);
       const Frag o = *(const Frag*)(ot + vl * OS + cg * 16);
-      *(Frag*)(yout + ov * a.Cout_stride + cg * EPG) = o;
-      if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * EPG) = o; });
+      store16_handoff(yout + ov * a.Cout_stride + cg * EPG, o);
+      if (a.pad) pad_copies(a, ov, [&](long c) { store16_handoff(yout + c * a.Cout_stride + cg * EPG, o); });
     }
   }
 }
@@ -287,16 +287,16 @@ __global__ __launch_bounds__(256, 2) void deconv_k2s2_ksplit_kernel(DeconvArgs a
         Frag f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = (T)(o[e] + a.bias[ct * BN + cg * 8 + e]);
-        *(Frag*)dst = f;
-        if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * 8) = f; });
+        store16_handoff(dst, f);
+        if (a.pad) pad_copies(a, ov, [&](long c) { store16_handoff(yout + c * a.Cout_stride + cg * 8, f); });
       } else {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
           Frag f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) f[e] = (T)(o[4 * g + e] + a.bias[ct * BN + cg * 8 + 4 * g + e]);
-          *(Frag*)(dst + 4 * g) = f;
-          if (a.pad) pad_copies(a, ov, [&](long c) { *(Frag*)(yout + c * a.Cout_stride + cg * 8 + 4 * g) = f; });
+          store16_handoff(dst + 4 * g, f);
+          if (a.pad) pad_copies(a, ov, [&](long c) { store16_handoff(yout + c * a.Cout_stride + cg * 8 + 4 * g, f); });
         }
       }
     }
@@ -448,8 +448,8 @@ __global__ __launch_bounds__(256) void deconv_k2s2_alltaps_kernel(DeconvArgs a) 
         if (ovb[it] >= 0 && ct * BN + q * 32 + cg * EPG < a.Cout) {
           const Frag o = *(const Frag*)(ot + j * RB + cg * 16);
           const int c0 = a.Cout_off + ct * BN + q * 32 + cg * EPG;
-          *(Frag*)(yout + chan_off(a.out_blk, ovb[it] + toff, c0, a.Cout_stride, ovox)) = o;
-          if (a.pad) pad_copies(a, ovb[it] + toff, [&](long c) { *(Frag*)(yout + chan_off(a.out_blk, c, c0, a.Cout_stride, ovox)) = o; });
+          store16_handoff(yout + chan_off(a.out_blk, ovb[it] + toff, c0, a.Cout_stride, ovox), o);
+          if (a.pad) pad_copies(a, ovb[it] + toff, [&](long c) { store16_handoff(yout + chan_off(a.out_blk, c, c0, a.Cout_stride, ovox), o); });
         }
       }
       __builtin_amdgcn_wave_barrier();

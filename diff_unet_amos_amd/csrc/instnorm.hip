@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void materialize_kernel(const T* __restrict__ 
 #pragma unroll
       for (int e = 0; e < EPG; ++e) po[e] = (T)mx[e];
       const long pv = n * (ODD ? (long)(D >> 1) * H2 * W2 : vox_n >> 3) + ((long)pd * H2 + ph) * W2 + pw;
-      *(Frag*)(pooled + pv * pool_stride + cg * EPG) = po;
+      store16_handoff(pooled + pv * pool_stride + cg * EPG, po);     // the next level's first convolution reads it next
     }
   }
 }

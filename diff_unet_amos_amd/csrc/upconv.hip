@@ -466,8 +466,8 @@ __global__ __launch_bounds__(256, 2) DUA_NAMED_ACC_KERNEL void upconv_k3_kernel(
       const int v = it * 8 + (lane3 >> 3), cg = lane3 & 7;         // v = staged row: cz_lo = v >> 5, cy = (v >> 3) & 3, w = v & 7
       const int gd = d0 + 2 * (2 * czh + (v >> 5)) + pd, ghh = h0 + 2 * ((v >> 3) & 3) + ph, gww = w0 + (v & 7);
       if (ct * BN + cg * 8 < a.Cout)
-        *(f16x8*)(yout + chan_off(a.out_blk, ((long)gd * a.H + ghh) * a.W + gww, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox)) =
-            *(const f16x8*)(ot + v * 128 + cg * 16);
+        store16_handoff(yout + chan_off(a.out_blk, ((long)gd * a.H + ghh) * a.W + gww, a.Cout_off + ct * BN + cg * 8, a.Cout_stride, nvox),
+                        *(const f16x8*)(ot + v * 128 + cg * 16));
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
